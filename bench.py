@@ -2,6 +2,14 @@
 """bench.py -- headline benchmark of the Mandelbrot tile escape-time path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--kernel default] [--shard own|queue|bands]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: set up, ramp the clock, W warm-up steps, the K timed steps, one reduction
+of the last step's counts (the pixel-iterations `value` counts), the line.  Everything else described below -- the
+per-launch event pass, `output_verified`, the cycle-test leg, the SMI readings, the extra objects of N = 1 and
+`cpu_baseline` -- runs only with `--full`.  `--dump-outputs DIR` (--shard own) writes what the last timed step computed:
+counts.npy (float32; the int32 escape indices), nu.npy (float64; cfg5) and bytes.npy (float32; --outputs both), every
+pixel in row-major order or, beyond 48 MiB in all, the same seeded sample of pixels in each (`outputs_dumped` in the line).
 
 One "step" = one pass of the hot path over one batch of synthetic input already described in HBM terms: the
 kernel generates its coordinates itself and writes int32 escape indices to a resident HBM buffer
@@ -131,6 +139,8 @@ EXTRA_CONFIGS = {"cfg3": ("cfg3", None, 2, 1), "cfg5": ("cfg5", None, 3, 1), "ch
 MIN_LEG_MS = 50.0   # every leg beside the headline is repeated until it holds at least this much device time (its `steps_run`)
 SUSTAINED_S = 1.0   # the `sustained` object: the headline's launches back to back for at least this long, clock and power sampled
 GOLDEN_OUTPUTS = os.path.join(ROOT, "tests", "golden", "bench_outputs.json")   # made by tests/golden/make_bench_golden.py
+DUMP_BUDGET_BYTES = 48 * 2 ** 20   # --dump-outputs: at most this much in all; a seeded sample of the pixels beyond it
+DUMP_SEED = 1000
 PMC_SUMMARIES = [("r06", "cfg2_default_pmc_summary.json"), ("r05", "cfg2_default_pmc_summary.json"), ("r04", "cfg2_default_pmc_summary.json"), ("r03", "cfg2_default_pmc_summary.json"), ("r02", "cfg2_default_pmc_summary.json"), ("r01", "cfg2_default_pmc_summary.json")]
 
 
@@ -152,9 +162,17 @@ def parse_args(argv=None):
     ap.add_argument("--outputs", default="counts", choices=["counts", "both"],
                     help="counts (default, the contract's workload): int32 escape indices. both: also the quantised "
                          "uint8 tile the worker sends (what a DataChunk launch writes), for kernel studies")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: output_verified against the CPU oracle's hashes, the "
+                         "per-launch event pass (kernel_ms_median / min), the cycle-test leg, SMI readings and box versions, "
+                         "at N = 1 the extra objects (sustained, xcd_balance_opt_in, two_streams, end_to_end, queue_job, "
+                         "configs) and cpu_baseline.  Off: the line holds the headline and what the timed steps give")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64; a fixed, seeded sample of the pixels when the whole would exceed 48 MiB); --shard own only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip the end_to_end and queue_job objects (kernel studies, profiling passes)")
+                    help="--full, N = 1: skip the end_to_end and queue_job objects (kernel studies, profiling passes)")
     ap.add_argument("--shard", default=None, choices=["own", "tiles", "queue", "bands"],
                     help="own (default for N = 1; 'tiles' is its old name): every rank computes its own tile per step "
                          "(weak scaling). queue (default for N > 1): one step = a fixed set of grid x grid 4096^2 tiles "
@@ -188,6 +206,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.shard == "tiles":
         args.shard = "own"
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     return args
 
 
@@ -458,6 +478,37 @@ def verify_output(name, d_counts, pixel_iterations, never_pixels, view, mrd, pre
             "golden": f"tests/golden/bench_outputs.json['{name}'] (CPU oracle, {g['oracle']})"}
 
 
+def dump_sample(npix, bytes_per_pixel, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: None (every pixel fits in `budget`) or the sorted pixel indices of a fixed, seeded sample of at most
+    budget / bytes_per_pixel pixels -- the same indices for every output of a step and in every run with the same arguments:
+    one pixel at a seeded random offset in every stride of ceil(npix / keep) pixels (increasing, hence unique)."""
+    import numpy as np
+    keep = budget // bytes_per_pixel
+    if npix <= keep:
+        return None
+    stride = -(-npix // keep)
+    base = np.arange(0, npix, stride, dtype=np.int64)
+    return np.minimum(base + np.random.default_rng(seed).integers(0, stride, size=base.size, dtype=np.int64), npix - 1)
+
+
+def dump_outputs(out_dir, outputs, npix):
+    """Write what the last timed step computed, DIR/<name>.npy per output.  `outputs`: (name, flat device tensor of npix
+    elements, numpy dtype float32 | float64).  A sample, when needed, is gathered on the device: one short D2H per output."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx = dump_sample(npix, sum(np.dtype(dt).itemsize for _, _, dt in outputs))
+    d_idx = torch.from_numpy(idx).to(outputs[0][1].device) if idx is not None else None
+    files = {}
+    for name, t, dt in outputs:
+        a = (t if d_idx is None else t[d_idx]).cpu().numpy().astype(dt)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = {"dtype": np.dtype(dt).name, "elements": int(a.size)}
+    return {"dir": out_dir, "files": files,
+            "sample": None if idx is None else f"{idx.size} of {npix} pixels (bench.dump_sample: one at a seeded offset in every "
+                                               f"stride of {-(-npix // idx.size)}), row-major pixel order"}
+
+
 def extra_configs(dev, torch, gpu_index, device_info, ramp_ms=150.0):
     """Short strict legs (cycle test off, library defaults otherwise) of the other single-GPU BASELINE configs, so that the
     one command the driver times shows every one of them: per config `value`, `ms_per_step`, `roofline.frac` and
@@ -645,6 +696,8 @@ def main():
         raise SystemExit("cfg5 (smooth colouring) runs with --shard own in fp64")
     if args.grid < 1 or args.grid > 15:
         raise SystemExit("--grid must be in 1..15 (the grid view has grid x 4096 < 2^16 columns)")
+    if args.dump_outputs and (not own_mode or fake_env):
+        raise SystemExit("--dump-outputs needs --shard own on the GPU path (one tile per step: its buffers are the step's outputs)")
     options = {}
     for item in args.opt:
         k, _, v = item.partition("=")
@@ -879,7 +932,7 @@ def main():
         if rank == 0:
             cursor.reset(0)
         barrier()
-    smi = SmiSampler(gpu_index) if (not fake and rank == 0) else None
+    smi = SmiSampler(gpu_index) if (args.full and not fake and rank == 0) else None
     # (sampled HERE, before the ramp, not between the warm-up and the timed region: the two SMI reads take ~2 ms, and a 2 ms idle
     # gap costs the next twenty launches 5-10 % -- scripts/burst_probe.py, profiles/r06/burst_probe_0.txt)
     smi_before = smi.sample() if smi else None
@@ -903,6 +956,15 @@ def main():
     smi_after = smi.sample() if smi else None     # (after the clock has been read: the SMI calls take milliseconds)
     # (units kernel, MBK_OPT_XCD_BALANCE: what share of a tile's heavy blocks every XCD was getting when the region ended)
     xcd_after_timed = dev.xcd_shares() if not fake and hasattr(dev, "xcd_shares") else None
+    dumped = None
+    if args.dump_outputs and rank == 0:   # (own mode on the GPU, checked before any work): the buffers of the last timed launch
+        last = (turn[0] - 1) % nstreams
+        outs = [("counts", d_counts_all[last], "float32")]          # int32 escape indices < 2^24: exact in float32
+        if smooth:
+            outs.append(("nu", d_smooth_all[last], "float64"))
+        if d_bytes_all:
+            outs.append(("bytes", d_bytes_all[last], "float32"))
+        dumped = dump_outputs(args.dump_outputs, outs, npix)
 
     never = 0
     verified = None
@@ -921,21 +983,22 @@ def main():
             sync()
         st = dev.reduce_counts(d_counts_all[0].data_ptr(), npix, mrd, stream=streams[0].cuda_stream)
         iters_per_step, never = st.pixel_iterations, st.never_pixels
-        if own_mode and rank == 0 and args.workload in golden_outputs():
+        if args.full and own_mode and rank == 0 and args.workload in golden_outputs():
             # the buffer the LAST TIMED launch wrote, against the CPU oracle's hash (VERDICT r4 missing 3)
             try:
                 verified = verify_output(args.workload, d_counts_all[(turn[0] - 1) % nstreams], iters_per_step, never, view, mrd, args.precision)
             except Exception as e:   # noqa: BLE001 -- reported, must not cost the headline
                 verified = {"verified": None, "why": repr(e)}
         region_events = bool(events) and len(events[0]) == 3
-        if region_events:   # one pair around the K launches: the average; then an untimed pass with a pair per launch
+        if region_events:   # one pair around the K launches: the average; then (--full) an untimed pass with a pair per launch
             kernel_ms_region = events[0][0].elapsed_time(events[0][1]) / events[0][2]
             per_launch = []
-            saved, args.launch_events = args.launch_events, "per-launch"
-            ramp_clock()     # (the GPU idled through the hash above)
-            run_steps(max(min(args.steps, 64), 32), per_launch)
-            sync()
-            args.launch_events = saved
+            if args.full:
+                saved, args.launch_events = args.launch_events, "per-launch"
+                ramp_clock()     # (the GPU idled through the hash above)
+                run_steps(max(min(args.steps, 64), 32), per_launch)
+                sync()
+                args.launch_events = saved
             kernel_ms = [a.elapsed_time(b) for a, b in per_launch]
         else:
             kernel_ms_region = None
@@ -968,7 +1031,7 @@ def main():
     # A failure here must not cost the headline: errors are caught (the barriers stay unconditional, so the ranks
     # stay in step) and reported in config.cycle_leg_error instead of the cycle_detection object.
     cyc_leg, cyc_err, cyc_verified = None, None, None
-    second_leg = not fake and own_mode and "cycle_detect" not in options and args.kernel in ("default", "group", "scan")
+    second_leg = args.full and not fake and own_mode and "cycle_detect" not in options and args.kernel in ("default", "group", "scan")
     cyc_steps, cyc_submit_s, cyc_event_ms = args.steps, None, None
     if second_leg:
         ce0, ce1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1038,9 +1101,10 @@ def main():
     iters_all = float(iters_per_step) * (world if own_mode else 1)
 
     if rank == 0:
-        avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         if kernel_ms_region is not None:   # events around the whole timed region / K (what the roofline is priced on)
             avg_kernel_s = kernel_ms_region / 1e3
+        else:
+            avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         if not own_mode:      # per-GPU average time per step, idle time included
             avg_kernel_s = elapsed_max / args.steps
         cus, mhz = device_info["compute_units"], device_info["clock_mhz"]
@@ -1127,14 +1191,15 @@ def main():
                 "traffic": traffic,
                 "traffic_source": traffic_source,
                 "basis": ("one pair of HIP events on the launch stream around the K launches of the timed region, elapsed / K "
-                          "(gaps between launches included); median / min / kernel_ms_avg_per_launch_pass: an untimed pass of "
-                          f"{len(kernel_ms)} launches with a pair of events per launch" if kernel_ms_region is not None else
-                          "HIP events around each launch on its stream") if own_mode
+                          "(gaps between launches included); median / min / kernel_ms_avg_per_launch_pass: "
+                          + (f"an untimed pass of {len(kernel_ms)} launches with a pair of events per launch" if kernel_ms
+                             else "not measured (--full runs a pass with a pair of events per launch)")
+                          if kernel_ms_region is not None else "HIP events around each launch on its stream") if own_mode
                          else "whole-job wall time per step per GPU (idle time included)",
-                "kernel_ms_avg_per_launch_pass": sum(kernel_ms) / len(kernel_ms) if kernel_ms_region is not None else None,
+                "kernel_ms_avg_per_launch_pass": sum(kernel_ms) / len(kernel_ms) if kernel_ms_region is not None and kernel_ms else None,
                 "kernel_ms_avg": avg_kernel_s * 1e3,
-                "kernel_ms_median": sorted(kernel_ms)[len(kernel_ms) // 2] if own_mode else avg_kernel_s * 1e3,
-                "kernel_ms_min": min(kernel_ms),
+                "kernel_ms_median": (sorted(kernel_ms)[len(kernel_ms) // 2] if kernel_ms else None) if own_mode else avg_kernel_s * 1e3,
+                "kernel_ms_min": min(kernel_ms) if kernel_ms else None,
                 "flops_per_pixel_iteration": FLOPS_PER_PIXEL_ITER,
                 "valu_slots_per_pixel_iteration": slots,
                 # with the cycle test in the headline (--opt cycle_detect=1) fewer steps are executed than the
@@ -1177,7 +1242,9 @@ def main():
                 "same_pixel_iterations_and_never_count": bool(cyc_leg[1]),
                 "output_verified": cyc_verified,
             }
-        if (world == 1 and own_mode and not fake and not args.no_extras and args.workload == "cfg2" and not smooth
+        if dumped is not None:
+            rec["outputs_dumped"] = dumped
+        if (args.full and world == 1 and own_mode and not fake and not args.no_extras and args.workload == "cfg2" and not smooth
                 and args.precision == "f64" and args.kernel == "default" and not options):
             # beside the headline (never in `value`): the end-to-end tile rate, and the N > 1 default job on this GPU
             # -- `sustained`: the headline's launches back to back for >= SUSTAINED_S, clock / power sampled through librocm_smi64
@@ -1283,9 +1350,9 @@ def main():
                 rec["configs"] = extra_configs(dev, torch, gpu_index, device_info, ramp_ms=args.ramp_ms if args.ramp_ms > 0 else 0.0)
             except Exception as e:   # noqa: BLE001
                 rec["configs"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and not fake:
+        if args.full and world == 1 and not args.no_cpu_baseline and not fake:
             rec["cpu_baseline"] = cpu_baseline(args.workload, workload, args.precision)
-        elif world == 1 and fake:
+        elif args.full and world == 1 and fake:
             rec["cpu_baseline"] = None
         print(json.dumps(rec), flush=True)
 
@@ -1305,7 +1372,7 @@ def queue_job_single(args, headline_value):
     scaling curve (value(N) / (N x this) is the efficiency of the queue; `value` of the headline is a single tile
     per step, whose rate differs by the tiles' pitch)."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--shard", "queue", "--no-cpu-baseline", "--no-extras",
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--shard", "queue", "--full", "--no-cpu-baseline", "--no-extras",
            "--workload", args.workload, "--kernel", args.kernel, "--grid", str(args.grid), "--steps", "3", "--warmup", "1",
            "--queue-order", args.queue_order]
     for item in args.opt:

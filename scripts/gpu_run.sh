@@ -7,7 +7,7 @@
 #   soak[:S[:SEED]]  randomized parity soak for S seconds (default 120; seed 17)
 #   issue        profiles/microbench/valu_issue.hip (fp64 issue rate in shader cycles)
 #   clock[:W:K ...]  the shader clock (s_memtime / s_memrealtime, a one-wave probe in a second process) while bench.py runs workload W for K steps
-#   headline     bench.py as the driver runs it
+#   headline     bench.py --full: the headline and every leg beside it
 #   balance      MBK_OPT_XCD_BALANCE on / off on the same box (queue job, cfg2, DataChunk (1,0,0))
 #   n2           the N > 1 paths with two ranks on this box's one GPU (--oversubscribe; functional)
 #   emulate      scripts/scale_emulate.py -> scale_prediction.json
@@ -44,7 +44,7 @@ for SEC in "$@"; do
         /tmp/valu_issue --probe 9000 > "$OUT/clock_probe_$W.txt" 2>&1 &
         PROBE=$!
         sleep 1.5
-        timeout 300 python bench.py --workload $W --no-cpu-baseline --no-extras --steps $K --opt cycle_detect=0 > "$OUT/bench_clock_$W.log" 2>&1
+        timeout 300 python bench.py --full --workload $W --no-cpu-baseline --no-extras --steps $K --opt cycle_detect=0 > "$OUT/bench_clock_$W.log" 2>&1
         wait $PROBE
         line "$OUT/bench_clock_$W.log"
         python - "$OUT/clock_probe_$W.txt" <<'PY'
@@ -173,7 +173,7 @@ PY
   gaps) # kernel-trace of back-to-back steps: tile kernel, gap, where the next launch's pre-pass ran.  gaps:W:OPT+OPT...
       W=${ARG%%:*}; O=${ARG#*:}; [ "$O" = "$ARG" ] && O=""; OPTS=""; for o in ${O//+/ }; do OPTS="$OPTS --opt $o"; done
       N=gaps_${W}_${O//[=+]/}
-      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/$N" -o t -- python "$ROOT/bench.py" --no-cpu-baseline --no-extras --workload $W --steps 150 --warmup 20 $OPTS > "$OUT/$N.log" 2>&1)
+      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/$N" -o t -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras --workload $W --steps 150 --warmup 20 $OPTS > "$OUT/$N.log" 2>&1)
       line "$OUT/$N.log"; python scripts/analyze_gaps.py "$OUT/$N" | tee "$OUT/$N.txt"; rm -rf "$OUT/$N";;
   strip) timeout 400 python scripts/strip_ab.py ${ARG:-5} 2>&1 | grep -v amdgpu.ids | tee "$OUT/strip_ab.txt";;
   fill) hipcc --offload-arch=gfx950 -O3 -o /tmp/fill profiles/microbench/fill.hip 2> "$OUT/build_fill.log" && timeout 300 /tmp/fill > "$OUT/fill.txt" 2>&1; cat "$OUT/fill.txt"
@@ -222,7 +222,7 @@ PY
        done
        rm -rf "$OUT"/pmc_*_?;;
   power) for spec in "cfg3 default 150" "inset default 600" "cfg2 default 4000"; do set -- $spec
-        timeout 300 python scripts/power_trace.py "$OUT/power_$1_$2.json" -- python bench.py --workload $1 --kernel $2 --no-cpu-baseline --no-extras --steps $3 --opt cycle_detect=0 > "$OUT/power_$1_$2.log" 2>&1
+        timeout 300 python scripts/power_trace.py "$OUT/power_$1_$2.json" -- python bench.py --full --workload $1 --kernel $2 --no-cpu-baseline --no-extras --steps $3 --opt cycle_detect=0 > "$OUT/power_$1_$2.log" 2>&1
         python - "$OUT/power_$1_$2.json" <<'PY'
 import json,sys
 try:

@@ -7,13 +7,14 @@ reference's decoder turns back into the reference's own tile".  Here
   * the CPU suite checks that the codec restatement (oracle/serializer.py) AND the product's host codec
     (chunkstore.serialize_chunk) reproduce every pinned stream, that the runs are maximal and the Raw/RLE choice
     follows DataChunk.cs:186-196 -- which together make the stream the unique one the C# encoder writes;
-  * where /root/reference exists (the build container) the reference's get_chunk is run live against the DataServer
-    stand-in over a ChunkStore;
+  * the DataServer stand-in, over a ChunkStore and read the way the reference's get_chunk reads it, answers with the
+    pinned streams, which decode to what the reference's get_chunk returned (codec_vectors.npz "get_chunk/...");
   * the GPU suite asserts that the on-device serialiser (mbk_serialize_last) emits exactly the pinned streams for the
     six golden tiles."""
 import hashlib
 import importlib.util
 import os
+import socket
 import struct
 
 import numpy as np
@@ -23,9 +24,6 @@ from conftest import ROOT
 from distributedmandelbrot_amd.chunkstore import ChunkStore, deserialize_chunk, serialize_chunk
 from distributedmandelbrot_amd.server import DataServer
 from oracle.serializer import deserialize, rle_runs, serialize
-
-REF_VIEWER = "/root/reference/DistributedMandelbrotViewer/DistributedMandelbrotViewer.py"
-
 
 def _load(path, name):
     spec = importlib.util.spec_from_file_location(name, path)
@@ -93,27 +91,42 @@ def test_golden_tiles_reproduce_the_streams_the_reference_decoder_accepted(codec
         assert str(codec_golden[f"tile/{key}/decoded_sha256"]) == str(golden[f"full/{key}/bytes_sha256"])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_VIEWER), reason="the reference tree is not on this machine (GPU box)")
-def test_reference_viewer_reads_the_dataserver_stand_in_live(tmp_path, codec_golden, gen):
-    """The reference's unmodified get_chunk / chunk_data_to_value_array (Viewer.py:35-108) against server.DataServer over
-    a ChunkStore: Regular (RLE and Raw files), Never, Immediate, not-available and rejected requests."""
-    os.environ.setdefault("MPLBACKEND", "Agg")
-    viewer = _load(REF_VIEWER, "reference_viewer_live")
-    assert sha(open(REF_VIEWER, "rb").read()) == str(codec_golden["meta/reference_viewer_sha256"])
+def _viewer_request(port, level, index_real, index_imag):
+    """One request as the Viewer's get_chunk (Viewer.py:62-108) makes it: (status byte, response body | None)."""
+    with socket.create_connection(("127.0.0.1", port)) as s:
+        s.sendall(struct.pack("<III", level, index_real, index_imag))
+        status = s.recv(1)[0]
+        if status != 0x00:
+            return status, None
+        n = struct.unpack("<I", s.recv(4))[0]
+        body = bytearray()
+        while len(body) < n:
+            part = s.recv(n - len(body))
+            assert part, "EOF inside a response"
+            body += part
+    return status, bytes(body)
+
+
+def test_viewer_protocol_reads_the_dataserver_stand_in(tmp_path, codec_golden, gen):
+    """server.DataServer over a ChunkStore, read the way the reference's get_chunk reads it (Viewer.py:62-108): Regular (RLE
+    and Raw files), Never, Immediate, not-available and rejected requests.  Every body must be the stream pinned for its
+    pattern (the one the reference's decoder accepted), and decode to what the reference's get_chunk returned for it."""
     store = ChunkStore(str(tmp_path))
     placed = {(1, 2): "long_runs_chunk", (0, 0): "all_zero_chunk", (4, 4): "all_one_chunk", (3, 3): "noisy_chunk"}
     for (ir, ii), name in placed.items():
         store.save_chunk(5, ir, ii, gen.pattern(name))
     with DataServer(store) as ds:
         for (ir, ii), name in placed.items():
-            vs, ok = viewer.get_chunk("127.0.0.1", ds.port, 5, ir, ii)
-            assert ok and vs.dtype == np.uint8 and sha(vs.tobytes()) == str(codec_golden[f"get_chunk/{name}/sha256"])
-        assert viewer.get_chunk("127.0.0.1", ds.port, 5, 2, 2) == (None, False)
-        with pytest.raises(Exception, match="rejected"):
-            viewer.get_chunk("127.0.0.1", ds.port, 5, 5, 0)
-    # and the decoder on a stream the product's host codec makes right now
-    stream = serialize_chunk(gen.pattern("rle_wins_by_a_hair_chunk")[: 5 * 4000])
-    assert bytes(viewer.chunk_data_to_value_array(bytearray(stream))) == gen.pattern("rle_wins_by_a_hair_chunk")[: 5 * 4000].tobytes()
+            status, body = _viewer_request(ds.port, 5, ir, ii)
+            assert status == 0x00 and sha(body) == str(codec_golden[f"pattern/{name}/stream_sha256"]), name
+            assert len(body) == int(codec_golden[f"pattern/{name}/stream_len"]) and body[0] == int(codec_golden[f"pattern/{name}/codec"])
+            vs = deserialize(body, 4096 * 4096)
+            assert vs.dtype == np.uint8 and sha(vs.tobytes()) == str(codec_golden[f"get_chunk/{name}/sha256"]), name
+        assert _viewer_request(ds.port, 5, 2, 2) == (0x02, None)      # not available: get_chunk -> (None, False)
+        assert _viewer_request(ds.port, 5, 5, 0) == (0x01, None)      # index >= level: get_chunk raises "rejected"
+    # and a stream the product's host codec makes right now decodes back to its data
+    data = gen.pattern("rle_wins_by_a_hair_chunk")[: 5 * 4000]
+    assert np.array_equal(deserialize(serialize_chunk(data), data.size), data)
 
 
 @pytest.mark.gpu

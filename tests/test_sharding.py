@@ -289,7 +289,7 @@ def test_bench_json_contract_single_rank_fake():
     """The one-line JSON of bench.py carries every field the round contract names (checked on the CPU
     with the stub backend; the real numbers come from the GPU run)."""
     env = dict(os.environ, MBK_BENCH_FAKE="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -413,11 +413,11 @@ def test_bench_golden_outputs_describe_the_bench_workloads():
 
 @pytest.mark.gpu
 def test_real_bench_default_line_pins_its_outputs_and_shows_every_config():
-    """The command the driver runs (`python bench.py --gpus 1 --steps K --warmup W`): the timed launches' own buffer hashes
+    """The command the driver runs with --full (`python bench.py --gpus 1 --steps K --warmup W --full`): the timed launches' own buffer hashes
     to the CPU oracle's counts (strict leg and cycle-test leg), and the line carries a short strict leg of every other
     single-GPU BASELINE config, each verified the same way."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MBK_BENCH_FAKE")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -448,3 +448,60 @@ def test_real_bench_default_line_pins_its_outputs_and_shows_every_config():
     assert e2e["slots"] == 4 and e2e["tiles_per_s_all_slots_in_flight_lazy_uniform"] > e2e["tiles_per_s_synchronous"]
     assert e2e["worker_depth"] == 3 and e2e["tiles_per_s_three_in_flight_lazy_uniform"] > e2e["tiles_per_s_synchronous"]
     assert e2e["host_answered_tiles"] == 32      # level 16: the corners of [-2, 2]^2 outside |c| = 2
+
+
+def test_bench_plain_line_leaves_the_extra_legs_to_full():
+    """A plain `bench.py --steps K --warmup W` line holds the headline and what its timed steps give; cpu_baseline and the
+    other legs beside it come with --full (stub backend).  --dump-outputs needs the GPU's own-mode buffers."""
+    env = dict(os.environ, MBK_BENCH_FAKE="1")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+                         env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["unit"] == "G pixel-iterations/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f64" and rec["ms_per_step"] > 0 and rec["value"] > 0 and "roofline" in rec
+    for key in ("cpu_baseline", "cycle_detection", "output_verified", "configs", "end_to_end", "sustained", "outputs_dumped"):
+        assert key not in rec, key
+    assert rec["config"]["versions"] is None and rec["config"]["smi_around_timed_region"] is None
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--dump-outputs", "unused"],
+                         env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--dump-outputs needs --shard own" in out.stderr
+    assert not os.path.exists(os.path.join(ROOT, "unused"))
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: every pixel while the outputs fit in the budget, else the same seeded sample of pixels each time."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_sample(512 * 512, 4) is None
+    assert bench.dump_sample(bench.DUMP_BUDGET_BYTES // 4, 4) is None
+    for npix, per_px in ((4096 * 4096, 4), (4096 * 4096, 4 + 8 + 4), (16384 * 16384, 4)):
+        a, b = bench.dump_sample(npix, per_px), bench.dump_sample(npix, per_px)
+        assert np.array_equal(a, b) and a.size * per_px <= bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+        assert a.size > bench.DUMP_BUDGET_BYTES // per_px // 2 and (np.diff(a) > 0).all() and 0 <= a[0] and a[-1] < npix
+
+
+@pytest.mark.gpu
+def test_real_bench_plain_line_dumps_the_last_step(tmp_path, oracle):
+    """The plain command with --dump-outputs: exactly --steps timed steps, no leg beside the headline, and counts.npy holds
+    the escape indices of the last timed launch -- a seeded sample of cfg2's 4096^2 pixels -- equal to the CPU oracle's."""
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MBK_BENCH_FAKE")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 7 and rec["warmup"] == 2 and rec["value"] > 1000.0 and rec["ms_per_step"] > 0
+    for key in ("cpu_baseline", "cycle_detection", "output_verified", "configs", "end_to_end", "sustained"):
+        assert key not in rec, key
+    assert sorted(os.listdir(tmp_path)) == ["counts.npy"] and list(rec["outputs_dumped"]["files"]) == ["counts"]
+    counts = np.load(tmp_path / "counts.npy")
+    sr, si, rng, w, h, mrd, _ = bench.WORKLOADS["cfg2"]
+    idx = bench.dump_sample(w * h, 4)
+    assert counts.dtype == np.float32 and counts.shape == idx.shape
+    oc, _, total = oracle.view(sr, si, rng, rng, w, h, mrd, want_bytes=False)
+    assert np.array_equal(counts, oc.ravel()[idx].astype(np.float32))
+    assert abs(rec["value"] - total * 7 / (rec["ms_per_step"] * 7 / 1e3) / 1e9) / rec["value"] < 1e-9
