@@ -13,6 +13,6 @@ sharding.py      row-band work items and the per-GPU queue used to shard one vie
 
 There is no CPU fallback anywhere in this package.
 """
-from .device import MandelbrotDevice, MbkError, TileStats, View, device_count  # noqa: F401
+from .device import DeepOrbit, DeepView, MandelbrotDevice, MbkError, TileStats, View, device_count  # noqa: F401
 
-__all__ = ["MandelbrotDevice", "MbkError", "TileStats", "View", "device_count"]
+__all__ = ["DeepOrbit", "DeepView", "MandelbrotDevice", "MbkError", "TileStats", "View", "device_count"]

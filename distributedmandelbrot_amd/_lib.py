@@ -41,12 +41,19 @@ MBK_CODEC_RAW = 0x00
 MBK_CODEC_RLE = 0x01
 MBK_CHUNK_DEFINITION = 4096
 MBK_CHUNK_BYTES = 4096 * 4096
-MBK_ABI_VERSION = 4
+MBK_ABI_VERSION = 5
 
 
 class mbk_view(C.Structure):
     _fields_ = [("start_r", C.c_double), ("start_i", C.c_double),
                 ("range_r", C.c_double), ("range_i", C.c_double),
+                ("width", C.c_uint32), ("height", C.c_uint32),
+                ("col0", C.c_uint32), ("row0", C.c_uint32),
+                ("ncols", C.c_uint32), ("nrows", C.c_uint32)]
+
+
+class mbk_deep_view(C.Structure):
+    _fields_ = [("range_r", C.c_double), ("range_i", C.c_double),
                 ("width", C.c_uint32), ("height", C.c_uint32),
                 ("col0", C.c_uint32), ("row0", C.c_uint32),
                 ("ncols", C.c_uint32), ("nrows", C.c_uint32)]
@@ -136,6 +143,17 @@ SIGNATURES = {
     "mbk_net_get_option": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)]),
     "mbk_feeder_run": (C.c_int, [C.POINTER(mbk_feeder_ops), C.c_char_p, C.c_uint16, C.c_uint64, C.c_uint32,
                                  C.POINTER(mbk_worker_report)]),
+    "mbk_deep_orbit_create": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mbk_deep_orbit_destroy": (None, [C.c_void_p]),
+    "mbk_deep_orbit_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32)]),
+    "mbk_deep_orbit_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mbk_deep_view_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_view_submit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

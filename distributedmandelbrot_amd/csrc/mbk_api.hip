@@ -24,6 +24,8 @@
 #include "mbk_units.h"
 #include "mbk_spill.h"
 #include "mbk_feeder.h"
+#include "mbk_deep_orbit.h"
+#include "mbk_deep.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -126,8 +128,15 @@ struct mbk_ctx {
     struct ProbeKey { Axis re, im; uint32_t col0, row0, ncols, nrows; } probe_key = {};
     double probe_share = 0.0;
     bool probe_valid = false;
+    // deep-zoom views: this ctx's device copies of the orbits it has used, by orbit id (deep_copy)
+    struct DeepCopy { uint64_t id; double4 *d; };
+    std::vector<DeepCopy> deep;
     hipDeviceProp_t prop;
     std::string err;
+};
+
+struct mbk_deep_orbit {
+    mbk::DeepOrbit o;
 };
 
 static thread_local std::string g_err;
@@ -1366,8 +1375,9 @@ void mbk_destroy(mbk_ctx *ctx)
         if (sl.ev_c1) (void)hipEventDestroy(sl.ev_c1);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
     }
-    if (!ctx->scratch.empty()) (void)hipDeviceSynchronize();  // caller streams may still use the scratch
+    if (!ctx->scratch.empty() || !ctx->deep.empty()) (void)hipDeviceSynchronize();  // caller streams may still use them
     for (StreamScratch &sc : ctx->scratch) free_scratch(sc);
+    for (mbk_ctx::DeepCopy &c : ctx->deep) (void)hipFree(c.d);
     if (ctx->d_rle) (void)hipFree(ctx->d_rle);
     if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
     delete ctx;
@@ -1924,6 +1934,241 @@ int mbk_reduce_counts(mbk_ctx *ctx, const int32_t *d_counts, uint64_t n, uint32_
     MBK_HIP(ctx, hipStreamSynchronize(s));
     std::memset(stats, 0, sizeof(*stats));
     fill_stats_from_reduce(sc->h_red, stats, false);
+    return MBK_OK;
+}
+
+// ---- deep-zoom views (mbk_deep_orbit.h, mbk_deep.h) ---------------------------------------------------------
+
+int mbk_deep_orbit_create(const char *center_r, const char *center_i, uint32_t precision_bits, uint32_t mrd,
+                          mbk_deep_orbit **out)
+{
+    if (!out) return fail(nullptr, MBK_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    mbk_deep_orbit *o = new (std::nothrow) mbk_deep_orbit();
+    if (!o) return fail(nullptr, MBK_ERR_NOMEM, "out of host memory");
+    std::string why;
+    bool ok = false;
+    try {
+        ok = mbk::build_deep_orbit(center_r, center_i, precision_bits, mrd, &o->o, &why);
+    } catch (const std::bad_alloc &) {
+        delete o;
+        return fail(nullptr, MBK_ERR_NOMEM, "out of host memory for the reference orbit");
+    }
+    if (!ok) {
+        delete o;
+        return fail(nullptr, MBK_ERR_INVALID, why);
+    }
+    *out = o;
+    return MBK_OK;
+}
+
+void mbk_deep_orbit_destroy(mbk_deep_orbit *orbit) { delete orbit; }
+
+int mbk_deep_orbit_info(const mbk_deep_orbit *orbit, uint32_t *length, uint32_t *escaped, uint32_t *precision_bits,
+                        uint32_t *mrd)
+{
+    if (!orbit) return fail(nullptr, MBK_ERR_INVALID, "orbit is NULL");
+    if (length) *length = orbit->o.length;
+    if (escaped) *escaped = orbit->o.escaped;
+    if (precision_bits) *precision_bits = orbit->o.precision_bits;
+    if (mrd) *mrd = orbit->o.mrd;
+    return MBK_OK;
+}
+
+int mbk_deep_orbit_read(const mbk_deep_orbit *orbit, double *zr, double *zi, uint64_t n)
+{
+    if (!orbit || !zr || !zi) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    const uint64_t entries = (uint64_t)orbit->o.length + 1u;
+    if (n < entries) return fail(nullptr, MBK_ERR_INVALID, "the output holds fewer than length + 1 entries");
+    for (uint64_t k = 0; k < entries; ++k) {
+        zr[k] = orbit->o.table[4 * k];
+        zi[k] = orbit->o.table[4 * k + 1];
+    }
+    return MBK_OK;
+}
+
+static const size_t kMaxDeepCopies = 8;
+
+// This ctx's device copy of `orbit`, uploaded on first use.  A copy is never overwritten, and none is freed while a launch
+// that reads it may still be queued: past kMaxDeepCopies copies the device is drained and all of them go (mbk.h).
+static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const double4 **out)
+{
+    for (const mbk_ctx::DeepCopy &c : ctx->deep)
+        if (c.id == orbit->o.id) {
+            *out = c.d;
+            return MBK_OK;
+        }
+    if (ctx->deep.size() >= kMaxDeepCopies) {
+        MBK_HIP(ctx, hipDeviceSynchronize());
+        for (mbk_ctx::DeepCopy &c : ctx->deep) (void)hipFree(c.d);
+        ctx->deep.clear();
+    }
+    const size_t bytes = orbit->o.table.size() * sizeof(double);
+    double4 *d = nullptr;
+    MBK_HIP(ctx, hipMalloc((void **)&d, bytes));
+    const hipError_t e = hipMemcpy(d, orbit->o.table.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(ctx, MBK_ERR_HIP, std::string("hipMemcpy (reference orbit): ") + hipGetErrorString(e));
+    }
+    ctx->deep.push_back({orbit->o.id, d});
+    *out = d;
+    return MBK_OK;
+}
+
+static int validate_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd, uint32_t flags)
+{
+    if (!orbit) return fail(ctx, MBK_ERR_INVALID, "orbit is NULL");
+    if (!v) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES))
+        return fail(ctx, MBK_ERR_INVALID, "deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
+    if (v->width == 0 || v->height == 0) return fail(ctx, MBK_ERR_INVALID, "empty view");
+    if (v->ncols == 0 || v->nrows == 0) return fail(ctx, MBK_ERR_INVALID, "empty window");
+    if ((uint64_t)v->col0 + v->ncols > v->width || (uint64_t)v->row0 + v->nrows > v->height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    if ((uint64_t)v->ncols * v->nrows > (1ull << 31)) return fail(ctx, MBK_ERR_INVALID, "window larger than 2^31 pixels");
+    for (double r : {v->range_r, v->range_i})
+        if (!std::isfinite(r) || !(r >= 0x1p-960) || !(r <= 4.0))
+            return fail(ctx, MBK_ERR_INVALID, "deep view ranges must be finite and lie in [2^-960, 4]");
+    if (mrd > orbit->o.mrd) return fail(ctx, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    return MBK_OK;
+}
+
+static double deep_step(double range, uint32_t n)
+{
+    if (n <= 1u) return 0.0;
+    volatile double s = range / (double)(n - 1u);
+    return s;
+}
+
+// the deep kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
+                       int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+{
+    const double4 *d_orbit = nullptr;
+    int rc = deep_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepArgs a;
+    std::memset(&a, 0, sizeof(a));
+    const std::vector<double> &t = orbit->o.table;
+    a.orbit = d_orbit;
+    a.z1 = make_double4(t[4], t[5], t[6], t[7]);
+    a.M = orbit->o.length;
+    a.half_r = (double)(v->width - 1u) * 0.5;
+    a.half_i = (double)(v->height - 1u) * 0.5;
+    a.step_r = deep_step(v->range_r, v->width);
+    a.step_i = deep_step(v->range_i, v->height);
+    a.col0 = v->col0;
+    a.row0 = v->row0;
+    a.ncols = v->ncols;
+    a.nrows = v->nrows;
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
+    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
+    a.counts = d_counts;
+    a.bytes = d_bytes;
+    a.smooth = d_smooth;
+    const uint32_t blocks = a.blocks_x * ((v->nrows + 7u) / 8u);
+    hipLaunchKernelGGL(mbk::deep_view_kernel, dim3(blocks), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                         int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_deep(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
+    if (wc && !d_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
+    if (wb && !d_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_deep(ctx, orbit, view, mrd, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
+                       (hipStream_t)hip_stream);
+}
+
+int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                          int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_deep(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    if (!wc && !wb && !h_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and h_smooth select no output");
+    if (wc && !h_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
+    if (wb && !h_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[0];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    const size_t px = (size_t)view->ncols * view->nrows;
+    rc = ensure_buffers(ctx, sl, px);
+    if (rc != MBK_OK) return rc;
+    if (h_smooth && px > ctx->smooth_cap_px) {
+        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
+        ctx->d_smooth = nullptr;
+        ctx->smooth_cap_px = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
+        ctx->smooth_cap_px = px;
+    }
+    // counts always go to the device: they feed the statistics
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+    rc = launch_deep(ctx, orbit, view, mrd, sl.d_counts, wb ? sl.d_bytes : nullptr, h_smooth ? ctx->d_smooth : nullptr, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+    rc = launch_reduce(ctx, sl, sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    if (wc) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+    if (wb) MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sl.d_bytes, px, hipMemcpyDeviceToHost, sl.stream));
+    if (h_smooth) MBK_HIP(ctx, hipMemcpyAsync(h_smooth, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    ctx->last_px = wb ? px : 0;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+        fill_stats_from_reduce(sl, stats, wb);
+    }
+    return MBK_OK;
+}
+
+int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                         uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
+    int rc = validate_deep(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    if (!wc && !wb) return fail(ctx, MBK_ERR_INVALID, "flags select no output");
+    if (wc && !h_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
+    if (wb && !h_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[slot];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
+    const size_t px = (size_t)view->ncols * view->nrows;
+    rc = ensure_buffers(ctx, sl, px);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+    rc = launch_deep(ctx, orbit, view, mrd, sl.d_counts, wb ? sl.d_bytes : nullptr, nullptr, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+    rc = launch_reduce(ctx, sl, sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    if (wc) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+    if (wb) MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sl.d_bytes, px, hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    sl.immediate = false;
+    sl.lazy_h_bytes = nullptr;
+    sl.busy = true;
+    sl.with_bytes = wb;
+    if (&sl == &ctx->s[0]) ctx->last_px = wb ? px : 0;
     return MBK_OK;
 }
 

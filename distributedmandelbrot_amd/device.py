@@ -7,8 +7,11 @@ the escape-time kernel (calc_mb_value, :39-68) and the uint8 quantiser (:96-98) 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from decimal import Decimal
+from fractions import Fraction
+from typing import Optional, Tuple, Union
 
 import numpy as np
 
@@ -36,6 +39,102 @@ class View:
     def centered(center_r: float, center_i: float, span: float, width: int, height: Optional[int] = None):
         height = width if height is None else height
         return View(center_r - span / 2, center_i - span / 2, span, span, width, height)
+
+
+@dataclass(frozen=True)
+class DeepView:
+    """A deep-zoom view (include/mbk.h, "Deep-zoom views"): width x height pixels centred on a DeepOrbit's centre, spans
+    span_r x span_i (end samples included).  span_i defaults to square pixels: span_r * (height-1) / (width-1)."""
+    span_r: float
+    width: int
+    height: Optional[int] = None
+    span_i: Optional[float] = None
+
+    def __post_init__(self):
+        h = self.width if self.height is None else int(self.height)
+        object.__setattr__(self, "height", h)
+        if self.span_i is None:
+            si = self.span_r if (self.width <= 1 or h <= 1 or h == self.width) else self.span_r * (h - 1) / (self.width - 1)
+            object.__setattr__(self, "span_i", float(si))
+
+
+def _decimal_string(x, precision_bits: int) -> str:
+    """An exact decimal for str / Decimal / int / float; for a Fraction with no finite decimal form, enough digits that
+    the truncation to precision_bits fraction bits is the same as that of the Fraction itself."""
+    if isinstance(x, str):
+        return x.strip()
+    if isinstance(x, bool):
+        raise TypeError("a centre coordinate must be str, Decimal, Fraction, int or float")
+    if isinstance(x, int):
+        return str(x)
+    if isinstance(x, float):
+        return str(Decimal(x))   # exact; nan / inf are refused by the library's parser
+    if isinstance(x, Decimal):
+        return str(x)
+    if isinstance(x, Fraction):
+        num, den = abs(x.numerator), x.denominator
+        d, a, b = den, 0, 0
+        while d % 2 == 0:
+            d, a = d // 2, a + 1
+        while d % 5 == 0:
+            d, b = d // 5, b + 1
+        # terminating: exact.  Otherwise the fraction part of x * 2^P is >= 1/den, so 10^-k < 2^-P / den keeps the floor.
+        k = max(a, b) if d == 1 else math.ceil(precision_bits * math.log10(2)) + len(str(den)) + 2
+        q = str(num * 10 ** k // den).rjust(k + 1, "0")
+        body = q[:-k] + "." + q[-k:] if k else q
+        return ("-" if x < 0 else "") + body
+    raise TypeError("a centre coordinate must be str, Decimal, Fraction, int or float")
+
+
+def default_precision_bits(min_span: Optional[float]) -> int:
+    """64 + ceil(-log2 min_span), rounded up to a multiple of 64 (min_span None: 2^-960, the deepest span a view takes)."""
+    span = 2.0 ** -960 if min_span is None else float(min_span)
+    if not (span > 0.0 and math.isfinite(span)):
+        raise ValueError("min_span must be finite and > 0")
+    bits = 64 + max(0, math.ceil(-math.log2(span)))
+    return min(4096, max(64, -(-bits // 64) * 64))
+
+
+class DeepOrbit:
+    """The reference orbit of a deep view's centre (mbk_deep_orbit_*): computed on the host in fixed point with
+    precision_bits fraction bits, up to mrd; needs no GPU.  Read-only; any MandelbrotDevice may use it."""
+
+    def __init__(self, center_r: Union[str, Decimal, Fraction, int, float], center_i: Union[str, Decimal, Fraction, int, float],
+                 mrd: int, *, min_span: Optional[float] = None, precision_bits: Optional[int] = None):
+        self._lib = L.load()
+        self._h = None
+        bits = int(precision_bits) if precision_bits is not None else default_precision_bits(min_span)
+        self.center = (_decimal_string(center_r, bits), _decimal_string(center_i, bits))
+        h = C.c_void_p()
+        st = self._lib.mbk_deep_orbit_create(self.center[0].encode(), self.center[1].encode(), bits, int(mrd), C.byref(h))
+        if st != L.MBK_OK:
+            raise MbkError(st, (self._lib.mbk_last_error(None) or b"").decode())
+        self._h = h
+        n, esc, p, m = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.mbk_deep_orbit_info(h, C.byref(n), C.byref(esc), C.byref(p), C.byref(m)))
+        self.length, self.escaped, self.precision_bits, self.mrd = int(n.value), bool(esc.value), int(p.value), int(m.value)
+
+    def _check(self, st: int) -> None:
+        if st != L.MBK_OK:
+            raise MbkError(st, (self._lib.mbk_last_error(None) or b"").decode())
+
+    def table(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(Zr, Zi): Z_0 .. Z_M as float64."""
+        zr = np.empty(self.length + 1, np.float64)
+        zi = np.empty(self.length + 1, np.float64)
+        self._check(self._lib.mbk_deep_orbit_read(self._h, zr.ctypes.data, zi.ctypes.data, zr.size))
+        return zr, zi
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.mbk_deep_orbit_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 @dataclass
@@ -296,6 +395,60 @@ class MandelbrotDevice:
                  | (L.MBK_WANT_BYTES if d_bytes else 0))
         self._check(self._lib.mbk_view_launch(self._h, C.byref(cv), mrd, flags,
                                               d_counts or None, d_bytes or None, stream or None))
+
+    # -- deep-zoom views (include/mbk.h, "Deep-zoom views") ------------------------------------
+    @staticmethod
+    def _cdeep(view: DeepView, window) -> L.mbk_deep_view:
+        col0, row0, ncols, nrows = window if window is not None else (0, 0, view.width, view.height)
+        return L.mbk_deep_view(view.span_r, view.span_i, view.width, view.height, col0, row0, ncols, nrows)
+
+    def compute_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_counts: bool = True,
+                          want_bytes: bool = True, want_smooth: bool = False, out_counts: Optional[np.ndarray] = None,
+                          out_bytes: Optional[np.ndarray] = None):
+        """Synchronous: (counts int32 | None, bytes uint8 | None, smooth float64 | None, TileStats), each [nrows, ncols]."""
+        cv = self._cdeep(view, window)
+        shape = (cv.nrows, cv.ncols)
+        flags = 0
+        counts = byts = smooth = None
+        if want_counts:
+            counts = out_counts if out_counts is not None else np.empty(shape, np.int32)
+            assert counts.dtype == np.int32 and counts.size == shape[0] * shape[1] and counts.flags.c_contiguous
+            flags |= L.MBK_WANT_COUNTS
+        if want_bytes:
+            byts = out_bytes if out_bytes is not None else np.empty(shape, np.uint8)
+            assert byts.dtype == np.uint8 and byts.size == shape[0] * shape[1] and byts.flags.c_contiguous
+            flags |= L.MBK_WANT_BYTES
+        if want_smooth:
+            smooth = np.empty(shape, np.float64)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_view_compute(
+            self._h, orbit._h, C.byref(cv), mrd, flags,
+            counts.ctypes.data if counts is not None else None, byts.ctypes.data if byts is not None else None,
+            smooth.ctypes.data if smooth is not None else None, C.byref(st)))
+        return counts, byts, smooth, _stats(st)
+
+    def submit_deep_view(self, slot: int, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None,
+                         out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None) -> None:
+        """Enqueue a deep view / window on `slot`; the host arrays are valid after wait(slot)."""
+        cv = self._cdeep(view, window)
+        n = cv.nrows * cv.ncols
+        flags = 0
+        for arr, dt, flag in ((out_counts, np.int32, L.MBK_WANT_COUNTS), (out_bytes, np.uint8, L.MBK_WANT_BYTES)):
+            if arr is not None:
+                assert arr.dtype == dt and arr.size == n and arr.flags.c_contiguous
+                flags |= flag
+        self._check(self._lib.mbk_deep_view_submit(
+            self._h, slot, orbit._h, C.byref(cv), mrd, flags,
+            out_counts.ctypes.data if out_counts is not None else None,
+            out_bytes.ctypes.data if out_bytes is not None else None))
+
+    def launch_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_counts: int = 0, d_bytes: int = 0,
+                         d_smooth: int = 0, stream: int = 0, window=None) -> None:
+        """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cdeep(view, window)
+        flags = (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0)
+        self._check(self._lib.mbk_deep_view_launch(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None,
+                                                   d_bytes or None, d_smooth or None, stream or None))
 
     def reduce_counts(self, d_counts: int, n: int, mrd: int, stream: int = 0) -> TileStats:
         st = L.mbk_stats()

@@ -140,9 +140,41 @@ def render_view(devices: Sequence, view, mrd: int, *, band_rows: int = 128, want
     `devices` are MandelbrotDevice-like objects: submit_view(slot, view, mrd, window=..., out_counts=...,
     out_bytes=..., kernel=...) + wait(slot), or -- simpler stand-ins -- just compute_view(...).
     Returns (counts | None, bytes | None, per-device stats)."""
-    bands = make_bands(view.height, band_rows)
+    def submit(dev, s, window, oc, ob):
+        dev.submit_view(s, view, mrd, window=window, out_counts=oc, out_bytes=ob, kernel=kernel)
+
+    def compute(dev, window, oc, ob):
+        return dev.compute_view(view, mrd, window=window, want_counts=want_counts, want_bytes=want_bytes, kernel=kernel,
+                                out_counts=oc, out_bytes=ob)[2]
+
+    return _render_bands(devices, view.width, view.height, band_rows, want_counts, want_bytes, out_counts, out_bytes,
+                         submit, compute, "submit_view")
+
+
+def render_deep_view(devices: Sequence, orbit, view, mrd: int, *, band_rows: int = 128, want_counts: bool = True,
+                     want_bytes: bool = True, out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None
+                     ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], List[dict]]:
+    """render_view for a deep-zoom view (device.DeepView) over one DeepOrbit: row bands from a shared queue, two in flight
+    per device (submit_deep_view / wait).  A band's offsets come from the whole view, so the image is bit-identical to
+    compute_deep_view's."""
+    def submit(dev, s, window, oc, ob):
+        dev.submit_deep_view(s, orbit, view, mrd, window=window, out_counts=oc, out_bytes=ob)
+
+    def compute(dev, window, oc, ob):
+        return dev.compute_deep_view(orbit, view, mrd, window=window, want_counts=want_counts, want_bytes=want_bytes,
+                                     out_counts=oc, out_bytes=ob)[3]
+
+    return _render_bands(devices, view.width, view.height, band_rows, want_counts, want_bytes, out_counts, out_bytes,
+                         submit, compute, "submit_deep_view")
+
+
+def _render_bands(devices, width, height, band_rows, want_counts, want_bytes, out_counts, out_bytes, submit, compute,
+                  submit_name):
+    """The feeder loop of render_view / render_deep_view: submit(dev, slot, window, out_counts, out_bytes) + dev.wait(slot)
+    on devices that have `submit_name`, compute(dev, window, out_counts, out_bytes) -> stats on the others."""
+    bands = make_bands(height, band_rows)
     queue = WorkQueue(bands)
-    shape = (view.height, view.width)
+    shape = (height, width)
     counts = byts = None
     if want_counts:
         counts = out_counts if out_counts is not None else np.empty(shape, np.int32)
@@ -164,15 +196,12 @@ def render_view(devices: Sequence, view, mrd: int, *, band_rows: int = 128, want
     def feeder(slot: int) -> None:
         dev = devices[slot]
         try:
-            if not hasattr(dev, "submit_view"):      # synchronous stand-in: still no temporary
+            if not hasattr(dev, submit_name):      # synchronous stand-in: still no temporary
                 while True:
                     band = queue.pop()
                     if band is None:
                         return
-                    _, _, st = dev.compute_view(view, mrd, window=(0, band.row0, view.width, band.nrows),
-                                                want_counts=want_counts, want_bytes=want_bytes, kernel=kernel,
-                                                out_counts=rows(counts, band), out_bytes=rows(byts, band))
-                    account(slot, st)
+                    account(slot, compute(dev, (0, band.row0, width, band.nrows), rows(counts, band), rows(byts, band)))
             busy = [False, False]
             s = 0
             while True:
@@ -180,8 +209,7 @@ def render_view(devices: Sequence, view, mrd: int, *, band_rows: int = 128, want
                 if band is not None:
                     if busy[s]:
                         account(slot, dev.wait(s))
-                    dev.submit_view(s, view, mrd, window=(0, band.row0, view.width, band.nrows),
-                                    out_counts=rows(counts, band), out_bytes=rows(byts, band), kernel=kernel)
+                    submit(dev, s, (0, band.row0, width, band.nrows), rows(counts, band), rows(byts, band))
                     busy[s] = True
                     s ^= 1
                 else:

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MBK_ABI_VERSION 4
+#define MBK_ABI_VERSION 5
 
 /* DataChunk.cs:20 (dataChunkRange), WorkerCUDA.py:80 (definition = 4096). */
 #define MBK_CHUNK_DEFINITION 4096u
@@ -229,6 +229,73 @@ int mbk_view_needs_literal_doubling(const mbk_view *view, uint32_t flags, int *l
  * `slot`, results land in h_counts / h_bytes (either may be NULL according to flags) after mbk_wait. */
 int mbk_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, uint32_t mrd, uint32_t flags,
                     int32_t *h_counts, uint8_t *h_bytes);
+
+/*
+ * Deep-zoom views (ABI 5; NOT in the reference): perturbation with rebasing.  A view's pixels above are np.linspace samples
+ * in binary64, which stop being distinct below a span of ~1e-13 around |c| ~ 1.  A deep view instead names its centre C as a
+ * decimal string, computes one reference orbit of C in fixed point on the host, and iterates every pixel's OFFSET from it in
+ * binary64 on the GPU.  DataChunk tiles, the worker protocol and the mbk_view_* calls are untouched (a tile's pixel step is
+ * >= 4 / (2^32 * 4095), ~1000 ulps at |c| ~ 1.5).
+ *
+ * Contract (bit-exact; tests/deep_model.py restates it in numpy, tests/test_gpu_deep.py holds the GPU to it):
+ *   reference orbit  C parsed from [+-]?digits[.digits]?([eE][+-]?digits)? as sign * floor(|C| 2^P) / 2^P (P fraction
+ *                    bits, 64 <= P <= 4096, a multiple of 64; |Cr|, |Ci| < 4).  Z_0 = 0, Z_{k+1} = Z_k^2 + C in fixed
+ *                    point, every product truncated toward zero to P bits; stop at the first M with |Z_M|^2 >= 4 (of the
+ *                    truncated squares), or at M = the orbit's mrd.  Z_0 .. Z_M are stored rounded to nearest binary64.
+ *   pixel offsets    column k of a view of width W and span R_r: dc_r = fl(fl(k - (W-1)/2) * s_r), s_r = fl(R_r / (W-1));
+ *                    dc_r = 0 for W = 1; rows likewise.  A window's offsets come from the full view, so a band is
+ *                    bit-identical to the same rows of the whole view.  Row 0 is the lowest imaginary part, as for mbk_view.
+ *   step             dz = dc, m = 1 (if M == 1: dz = fl(Z_1 + dc), m = 0).  For i = 1 .. mrd-1, every operation
+ *                    individually rounded, no contraction:
+ *                      ar = fl(2 Z_m.r + dz.r); ai = fl(2 Z_m.i + dz.i)
+ *                      dz = (fl(fl(fl(ar dz.r) - fl(ai dz.i)) + dc.r), fl(fl(fl(ar dz.i) + fl(ai dz.r)) + dc.i)); m = m + 1
+ *                      z = (fl(Z_m.r + dz.r), fl(Z_m.i + dz.i)); mag = fl(fl(z.r z.r) + fl(z.i z.i))
+ *                      mag >= 4: count = i, stop
+ *                      mag < fl(fl(dz.r dz.r) + fl(dz.i dz.i)) or m == M: dz = z, m = 0
+ *                    count 0 if the pixel never escapes -- calc_mb_value's convention (z starts at c, c is never tested),
+ *                    so bytes are the usual quantiser of the count and smooth = n + 1 - log2(0.5 ln mag) as for mbk_view.
+ * Limits: spans (range_r, range_i) in [2^-960, 4] (binary64 offsets stay normal); P <= 4096 (spans below 2^(64-P) resolve the
+ * centre more finely than the orbit does: Python's DeepOrbit picks P = 64 + ceil(-log2 min_span) by default); a launch's mrd
+ * <= the orbit's mrd.  Extended-exponent offsets (spans below 2^-960) and series approximation are not implemented.
+ *
+ * An orbit is read-only after mbk_deep_orbit_create and may be used by any number of ctxs on any threads (it needs no device
+ * and no ctx).  Each ctx uploads its own device copy on the orbit's first launch there, keyed by an id that is never
+ * reused: 32 bytes x (M + 1) per copy (Z and 2Z, which is exact).  A copy lives until mbk_destroy -- or until a ctx holds 8
+ * copies and needs a ninth: then the ctx synchronises the device (no launch that may read a copy is left) and frees all of
+ * them.  Destroying an orbit does not free its copies.  The first launch of an orbit on a ctx allocates and copies
+ * synchronously: launch once before capturing deep launches into a graph.
+ */
+typedef struct mbk_deep_orbit mbk_deep_orbit;
+
+/* A deep view: width x height pixels centred on the orbit's C, spans range_r x range_i (end samples included); the window
+ * (col0, row0, ncols, nrows) selects the pixels computed, laid out as for mbk_view. */
+typedef struct mbk_deep_view {
+    double range_r, range_i;
+    uint32_t width, height;
+    uint32_t col0, row0, ncols, nrows;
+} mbk_deep_view;
+
+/* The reference orbit of (center_r, center_i) at precision_bits fraction bits, up to mrd (>= 2).  Host only: no device, no
+ * ctx.  MBK_ERR_INVALID for a malformed string, |component| >= 4, precision_bits outside {64, 128, ..., 4096}, mrd < 2. */
+int mbk_deep_orbit_create(const char *center_r, const char *center_i, uint32_t precision_bits, uint32_t mrd,
+                          mbk_deep_orbit **out);
+void mbk_deep_orbit_destroy(mbk_deep_orbit *orbit);
+/* M, whether |Z_M|^2 >= 4 (else M = mrd), P, and the orbit's mrd; any output pointer may be NULL. */
+int mbk_deep_orbit_info(const mbk_deep_orbit *orbit, uint32_t *length, uint32_t *escaped, uint32_t *precision_bits,
+                        uint32_t *mrd);
+/* Z_0 .. Z_M as binary64 into zr[0..M], zi[0..M]; n is their capacity (MBK_ERR_INVALID below M + 1). */
+int mbk_deep_orbit_read(const mbk_deep_orbit *orbit, double *zr, double *zi, uint64_t n);
+/* The three forms of the view calls.  flags: MBK_WANT_COUNTS | MBK_WANT_BYTES only (kernel selection, MBK_PRECISION_F32 and
+ * MBK_LAZY_UNIFORM are MBK_ERR_INVALID), as are a NULL orbit, a view without output, ranges outside [2^-960, 4] and
+ * mrd > the orbit's mrd.  _launch: DEVICE pointers on the caller's stream (d_smooth may be NULL; no statistics).  _compute:
+ * synchronous into HOST buffers on slot 0 (h_smooth may be NULL), stats as for mbk_view_compute -- pixel_iterations counts
+ * the reference's iterations (count, or mrd - 1 for 0).  _submit: on `slot`, completed by mbk_wait. */
+int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                         int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream);
+int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                          int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats);
+int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                         uint32_t flags, int32_t *h_counts, uint8_t *h_bytes);
 
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
