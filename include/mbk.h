@@ -257,6 +257,8 @@ int mbk_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, uint32_t mrd, 
  * Limits: spans (range_r, range_i) in [2^-960, 4] (binary64 offsets stay normal); P <= 4096 (spans below 2^(64-P) resolve the
  * centre more finely than the orbit does: Python's DeepOrbit picks P = 64 + ceil(-log2 min_span) by default); a launch's mrd
  * <= the orbit's mrd.  Extended-exponent offsets (spans below 2^-960) and series approximation are not implemented.
+ * Centres within ~1e-16 of -2 render wrong below spans of ~1e-15: the real orbit stays just inside |z| = 2, the binary64 table
+ * holds 2.0, and every pixel retires at count 1 (tests/test_deep_truth.py, the strict xfail cases).
  *
  * An orbit is read-only after mbk_deep_orbit_create and may be used by any number of ctxs on any threads (it needs no device
  * and no ctx).  Each ctx uploads its own device copy on the orbit's first launch there, keyed by an id that is never

@@ -30,8 +30,9 @@ def offsets(view, window=None):
     return np.tile(dr, nrows), np.repeat(di, ncols)
 
 
-def model_counts(zr, zi, dcr, dci, mrd: int):
-    """(counts int32, |z|^2 at the escaping step float64) of the pixels with offsets (dcr, dci)."""
+def model_counts(zr, zi, dcr, dci, mrd: int, on_step=None):
+    """(counts int32, |z|^2 at the escaping step float64) of the pixels with offsets (dcr, dci).  on_step, if given, sees
+    the new offsets (dz.r, dz.i) of the live pixels after every step."""
     zr = np.asarray(zr, np.float64)
     zi = np.asarray(zi, np.float64)
     M = zr.size - 1
@@ -55,6 +56,8 @@ def model_counts(zr, zi, dcr, dci, mrd: int):
         ndr = (ar * dr - ai * di) + cr
         ndi = (ar * di + ai * dr) + ci
         m = m + 1
+        if on_step is not None:
+            on_step(ndr, ndi)
         xr = zr[m] + ndr
         xi = zi[m] + ndi
         mg = xr * xr + xi * xi

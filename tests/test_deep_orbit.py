@@ -40,11 +40,22 @@ def test_abi_5_and_the_deep_symbols_bind():
     assert m.DeepOrbit and m.DeepView and "DeepOrbit" in m.__all__ and "DeepView" in m.__all__
 
 
-@pytest.mark.parametrize("s", ["0", "-0", "+1", "1.5", "-3.99999999", "1e-3", "1.25E+0", "0.1e1", "00012e-4", "3.9e0",
-                               "1" + "0" * 60 + "e-60", "-0.000000000000000000000000000000000001", "2E-400", "7e-5000"])
+ACCEPTED = ["0", "-0", "+1", "1.5", "-3.99999999", "1e-3", "1.25E+0", "0.1e1", "00012e-4", "3.9e0",
+            "1" + "0" * 60 + "e-60", "-0.000000000000000000000000000000000001", "2E-400", "7e-5000"]
+
+
+@pytest.mark.parametrize("s", ACCEPTED)
 def test_parser_accepts_and_truncates_toward_zero(s):
+    _check_parsed(s, 128)
+
+
+@pytest.mark.parametrize("s", ACCEPTED)
+def test_parser_accepts_and_truncates_toward_zero_at_4096_bits(s):
+    _check_parsed(s, 4096)
+
+
+def _check_parsed(s, P):
     from distributedmandelbrot_amd import DeepOrbit
-    P = 128
     o = DeepOrbit(s, "0", 2, precision_bits=P)
     v = D.exact(s)
     x = (abs(v.numerator) << P) // v.denominator        # floor(|C| 2^P)
@@ -108,6 +119,46 @@ def test_escaping_centre_length_matches_the_restatement(c, P):
     assert (o.length, o.escaped) == (M, esc) and esc
     zr, zi = o.table()
     assert [(a, b) for a, b in zip(zr, zi)] == [(x / (1 << P), y / (1 << P)) for x, y in zs]
+
+
+@pytest.mark.parametrize("P", [64, 1024, 2048, 4096])
+def test_generic_centre_table_is_exact_at_p(P):
+    """Every entry of a 400-step orbit equals the restatement's fixed-point Z_k, correctly rounded to binary64."""
+    from distributedmandelbrot_amd import DeepOrbit
+    o = DeepOrbit(*SEAHORSE, 400, precision_bits=P)
+    zs, M, esc = D.fixed_orbit(*SEAHORSE, P, 400)
+    assert (o.length, o.escaped) == (M, esc) == (400, False)
+    zr, zi = o.table()
+    assert [(a, b) for a, b in zip(zr, zi)] == [(x / (1 << P), y / (1 << P)) for x, y in zs]
+
+
+def _pow2_decimal(num: int, k: int) -> str:
+    """num / 2^k as an exact decimal string."""
+    return "%de-%d" % (num * 5 ** k, k)
+
+
+@pytest.mark.parametrize("s, want", [
+    ("1e-320", None),
+    ("2.4703282292062327e-320", None),
+    (_pow2_decimal(1, 1075), 0.0),                                  # exactly half the least subnormal: ties to even, 0
+    (_pow2_decimal((1 << 3021) + 1, 4096), 2.0 ** -1074),           # 2^-1075 + 2^-4096: the sticky bit rounds up
+    (_pow2_decimal((1 << 53) - 1, 1075), 2.0 ** -1022),             # largest subnormal + half an ulp: up to the normal
+    (_pow2_decimal((1 << 53) - 3, 1075), (2 ** 52 - 2) * 2.0 ** -1074),   # a tie below it goes down to the even one
+    (_pow2_decimal(3, 1075), 2.0 ** -1073),                         # 1.5 ulp: ties to even, up
+], ids=["1e-320", "2.47e-320", "tie-2^-1075", "tie+sticky", "max-sub+half", "tie-down", "tie-up"])
+@pytest.mark.parametrize("sign", ["", "-"])
+def test_subnormal_rounding_at_4096_bits(s, want, sign):
+    """fx_to_double below 2^-1022 (reachable only with P > 1022): one rounding, to nearest on the subnormal grid, ties to
+    even, every dropped bit in the sticky; Python's int / int is the correctly rounded reference."""
+    from distributedmandelbrot_amd import DeepOrbit
+    P = 4096
+    zr, zi = DeepOrbit("0", sign + s, 2, precision_bits=P).table()
+    v = D.exact(s)
+    x = (v.numerator << P) // v.denominator
+    if want is not None:
+        assert x / (1 << P) == want
+    ref = (-x if sign else x) / (1 << P)                  # a negative value that rounds to zero is -0.0
+    assert zi[1] == ref and math.copysign(1.0, zi[1]) == math.copysign(1.0, ref)
 
 
 def test_python_centre_types_and_default_precision():
