@@ -121,7 +121,11 @@ __device__ __forceinline__ uint8_t quantise(int32_t count, const TileArgs &p)
 // BASELINE config 5 (NOT in the reference): continuous ("smooth") escape-time value at the
 // reference's own bailout, nu = n + 1 - log2(0.5 * ln |z_n|^2) for an escaped pixel (n = escape index,
 // |z_n|^2 = the value that tripped `>= 4`), 0 for a pixel that never escaped.  The integer information
-// is the exact count; only log/log2 are subject to libm-vs-ocml rounding (tests allow 1e-12).
+// is the exact count; only log/log2 are subject to libm-vs-ocml rounding.  m must reach log() as the binary64 value
+// that tripped the test: the tests hold nu to the correctly rounded value of the formula at that m within
+// 2.57 ulp(nu) + 3.38 * 2^-52 (glibc's libm: 1.57 and 1.38; include/mbk.h).  Measured on gfx950:
+// 1.570 ulp(nu) at n = 1, m = 11337031.25 and 1.379 * 2^-52 at n = 1, m = 75820.85571289062.
+// m == +inf (|z_1|^2 overflowed, |c| above ~1e77) gives -inf, never NaN.
 __device__ __forceinline__ double smooth_value(int32_t count, double m)
 {
     return count > 0 ? (double)count + 1.0 - log2(0.5 * log(m)) : 0.0;

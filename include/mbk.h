@@ -177,9 +177,20 @@ int mbk_datachunk(mbk_ctx *ctx, uint32_t level, uint32_t mrd, uint32_t index_rea
  * is the integer index quantised to a byte, WorkerCUDA.py:96-98); defined here as
  *     nu = n + 1 - log2(0.5 * ln |z_n|^2)   for a pixel that escapes at step n (|z_n|^2 >= 4 is the
  *                                            reference's own bailout value), and 0 if it never escapes,
- * in binary64.  n is the bit-exact count of the parity kernels (also returned); the logarithms are the
- * device's (tests allow 1e-12 against libm).  Asynchronous form on DEVICE pointers / caller's stream,
- * and synchronous form into HOST buffers.  d_counts / h_counts may be NULL.
+ * in binary64.  n is the bit-exact count of the parity kernels (also returned) and |z_n|^2 the binary64 value that
+ * tripped the test, every operation rounded on its own; the logarithms are the device's (ocml).  Against the
+ * correctly rounded value of the formula at that |z_n|^2 the tests allow A ulp(nu) + B 2^-52 with A = 2.57, B = 3.38:
+ * glibc's libm measures A0 = 1.57, B0 = 1.38 on the same cases (A where |nu| >= 1, B where |nu| < 1, both worst at
+ * n = 1 with |c| ~ 50), and the device gets one more ulp(nu) and two more 2^-52.  Measured on gfx950:
+ * A = 1.570 at n = 1, |z_1|^2 = 11337031.25 and B = 1.379 at n = 1, |z_1|^2 = 75820.85571289062, the same pixels and
+ * digits as glibc; over cfg5 at full size the worst sampled pixel is 1.195 ulp(nu) (n = 1, |z_1|^2 = 18.177277466062407).
+ * When |z_n|^2 overflows binary64 (possible at n = 1 only, for |c| above ~1e77) nu is -inf, the limit of the formula
+ * and what IEEE logarithms return; it is never NaN.  mrd 0 and 1 run no step: every count and nu is 0.
+ * Asynchronous form on DEVICE pointers / caller's stream (window-sized buffers, ncols * nrows elements, nothing is
+ * written outside them), and synchronous form into HOST buffers.  d_counts / h_counts may be NULL.  MBK_ERR_INVALID,
+ * with nothing written: NULL d_smooth / h_smooth, MBK_PRECISION_F32 in the flags of _launch_smooth (there is no
+ * binary32 form; _compute_smooth ignores every flag but the kernel), the kernels MBK_KERNEL_SIMPLE and
+ * MBK_KERNEL_REFILL, mrd >= 2^31, and whatever mbk_view_launch refuses in a view.
  */
 int mbk_view_launch_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
                            int32_t *d_counts, double *d_smooth, void *hip_stream);

@@ -253,9 +253,18 @@ void mbo_view_cycle_w(double start_r, double start_i, double range_r, double ran
 }
 
 /* BASELINE config 5 (NOT in the reference): continuous escape-time value at the reference's bailout.
- * Runs the reference loop, keeps |z|^2 of the escaping step, nu = n + 1 - log2(0.5 * ln |z_n|^2); 0 if the
- * pixel never escapes.  *count_out receives the integer escape index. */
-double mbo_escape_smooth(double cr, double ci, int32_t mrd, int32_t *count_out)
+ * mbo_smooth_value is the formula alone, nu = n + 1 - log2(0.5 * ln mag) with libm's logarithms, 0 for n == 0
+ * (the pixel never escaped).  mag == +inf (|z_n|^2 overflowed) gives -inf: log(inf) = inf, log2(inf) = inf. */
+double mbo_smooth_value(int32_t n, double mag)
+{
+    return n > 0 ? (double)n + 1.0 - log2(0.5 * log(mag)) : 0.0;
+}
+
+/* Runs the reference loop and keeps |z|^2 of the escaping step: the value that tripped `>= 4`, every operation
+ * rounded on its own.  *count_out receives the integer escape index, *mag_out that |z_n|^2 (0 if the pixel never
+ * escapes): the input of tests/smooth_truth.py, which evaluates the formula at high precision on exactly this
+ * double. */
+double mbo_escape_smooth_mag(double cr, double ci, int32_t mrd, int32_t *count_out, double *mag_out)
 {
     double zr = cr, zi = ci;
     for (int32_t n = 1; n < mrd; ++n) {
@@ -271,15 +280,24 @@ double mbo_escape_smooth(double cr, double ci, int32_t mrd, int32_t *count_out)
         double m = m0 + m1;
         if (m >= 4.0) {
             if (count_out) *count_out = n;
-            return (double)n + 1.0 - log2(0.5 * log(m));
+            if (mag_out) *mag_out = m;
+            return mbo_smooth_value(n, m);
         }
     }
     if (count_out) *count_out = 0;
+    if (mag_out) *mag_out = 0.0;
     return 0.0;
 }
 
-void mbo_view_smooth(double start_r, double start_i, double range_r, double range_i,
-                     uint32_t width, uint32_t height, int32_t mrd, double *smooth, int32_t *counts)
+double mbo_escape_smooth(double cr, double ci, int32_t mrd, int32_t *count_out)
+{
+    return mbo_escape_smooth_mag(cr, ci, mrd, count_out, NULL);
+}
+
+/* The window (col0, row0, ncols, nrows) of the view, outputs [nrows][ncols]; counts and mag may be NULL. */
+void mbo_view_smooth_window(double start_r, double start_i, double range_r, double range_i,
+                            uint32_t width, uint32_t height, uint32_t col0, uint32_t row0, uint32_t ncols,
+                            uint32_t nrows, int32_t mrd, double *smooth, int32_t *counts, double *mag)
 {
     double *xr = (double *)malloc(sizeof(double) * (width ? width : 1));
     double *xi = (double *)malloc(sizeof(double) * (height ? height : 1));
@@ -288,14 +306,23 @@ void mbo_view_smooth(double start_r, double start_i, double range_r, double rang
 #ifdef _OPENMP
 #pragma omp parallel for schedule(dynamic, 4)
 #endif
-    for (int64_t r = 0; r < (int64_t)height; ++r)
-        for (uint32_t c = 0; c < width; ++c) {
+    for (int64_t r = 0; r < (int64_t)nrows; ++r)
+        for (uint32_t c = 0; c < ncols; ++c) {
             int32_t cnt;
-            smooth[(size_t)r * width + c] = mbo_escape_smooth(xr[c], xi[r], mrd, &cnt);
-            if (counts) counts[(size_t)r * width + c] = cnt;
+            double m;
+            smooth[(size_t)r * ncols + c] = mbo_escape_smooth_mag(xr[col0 + c], xi[row0 + r], mrd, &cnt, &m);
+            if (counts) counts[(size_t)r * ncols + c] = cnt;
+            if (mag) mag[(size_t)r * ncols + c] = m;
         }
     free(xr);
     free(xi);
+}
+
+void mbo_view_smooth(double start_r, double start_i, double range_r, double range_i,
+                     uint32_t width, uint32_t height, int32_t mrd, double *smooth, int32_t *counts)
+{
+    mbo_view_smooth_window(start_r, start_i, range_r, range_i, width, height, 0, 0, width, height, mrd, smooth, counts,
+                           NULL);
 }
 
 /* WorkerCUDA.py:96-98: out = (out.astype(float64) * 256) / mrd; ceil(out).astype(uint8).

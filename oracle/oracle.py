@@ -56,6 +56,12 @@ class COracle:
         L.mbo_view_smooth.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
                                       C.c_int32, C.c_void_p, C.c_void_p]
         L.mbo_view_smooth.restype = None
+        L.mbo_view_smooth_window.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mbo_view_smooth_window.restype = None
+        L.mbo_smooth_value.argtypes = [C.c_int32, C.c_double]
+        L.mbo_smooth_value.restype = C.c_double
         L.mbo_datachunk.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_int]
         L.mbo_datachunk.restype = C.c_uint64
@@ -117,6 +123,22 @@ class COracle:
         self.lib.mbo_view_smooth(start_r, start_i, range_r, range_i, width, height, mrd,
                                  smooth.ctypes.data, counts.ctypes.data)
         return smooth, counts
+
+    def view_smooth_mag(self, start_r, start_i, range_r, range_i, width, height, mrd, *, window=None):
+        """(smooth float64, counts int32, mag float64), each [nrows, ncols] of the window (default: the whole view).
+        mag is |z_n|^2 of the escaping step, the double that tripped `>= 4` (0 where count is 0): what
+        tests/smooth_truth.py evaluates the formula on at high precision."""
+        col0, row0, ncols, nrows = window if window is not None else (0, 0, width, height)
+        smooth = np.empty((nrows, ncols), np.float64)
+        counts = np.empty((nrows, ncols), np.int32)
+        mag = np.empty((nrows, ncols), np.float64)
+        self.lib.mbo_view_smooth_window(start_r, start_i, range_r, range_i, width, height, col0, row0, ncols, nrows,
+                                        mrd, smooth.ctypes.data, counts.ctypes.data, mag.ctypes.data)
+        return smooth, counts, mag
+
+    def smooth_value(self, n: int, mag: float) -> float:
+        """The formula alone with libm's logarithms (mbo_smooth_value)."""
+        return float(self.lib.mbo_smooth_value(int(n), float(mag)))
 
     def view_contracted(self, start_r, start_i, range_r, range_i, width, height, mrd, *, nthreads=0):
         """Counts under default CUDA-style FMA contraction (see mbo_escape_contracted): a what-if, not the oracle."""

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import deep_model as D
+import smooth_truth as T
 from distributedmandelbrot_amd import DeepOrbit, DeepView, MbkError, View
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +24,19 @@ CASES = [
 ]
 
 
+def _smooth_against_truth(sm, mc, mag, what, sample=4000):
+    """The kernel's nu against the truth at (model count, model mag) -- the GPU's counts equal the model's, and so does
+    the mag it took its logarithms of unless nu shows otherwise -- within A ulp(nu) + B 2^-52 (tests/smooth_truth.py) on
+    every escaped pixel up to `sample`, a seeded sample beyond; and against numpy's evaluation on the whole array by the
+    sum of the two bounds."""
+    T.assert_pair(sm, D.smooth_from(mc, mag), mc, what)
+    esc = np.flatnonzero(mc.ravel() > 0)
+    if esc.size > sample:
+        esc = np.random.RandomState(4).choice(esc, sample, replace=False)
+    if esc.size:
+        T.assert_within(sm.ravel()[esc], mc.ravel()[esc], mag.ravel()[esc], what)
+
+
 def _model(orbit, view, mrd, window=None):
     zr, zi = orbit.table()
     dr, di = D.offsets(view, window)
@@ -40,9 +54,8 @@ def test_counts_bytes_smooth_equal_the_model(gpu, centre, span, size, mrd, disti
     assert np.array_equal(c, mc), int((c != mc).sum())
     assert len(np.unique(c)) >= distinct
     assert np.array_equal(b, gpu.quantise_counts(c, mrd))
-    msm = D.smooth_from(mc, mag)
     assert (sm[mc == 0] == 0.0).all()
-    assert np.allclose(sm, msm, rtol=0, atol=1e-12 * max(1, mrd)), float(np.abs(sm - msm).max())
+    _smooth_against_truth(sm, mc, mag, f"deep {centre[0][:8]} {span:g}")
     assert st.pixel_iterations == int(np.where(c > 0, c, mrd - 1).astype(np.int64).sum())
     assert st.never_pixels == int((c == 0).sum())
     if centre == ("1e-21", "1"):
@@ -161,9 +174,8 @@ def _check(gpu, orbit, view, mrd, window=None, smooth=True):
     assert np.array_equal(c, mc), (mrd, window, int((c != mc).sum()))
     assert np.array_equal(b, _bytes(mc, mrd)), (mrd, window)
     if smooth:
-        msm = D.smooth_from(mc, mag)
         assert (sm[mc == 0] == 0.0).all()
-        assert np.allclose(sm, msm, rtol=0, atol=1e-12 * max(1, mrd)), float(np.abs(sm - msm).max())
+        _smooth_against_truth(sm, mc, mag, f"deep mrd {mrd} window {window}")
     assert st.pixel_iterations == int(np.where(c > 0, c, mrd - 1).astype(np.int64).sum()), mrd
     assert st.never_pixels == int((c == 0).sum())
     return c
@@ -278,7 +290,6 @@ def test_smooth_on_a_window_and_through_launch(gpu):
     _check(gpu, orbit, view, mrd, window)
     _, _, sm, _ = gpu.compute_deep_view(orbit, view, mrd, want_smooth=True)
     mc, mag = _model(orbit, view, mrd)
-    msm = D.smooth_from(mc, mag)
     for with_counts in (False, True):
         dc = torch.full((60 * 90,), -5, dtype=torch.int32, device="cuda:0")
         ds = torch.full((60 * 90,), -1.0, dtype=torch.float64, device="cuda:0")
@@ -287,8 +298,21 @@ def test_smooth_on_a_window_and_through_launch(gpu):
         torch.cuda.synchronize()
         got = ds.cpu().numpy().reshape(60, 90)
         assert np.array_equal(got, sm)          # the same kernel, bit for bit
-        assert np.allclose(got, msm, rtol=0, atol=1e-12 * mrd)
+        _smooth_against_truth(got, mc, mag, f"deep launch counts={with_counts}")
         assert np.array_equal(dc.cpu().numpy().reshape(60, 90), mc if with_counts else np.full_like(mc, -5))
+
+
+@pytest.mark.parametrize("case", T.DEEP_CASES[7:], ids=["span-2^-960", "span-4", "M-1"])
+def test_smooth_at_the_deepest_and_widest_span_and_on_a_one_step_orbit(gpu, case):
+    """nu against the truth at span 2^-960 (|dz|^2 subnormal for most of the run), at span 4, and on the M == 1 orbit of
+    centre -2, where the escaping |z|^2 comes from a state that was rebased every step."""
+    orbit, view, mrd, window, mc, mag = T.deep_model_case(case)
+    c, _, sm, _ = gpu.compute_deep_view(orbit, view, mrd, window=window, want_bytes=False, want_smooth=True)
+    assert np.array_equal(c, mc)
+    assert (sm[mc == 0] == 0.0).all() and (mc > 0).sum() >= 400 and len(np.unique(mc)) >= 8
+    _smooth_against_truth(sm, mc, mag, f"deep {case[0][0]} span {case[1]:g}")
+    if case[0] == ("-2", "0"):
+        assert orbit.length == 1 and orbit.escaped
 
 
 def _cusp_orbit(k, mrd):
