@@ -9,10 +9,12 @@ _lib.py          ctypes binding of the C ABI (fails loudly when the library or a
 device.py        MandelbrotDevice: one GPU context; views, DataChunk tiles, async launches
 worker.py        the reference worker's interface (process_workload / do_workload_single / main)
                  speaking the unchanged Distributer TCP protocol, plus a per-GPU work-queue farm
+image.py         Palette (for MandelbrotDevice.render_view / render_deep_view) and a standard-library PNG writer
 sharding.py      row-band work items and the per-GPU queue used to shard one view over N GPUs
 
 There is no CPU fallback anywhere in this package.
 """
 from .device import DeepOrbit, DeepView, MandelbrotDevice, MbkError, TileStats, View, device_count  # noqa: F401
+from .image import Palette, write_png  # noqa: F401
 
-__all__ = ["DeepOrbit", "DeepView", "MandelbrotDevice", "MbkError", "TileStats", "View", "device_count"]
+__all__ = ["DeepOrbit", "DeepView", "MandelbrotDevice", "MbkError", "Palette", "TileStats", "View", "device_count", "write_png"]

@@ -42,6 +42,11 @@ MBK_CODEC_RLE = 0x01
 MBK_CHUNK_DEFINITION = 4096
 MBK_CHUNK_BYTES = 4096 * 4096
 MBK_ABI_VERSION = 5
+MBK_RENDER_BYTES = 0
+MBK_RENDER_SMOOTH = 1
+RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH}
+RENDER_SUPERSAMPLES = (1, 2, 3, 4, 8)
+MBK_RENDER_BAND_BYTES = 256 << 20
 
 
 class mbk_view(C.Structure):
@@ -57,6 +62,12 @@ class mbk_deep_view(C.Structure):
                 ("width", C.c_uint32), ("height", C.c_uint32),
                 ("col0", C.c_uint32), ("row0", C.c_uint32),
                 ("ncols", C.c_uint32), ("nrows", C.c_uint32)]
+
+
+class mbk_render_spec(C.Structure):
+    _fields_ = [("source", C.c_uint32), ("supersample", C.c_uint32), ("palette", C.c_void_p),
+                ("palette_len", C.c_uint32), ("inside", C.c_uint8 * 4),
+                ("scale", C.c_double), ("offset", C.c_double), ("max_band_rows", C.c_uint32)]
 
 
 class mbk_stats(C.Structure):
@@ -154,6 +165,17 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_deep_view_submit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                        C.c_void_p, C.c_void_p]),
+    "mbk_view_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                         C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_view_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                          C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_view_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                              C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                               C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_palette_viewer": (C.c_int, [C.c_void_p]),
+    "mbk_render_resolve_host": (C.c_int, [C.POINTER(mbk_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -26,6 +26,7 @@
 #include "mbk_feeder.h"
 #include "mbk_deep_orbit.h"
 #include "mbk_deep.h"
+#include "mbk_render.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -83,6 +84,11 @@ struct StreamScratch {
     double xcd_f[8] = {0.125, 0.125, 0.125, 0.125, 0.125, 0.125, 0.125, 0.125};
     uint32_t xcd_issued = 0, xcd_consumed = 0;
     struct SharesUsed { uint32_t seq, switches; float f[8]; } xcd_ring[64] = {};   // switches: the ctx' stream_switches at the launch
+    // renders (mbk_render.h): the samples of one band, at most MBK_RENDER_BAND_BYTES, and the palette of the last render
+    void *d_render = nullptr;
+    size_t render_cap = 0;            // bytes
+    uint32_t *d_palette = nullptr;    // 65536 entries
+    std::vector<uint32_t> palette;    // what d_palette holds
 };
 static const size_t kMaxStreamScratch = 64;
 static const uint32_t kStampSlots = 16, kShareRing = 64;
@@ -112,6 +118,8 @@ struct mbk_ctx {
     size_t last_px = 0;              // pixels of the last tile computed with bytes (for mbk_serialize_last)
     double *d_smooth = nullptr;      // smooth-colouring output of the synchronous API
     size_t smooth_cap_px = 0;
+    uint32_t *d_rgba = nullptr;      // the image of the synchronous renders (mbk_*_render_compute)
+    size_t rgba_cap_px = 0;
     uint8_t *d_rle = nullptr;        // RLE scratch: block counts | run starts | run values | output stream
     size_t rle_cap_px = 0;
     uint32_t opt[MBK_OPT_COUNT_];    // tuning options (mbk_set_option); every value is bit-exact
@@ -313,6 +321,8 @@ static void free_scratch(StreamScratch &sc)
     if (sc.h_stamps) (void)hipHostFree(sc.h_stamps);
     if (sc.d_red) (void)hipFree(sc.d_red);
     if (sc.h_red) (void)hipHostFree(sc.h_red);
+    if (sc.d_render) (void)hipFree(sc.d_render);
+    if (sc.d_palette) (void)hipFree(sc.d_palette);
     sc = StreamScratch();
 }
 
@@ -1380,6 +1390,7 @@ void mbk_destroy(mbk_ctx *ctx)
     for (mbk_ctx::DeepCopy &c : ctx->deep) (void)hipFree(c.d);
     if (ctx->d_rle) (void)hipFree(ctx->d_rle);
     if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
+    if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
     delete ctx;
 }
 
@@ -2169,6 +2180,350 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
     sl.busy = true;
     sl.with_bytes = wb;
     if (&sl == &ctx->s[0]) ctx->last_px = wb ? px : 0;
+    return MBK_OK;
+}
+
+// ---- rendering (mbk_render.h; mbk.h "Rendering") -----------------------------------------------------------
+
+static int validate_render_spec(mbk_ctx *ctx, const mbk_render_spec *spec)
+{
+    if (!spec) return fail(ctx, MBK_ERR_INVALID, "render spec is NULL");
+    if (!spec->palette) return fail(ctx, MBK_ERR_INVALID, "palette is NULL");
+    const uint32_t s = spec->supersample;
+    if (s != 1u && s != 2u && s != 3u && s != 4u && s != 8u) return fail(ctx, MBK_ERR_INVALID, "supersample must be 1, 2, 3, 4 or 8");
+    if (spec->source == MBK_RENDER_BYTES) {
+        if (spec->palette_len != 256u) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_BYTES takes a palette of 256 entries");
+    } else if (spec->source == MBK_RENDER_SMOOTH) {
+        if (spec->palette_len < 2u || spec->palette_len > 65536u)
+            return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_SMOOTH takes a palette of 2 .. 65536 entries");
+        if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^20]");
+        if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
+    } else {
+        return fail(ctx, MBK_ERR_INVALID, "unknown MBK_RENDER_* source");
+    }
+    return MBK_OK;
+}
+
+static uint32_t pack_rgba(const uint8_t *c)
+{
+    return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24);
+}
+
+static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint32_t *entries)
+{
+    mbk::RenderPalette p;
+    p.entries = entries;
+    p.n = spec->palette_len;
+    p.n_rcp = 1.0 / (double)spec->palette_len;
+    p.inside = pack_rgba(spec->inside);
+    p.scale = spec->scale;
+    p.offset = spec->offset;
+    return p;
+}
+
+// What a render renders: a view (deep == nullptr) or a deep view on its orbit.
+struct RenderTarget {
+    const mbk_view *view;
+    const mbk_deep_orbit *orbit;
+    const mbk_deep_view *deep;
+    uint32_t width, height, col0, row0, ncols, nrows;   // of the OUTPUT
+};
+
+// The sample view / window of the output window (col0, row0, ncols, nrows) of `t`
+static void sample_window(const RenderTarget &t, uint32_t s, uint32_t col0, uint32_t row0, uint32_t ncols, uint32_t nrows,
+                          mbk_view *v, mbk_deep_view *d)
+{
+    if (t.deep) {
+        *d = *t.deep;
+        d->width = t.width * s;
+        d->height = t.height * s;
+        d->col0 = col0 * s;
+        d->row0 = row0 * s;
+        d->ncols = ncols * s;
+        d->nrows = nrows * s;
+    } else {
+        *v = *t.view;
+        v->width = t.width * s;
+        v->height = t.height * s;
+        v->col0 = col0 * s;
+        v->row0 = row0 * s;
+        v->ncols = ncols * s;
+        v->nrows = nrows * s;
+    }
+}
+
+// Everything a render can refuse, before anything is allocated, enqueued or written.
+static int render_check(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit *orbit, const mbk_deep_view *deep, bool is_deep,
+                        uint32_t mrd, uint32_t flags, const mbk_render_spec *spec, const void *out, RenderTarget *t)
+{
+    int rc = validate_render_spec(ctx, spec);
+    if (rc != MBK_OK) return rc;
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (is_deep ? !deep : !view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    t->view = is_deep ? nullptr : view;
+    t->orbit = orbit;
+    t->deep = is_deep ? deep : nullptr;
+    t->width = is_deep ? deep->width : view->width;
+    t->height = is_deep ? deep->height : view->height;
+    t->col0 = is_deep ? deep->col0 : view->col0;
+    t->row0 = is_deep ? deep->row0 : view->row0;
+    t->ncols = is_deep ? deep->ncols : view->ncols;
+    t->nrows = is_deep ? deep->nrows : view->nrows;
+    const uint32_t s = spec->supersample;
+    if ((uint64_t)t->width * s > 0xffffffffull || (uint64_t)t->height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t->col0 + t->ncols > t->width || (uint64_t)t->row0 + t->nrows > t->height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH;
+    mbk_view sv;
+    mbk_deep_view sd;
+    sample_window(*t, s, t->col0, t->row0, t->ncols, t->nrows, &sv, &sd);
+    if (is_deep) {
+        if (flags) return fail(ctx, MBK_ERR_INVALID, "deep renders take no flags (no kernel selection, no fp32)");
+        return validate_deep(ctx, orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
+    }
+    if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
+        return fail(ctx, MBK_ERR_INVALID, "render flags carry kernel selection (and MBK_PRECISION_F32) only");
+    const bool f32 = (flags & MBK_PRECISION_F32) != 0;
+    bool dummy;
+    rc = validate_view(ctx, &sv, &dummy, f32);
+    if (rc != MBK_OK) return rc;
+    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (!smooth && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
+    if ((smooth || f32) && (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL))
+        return fail(ctx, MBK_ERR_INVALID, "smooth colouring and MBK_PRECISION_F32 are implemented by the scan / asm / group kernels only");
+    if (smooth && f32) return fail(ctx, MBK_ERR_INVALID, "smooth colouring is implemented in binary64 only");
+    return MBK_OK;
+}
+
+static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+
+// A checked render (render_check) onto the device image d_out (ncols x nrows words), on `stream`.  stat: the slot whose
+// reduction scratch adds up the statistics of the samples and whose ev_k1 marks the last resolve kernel (_compute), or NULL.
+static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                      uint32_t *d_out, hipStream_t stream, Slot *stat)
+{
+    const uint32_t s = spec->supersample;
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH;
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+
+    // the palette: uploaded when it differs from what this stream's device copy holds, after the launches that read that
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    if (!sc->d_palette) MBK_HIP(ctx, hipMalloc((void **)&sc->d_palette, 65536u * sizeof(uint32_t)));
+    if (words != sc->palette) {
+        MBK_HIP(ctx, hipStreamSynchronize(stream));
+        sc->palette.clear();
+        MBK_HIP(ctx, hipMemcpy(sc->d_palette, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        sc->palette = words;
+    }
+
+    // bands: rows of the output window whose samples fit the budget, and pieces of columns if one row's do not
+    const uint64_t per_px = (uint64_t)s * s * (smooth ? 12u : (stat ? 5u : 1u));
+    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;   // (the parts of the scratch start on 256-byte lines)
+    uint32_t tile_cols = t.ncols, band_rows;
+    if ((uint64_t)t.ncols * per_px <= budget) {
+        band_rows = (uint32_t)std::min<uint64_t>(t.nrows, budget / ((uint64_t)t.ncols * per_px));
+    } else {
+        band_rows = 1u;
+        tile_cols = (uint32_t)(budget / per_px);
+    }
+    if (spec->max_band_rows) band_rows = std::min(band_rows, spec->max_band_rows);
+    const size_t cap_samples = (size_t)tile_cols * s * band_rows * s;
+    // layout: SMOOTH nu | counts; BYTES counts (statistics only) | bytes
+    const size_t off2 = smooth ? round_up_256(cap_samples * 8u) : (stat ? round_up_256(cap_samples * 4u) : 0u);
+    const size_t need = off2 + (smooth ? cap_samples * 4u : cap_samples);
+    if (need > sc->render_cap) {
+        if (sc->d_render) (void)hipFree(sc->d_render);   // (hipFree waits for the launches that may still read it)
+        sc->d_render = nullptr;
+        sc->render_cap = 0;
+        MBK_HIP(ctx, hipMalloc(&sc->d_render, need));
+        sc->render_cap = need;
+    }
+    uint8_t *base = (uint8_t *)sc->d_render;
+    double *d_nu = smooth ? (double *)base : nullptr;
+    int32_t *d_counts = smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr);
+    uint8_t *d_bytes = smooth ? nullptr : base + off2;
+    const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
+
+    const size_t lds = (size_t)spec->palette_len * sizeof(uint32_t);
+    const bool use_lds = spec->palette_len <= mbk::kRenderLdsEntries && lds <= ctx->prop.sharedMemPerBlock;
+    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
+    const uint32_t wg_per_cu = use_lds ? (uint32_t)std::min<size_t>(8u, std::max<size_t>(1u, (160u << 10) / lds)) : 8u;
+
+    for (uint32_t r = 0; r < t.nrows; r += band_rows) {
+        const uint32_t nr = std::min(band_rows, t.nrows - r);
+        for (uint32_t c = 0; c < t.ncols; c += tile_cols) {
+            const uint32_t nc = std::min(tile_cols, t.ncols - c);
+            mbk_view sv;
+            mbk_deep_view sd;
+            sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
+            if (t.deep)
+                rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream);
+            else
+                rc = launch_tile(ctx, &sv, mrd, flags | (d_counts ? MBK_WANT_COUNTS : 0u) | (d_bytes ? MBK_WANT_BYTES : 0u),
+                                 d_counts, d_bytes, stream, d_nu);
+            if (rc != MBK_OK) return rc;
+            mbk::RenderArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.counts = d_counts;
+            a.smooth = d_nu;
+            a.bytes = d_bytes;
+            a.out = d_out + (size_t)r * t.ncols + c;
+            a.pitch = (uint64_t)nc * s;
+            a.out_pitch = t.ncols;
+            a.ncols = nc;
+            a.nrows = nr;
+            const uint32_t px_per_wg = mbk::kRenderThreads * (smooth ? 1u : mbk::kRenderBytesPx);
+            a.chunks_x = (nc + px_per_wg - 1u) / px_per_wg;
+            a.lds_palette = use_lds ? 1u : 0u;
+            a.pal = render_palette(spec, d_palette);
+            const uint64_t pieces = (uint64_t)a.chunks_x * nr;
+            const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
+            if (smooth)
+                mbk::launch_resolve<true>(s, grid, use_lds ? lds : 0u, stream, a);
+            else
+                mbk::launch_resolve<false>(s, grid, use_lds ? lds : 0u, stream, a);
+            MBK_HIP(ctx, hipGetLastError());
+            if (stat) {
+                if (r + nr == t.nrows && c + nc == t.ncols) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
+                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, (uint64_t)nc * s * nr * s, mrd, stream, false);
+                if (rc != MBK_OK) return rc;
+            }
+        }
+    }
+    return MBK_OK;
+}
+
+static int render_launch(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit *orbit, const mbk_deep_view *deep, bool is_deep,
+                         uint32_t mrd, uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    RenderTarget t;
+    int rc = render_check(ctx, view, orbit, deep, is_deep, mrd, flags, spec, d_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+}
+
+static int render_compute(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit *orbit, const mbk_deep_view *deep, bool is_deep,
+                          uint32_t mrd, uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    RenderTarget t;
+    int rc = render_check(ctx, view, orbit, deep, is_deep, mrd, flags, spec, h_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[0];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    const size_t px = (size_t)t.ncols * t.nrows;
+    if (px > ctx->rgba_cap_px) {
+        if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
+        ctx->d_rgba = nullptr;
+        ctx->rgba_cap_px = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_rgba, px * sizeof(uint32_t)));
+        ctx->rgba_cap_px = px;
+    }
+    MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+    rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl);
+    if (rc != MBK_OK) {
+        (void)hipStreamSynchronize(sl.stream);   // nothing of a failed render stays queued on the slot
+        return rc;
+    }
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+        fill_stats_from_reduce(sl, stats, false);
+    }
+    return MBK_OK;
+}
+
+int mbk_view_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                           uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, view, nullptr, nullptr, false, mrd, flags, spec, d_rgba, hip_stream);
+}
+
+int mbk_view_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                            uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, view, nullptr, nullptr, false, mrd, flags, spec, h_rgba, stats);
+}
+
+int mbk_deep_view_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, nullptr, orbit, view, true, mrd, flags, spec, d_rgba, hip_stream);
+}
+
+int mbk_deep_view_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, nullptr, orbit, view, true, mrd, flags, spec, h_rgba, stats);
+}
+
+// jet as matplotlib defines it (a public piecewise-linear colour map; the reference's Viewer looks colours up in its 256-entry
+// table): entry i of the table of a channel with knots (x, y), built the way LinearSegmentedColormap builds it -- positions
+// 255 fl(i fl(1 / 255)), the first knot at or beyond one, and a linear step between that knot and the one before, every
+// operation rounded on its own.
+struct JetKnot { double x, y; };
+static double jet_entry(const JetKnot *k, int m, int i)
+{
+    if (i == 0) return k[0].y;
+    if (i == 255) return k[m - 1].y;
+    const double step = 1.0 / 255.0;
+    const double xi = 255.0 * ((double)i * step);
+    int j = 1;
+    while (j < m - 1 && k[j].x * 255.0 < xi) ++j;
+    const double xa = k[j - 1].x * 255.0, xb = k[j].x * 255.0;
+    const double d = (xi - xa) / (xb - xa);
+    const double v = d * (k[j].y - k[j - 1].y) + k[j - 1].y;
+    return v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+}
+
+int mbk_palette_viewer(uint8_t out[1024])
+{
+    if (!out) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    static const JetKnot red[] = {{0.0, 0.0}, {0.35, 0.0}, {0.66, 1.0}, {0.89, 1.0}, {1.0, 0.5}};
+    static const JetKnot green[] = {{0.0, 0.0}, {0.125, 0.0}, {0.375, 1.0}, {0.64, 1.0}, {0.91, 0.0}, {1.0, 0.0}};
+    static const JetKnot blue[] = {{0.0, 0.5}, {0.11, 1.0}, {0.34, 1.0}, {0.65, 0.0}, {1.0, 0.0}};
+    // Viewer.py:110-135: v = 1 - b / 256 (exact), black where v == 1, else jet(v), whose table index is
+    // min(int(256 v), 255) = 256 - b for b >= 1
+    out[0] = out[1] = out[2] = 0u;
+    out[3] = 255u;
+    for (int b = 1; b < 256; ++b) {
+        const int i = 256 - b;
+        const double ch[4] = {jet_entry(red, 5, i), jet_entry(green, 6, i), jet_entry(blue, 5, i), 1.0};
+        for (int c = 0; c < 4; ++c) out[4 * b + c] = (uint8_t)std::floor(255.0 * ch[c] + 0.5);
+    }
+    return MBK_OK;
+}
+
+int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                            const uint8_t *bytes, const double *smooth, uint8_t *rgba)
+{
+    int rc = validate_render_spec(nullptr, spec);
+    if (rc != MBK_OK) return rc;
+    if (!rgba) return fail(nullptr, MBK_ERR_INVALID, "output pointer is NULL");
+    const uint32_t s = spec->supersample;
+    if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
+        return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
+    const bool sm = spec->source == MBK_RENDER_SMOOTH;
+    if (sm ? (!counts || !smooth) : !bytes) return fail(nullptr, MBK_ERR_INVALID, "the source's sample arrays are NULL");
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    mbk::render_resolve_host(render_palette(spec, words.data()), sm, s, width, height, counts, bytes, smooth, rgba);
     return MBK_OK;
 }
 

@@ -450,6 +450,57 @@ class MandelbrotDevice:
         self._check(self._lib.mbk_deep_view_launch(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None,
                                                    d_bytes or None, d_smooth or None, stream or None))
 
+    # -- rendering (include/mbk.h, "Rendering") ---------------------------------------------------
+    def _render_out(self, cv, out):
+        shape = (cv.nrows, cv.ncols, 4)
+        if out is None:
+            return np.empty(shape, np.uint8)
+        assert out.dtype == np.uint8 and out.size == shape[0] * shape[1] * 4 and out.flags.c_contiguous
+        return out.reshape(shape)
+
+    def render_view(self, view: View, mrd: int, *, palette, source: str = "smooth", supersample: int = 1, window=None,
+                    kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+        """The view as an RGBA8 image, coloured and anti-aliased on the GPU: (width * s) x (height * s) samples of the
+        same rectangle, each through `palette` (image.Palette; source "smooth": nu, "bytes": the quantised byte), s x s
+        of them averaged per pixel.  Only the image crosses PCIe.  `window` is in output pixels; `out` may be a
+        (pinned) uint8 array of the window's size.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples);
+        row 0 is the lowest imaginary part."""
+        cv = self._cview(view, window)
+        rgba = self._render_out(cv, out)
+        spec = palette.spec(source, supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                      rgba.ctypes.data, C.byref(st)))
+        return rgba, _stats(st)
+
+    def render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, source: str = "smooth",
+                         supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+        """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height."""
+        cv = self._cdeep(view, window)
+        rgba = self._render_out(cv, out)
+        spec = palette.spec(source, supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_view_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                           rgba.ctypes.data, C.byref(st)))
+        return rgba, _stats(st)
+
+    def launch_render_view(self, view: View, mrd: int, *, palette, d_rgba: int, source: str = "smooth", supersample: int = 1,
+                           stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0) -> None:
+        """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes (e.g. a torch tensor's data_ptr()) on
+        ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        spec = palette.spec(source, supersample, max_band_rows)
+        self._check(self._lib.mbk_view_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                     d_rgba or None, stream or None))
+
+    def launch_render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, d_rgba: int,
+                                source: str = "smooth", supersample: int = 1, stream: int = 0, window=None,
+                                max_band_rows: int = 0) -> None:
+        cv = self._cdeep(view, window)
+        spec = palette.spec(source, supersample, max_band_rows)
+        self._check(self._lib.mbk_deep_view_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                          d_rgba or None, stream or None))
+
     def reduce_counts(self, d_counts: int, n: int, mrd: int, stream: int = 0) -> TileStats:
         st = L.mbk_stats()
         self._check(self._lib.mbk_reduce_counts(self._h, d_counts, n, mrd, stream or None, C.byref(st)))

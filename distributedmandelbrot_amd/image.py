@@ -1,0 +1,115 @@
+"""Palettes for MandelbrotDevice.render_view / render_deep_view (include/mbk.h, "Rendering") and a PNG writer.
+
+Nothing here needs a GPU, and no imaging library is imported: the PNG writer is zlib + struct.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import struct
+import zlib
+from dataclasses import dataclass
+from typing import Tuple
+
+import numpy as np
+
+from . import _lib as L
+
+
+@dataclass(frozen=True)
+class Palette:
+    """n RGBA8 entries plus, for source "smooth", the colour of never-escaping samples and the map from the smooth value
+    nu to a palette position, t = nu * scale + offset (entries are blended linearly and the palette is cyclic).
+    Source "bytes" takes 256 entries, indexed by the quantised byte; `inside`, `scale` and `offset` are not used there."""
+    entries: np.ndarray
+    inside: Tuple[int, int, int, int] = (0, 0, 0, 255)
+    scale: float = 1.0
+    offset: float = 0.0
+
+    def __post_init__(self):
+        e = np.ascontiguousarray(self.entries, dtype=np.uint8)
+        if e.ndim != 2 or e.shape[1] != 4:
+            raise ValueError("a palette is an (n, 4) uint8 array of RGBA entries")
+        object.__setattr__(self, "entries", e)
+        object.__setattr__(self, "inside", tuple(int(v) for v in self.inside))
+
+    def __len__(self) -> int:
+        return int(self.entries.shape[0])
+
+    @staticmethod
+    def viewer() -> "Palette":
+        """The reference Viewer's colouring of a chunk's bytes (DistributedMandelbrotViewer.py:110-135): black for byte 0,
+        jet(1 - b / 256) otherwise -- mbk_palette_viewer."""
+        out = np.empty((256, 4), np.uint8)
+        st = L.load().mbk_palette_viewer(out.ctypes.data)
+        if st != L.MBK_OK:
+            raise RuntimeError(f"mbk_palette_viewer failed with status {st}")
+        return Palette(out)
+
+    @staticmethod
+    def cosine(n: int = 1024, *, phase=(0.0, 0.33, 0.67), period: float = 32.0, inside=(0, 0, 0, 255)) -> "Palette":
+        """A cyclic palette of n entries, channel c = 0.5 - 0.5 cos(2 pi (k / n + phase[c])); one turn of the palette spans
+        `period` units of nu."""
+        k = np.arange(n, dtype=np.float64)[:, None] / n
+        rgb = 0.5 - 0.5 * np.cos(2.0 * np.pi * (k + np.asarray(phase, np.float64)[None, :]))
+        e = np.empty((n, 4), np.uint8)
+        e[:, :3] = np.floor(255.0 * rgb + 0.5).astype(np.uint8)
+        e[:, 3] = 255
+        return Palette(e, inside=inside, scale=n / float(period))
+
+    @staticmethod
+    def gradient(stops, n: int = 1024, *, period: float = 32.0, inside=(0, 0, 0, 255)) -> "Palette":
+        """A cyclic palette of n entries that runs linearly through the RGB `stops` and back to the first one."""
+        s = np.asarray(list(stops) + [stops[0]], np.float64)
+        x = np.arange(n, dtype=np.float64) * (len(s) - 1) / n
+        e = np.empty((n, 4), np.uint8)
+        for c in range(3):
+            e[:, c] = np.floor(np.interp(x, np.arange(len(s)), s[:, c]) + 0.5).astype(np.uint8)
+        e[:, 3] = 255
+        return Palette(e, inside=inside, scale=n / float(period))
+
+    def spec(self, source: str, supersample: int, max_band_rows: int = 0) -> L.mbk_render_spec:
+        """The C struct; it points into self.entries, which the caller keeps alive for the call."""
+        return L.mbk_render_spec(L.RENDER_SOURCES[source], int(supersample), self.entries.ctypes.data, len(self),
+                                 (C.c_uint8 * 4)(*self.inside), float(self.scale), float(self.offset), int(max_band_rows))
+
+
+def resolve_host(palette: Palette, source: str, supersample: int, width: int, height: int, *, counts=None, bytes_=None,
+                 smooth=None) -> np.ndarray:
+    """mbk_render_resolve_host: colour and resolve caller-supplied samples of (height s, width s) on the host -- the same
+    code the kernel is compiled from, without a device."""
+    lib = L.load()
+    out = np.empty((height, width, 4), np.uint8)
+    arrs = []
+    for a, dt in ((counts, np.int32), (bytes_, np.uint8), (smooth, np.float64)):
+        arrs.append(None if a is None else np.ascontiguousarray(a, dtype=dt))
+    for a in arrs:
+        if a is not None and a.size != width * height * supersample * supersample:
+            raise ValueError("sample arrays must hold (height * s) x (width * s) elements")
+    spec = palette.spec(source, supersample)
+    st = lib.mbk_render_resolve_host(C.byref(spec), width, height, *[a.ctypes.data if a is not None else None for a in arrs],
+                                     out.ctypes.data)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return out
+
+
+def _chunk(tag: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+
+def write_png(path, rgba: np.ndarray, *, flip: bool = True, level: int = 6) -> None:
+    """Write an (h, w, 4) uint8 array as an 8-bit RGBA, non-interlaced PNG.  Row 0 of a render is the LOWEST imaginary part;
+    PNG rows run top to bottom, so by default the rows are written in reverse (flip=False writes them as they are)."""
+    a = np.asarray(rgba)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("write_png takes a non-empty (h, w, 4) uint8 array")
+    if flip:
+        a = a[::-1]
+    h, w = a.shape[:2]
+    raw = np.zeros((h, 1 + 4 * w), np.uint8)   # filter type 0 in front of every row
+    raw[:, 1:] = a.reshape(h, 4 * w)
+    png = (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0))
+           + _chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + _chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(png)

@@ -310,6 +310,94 @@ int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_d
 int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes);
 
+/*
+ * Rendering: a view to an RGBA8 image on the device, with a palette and supersampling.  Replaces, for a view of any kind,
+ * what the reference's Viewer does on the host for a chunk (DistributedMandelbrotViewer.py:110-135, data_to_img_array: the
+ * bytes through matplotlib's jet, black where the byte is 0) -- mbk_palette_viewer is that colouring as a palette.  Additive
+ * (the ABI version stays 5): no existing call changes.
+ *
+ * Contract (bit-exact given the samples; tests/render_model.py restates it in numpy, tests/test_gpu_render.py holds the GPU to
+ * it).  A render of a view of W x H OUTPUT pixels with supersampling factor s:
+ *   samples   the sample view covers the same rectangle (start_*, range_*; for a deep view the same orbit and range_*) with
+ *             width W s and height H s.  Output pixel (x, y) owns sample columns x s .. x s + s - 1 and sample rows
+ *             y s .. y s + s - 1, and an output window (col0, row0, ncols, nrows) is the sample window scaled by s.  The samples
+ *             are exactly what mbk_view_launch (MBK_WANT_BYTES) / mbk_view_launch_smooth / mbk_deep_view_launch write for that
+ *             sample view with the kernel the flags select.  With end points included the s times finer linspace is NOT centred
+ *             on the pixels of the s = 1 view: a render with s > 1 is the box filter of the finer view, not of the same one.
+ *   colour    of one sample, RGBA8, from the caller's palette p of n RGBA8 entries:
+ *             MBK_RENDER_BYTES (n = 256): p[b], b the sample's quantised byte.
+ *             MBK_RENDER_SMOOTH (2 <= n <= 65536): `inside` if the sample's count is 0 (decided on the count, not on nu).
+ *             Otherwise, in binary64, every operation rounded on its own: t = fl(fl(nu * scale) + offset); t = 0 unless
+ *             0 <= t (negative, -inf, NaN); k = floor(t), f = floor((t - k) * 256) (both exact), i0 = k mod n,
+ *             i1 = (k + 1) mod n, and per channel (p[i0] (256 - f) + p[i1] f + 128) >> 8 in integers.  0 < scale <= 2^20 and
+ *             |offset| <= 2^20, so t < 2^52 for every nu a launch can produce (nu < 2^31 + 1; a t >= 2^52, which only
+ *             mbk_render_resolve_host can be handed, is taken as 0 too).
+ *   resolve   per channel, alpha included, with S the sum over the pixel's s^2 sample colours: (2 S + s^2) / (2 s^2) rounded
+ *             down (round half up; the identity for s = 1).  s is 1, 2, 3, 4 or 8.  The 8-bit palette values are averaged as
+ *             they are: the palette is in whatever colour space the caller wants.
+ *   output    uint8[nrows][ncols][4], row 0 the lowest imaginary part as everywhere else.
+ *
+ * Memory.  The samples never leave the device: they live in a scratch buffer the ctx keeps PER STREAM (like the launches'
+ * other scratch), which grows on demand up to MBK_RENDER_BAND_BYTES and no further.  The output window is cut into bands of
+ * rows -- and pieces of columns, should a single row's samples exceed the budget -- whose samples fit: 12 bytes per sample
+ * (int32 count + binary64 nu) for MBK_RENDER_SMOOTH, 1 byte for MBK_RENDER_BYTES through _launch and 5 through _compute (the
+ * counts feed the statistics).  A 4096-wide render at s = 4 takes bands of 341 rows; a 4096 x 4096 smooth render at s = 1 is one
+ * band of 192 MiB.  max_band_rows lowers the band height further.  Windows of a view are bit-identical to the whole view, so
+ * banding cannot change the image.  Beside the samples a stream keeps its palette on the device (<= 256 KiB), and _compute
+ * keeps one device image of 4 bytes per output pixel of the largest window rendered, per ctx.  The palette is copied during
+ * the call; a call whose palette or palette length differs from the previous render's on that stream first waits for the
+ * stream (like an orbit's first launch: render once before capturing renders into a graph).
+ *
+ * Out of scope: handing bands to several GPUs (sharding.py; a band of an image is a window, and windows are bit-identical,
+ * so a follow-up can), slot / submit forms, gamma-aware averaging, decoding stored chunk streams on the device, and fusing
+ * the colouring into the escape kernels.
+ */
+#define MBK_RENDER_BYTES 0u
+#define MBK_RENDER_SMOOTH 1u
+/* The most sample scratch a render keeps on one stream. */
+#define MBK_RENDER_BAND_BYTES (256u << 20)
+
+typedef struct mbk_render_spec {
+    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH */
+    uint32_t supersample;   /* 1, 2, 3, 4, 8 */
+    const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
+    uint32_t palette_len;
+    uint8_t inside[4];      /* MBK_RENDER_SMOOTH: the colour of a sample that never escapes */
+    double scale, offset;   /* MBK_RENDER_SMOOTH; ignored (not validated) for MBK_RENDER_BYTES */
+    uint32_t max_band_rows; /* 0 = the library's choice; any value gives the same image */
+} mbk_render_spec;
+
+/* Asynchronous, on the caller's stream: d_rgba is a DEVICE buffer of ncols * nrows * 4 bytes, and nothing is written outside
+ * it.  `flags` carries kernel selection (and MBK_PRECISION_F32 for MBK_RENDER_BYTES) only, under the rules of the call that
+ * makes the samples: MBK_RENDER_SMOOTH refuses MBK_KERNEL_SIMPLE / _REFILL / MBK_PRECISION_F32, a deep render refuses every
+ * flag.  MBK_ERR_INVALID, with nothing written: a NULL spec / palette / output, an unknown source, s outside the set,
+ * palette_len wrong for the source, scale / offset outside their ranges or not finite, W s or H s beyond what the sample call
+ * accepts (the whole sample window is validated as one), any other flag, and whatever the sample call refuses.
+ * _compute: synchronous into a HOST buffer on slot 0 (the slot-0 rule above applies); stats as for mbk_view_compute, over the
+ * SAMPLES: pixel_iterations, never_pixels; d2h_ms the copy of the image; all_bytes_* and rle_runs are 0; kernel_ms runs from
+ * the first sample kernel to the last resolve kernel (with several bands it includes the statistics passes between them).
+ * mbk_serialize_last still refers to the last tile computed with bytes: a render does not touch it. */
+int mbk_view_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                           uint8_t *d_rgba, void *hip_stream);
+int mbk_view_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                            uint8_t *h_rgba, mbk_stats *stats);
+int mbk_deep_view_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_view_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+/* The reference Viewer's colouring as a 256-entry palette for MBK_RENDER_BYTES, host only: entry 0 black (0, 0, 0, 255),
+ * entry b = jet(1 - b / 256) as data_to_img_array evaluates it, each channel floor(255 x + 0.5) (jet holds exact .5 ties, so
+ * the rounding rule is part of the contract).  Computed from jet's public definition (its knots and matplotlib's 256-entry
+ * table construction, every operation rounded on its own); held to the reference Viewer's recorded output, all 1024 bytes, by
+ * tests/test_render.py (tests/golden/viewer_palette.npz). */
+int mbk_palette_viewer(uint8_t out[1024]);
+/* "Colour" and "resolve" above applied on the HOST to caller-supplied samples of (width s) x (height s), row-major: no ctx, no
+ * device; the same functions the kernel is compiled from.  For the CPU tests.  MBK_RENDER_SMOOTH reads counts and smooth,
+ * MBK_RENDER_BYTES reads bytes; the others may be NULL.  rgba: width * height * 4 bytes.  MBK_ERR_INVALID as above, and for
+ * a width or height of 0 or width s, height s >= 2^31. */
+int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                            const uint8_t *bytes, const double *smooth, uint8_t *rgba);
+
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
 #define MBK_CODEC_RLE 0x01u
