@@ -10,6 +10,8 @@ device.py        MandelbrotDevice: one GPU context; views, DataChunk tiles, asyn
 worker.py        the reference worker's interface (process_workload / do_workload_single / main)
                  speaking the unchanged Distributer TCP protocol, plus a per-GPU work-queue farm
 image.py         Palette (for MandelbrotDevice.render_view / render_deep_view) and a standard-library PNG writer
+viewer.py        the reference Viewer's job: fetch chunk streams from a store or a DataServer and render them, one chunk
+                 or a downsampled mosaic of a level, on the GPU (render_level; python -m distributedmandelbrot_amd.viewer)
 sharding.py      row-band work items and the per-GPU queue used to shard one view over N GPUs
 
 There is no CPU fallback anywhere in this package.

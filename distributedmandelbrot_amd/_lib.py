@@ -47,6 +47,12 @@ MBK_RENDER_SMOOTH = 1
 RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH}
 RENDER_SUPERSAMPLES = (1, 2, 3, 4, 8)
 MBK_RENDER_BAND_BYTES = 256 << 20
+# reason codes of an invalid chunk stream (include/mbk.h, "Stored chunks")
+MBK_STREAM_OK, MBK_STREAM_BAD_CODEC, MBK_STREAM_BAD_SIZE, MBK_STREAM_ZERO_RUN, MBK_STREAM_TOO_LONG, MBK_STREAM_TOO_SHORT = range(6)
+STREAM_REASONS = {MBK_STREAM_OK: "MBK_STREAM_OK", MBK_STREAM_BAD_CODEC: "MBK_STREAM_BAD_CODEC", MBK_STREAM_BAD_SIZE: "MBK_STREAM_BAD_SIZE",
+                  MBK_STREAM_ZERO_RUN: "MBK_STREAM_ZERO_RUN", MBK_STREAM_TOO_LONG: "MBK_STREAM_TOO_LONG",
+                  MBK_STREAM_TOO_SHORT: "MBK_STREAM_TOO_SHORT"}
+CHUNK_SCALES = (1, 2, 4, 8, 16, 32, 64)
 
 
 class mbk_view(C.Structure):
@@ -68,6 +74,10 @@ class mbk_render_spec(C.Structure):
     _fields_ = [("source", C.c_uint32), ("supersample", C.c_uint32), ("palette", C.c_void_p),
                 ("palette_len", C.c_uint32), ("inside", C.c_uint8 * 4),
                 ("scale", C.c_double), ("offset", C.c_double), ("max_band_rows", C.c_uint32)]
+
+
+class mbk_chunk_spec(C.Structure):
+    _fields_ = [("palette", C.c_void_p), ("scale", C.c_uint32)]
 
 
 class mbk_stats(C.Structure):
@@ -176,6 +186,16 @@ SIGNATURES = {
     "mbk_palette_viewer": (C.c_int, [C.c_void_p]),
     "mbk_render_resolve_host": (C.c_int, [C.POINTER(mbk_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "mbk_chunk_stream_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32)]),
+    "mbk_chunk_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "mbk_chunk_resolve_host": (C.c_int, [C.POINTER(mbk_chunk_spec), C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mbk_chunk_decode_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_chunk_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(mbk_chunk_spec), C.c_void_p, C.c_uint64,
+                                          C.c_void_p, C.c_void_p]),
+    "mbk_chunk_decode_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_chunk_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(mbk_chunk_spec), C.c_void_p, C.c_uint64,
+                                           C.POINTER(mbk_stats)]),
 }
 
 _lib = None

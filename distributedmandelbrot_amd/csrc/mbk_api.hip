@@ -27,6 +27,7 @@
 #include "mbk_deep_orbit.h"
 #include "mbk_deep.h"
 #include "mbk_render.h"
+#include "mbk_chunks.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -89,6 +90,12 @@ struct StreamScratch {
     size_t render_cap = 0;            // bytes
     uint32_t *d_palette = nullptr;    // 65536 entries
     std::vector<uint32_t> palette;    // what d_palette holds
+    // stored chunks (mbk_chunks.h): payload | run starts | run values | block sums | block flags | state, sized for chunk_cap_n
+    // output bytes; the decoded bytes of the render form; the reason code of the synchronous forms (pinned)
+    uint8_t *d_chunk = nullptr;
+    size_t chunk_cap_n = 0;
+    uint8_t *d_chunk_bytes = nullptr;
+    uint32_t *h_chunk_status = nullptr;
 };
 static const size_t kMaxStreamScratch = 64;
 static const uint32_t kStampSlots = 16, kShareRing = 64;
@@ -323,6 +330,9 @@ static void free_scratch(StreamScratch &sc)
     if (sc.h_red) (void)hipHostFree(sc.h_red);
     if (sc.d_render) (void)hipFree(sc.d_render);
     if (sc.d_palette) (void)hipFree(sc.d_palette);
+    if (sc.d_chunk) (void)hipFree(sc.d_chunk);
+    if (sc.d_chunk_bytes) (void)hipFree(sc.d_chunk_bytes);
+    if (sc.h_chunk_status) (void)hipHostFree(sc.h_chunk_status);
     sc = StreamScratch();
 }
 
@@ -2221,6 +2231,21 @@ static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint
     return p;
 }
 
+// The stream's device palette: uploaded when it differs from what the device copy holds, after the launches that read that.
+static int stream_palette(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const uint8_t *palette, uint32_t len)
+{
+    std::vector<uint32_t> words(len);
+    for (uint32_t k = 0; k < len; ++k) words[k] = pack_rgba(palette + 4u * (size_t)k);
+    if (!sc->d_palette) MBK_HIP(ctx, hipMalloc((void **)&sc->d_palette, 65536u * sizeof(uint32_t)));
+    if (words != sc->palette) {
+        MBK_HIP(ctx, hipStreamSynchronize(stream));
+        sc->palette.clear();
+        MBK_HIP(ctx, hipMemcpy(sc->d_palette, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        sc->palette = words;
+    }
+    return MBK_OK;
+}
+
 // What a render renders: a view (deep == nullptr) or a deep view on its orbit.
 struct RenderTarget {
     const mbk_view *view;
@@ -2312,15 +2337,8 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     if (rc != MBK_OK) return rc;
 
     // the palette: uploaded when it differs from what this stream's device copy holds, after the launches that read that
-    std::vector<uint32_t> words(spec->palette_len);
-    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
-    if (!sc->d_palette) MBK_HIP(ctx, hipMalloc((void **)&sc->d_palette, 65536u * sizeof(uint32_t)));
-    if (words != sc->palette) {
-        MBK_HIP(ctx, hipStreamSynchronize(stream));
-        sc->palette.clear();
-        MBK_HIP(ctx, hipMemcpy(sc->d_palette, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        sc->palette = words;
-    }
+    rc = stream_palette(ctx, sc, stream, spec->palette, spec->palette_len);
+    if (rc != MBK_OK) return rc;
 
     // bands: rows of the output window whose samples fit the budget, and pieces of columns if one row's do not
     const uint64_t per_px = (uint64_t)s * s * (smooth ? 12u : (stat ? 5u : 1u));
@@ -2528,6 +2546,324 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
 }
 
 // ---- the native worker loop (mbk_feeder.h) ----------------------------------------------------------------
+
+// ---- stored chunks (mbk_chunks.h; mbk.h "Stored chunks") ------------------------------------------------------------
+
+static const char *stream_reason_text(uint32_t reason)
+{
+    switch (reason) {
+        case MBK_STREAM_OK: return "MBK_STREAM_OK";
+        case MBK_STREAM_BAD_CODEC: return "MBK_STREAM_BAD_CODEC: the code byte is neither Raw nor RLE";
+        case MBK_STREAM_BAD_SIZE: return "MBK_STREAM_BAD_SIZE: empty stream, Raw shorter than 1 + n, RLE payload not a multiple of 5 or longer than n";
+        case MBK_STREAM_ZERO_RUN: return "MBK_STREAM_ZERO_RUN: a run of length 0";
+        case MBK_STREAM_TOO_LONG: return "MBK_STREAM_TOO_LONG: the run lengths sum to more than n";
+        case MBK_STREAM_TOO_SHORT: return "MBK_STREAM_TOO_SHORT: the run lengths sum to less than n";
+    }
+    return "unknown MBK_STREAM_* reason";
+}
+
+static int fail_stream(mbk_ctx *ctx, uint32_t reason) { return fail(ctx, MBK_ERR_INVALID, std::string("invalid chunk stream: ") + stream_reason_text(reason)); }
+
+static uint32_t record_length(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// What can be said about a stream without walking its payload: the reason code (MBK_STREAM_OK = nothing against it so far),
+// the code byte and the number of RLE records.  A stream of one record is judged completely.
+static uint32_t stream_precheck(const uint8_t *stream, uint64_t size, uint64_t n, uint32_t *codec, uint64_t *runs)
+{
+    *codec = 0;
+    *runs = 0;
+    if (size == 0 || n == 0 || n > MBK_CHUNK_BYTES) return MBK_STREAM_BAD_SIZE;
+    *codec = stream[0];
+    if (stream[0] == MBK_CODEC_RAW) return size >= 1 + n ? MBK_STREAM_OK : MBK_STREAM_BAD_SIZE;
+    if (stream[0] != MBK_CODEC_RLE) return MBK_STREAM_BAD_CODEC;
+    if ((size - 1) % 5 != 0 || size > 1 + n) return MBK_STREAM_BAD_SIZE;
+    *runs = (size - 1) / 5;
+    if (*runs == 0) return MBK_STREAM_TOO_SHORT;
+    if (*runs == 1) return mbk::chunk_status_of(record_length(stream + 1) == 0, record_length(stream + 1), n);
+    return MBK_STREAM_OK;
+}
+
+static int chunk_scale_log2(uint32_t k)
+{
+    for (int lk = 0; lk <= 6; ++lk)
+        if (k == (1u << lk)) return lk;
+    return -1;
+}
+
+int mbk_chunk_stream_check(const uint8_t *stream, uint64_t size, uint64_t n, uint32_t *codec, uint64_t *runs, uint32_t *reason)
+{
+    if (!stream) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    uint32_t c;
+    uint64_t r;
+    uint32_t why = stream_precheck(stream, size, n, &c, &r);
+    if (why == MBK_STREAM_OK && r > 1) why = mbk::chunk_check_records_host(stream + 1, r, n);
+    if (codec) *codec = c;
+    if (runs) *runs = r;
+    if (reason) *reason = why;
+    return why == MBK_STREAM_OK ? MBK_OK : fail_stream(nullptr, why);
+}
+
+int mbk_chunk_decode_host(const uint8_t *stream, uint64_t size, uint64_t n, uint8_t *bytes)
+{
+    if (!bytes) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    uint32_t codec;
+    uint64_t runs;
+    const int rc = mbk_chunk_stream_check(stream, size, n, &codec, &runs, nullptr);
+    if (rc != MBK_OK) return rc;
+    if (codec == MBK_CODEC_RAW)
+        std::memcpy(bytes, stream + 1, n);
+    else
+        mbk::chunk_expand_host(stream + 1, runs, bytes);
+    return MBK_OK;
+}
+
+static int validate_chunk_spec(mbk_ctx *ctx, const mbk_chunk_spec *spec, const void *out, uint64_t pitch_px, int *lk)
+{
+    if (!spec || !spec->palette || !out) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    *lk = chunk_scale_log2(spec->scale);
+    if (*lk < 0) return fail(ctx, MBK_ERR_INVALID, "scale must be 1, 2, 4, 8, 16, 32 or 64");
+    if (pitch_px < (MBK_CHUNK_DEFINITION >> *lk) || pitch_px > (1ull << 40))
+        return fail(ctx, MBK_ERR_INVALID, "pitch_px must be at least 4096 / scale");
+    return MBK_OK;
+}
+
+int mbk_chunk_resolve_host(const mbk_chunk_spec *spec, const uint8_t *bytes, uint8_t *rgba, uint64_t pitch_px)
+{
+    int lk;
+    const int rc = validate_chunk_spec(nullptr, spec, rgba, pitch_px, &lk);
+    if (rc != MBK_OK) return rc;
+    if (!bytes) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    uint32_t words[256];
+    for (uint32_t k = 0; k < 256u; ++k) words[k] = pack_rgba(spec->palette + 4u * k);
+    mbk::chunk_resolve_host(words, (uint32_t)lk, bytes, rgba, pitch_px);
+    return MBK_OK;
+}
+
+// The parts of a stream's chunk scratch for n output bytes (all on 256-byte lines).
+struct ChunkScratch {
+    uint32_t *words;                  // the payload: at most n bytes, read in groups of 20
+    uint32_t *starts;                 // n / 5 records, in whole groups of four
+    uint8_t *values;
+    unsigned long long *block_sum;
+    uint32_t *block_zero, *state;
+    size_t total;
+};
+static ChunkScratch chunk_scratch_layout(uint8_t *base, size_t n)
+{
+    const size_t recs = (n / 5u + 4u) & ~(size_t)3u, blocks = recs / mbk::kChunkScanRecords + 1u;
+    size_t off = 0;
+    ChunkScratch c;
+    c.words = (uint32_t *)(base + off);
+    off = round_up_256(off + n + 32u);
+    c.starts = (uint32_t *)(base + off);
+    off = round_up_256(off + recs * 4u);
+    c.values = base + off;
+    off = round_up_256(off + recs);
+    c.block_sum = (unsigned long long *)(base + off);
+    off = round_up_256(off + blocks * 8u);
+    c.block_zero = (uint32_t *)(base + off);
+    off = round_up_256(off + blocks * 4u);
+    c.state = (uint32_t *)(base + off);
+    c.total = off + 256u;
+    return c;
+}
+
+// A prechecked stream (stream_precheck: MBK_STREAM_OK) decoded into d_bytes[n] on `stream`; the reason code goes to d_status
+// (may be NULL) and, with h_status (pinned), to the host.  ev_k0 (may be NULL) is recorded behind the upload of the stream:
+// where the kernel time of the synchronous forms starts.
+static int chunk_decode_run(mbk_ctx *ctx, StreamScratch *sc, const uint8_t *h_stream, uint64_t size, uint64_t n, uint32_t codec,
+                            uint64_t runs, uint8_t *d_bytes, uint32_t *d_status, uint32_t *h_status, hipEvent_t ev_k0,
+                            hipStream_t stream)
+{
+    if (codec == MBK_CODEC_RAW || runs == 1) {
+        if (codec == MBK_CODEC_RAW)
+            MBK_HIP(ctx, hipMemcpyAsync(d_bytes, h_stream + 1, n, hipMemcpyHostToDevice, stream));
+        if (ev_k0) MBK_HIP(ctx, hipEventRecord(ev_k0, stream));
+        if (codec != MBK_CODEC_RAW)
+            MBK_HIP(ctx, hipMemsetAsync(d_bytes, h_stream[5], n, stream));
+        if (d_status) MBK_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream));
+        if (h_status) *h_status = MBK_STREAM_OK;
+        return MBK_OK;
+    }
+    if (n > sc->chunk_cap_n) {
+        if (sc->d_chunk) (void)hipFree(sc->d_chunk);   // (hipFree waits for the launches that may still read it)
+        sc->d_chunk = nullptr;
+        sc->chunk_cap_n = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&sc->d_chunk, chunk_scratch_layout(nullptr, n).total));
+        sc->chunk_cap_n = n;
+    }
+    const ChunkScratch c = chunk_scratch_layout(sc->d_chunk, sc->chunk_cap_n);
+    MBK_HIP(ctx, hipMemcpyAsync(c.words, h_stream + 1, size - 1, hipMemcpyHostToDevice, stream));
+    if (ev_k0) MBK_HIP(ctx, hipEventRecord(ev_k0, stream));
+    const uint32_t r = (uint32_t)runs, nblocks = (r + mbk::kChunkScanRecords - 1u) / mbk::kChunkScanRecords;
+    hipLaunchKernelGGL(mbk::chunk_block_sums_kernel, dim3(nblocks), dim3(mbk::kChunkScanThreads), 0, stream, c.words, r, c.block_sum,
+                       c.block_zero);
+    hipLaunchKernelGGL(mbk::chunk_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, c.block_sum, c.block_zero, nblocks,
+                       (unsigned long long)n, c.state, d_status);
+    hipLaunchKernelGGL(mbk::chunk_starts_kernel, dim3(nblocks), dim3(mbk::kChunkScanThreads), 0, stream, c.words, r, c.block_sum,
+                       (unsigned long long)n, c.starts, (uint32_t *)c.values);
+    hipLaunchKernelGGL(mbk::chunk_expand_kernel, dim3((uint32_t)((n + mbk::kChunkPiece - 1u) / mbk::kChunkPiece)), dim3(256), 0, stream,
+                       c.starts, c.values, r, (uint32_t)n, d_bytes);
+    MBK_HIP(ctx, hipGetLastError());
+    if (h_status) MBK_HIP(ctx, hipMemcpyAsync(h_status, c.state, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    return MBK_OK;
+}
+
+// A prechecked stream of a whole chunk rendered to d_out (rows of `pitch` pixels) on `stream`.
+static int chunk_render_run(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, uint32_t codec, uint64_t runs,
+                            const mbk_chunk_spec *spec, int lk, uint32_t *d_out, uint64_t pitch, uint32_t *d_status,
+                            bool want_h_status, uint32_t **h_status, hipEvent_t ev_k0, hipStream_t stream)
+{
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    if (want_h_status && !sc->h_chunk_status) MBK_HIP(ctx, hipHostMalloc((void **)&sc->h_chunk_status, sizeof(uint32_t), hipHostMallocDefault));
+    if (h_status) *h_status = sc->h_chunk_status;
+    const uint32_t w = MBK_CHUNK_DEFINITION >> lk;
+    if (codec == MBK_CODEC_RLE && runs == 1) {   // a chunk of one value: no decode, no palette upload
+        if (ev_k0) MBK_HIP(ctx, hipEventRecord(ev_k0, stream));
+        hipLaunchKernelGGL(mbk::chunk_fill_kernel, dim3((w * (w / 4u) + 255u) / 256u), dim3(256), 0, stream, d_out, pitch, w,
+                           pack_rgba(spec->palette + 4u * (size_t)h_stream[5]));
+        MBK_HIP(ctx, hipGetLastError());
+        if (d_status) MBK_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream));
+        if (want_h_status) *sc->h_chunk_status = MBK_STREAM_OK;
+        return MBK_OK;
+    }
+    rc = stream_palette(ctx, sc, stream, spec->palette, 256u);
+    if (rc != MBK_OK) return rc;
+    if (!sc->d_chunk_bytes) MBK_HIP(ctx, hipMalloc((void **)&sc->d_chunk_bytes, MBK_CHUNK_BYTES));
+    rc = chunk_decode_run(ctx, sc, h_stream, size, MBK_CHUNK_BYTES, codec, runs, sc->d_chunk_bytes, d_status,
+                          want_h_status ? sc->h_chunk_status : nullptr, ev_k0, stream);
+    if (rc != MBK_OK) return rc;
+    mbk::ChunkRenderArgs a;
+    a.bytes = sc->d_chunk_bytes;
+    a.palette = sc->d_palette;
+    a.out = d_out;
+    a.pitch = pitch;
+    mbk::launch_chunk_resolve((uint32_t)lk, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_chunk_decode_launch(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, uint64_t n, uint8_t *d_bytes,
+                            uint32_t *d_status, void *hip_stream)
+{
+    if (!ctx || !h_stream || !d_bytes) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    uint32_t codec;
+    uint64_t runs;
+    const uint32_t why = stream_precheck(h_stream, size, n, &codec, &runs);
+    if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    StreamScratch *sc = nullptr;
+    const int rc = get_scratch(ctx, (hipStream_t)hip_stream, &sc);
+    if (rc != MBK_OK) return rc;
+    return chunk_decode_run(ctx, sc, h_stream, size, n, codec, runs, d_bytes, d_status, nullptr, nullptr, (hipStream_t)hip_stream);
+}
+
+int mbk_chunk_render_launch(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, const mbk_chunk_spec *spec, uint8_t *d_rgba,
+                            uint64_t pitch_px, uint32_t *d_status, void *hip_stream)
+{
+    if (!ctx || !h_stream) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    int lk;
+    const int rc = validate_chunk_spec(ctx, spec, d_rgba, pitch_px, &lk);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    uint32_t codec;
+    uint64_t runs;
+    const uint32_t why = stream_precheck(h_stream, size, MBK_CHUNK_BYTES, &codec, &runs);
+    if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return chunk_render_run(ctx, h_stream, size, codec, runs, spec, lk, (uint32_t *)d_rgba, pitch_px, d_status, false, nullptr,
+                            nullptr, (hipStream_t)hip_stream);
+}
+
+int mbk_chunk_decode_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, uint64_t n, uint8_t *h_bytes, mbk_stats *stats)
+{
+    if (!ctx || !h_stream || !h_bytes) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    uint32_t codec;
+    uint64_t runs;
+    const uint32_t why = stream_precheck(h_stream, size, n, &codec, &runs);
+    if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[0];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, sl.stream, &sc);
+    if (rc != MBK_OK) return rc;
+    if (!sc->h_chunk_status) MBK_HIP(ctx, hipHostMalloc((void **)&sc->h_chunk_status, sizeof(uint32_t), hipHostMallocDefault));
+    // the decoded bytes live in the stream's scratch, not in the slot's tile buffer: mbk_serialize_last is not affected
+    if (!sc->d_chunk_bytes) MBK_HIP(ctx, hipMalloc((void **)&sc->d_chunk_bytes, MBK_CHUNK_BYTES));
+    rc = chunk_decode_run(ctx, sc, h_stream, size, n, codec, runs, sc->d_chunk_bytes, nullptr, sc->h_chunk_status, sl.ev_k0, sl.stream);
+    if (rc == MBK_OK) {
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+        rc = launch_reduce(ctx, sl, nullptr, sc->d_chunk_bytes, n, 0u, sl.stream);
+    }
+    if (rc != MBK_OK) {
+        (void)hipStreamSynchronize(sl.stream);
+        return rc;
+    }
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    if (*sc->h_chunk_status != MBK_STREAM_OK) return fail_stream(ctx, *sc->h_chunk_status);
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sc->d_chunk_bytes, n, hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+        fill_stats_from_reduce(sl, stats, true);
+    }
+    return MBK_OK;
+}
+
+int mbk_chunk_render_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, const mbk_chunk_spec *spec, uint8_t *h_rgba,
+                             uint64_t pitch_px, mbk_stats *stats)
+{
+    if (!ctx || !h_stream) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    int lk;
+    int rc = validate_chunk_spec(ctx, spec, h_rgba, pitch_px, &lk);
+    if (rc != MBK_OK) return rc;
+    uint32_t codec;
+    uint64_t runs;
+    const uint32_t why = stream_precheck(h_stream, size, MBK_CHUNK_BYTES, &codec, &runs);
+    if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[0];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    const uint32_t w = MBK_CHUNK_DEFINITION >> lk;
+    const size_t px = (size_t)w * w;
+    if (px > ctx->rgba_cap_px) {
+        if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
+        ctx->d_rgba = nullptr;
+        ctx->rgba_cap_px = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_rgba, px * sizeof(uint32_t)));
+        ctx->rgba_cap_px = px;
+    }
+    uint32_t *h_status = nullptr;
+    rc = chunk_render_run(ctx, h_stream, size, codec, runs, spec, lk, ctx->d_rgba, w, nullptr, true, &h_status, sl.ev_k0, sl.stream);
+    if (rc != MBK_OK) {
+        (void)hipStreamSynchronize(sl.stream);   // nothing of a failed render stays queued on the slot
+        return rc;
+    }
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    if (*h_status != MBK_STREAM_OK) return fail_stream(ctx, *h_status);
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    if (pitch_px == w)
+        MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+    else
+        MBK_HIP(ctx, hipMemcpy2DAsync(h_rgba, pitch_px * sizeof(uint32_t), ctx->d_rgba, (size_t)w * sizeof(uint32_t),
+                                      (size_t)w * sizeof(uint32_t), w, hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+    }
+    return MBK_OK;
+}
 
 static int ctx_submit(void *user, int slot, uint32_t level, uint32_t mrd, uint32_t ir, uint32_t ii, uint8_t *h_bytes)
 {

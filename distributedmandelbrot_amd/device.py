@@ -167,6 +167,49 @@ def datachunk_geometry(level: int, index_real: int, index_imag: int) -> Tuple[fl
     return a.value, b.value, c.value
 
 
+def _stream_array(stream) -> np.ndarray:
+    """A chunk stream (bytes, bytearray, memoryview or uint8 array) as a contiguous uint8 array, without a copy where possible."""
+    if isinstance(stream, np.ndarray):
+        a = np.ascontiguousarray(stream, dtype=np.uint8).ravel()
+    else:
+        a = np.frombuffer(stream, np.uint8)
+    return a
+
+
+class ChunkStreamError(MbkError):
+    """An invalid chunk stream; `reason` is one of _lib.MBK_STREAM_* (include/mbk.h, "Stored chunks")."""
+
+    def __init__(self, reason: int, message: str):
+        super().__init__(L.MBK_ERR_INVALID, message)
+        self.reason = reason
+
+
+def chunk_stream_check(stream, n: int = L.MBK_CHUNK_BYTES) -> Tuple[int, int]:
+    """mbk_chunk_stream_check on the host: (codec, runs) of a valid stream of an n-byte chunk; ChunkStreamError otherwise."""
+    lib = L.load()
+    a = _stream_array(stream)
+    codec, runs, reason = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+    st = lib.mbk_chunk_stream_check(a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size, n, C.byref(codec),
+                                    C.byref(runs), C.byref(reason))
+    if st != L.MBK_OK:
+        raise ChunkStreamError(int(reason.value), (lib.mbk_last_error(None) or b"").decode())
+    return int(codec.value), int(runs.value)
+
+
+def decode_chunk_host(stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """mbk_chunk_decode_host: the decoded chunk (uint8[n]) without a device -- the functions the kernels are compiled from.
+    `out` is left untouched when the stream is invalid (MbkError)."""
+    lib = L.load()
+    a = _stream_array(stream)
+    if out is None:
+        out = np.empty(n, np.uint8)
+    assert out.dtype == np.uint8 and out.size == n and out.flags.c_contiguous
+    st = lib.mbk_chunk_decode_host(a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size, n, out.ctypes.data)
+    if st != L.MBK_OK:
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return out
+
+
 class MandelbrotDevice:
     """One mbk_ctx == one GPU.  Not thread-safe: use one host thread per instance."""
 
@@ -500,6 +543,70 @@ class MandelbrotDevice:
         spec = palette.spec(source, supersample, max_band_rows)
         self._check(self._lib.mbk_deep_view_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
                                                           d_rgba or None, stream or None))
+
+    # -- stored chunks (include/mbk.h, "Stored chunks") ---------------------------------------------
+    def decode_chunk(self, stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None):
+        """A chunk stream (what DataChunk.Serialize writes / a DataServer sends) decoded on the GPU: (uint8[n], TileStats).
+        The statistics are those of the decoded bytes (all_bytes_zero / all_bytes_one, rle_runs).  MbkError for an invalid
+        stream, with `out` untouched."""
+        a = _stream_array(stream)
+        if out is None:
+            out = np.empty(n, np.uint8)
+        assert out.dtype == np.uint8 and out.size == n and out.flags.c_contiguous
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_chunk_decode_compute(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size,
+                                                       n, out.ctypes.data, C.byref(st)))
+        return out, _stats(st)
+
+    @staticmethod
+    def _chunk_spec(palette, scale: int) -> L.mbk_chunk_spec:
+        if len(palette) != 256:
+            raise ValueError("a chunk is coloured through a palette of 256 entries")
+        return L.mbk_chunk_spec(palette.entries.ctypes.data, int(scale))
+
+    def render_chunk(self, stream, *, palette=None, scale: int = 1, out: Optional[np.ndarray] = None,
+                     pitch: Optional[int] = None):
+        """A stored 4096 x 4096 chunk as an RGBA8 image of (4096 / scale)^2 pixels, decoded, coloured (palette[byte]; default
+        the reference Viewer's colouring) and box-filtered on the GPU.  `out` may be a (pinned) uint8 array -- or a view
+        into a larger image: then `pitch` is the distance of its rows in pixels, and the chunk lands at out's first
+        element.  Returns (uint8[h, w, 4] -- a view into `out` if given --, TileStats); row 0 is the lowest imaginary part."""
+        from .image import Palette
+        palette = Palette.viewer() if palette is None else palette
+        a = _stream_array(stream)
+        w = L.MBK_CHUNK_DEFINITION // int(scale) if scale in L.CHUNK_SCALES else 0
+        if out is None:
+            out = np.empty((w, w, 4), np.uint8)
+            pitch = w
+        else:
+            pitch = w if pitch is None else int(pitch)
+            if out.dtype != np.uint8 or (w and out.ndim == 3 and out.strides != (4 * pitch, 4, 1)):
+                raise ValueError("out must be uint8 rows of 4-byte pixels, `pitch` pixels apart")
+        spec = self._chunk_spec(palette, scale)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_chunk_render_compute(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size,
+                                                       C.byref(spec), out.ctypes.data, pitch, C.byref(st)))
+        return out, _stats(st)
+
+    def launch_decode_chunk(self, stream, *, d_bytes: int, n: int = L.MBK_CHUNK_BYTES, d_status: int = 0,
+                            hip_stream: int = 0) -> None:
+        """Asynchronous decode into a DEVICE buffer of n bytes on ``hip_stream`` (0 = HIP's null stream); the reason code goes
+        to the device word d_status.  `stream` must stay alive until the HIP stream has passed the copy; a uint8 array over
+        pinned memory (`pinned_empty`) makes the copy asynchronous."""
+        a = _stream_array(stream)
+        self._check(self._lib.mbk_chunk_decode_launch(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size, n,
+                                                      d_bytes or None, d_status or None, hip_stream or None))
+
+    def launch_render_chunk(self, stream, *, d_rgba: int, palette=None, scale: int = 1, pitch: Optional[int] = None,
+                            d_status: int = 0, hip_stream: int = 0) -> None:
+        """Asynchronous render into a DEVICE image on ``hip_stream``: the chunk's pixel (x, y) at d_rgba + 4 (y pitch + x)."""
+        from .image import Palette
+        palette = Palette.viewer() if palette is None else palette
+        a = _stream_array(stream)
+        spec = self._chunk_spec(palette, scale)
+        w = L.MBK_CHUNK_DEFINITION // int(scale) if scale in L.CHUNK_SCALES else 0
+        self._check(self._lib.mbk_chunk_render_launch(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size,
+                                                      C.byref(spec), d_rgba or None, w if pitch is None else int(pitch),
+                                                      d_status or None, hip_stream or None))
 
     def reduce_counts(self, d_counts: int, n: int, mrd: int, stream: int = 0) -> TileStats:
         st = L.mbk_stats()

@@ -94,6 +94,27 @@ def resolve_host(palette: Palette, source: str, supersample: int, width: int, he
     return out
 
 
+def resolve_chunk_host(palette: Palette, scale: int, bytes_, *, out=None, pitch=None) -> np.ndarray:
+    """mbk_chunk_resolve_host: a decoded 4096 x 4096 chunk coloured through `palette` (256 entries) and box-filtered by
+    `scale` on the host -- the same code the kernels are compiled from, without a device.  `out` / `pitch` as for
+    MandelbrotDevice.render_chunk."""
+    lib = L.load()
+    b = np.ascontiguousarray(bytes_, dtype=np.uint8).ravel()
+    if b.size != L.MBK_CHUNK_BYTES or len(palette) != 256:
+        raise ValueError("a chunk holds 4096 x 4096 bytes and is coloured through 256 entries")
+    w = L.MBK_CHUNK_DEFINITION // int(scale) if scale in L.CHUNK_SCALES else 0
+    if out is None:
+        out = np.empty((w, w, 4), np.uint8)
+        pitch = w
+    pitch = w if pitch is None else int(pitch)
+    spec = L.mbk_chunk_spec(palette.entries.ctypes.data, int(scale))
+    st = lib.mbk_chunk_resolve_host(C.byref(spec), b.ctypes.data, out.ctypes.data, pitch)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return out
+
+
 def _chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
 

@@ -349,8 +349,8 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
  * stream (like an orbit's first launch: render once before capturing renders into a graph).
  *
  * Out of scope: handing bands to several GPUs (sharding.py; a band of an image is a window, and windows are bit-identical,
- * so a follow-up can), slot / submit forms, gamma-aware averaging, decoding stored chunk streams on the device, and fusing
- * the colouring into the escape kernels.
+ * so a follow-up can), slot / submit forms, gamma-aware averaging, and fusing the colouring into the escape kernels.
+ * (Decoding stored chunk streams on the device: "Stored chunks", below.)
  */
 #define MBK_RENDER_BYTES 0u
 #define MBK_RENDER_SMOOTH 1u
@@ -411,6 +411,88 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
  * cross PCIe.  h_out must hold *size <= 1 + n bytes; cap is its capacity (MBK_ERR_INVALID if too
  * small, with *size set to the needed size). */
 int mbk_serialize_last(mbk_ctx *ctx, uint8_t *h_out, uint64_t cap, uint64_t *size, uint32_t *codec);
+
+/*
+ * Stored chunks: the inverse of mbk_serialize_last, and the picture of a chunk.  A chunk that lies in a store or comes from a
+ * DataServer is decoded ON THE DEVICE, coloured through a 256-entry palette and box-filtered into an RGBA8 rectangle that may
+ * lie inside a larger image -- what the reference's Viewer does on the host for one chunk at full size
+ * (DistributedMandelbrotViewer.py:35-60,110-135).  Additive (the ABI version stays 5): no existing call changes.
+ *
+ * Contract (bit-exact; tests/chunk_model.py restates it in numpy, tests/test_chunks.py and tests/test_gpu_chunks.py hold the
+ * host and the GPU to it):
+ *   stream    what DataChunk.Serialize writes (DataChunk.cs:173-206): one code byte, then a payload, `size` bytes in all, for a
+ *             chunk of n bytes, 1 <= n <= MBK_CHUNK_BYTES (the render calls take n = MBK_CHUNK_BYTES only).
+ *             MBK_CODEC_RAW: valid iff size >= 1 + n; the chunk is the first n payload bytes, what follows is ignored.
+ *             MBK_CODEC_RLE: records of 5 bytes (u32 run length, little-endian; u8 value).  Valid iff the payload length is a
+ *             multiple of 5, size <= 1 + n, no run length is 0 and the run lengths sum to exactly n, the sum taken in 64 bits
+ *             (lengths are arbitrary u32: a sum that wraps does not pass).  Runs need not be maximal: equal neighbouring
+ *             values are legal.  Against the reference's reader (DataChunkSerializer.cs:102-142) this is stricter in one
+ *             respect: the C# loop stops reading once n bytes are filled and never looks at trailing records, which are
+ *             refused here.  The limit size <= 1 + n bounds the scratch (an accepted stream holds at most n / 5 runs); no
+ *             serializer writes a longer RLE stream (Raw wins unless RLE is strictly shorter, DataChunk.cs:186-196).
+ *             Any other code is invalid.
+ *   reason    why a stream is invalid, MBK_STREAM_*.  Where several apply, the first of this list wins, on the host and on
+ *             the device alike: _BAD_SIZE for an empty stream (size 0: there is no code byte); _BAD_CODEC; _BAD_SIZE (Raw
+ *             shorter than 1 + n; RLE payload not a multiple of 5; RLE longer than 1 + n); _ZERO_RUN (a zero run anywhere,
+ *             whatever the sum); _TOO_LONG (sum > n); _TOO_SHORT (sum < n; an RLE stream of the code byte alone is that).
+ *   colour    a chunk rendered at scale k in {1, 2, 4, 8, 16, 32, 64}: output pixel (x, y) owns the bytes of columns
+ *             x k .. x k + k - 1 and rows y k .. y k + k - 1 of the 4096 x 4096 chunk; its colour is, per channel, alpha
+ *             included, (2 S + k^2) / (2 k^2) rounded down, S the sum of palette[b] over its k^2 bytes -- "resolve" of the
+ *             Rendering section with 32-bit sums.  The palette is 256 RGBA8 entries (HOST pointer, copied during the call, as
+ *             for MBK_RENDER_BYTES).  A chunk of one value v therefore renders as palette[v] exactly, at every k.
+ *   output    (4096 / k) rows of (4096 / k) pixels, row 0 the lowest imaginary part; pixel (x, y) at byte 4 (y pitch_px + x),
+ *             pitch_px >= 4096 / k, so that a chunk can land inside a larger image.  Nothing between the rows is written.
+ *
+ * The host forms need no ctx and no device; they are the functions the kernels are compiled from.  _launch: asynchronous on
+ * the caller's HIP stream.  h_stream is a HOST pointer that must stay valid until the stream has passed the copy (pinned
+ * memory, mbk_host_alloc, makes the copy asynchronous).  What the host sees without walking the payload -- NULL pointers, n or
+ * scale out of range, the code byte, the size rules, and a stream of a single record -- is refused at once with
+ * MBK_ERR_INVALID, nothing enqueued, d_status untouched.  Run lengths are validated ON THE DEVICE (the prefix sum that the
+ * expansion needs yields the total; the zero-run test is a reduction) and the reason code is written to d_status (a device
+ * uint32_t, may be NULL; MBK_STREAM_OK for a valid stream).  Whatever the stream holds, nothing is written outside the n
+ * output bytes / the (4096 / k)^2 output pixels: after a non-zero status the contents of the output are unspecified, its bounds
+ * are not.  d_rgba must be 4-byte aligned.  A stream of one run (what a DataServer sends for a Never / Immediate chunk) is not
+ * expanded: the output is filled with the value / with palette[value], bit-identical to the long way round.
+ * _compute: synchronous on slot 0 (the slot-0 rule applies); an invalid stream returns MBK_ERR_INVALID (mbk_last_error names
+ * the reason) with the host buffer untouched.  stats: kernel_ms (from the end of the stream's upload to the end of the decode /
+ * resolve kernels: next to nothing for the decode of a Raw stream, which IS its upload), d2h_ms; for decode also
+ * all_bytes_zero, all_bytes_one and rle_runs of the DECODED chunk (maximal runs, so a caller can re-derive the codec choice);
+ * the other fields 0.  mbk_serialize_last is not affected: it still refers to the last tile computed with bytes.
+ *
+ * Memory: per stream, grown on demand, freed with the ctx: the uploaded payload (<= 16 MiB), the run starts and values
+ * (5 bytes x n / 5), the decoded bytes of the render form (16 MiB), the palette (shared with the renders of that stream; the
+ * same wait-on-change rule).  mbk_chunk_render_compute uses the ctx's device image of the synchronous renders.
+ *
+ * Out of scope: overlapping one chunk's upload with another's kernels (slot / submit forms), and mosaics in native code
+ * (distributedmandelbrot_amd/viewer.py places chunks through pitch_px).
+ */
+#define MBK_STREAM_OK 0u
+#define MBK_STREAM_BAD_CODEC 1u
+#define MBK_STREAM_BAD_SIZE 2u
+#define MBK_STREAM_ZERO_RUN 3u
+#define MBK_STREAM_TOO_LONG 4u
+#define MBK_STREAM_TOO_SHORT 5u
+
+typedef struct mbk_chunk_spec {
+    const uint8_t *palette; /* HOST pointer, 256 x RGBA8; copied during the call */
+    uint32_t scale;         /* k: 1, 2, 4, 8, 16, 32, 64 */
+} mbk_chunk_spec;
+
+/* MBK_OK, or MBK_ERR_INVALID with *reason set (MBK_STREAM_BAD_SIZE also for n outside [1, MBK_CHUNK_BYTES]).  *codec: the code
+ * byte; *runs: the records of an RLE payload, 0 for Raw.  Any output pointer may be NULL. */
+int mbk_chunk_stream_check(const uint8_t *stream, uint64_t size, uint64_t n, uint32_t *codec, uint64_t *runs, uint32_t *reason);
+/* The decoded chunk into bytes[n], or MBK_ERR_INVALID with nothing written. */
+int mbk_chunk_decode_host(const uint8_t *stream, uint64_t size, uint64_t n, uint8_t *bytes);
+/* "colour" and "output" above for a decoded 4096 x 4096 chunk. */
+int mbk_chunk_resolve_host(const mbk_chunk_spec *spec, const uint8_t *bytes, uint8_t *rgba, uint64_t pitch_px);
+int mbk_chunk_decode_launch(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, uint64_t n, uint8_t *d_bytes,
+                            uint32_t *d_status, void *hip_stream);
+int mbk_chunk_render_launch(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, const mbk_chunk_spec *spec, uint8_t *d_rgba,
+                            uint64_t pitch_px, uint32_t *d_status, void *hip_stream);
+int mbk_chunk_decode_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, uint64_t n, uint8_t *h_bytes,
+                             mbk_stats *stats);
+int mbk_chunk_render_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, const mbk_chunk_spec *spec, uint8_t *h_rgba,
+                             uint64_t pitch_px, mbk_stats *stats);
 
 /*
  * Tuning options.  They change scheduling only -- every value the setter accepts gives bit-identical
