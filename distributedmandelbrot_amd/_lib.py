@@ -44,7 +44,8 @@ MBK_CHUNK_BYTES = 4096 * 4096
 MBK_ABI_VERSION = 5
 MBK_RENDER_BYTES = 0
 MBK_RENDER_SMOOTH = 1
-RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH}
+MBK_RENDER_DISTANCE = 3
+RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH, "distance": MBK_RENDER_DISTANCE}
 RENDER_SUPERSAMPLES = (1, 2, 3, 4, 8)
 MBK_RENDER_BAND_BYTES = 256 << 20
 # reason codes of an invalid chunk stream (include/mbk.h, "Stored chunks")
@@ -142,6 +143,11 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "mbk_view_compute_smooth": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_view_launch_distance": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_view_compute_distance": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_distance_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32]),
     "mbk_datachunk_submit": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_void_p, C.c_void_p]),
     "mbk_datachunk_submit_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

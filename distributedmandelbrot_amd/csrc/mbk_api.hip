@@ -28,6 +28,7 @@
 #include "mbk_deep.h"
 #include "mbk_render.h"
 #include "mbk_chunks.h"
+#include "mbk_distance.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -96,6 +97,9 @@ struct StreamScratch {
     size_t chunk_cap_n = 0;
     uint8_t *d_chunk_bytes = nullptr;
     uint32_t *h_chunk_status = nullptr;
+    // distance estimates (mbk_distance.h): the counts of a two-pass launch whose caller wants none
+    int32_t *d_dist_counts = nullptr;
+    size_t dist_cap_px = 0;
 };
 static const size_t kMaxStreamScratch = 64;
 static const uint32_t kStampSlots = 16, kShareRing = 64;
@@ -333,6 +337,7 @@ static void free_scratch(StreamScratch &sc)
     if (sc.d_chunk) (void)hipFree(sc.d_chunk);
     if (sc.d_chunk_bytes) (void)hipFree(sc.d_chunk_bytes);
     if (sc.h_chunk_status) (void)hipHostFree(sc.h_chunk_status);
+    if (sc.d_dist_counts) (void)hipFree(sc.d_dist_counts);
     sc = StreamScratch();
 }
 
@@ -1745,6 +1750,130 @@ int mbk_view_compute_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, ui
     return MBK_OK;
 }
 
+// ---- distance estimates (mbk_distance.h; mbk.h "Distance estimates") ---------------------------------------------------
+
+// Everything a distance launch can refuse, before anything is allocated, enqueued or written.
+static int distance_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, bool *safe)
+{
+    int rc = validate_view(ctx, view, safe);
+    if (rc != MBK_OK) return rc;
+    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (flags & MBK_PRECISION_F32) return fail(ctx, MBK_ERR_INVALID, "distance estimates are implemented in binary64 only");
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
+    if (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL)
+        return fail(ctx, MBK_ERR_INVALID, "distance estimates are implemented with the scan / asm / group kernels only");
+    return MBK_OK;
+}
+
+// A checked launch.  Kernel "asm": one pass, the derivative rides in a per-step escape loop.  Every other selector: the
+// escape kernels it names write the counts, then the derivative pass runs each escaped pixel for exactly its count.
+static int launch_distance(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags, bool safe, int32_t *d_counts,
+                           double *d_distance, hipStream_t stream)
+{
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    const bool one_pass = kernel == MBK_KERNEL_ASM;
+    const size_t px = (size_t)v->ncols * v->nrows;
+    if (!one_pass) {
+        if (!d_counts) {
+            StreamScratch *sc = nullptr;
+            int rc = get_scratch(ctx, stream, &sc);
+            if (rc != MBK_OK) return rc;
+            if (px > sc->dist_cap_px) {
+                if (sc->d_dist_counts) (void)hipFree(sc->d_dist_counts);   // (hipFree waits for the launches that may still read it)
+                sc->d_dist_counts = nullptr;
+                sc->dist_cap_px = 0;
+                MBK_HIP(ctx, hipMalloc((void **)&sc->d_dist_counts, px * sizeof(int32_t)));
+                sc->dist_cap_px = px;
+            }
+            d_counts = sc->d_dist_counts;
+        }
+        int rc = launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+        if (rc != MBK_OK) return rc;
+    }
+    mbk::DistanceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.re = make_axis(v->start_r, v->range_r, v->width);
+    a.im = make_axis(v->start_i, v->range_i, v->height);
+    a.col0 = v->col0;
+    a.row0 = v->row0;
+    a.ncols = v->ncols;
+    a.nrows = v->nrows;
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+    a.counts_in = one_pass ? nullptr : d_counts;
+    a.counts_out = one_pass ? d_counts : nullptr;
+    a.distance = d_distance;
+    const dim3 grid(a.blocks_x * ((v->nrows + 7u) / 8u)), block(64);   // (at most 2^31 / 64 blocks: validate_view)
+    if (one_pass) {
+        if (safe) hipLaunchKernelGGL((mbk::distance_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mbk::distance_kernel<true, true>), grid, block, 0, stream, a);
+    } else {
+        if (safe) hipLaunchKernelGGL((mbk::distance_kernel<false, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mbk::distance_kernel<true, false>), grid, block, 0, stream, a);
+    }
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                             int32_t *d_counts, double *d_distance, void *hip_stream)
+{
+    if (!ctx || !d_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = distance_check(ctx, view, mrd, flags, &safe);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_distance(ctx, view, mrd, flags, safe, d_counts, d_distance, (hipStream_t)hip_stream);
+}
+
+int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                              int32_t *h_counts, double *h_distance, mbk_stats *stats)
+{
+    if (!ctx || !view || !h_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = distance_check(ctx, view, mrd, flags & MBK_KERNEL_MASK, &safe);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    // the synchronous calls run on slot 0: its buffers, events and reduction scratch belong to a tile in flight
+    Slot &sl = ctx->s[0];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    const size_t px = (size_t)view->ncols * view->nrows;
+    rc = ensure_buffers(ctx, sl, px);
+    if (rc != MBK_OK) return rc;
+    if (px > ctx->smooth_cap_px) {
+        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
+        ctx->d_smooth = nullptr;
+        ctx->smooth_cap_px = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
+        ctx->smooth_cap_px = px;
+    }
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+    rc = launch_distance(ctx, view, mrd, flags & MBK_KERNEL_MASK, safe, sl.d_counts, ctx->d_smooth, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+    rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    MBK_HIP(ctx, hipMemcpyAsync(h_distance, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+    if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    ctx->last_px = 0;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+        fill_stats_from_reduce(sl, stats, false);
+    }
+    return MBK_OK;
+}
+
+double mbk_distance_value_host(double mag, double dmag, int32_t count)
+{
+    return mbk::distance_value(mag, dmag, count);
+}
+
 int mbk_serialize_last(mbk_ctx *ctx, uint8_t *h_out, uint64_t cap, uint64_t *size, uint32_t *codec)
 {
     if (!ctx || !h_out || !size || !codec) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
@@ -2208,6 +2337,11 @@ static int validate_render_spec(mbk_ctx *ctx, const mbk_render_spec *spec)
             return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_SMOOTH takes a palette of 2 .. 65536 entries");
         if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^20]");
         if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
+    } else if (spec->source == MBK_RENDER_DISTANCE) {
+        if (spec->palette_len < 2u || spec->palette_len > 65536u)
+            return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE takes a palette of 2 .. 65536 entries");
+        if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p80)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^80]");
+        if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
     } else {
         return fail(ctx, MBK_ERR_INVALID, "unknown MBK_RENDER_* source");
     }
@@ -2299,11 +2433,13 @@ static int render_check(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit
         return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
     if ((uint64_t)t->col0 + t->ncols > t->width || (uint64_t)t->row0 + t->nrows > t->height)
         return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    const bool smooth = spec->source == MBK_RENDER_SMOOTH;
+    const bool dist = spec->source == MBK_RENDER_DISTANCE;
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist;   // (the distance samples obey the smooth launch's rules)
     mbk_view sv;
     mbk_deep_view sd;
     sample_window(*t, s, t->col0, t->row0, t->ncols, t->nrows, &sv, &sd);
     if (is_deep) {
+        if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)");
         if (flags) return fail(ctx, MBK_ERR_INVALID, "deep renders take no flags (no kernel selection, no fp32)");
         return validate_deep(ctx, orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
     }
@@ -2331,7 +2467,8 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
                       uint32_t *d_out, hipStream_t stream, Slot *stat)
 {
     const uint32_t s = spec->supersample;
-    const bool smooth = spec->source == MBK_RENDER_SMOOTH;
+    const bool dist = spec->source == MBK_RENDER_DISTANCE;
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist;   // (same sample layout: binary64 value | counts)
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
@@ -2380,9 +2517,13 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             mbk_view sv;
             mbk_deep_view sd;
             sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
-            if (t.deep)
+            if (t.deep) {
                 rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream);
-            else
+            } else if (dist) {
+                bool safe = false;
+                rc = distance_check(ctx, &sv, mrd, flags, &safe);
+                if (rc == MBK_OK) rc = launch_distance(ctx, &sv, mrd, flags, safe, d_counts, d_nu, stream);
+            } else
                 rc = launch_tile(ctx, &sv, mrd, flags | (d_counts ? MBK_WANT_COUNTS : 0u) | (d_bytes ? MBK_WANT_BYTES : 0u),
                                  d_counts, d_bytes, stream, d_nu);
             if (rc != MBK_OK) return rc;
@@ -2402,7 +2543,9 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             a.pal = render_palette(spec, d_palette);
             const uint64_t pieces = (uint64_t)a.chunks_x * nr;
             const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
-            if (smooth)
+            if (dist)
+                mbk::launch_resolve<true, true>(s, grid, use_lds ? lds : 0u, stream, a);
+            else if (smooth)
                 mbk::launch_resolve<true>(s, grid, use_lds ? lds : 0u, stream, a);
             else
                 mbk::launch_resolve<false>(s, grid, use_lds ? lds : 0u, stream, a);
@@ -2537,11 +2680,12 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
     const uint32_t s = spec->supersample;
     if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
         return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
-    const bool sm = spec->source == MBK_RENDER_SMOOTH;
+    const bool dist = spec->source == MBK_RENDER_DISTANCE;
+    const bool sm = spec->source == MBK_RENDER_SMOOTH || dist;
     if (sm ? (!counts || !smooth) : !bytes) return fail(nullptr, MBK_ERR_INVALID, "the source's sample arrays are NULL");
     std::vector<uint32_t> words(spec->palette_len);
     for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
-    mbk::render_resolve_host(render_palette(spec, words.data()), sm, s, width, height, counts, bytes, smooth, rgba);
+    mbk::render_resolve_host(render_palette(spec, words.data()), sm, s, width, height, counts, bytes, smooth, rgba, dist);
     return MBK_OK;
 }
 

@@ -63,6 +63,21 @@ __host__ __device__ inline uint32_t render_colour_smooth(const RenderPalette &p,
     return render_blend(entries[i0], entries[i1], f);
 }
 
+// The colour of one MBK_RENDER_DISTANCE sample: the smooth rule with the distance estimate in place of nu, except that the
+// palette does not wrap: t >= n - 1 (+inf included) is the last entry.  t < n - 1 <= 65535 below: floor and f are exact.
+__host__ __device__ inline uint32_t render_colour_distance(const RenderPalette &p, const uint32_t *entries, int32_t count, double de)
+{
+    if (count == 0) return p.inside;
+    double t = de * p.scale;
+    t = t + p.offset;
+    if (!(t >= 0.0)) t = 0.0;   // negative, NaN
+    if (t >= (double)(p.n - 1u)) return entries[p.n - 1u];
+    const double k = floor(t);
+    const uint32_t f = (uint32_t)((t - k) * 256.0);
+    const uint32_t i0 = (uint32_t)k;
+    return render_blend(entries[i0], entries[i0 + 1u], f);
+}
+
 // The sum of a pixel's sample colours, two channels to a word (8 x 8 x 255 < 2^16), and its rounded mean
 // (2 sum + s^2) / (2 s^2), rounded down: round half up, the identity for s = 1.
 struct RenderSum {
@@ -129,7 +144,8 @@ __device__ inline void render_load_smooth(const RenderArgs &a, uint64_t at, doub
 // lane) adjacent output pixels, so that a wave's loads cover one contiguous stretch of each sample row and its stores one
 // contiguous stretch of the image.  The grid is sized to the chip and every workgroup takes pieces in turn, which is what
 // makes staging the palette in LDS worth its loads.  Pure streaming: s^2 x (12 | 1) bytes in, 4 bytes out per pixel.
-template <bool SMOOTH, int S>
+// DIST (with SMOOTH): the samples are distance estimates (render_colour_distance); same loads, same layout.
+template <bool SMOOTH, int S, bool DIST = false>
 __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const RenderArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_palette[];
@@ -153,7 +169,9 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
                 int32_t cnt[S];
                 render_load_smooth<S>(a, ((uint64_t)row * S + sy) * a.pitch + (uint64_t)col * S, nu, cnt);
 #pragma unroll
-                for (int sx = 0; sx < S; ++sx) sum.add(render_colour_smooth(a.pal, entries, cnt[sx], nu[sx]));
+                for (int sx = 0; sx < S; ++sx)
+                    sum.add(DIST ? render_colour_distance(a.pal, entries, cnt[sx], nu[sx])
+                                 : render_colour_smooth(a.pal, entries, cnt[sx], nu[sx]));
             }
             out_row[col] = sum.mean(S * S);
         } else {
@@ -192,22 +210,23 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
     }
 }
 
-template <bool SMOOTH>
+template <bool SMOOTH, bool DIST = false>
 inline void launch_resolve(uint32_t s, dim3 grid, size_t lds, hipStream_t stream, const RenderArgs &a)
 {
     const dim3 block(kRenderThreads);
     switch (s) {
-        case 1: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 1>), grid, block, lds, stream, a); break;
-        case 2: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 2>), grid, block, lds, stream, a); break;
-        case 3: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 3>), grid, block, lds, stream, a); break;
-        case 4: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 4>), grid, block, lds, stream, a); break;
-        default: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 8>), grid, block, lds, stream, a); break;
+        case 1: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 1, DIST>), grid, block, lds, stream, a); break;
+        case 2: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 2, DIST>), grid, block, lds, stream, a); break;
+        case 3: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 3, DIST>), grid, block, lds, stream, a); break;
+        case 4: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 4, DIST>), grid, block, lds, stream, a); break;
+        default: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 8, DIST>), grid, block, lds, stream, a); break;
     }
 }
 
 // The same rule on the host, for caller-supplied samples of (width * s) x (height * s): mbk_render_resolve_host.
 inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, uint32_t s, uint32_t width, uint32_t height,
-                                const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba)
+                                const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba,
+                                bool distance = false)
 {
     const uint64_t pitch = (uint64_t)width * s;
     for (uint32_t y = 0; y < height; ++y)
@@ -216,7 +235,9 @@ inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, ui
             for (uint32_t sy = 0; sy < s; ++sy)
                 for (uint32_t sx = 0; sx < s; ++sx) {
                     const uint64_t at = ((uint64_t)y * s + sy) * pitch + (uint64_t)x * s + sx;
-                    sum.add(smooth_source ? render_colour_smooth(pal, pal.entries, counts[at], smooth[at]) : pal.entries[bytes[at]]);
+                    sum.add(!smooth_source ? pal.entries[bytes[at]]
+                            : distance     ? render_colour_distance(pal, pal.entries, counts[at], smooth[at])
+                                           : render_colour_smooth(pal, pal.entries, counts[at], smooth[at]));
                 }
             const uint32_t c = sum.mean(s * s);
             uint8_t *o = rgba + ((uint64_t)y * width + x) * 4u;

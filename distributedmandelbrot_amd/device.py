@@ -381,6 +381,28 @@ class MandelbrotDevice:
         self._check(self._lib.mbk_view_launch_smooth(self._h, C.byref(cv), mrd, L.KERNELS[kernel],
                                                      d_counts or None, d_smooth, stream or None))
 
+    def compute_view_distance(self, view: View, mrd: int, *, window=None, kernel: str = "default"):
+        """Exterior distance estimates (not in the reference; include/mbk.h, "Distance estimates"): de = 2 |z| ln |z| / |dz/dc|
+        in complex-plane units, evaluated after the orbit has run on to |z|^2 >= 2^32, 0 for never-escaped pixels.  The counts
+        are those of compute_view.  kernel "asm" takes the one-pass form, every other selector computes the counts with that
+        kernel first and the derivative in a second pass; both store the same values.
+        Returns (distance float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
+        cv = self._cview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        dist = np.empty(shape, np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_compute_distance(self._h, C.byref(cv), mrd, L.KERNELS[kernel],
+                                                        counts.ctypes.data, dist.ctypes.data, C.byref(st)))
+        return dist, counts, _stats(st)
+
+    def launch_view_distance(self, view: View, mrd: int, *, d_distance: int, d_counts: int = 0, stream: int = 0,
+                             window=None, kernel: str = "default") -> None:
+        """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_view_launch_distance(self._h, C.byref(cv), mrd, L.KERNELS[kernel],
+                                                       d_counts or None, d_distance, stream or None))
+
     def serialize_last(self) -> Tuple[bytes, int]:
         """The last tile's quantised bytes exactly as DataChunk.Serialize (DataChunk.cs:173-206) would
         write them (code byte + Raw or RLE payload, the shorter; Raw on ties), encoded on the GPU.
@@ -504,8 +526,8 @@ class MandelbrotDevice:
     def render_view(self, view: View, mrd: int, *, palette, source: str = "smooth", supersample: int = 1, window=None,
                     kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None):
         """The view as an RGBA8 image, coloured and anti-aliased on the GPU: (width * s) x (height * s) samples of the
-        same rectangle, each through `palette` (image.Palette; source "smooth": nu, "bytes": the quantised byte), s x s
-        of them averaged per pixel.  Only the image crosses PCIe.  `window` is in output pixels; `out` may be a
+        same rectangle, each through `palette` (image.Palette; source "smooth": nu, "bytes": the quantised byte,
+        "distance": the exterior distance estimate, palette not cyclic -- Palette.distance), s x s of them averaged per pixel.  Only the image crosses PCIe.  `window` is in output pixels; `out` may be a
         (pinned) uint8 array of the window's size.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples);
         row 0 is the lowest imaginary part."""
         cv = self._cview(view, window)
@@ -518,7 +540,8 @@ class MandelbrotDevice:
 
     def render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, source: str = "smooth",
                          supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
-        """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height."""
+        """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height.
+        Source "distance" is refused (MbkError): deep views carry no derivative."""
         cv = self._cdeep(view, window)
         rgba = self._render_out(cv, out)
         spec = palette.spec(source, supersample, max_band_rows)

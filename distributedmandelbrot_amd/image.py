@@ -19,7 +19,9 @@ from . import _lib as L
 class Palette:
     """n RGBA8 entries plus, for source "smooth", the colour of never-escaping samples and the map from the smooth value
     nu to a palette position, t = nu * scale + offset (entries are blended linearly and the palette is cyclic).
-    Source "bytes" takes 256 entries, indexed by the quantised byte; `inside`, `scale` and `offset` are not used there."""
+    Source "bytes" takes 256 entries, indexed by the quantised byte; `inside`, `scale` and `offset` are not used there.
+    Source "distance" maps the distance estimate de the same way, t = de * scale + offset, but the palette does not wrap:
+    t >= n - 1 is the last entry (Palette.distance / for_distance set scale from a view's pixel pitch)."""
     entries: np.ndarray
     inside: Tuple[int, int, int, int] = (0, 0, 0, 255)
     scale: float = 1.0
@@ -66,6 +68,34 @@ class Palette:
             e[:, c] = np.floor(np.interp(x, np.arange(len(s)), s[:, c]) + 0.5).astype(np.uint8)
         e[:, 3] = 255
         return Palette(e, inside=inside, scale=n / float(period))
+
+    def for_distance(self, view, width_px: float, *, inner_px: float = 0.0) -> "Palette":
+        """This palette stretched over distances of inner_px .. width_px OUTPUT pixels of `view` for source "distance":
+        scale = (n - 1) / ((width_px - inner_px) pitch), pitch the view's sample spacing (range_r / (width - 1)), and
+        offset = -inner_px (n - 1) / (width_px - inner_px).  Samples nearer than inner_px take entry 0, samples beyond
+        width_px the last entry."""
+        if not width_px > inner_px >= 0.0:
+            raise ValueError("0 <= inner_px < width_px")
+        if view.width > 1:
+            pitch = abs(view.range_r) / (view.width - 1)
+        else:
+            pitch = abs(view.range_i) / max(view.height - 1, 1)
+        if not pitch > 0.0:
+            raise ValueError("the view has no pixel pitch")
+        span = float(width_px) - float(inner_px)
+        return Palette(self.entries, self.inside, (len(self) - 1) / (span * pitch), -float(inner_px) * (len(self) - 1) / span)
+
+    @staticmethod
+    def distance(view, width_px: float = 8.0, *, inner_px: float = 0.0, near=(0, 0, 0), far=(255, 255, 255), n: int = 256,
+                 inside=(0, 0, 0, 255)) -> "Palette":
+        """A ramp of n entries from `near` to `far` for source "distance": `near` within inner_px output pixels of the set,
+        `far` beyond width_px -- Palette.distance(view, 8, inner_px=1) is black within 1 px of the set and white beyond 8."""
+        x = np.arange(n, dtype=np.float64)[:, None] / (n - 1)
+        rgb = (1.0 - x) * np.asarray(near, np.float64)[None, :] + x * np.asarray(far, np.float64)[None, :]
+        e = np.empty((n, 4), np.uint8)
+        e[:, :3] = np.floor(rgb + 0.5).astype(np.uint8)
+        e[:, 3] = 255
+        return Palette(e, inside=inside).for_distance(view, width_px, inner_px=inner_px)
 
     def spec(self, source: str, supersample: int, max_band_rows: int = 0) -> L.mbk_render_spec:
         """The C struct; it points into self.entries, which the caller keeps alive for the call."""

@@ -197,6 +197,57 @@ int mbk_view_launch_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uin
 int mbk_view_compute_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
                             int32_t *h_counts, double *h_smooth, mbk_stats *stats);
 
+/*
+ * Exterior distance estimates for plain views.  NOT in the reference; additive (the ABI version stays 5): no existing call
+ * changes.  The derivative d = dz/dc is carried along the orbit and the pixel reports
+ *     de = 2 |z| ln |z| / |d|,
+ * a length in the complex plane within a known factor of the true distance from c to the set (for a point outside, the
+ * distance lies between de / 4 and about de; Koebe's quarter theorem gives de <= 4 x distance).
+ *
+ * Contract (tests/distance_model.py restates it in numpy; tests/test_gpu_distance.py holds the GPU to it).  For a pixel with
+ * coordinate c = (cr, ci) of a view (the linspace of mbk_view), binary64, every operation rounded on its own:
+ *   state     z_0 = c, d_0 = (1, 0).  Step k -> k + 1, for the same steps the count loop runs (at most mrd - 1 updates):
+ *               u = fl(fl(zr dr) - fl(zi di)), v = fl(fl(zr di) + fl(zi dr))   both from z_k and d_k
+ *               dr' = fl(2u + 1), di' = 2v      (2u and 2v are exact, subnormals included, so fma(u, 2, 1) IS fl(2u + 1); where 2u
+ *                                                overflows, fl(2u + 1) and fl(fl(2u) + 1) are the same infinity: no case differs)
+ *               z_(k+1) by the recurrence of mbk_view_launch, unchanged.
+ *   count     n is exactly the count of mbk_view_launch (first k with |z_k|^2 >= 4, 0 if none; c is never tested).
+ *   run-on    a pixel with n > 0 runs on, uncounted, with the same two recurrences until mag = fl(fl(zr^2) + fl(zi^2)) >= 2^32 or
+ *             64 further steps have run, whichever comes first (these steps may go past mrd - 1; n does not change).  At the
+ *             reference's bailout radius 2 the formula is useless near the set: on c = -2 - t it reads 12 to 9e5 times the
+ *             true distance t at the step that trips `>= 4`, and 3.885 t .. 4 t at 2^32.  Next to c = -2 the excess over
+ *             |z| = 2 only triples per step (13 further steps at t = 1e-6, ~34 at 1e-16), hence 64 and not 8.
+ *   output    de = fl(fl(sqrt(fl(mag / dmag))) fl(ln mag)), dmag = fl(fl(dr^2) + fl(di^2)), at the final state; 0 if n = 0.
+ *             ln is the device's (ocml); division and square root are the correctly rounded ones.  Against the correctly rounded
+ *             value of the expression at (mag, dmag) the tests allow the host (glibc) what tests/distance_model.py measures,
+ *             and the device one ulp more.
+ *   special   never NaN: where the expression is NaN (mag = dmag = inf; a NaN in d after inf - inf) 0 is stored.  Infinities are
+ *             stored as IEEE arithmetic gives them: mag = inf (|c| above ~1e77, n = 1) gives +inf; an overflowed dmag with a
+ *             finite mag gives 0; dmag = 0 gives +inf.  c = -2 itself (n = 1, z stays at 2 through the run-on) is finite.
+ *   mrd       0 and 1 run no step: every count and de is 0.
+ * Windows of a view are bit-identical to the whole view.
+ *
+ * Two designs are built in, selected by the kernel bits of `flags`, bit-identical in what they store:
+ *   MBK_KERNEL_DEFAULT / _SCAN / _GROUP   two passes: mbk_view_launch with that selector writes the counts (cycle test and all:
+ *             it retires the interior, which needs no derivative), then a derivative pass runs each pixel with n > 0 for exactly
+ *             n steps without a bailout test, plus the run-on.  With d_counts == NULL the counts live in scratch the ctx keeps
+ *             per stream (4 bytes per pixel of the largest such window).
+ *   MBK_KERNEL_ASM                        one pass: the derivative rides in a per-step escape loop; no counts are read.
+ * Asynchronous form on DEVICE pointers / caller's stream (window-sized buffers, nothing is written outside them) and synchronous
+ * form into HOST buffers on slot 0 (the slot-0 rule below applies; stats as for mbk_view_compute_smooth: pixel_iterations counts
+ * the reference's iterations, the run-on steps are not in it).  d_counts / h_counts may be NULL.  MBK_ERR_INVALID, with nothing
+ * written: NULL d_distance / h_distance, MBK_PRECISION_F32 in the flags of _launch_distance (there is no binary32 form;
+ * _compute_distance ignores every flag but the kernel), MBK_KERNEL_SIMPLE and MBK_KERNEL_REFILL, mrd >= 2^31, and whatever
+ * mbk_view_launch refuses in a view.  Deep views (the derivative of a perturbed orbit) are not implemented.
+ */
+int mbk_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                             int32_t *d_counts, double *d_distance, void *hip_stream);
+int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                              int32_t *h_counts, double *h_distance, mbk_stats *stats);
+/* "output" and "special" above on the HOST, compiled from the function the kernel uses (with the host's ln): no ctx, no
+ * device.  For the CPU tests. */
+double mbk_distance_value_host(double mag, double dmag, int32_t count);
+
 /* NOTE on slot 0: the synchronous calls (mbk_view_compute, mbk_datachunk, mbk_view_compute_smooth,
  * mbk_quantise_counts) and mbk_serialize_last work on slot 0's buffers; while a tile submitted on slot 0 has not
  * been waited for they return MBK_ERR_INVALID instead of touching them. */
@@ -354,16 +405,24 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
  */
 #define MBK_RENDER_BYTES 0u
 #define MBK_RENDER_SMOOTH 1u
+/* MBK_RENDER_DISTANCE (plain views only; a deep render refuses it): the samples are what mbk_view_launch_distance writes for
+ * the sample view (12 bytes per sample, banded like MBK_RENDER_SMOOTH).  Colour of a sample: `inside` if its count is 0;
+ * otherwise the MBK_RENDER_SMOOTH rule with de in place of nu -- t = fl(fl(de * scale) + offset), t = 0 unless 0 <= t --
+ * except that the palette does NOT wrap: t >= n - 1 (+inf included) gives p[n - 1], otherwise k = floor(t),
+ * f = floor((t - k) * 256) and p[k], p[k + 1] are blended as above.  2 <= n <= 65536, |offset| <= 2^20 and, for this source
+ * only, 0 < scale <= 2^80 (de of a view 1e-13 wide is ~1e-16: scale is in units of 1 / pitch).  mbk_render_resolve_host takes
+ * the source too, reading de through its `smooth` argument. */
+#define MBK_RENDER_DISTANCE 3u
 /* The most sample scratch a render keeps on one stream. */
 #define MBK_RENDER_BAND_BYTES (256u << 20)
 
 typedef struct mbk_render_spec {
-    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH */
+    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH | MBK_RENDER_DISTANCE */
     uint32_t supersample;   /* 1, 2, 3, 4, 8 */
     const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
     uint32_t palette_len;
-    uint8_t inside[4];      /* MBK_RENDER_SMOOTH: the colour of a sample that never escapes */
-    double scale, offset;   /* MBK_RENDER_SMOOTH; ignored (not validated) for MBK_RENDER_BYTES */
+    uint8_t inside[4];      /* MBK_RENDER_SMOOTH, _DISTANCE: the colour of a sample that never escapes */
+    double scale, offset;   /* MBK_RENDER_SMOOTH, _DISTANCE; ignored (not validated) for MBK_RENDER_BYTES */
     uint32_t max_band_rows; /* 0 = the library's choice; any value gives the same image */
 } mbk_render_spec;
 
