@@ -45,7 +45,9 @@ MBK_ABI_VERSION = 5
 MBK_RENDER_BYTES = 0
 MBK_RENDER_SMOOTH = 1
 MBK_RENDER_DISTANCE = 3
-RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH, "distance": MBK_RENDER_DISTANCE}
+MBK_RENDER_DISTANCE_REL = 4
+RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH, "distance": MBK_RENDER_DISTANCE,
+                  "distance_rel": MBK_RENDER_DISTANCE_REL}
 RENDER_SUPERSAMPLES = (1, 2, 3, 4, 8)
 MBK_RENDER_BAND_BYTES = 256 << 20
 # reason codes of an invalid chunk stream (include/mbk.h, "Stored chunks")
@@ -181,6 +183,11 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_deep_view_submit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                        C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_launch_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_compute_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_distance_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32]),
     "mbk_view_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
                                          C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
     "mbk_view_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,

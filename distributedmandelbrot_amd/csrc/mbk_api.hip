@@ -29,6 +29,7 @@
 #include "mbk_render.h"
 #include "mbk_chunks.h"
 #include "mbk_distance.h"
+#include "mbk_deep_distance.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -2322,6 +2323,106 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
     return MBK_OK;
 }
 
+// ---- distance estimates for deep views (mbk_deep_distance.h; mbk.h "Distance estimates for deep views") ----------------
+
+static void fill_deep_args(mbk::DeepArgs &a, const double4 *d_orbit, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd)
+{
+    std::memset(&a, 0, sizeof(a));
+    const std::vector<double> &t = orbit->o.table;
+    a.orbit = d_orbit;
+    a.z1 = make_double4(t[4], t[5], t[6], t[7]);
+    a.M = orbit->o.length;
+    a.half_r = (double)(v->width - 1u) * 0.5;
+    a.half_i = (double)(v->height - 1u) * 0.5;
+    a.step_r = deep_step(v->range_r, v->width);
+    a.step_i = deep_step(v->range_i, v->height);
+    a.col0 = v->col0;
+    a.row0 = v->row0;
+    a.ncols = v->ncols;
+    a.nrows = v->nrows;
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+}
+
+// the deep distance kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
+                                int32_t *d_counts, double *d_rel, hipStream_t stream)
+{
+    const double4 *d_orbit = nullptr;
+    int rc = deep_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepDistanceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_deep_args(a.v, d_orbit, orbit, v, mrd);
+    a.v.counts = d_counts;
+    a.range_r = v->range_r;
+    a.rel = d_rel;
+    const uint32_t blocks = a.v.blocks_x * ((v->nrows + 7u) / 8u);
+    hipLaunchKernelGGL(mbk::deep_distance_kernel, dim3(blocks), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_deep_view_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
+    int rc = validate_deep(ctx, orbit, view, mrd, 0u);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_deep_distance(ctx, orbit, view, mrd, d_counts, d_rel, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
+    int rc = validate_deep(ctx, orbit, view, mrd, 0u);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[0];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    const size_t px = (size_t)view->ncols * view->nrows;
+    rc = ensure_buffers(ctx, sl, px);
+    if (rc != MBK_OK) return rc;
+    if (px > ctx->smooth_cap_px) {
+        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
+        ctx->d_smooth = nullptr;
+        ctx->smooth_cap_px = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
+        ctx->smooth_cap_px = px;
+    }
+    // counts always go to the device: they feed the statistics
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+    rc = launch_deep_distance(ctx, orbit, view, mrd, sl.d_counts, ctx->d_smooth, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+    rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    MBK_HIP(ctx, hipMemcpyAsync(h_rel, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+    if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    ctx->last_px = 0;
+    if (stats) {
+        std::memset(stats, 0, sizeof(*stats));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+        fill_stats_from_reduce(sl, stats, false);
+    }
+    return MBK_OK;
+}
+
+double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count)
+{
+    return mbk::deep_distance_value(mag, dmagD, e, range_r, count);
+}
+
 // ---- rendering (mbk_render.h; mbk.h "Rendering") -----------------------------------------------------------
 
 static int validate_render_spec(mbk_ctx *ctx, const mbk_render_spec *spec)
@@ -2337,9 +2438,9 @@ static int validate_render_spec(mbk_ctx *ctx, const mbk_render_spec *spec)
             return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_SMOOTH takes a palette of 2 .. 65536 entries");
         if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^20]");
         if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
-    } else if (spec->source == MBK_RENDER_DISTANCE) {
+    } else if (spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL) {
         if (spec->palette_len < 2u || spec->palette_len > 65536u)
-            return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE takes a palette of 2 .. 65536 entries");
+            return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE / _DISTANCE_REL take a palette of 2 .. 65536 entries");
         if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p80)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^80]");
         if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
     } else {
@@ -2434,7 +2535,8 @@ static int render_check(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit
     if ((uint64_t)t->col0 + t->ncols > t->width || (uint64_t)t->row0 + t->nrows > t->height)
         return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
     const bool dist = spec->source == MBK_RENDER_DISTANCE;
-    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist;   // (the distance samples obey the smooth launch's rules)
+    const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel;   // (the distance samples obey the smooth launch's rules)
     mbk_view sv;
     mbk_deep_view sd;
     sample_window(*t, s, t->col0, t->row0, t->ncols, t->nrows, &sv, &sd);
@@ -2443,6 +2545,7 @@ static int render_check(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit
         if (flags) return fail(ctx, MBK_ERR_INVALID, "deep renders take no flags (no kernel selection, no fp32)");
         return validate_deep(ctx, orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
     }
+    if (rel) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)");
     if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
         return fail(ctx, MBK_ERR_INVALID, "render flags carry kernel selection (and MBK_PRECISION_F32) only");
     const bool f32 = (flags & MBK_PRECISION_F32) != 0;
@@ -2467,7 +2570,8 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
                       uint32_t *d_out, hipStream_t stream, Slot *stat)
 {
     const uint32_t s = spec->supersample;
-    const bool dist = spec->source == MBK_RENDER_DISTANCE;
+    const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;              // (deep views: rel in place of de, the same colour rule)
+    const bool dist = spec->source == MBK_RENDER_DISTANCE || rel;
     const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist;   // (same sample layout: binary64 value | counts)
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
@@ -2518,7 +2622,8 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             mbk_deep_view sd;
             sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
             if (t.deep) {
-                rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream);
+                rc = rel ? launch_deep_distance(ctx, t.orbit, &sd, mrd, d_counts, d_nu, stream)
+                         : launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream);
             } else if (dist) {
                 bool safe = false;
                 rc = distance_check(ctx, &sv, mrd, flags, &safe);
@@ -2680,7 +2785,7 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
     const uint32_t s = spec->supersample;
     if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
         return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
-    const bool dist = spec->source == MBK_RENDER_DISTANCE;
+    const bool dist = spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL;
     const bool sm = spec->source == MBK_RENDER_SMOOTH || dist;
     if (sm ? (!counts || !smooth) : !bytes) return fail(nullptr, MBK_ERR_INVALID, "the source's sample arrays are NULL");
     std::vector<uint32_t> words(spec->palette_len);

@@ -515,6 +515,27 @@ class MandelbrotDevice:
         self._check(self._lib.mbk_deep_view_launch(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None,
                                                    d_bytes or None, d_smooth or None, stream or None))
 
+    def compute_deep_view_distance(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None):
+        """Exterior distance estimates of a deep view (include/mbk.h, "Distance estimates for deep views"): the derivative is
+        carried as D 2^e, so it cannot overflow however deep the view, and the value is rel = de / span_r, the distance as a
+        fraction of the view's real span (rel * (width - 1) is the distance in pixels); 0 for never-escaped pixels.  The counts
+        are those of compute_deep_view.  Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
+        cv = self._cdeep(view, window)
+        shape = (cv.nrows, cv.ncols)
+        rel = np.empty(shape, np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_view_compute_distance(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
+                                                             rel.ctypes.data, C.byref(st)))
+        return rel, counts, _stats(st)
+
+    def launch_deep_view_distance(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
+                                  stream: int = 0, window=None) -> None:
+        """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cdeep(view, window)
+        self._check(self._lib.mbk_deep_view_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
+                                                            d_rel or None, stream or None))
+
     # -- rendering (include/mbk.h, "Rendering") ---------------------------------------------------
     def _render_out(self, cv, out):
         shape = (cv.nrows, cv.ncols, 4)
@@ -541,7 +562,8 @@ class MandelbrotDevice:
     def render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, source: str = "smooth",
                          supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
         """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height.
-        Source "distance" is refused (MbkError): deep views carry no derivative."""
+        Source "distance_rel" colours the deep distance estimate (compute_deep_view_distance; Palette.deep_distance); source
+        "distance", the plain views' estimate in plane units, is refused (MbkError)."""
         cv = self._cdeep(view, window)
         rgba = self._render_out(cv, out)
         spec = palette.spec(source, supersample, max_band_rows)

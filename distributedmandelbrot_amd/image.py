@@ -21,7 +21,8 @@ class Palette:
     nu to a palette position, t = nu * scale + offset (entries are blended linearly and the palette is cyclic).
     Source "bytes" takes 256 entries, indexed by the quantised byte; `inside`, `scale` and `offset` are not used there.
     Source "distance" maps the distance estimate de the same way, t = de * scale + offset, but the palette does not wrap:
-    t >= n - 1 is the last entry (Palette.distance / for_distance set scale from a view's pixel pitch)."""
+    t >= n - 1 is the last entry (Palette.distance / for_distance set scale from a view's pixel pitch).  Source "distance_rel"
+    (deep views) does the same with the distance as a fraction of the view's span (Palette.deep_distance / for_deep_distance)."""
     entries: np.ndarray
     inside: Tuple[int, int, int, int] = (0, 0, 0, 255)
     scale: float = 1.0
@@ -90,12 +91,35 @@ class Palette:
                  inside=(0, 0, 0, 255)) -> "Palette":
         """A ramp of n entries from `near` to `far` for source "distance": `near` within inner_px output pixels of the set,
         `far` beyond width_px -- Palette.distance(view, 8, inner_px=1) is black within 1 px of the set and white beyond 8."""
+        return Palette(Palette._ramp(near, far, n), inside=inside).for_distance(view, width_px, inner_px=inner_px)
+
+    def for_deep_distance(self, view, width_px: float, *, inner_px: float = 0.0) -> "Palette":
+        """for_distance for a DeepView and source "distance_rel", whose samples are fractions of the view's real span: one
+        OUTPUT pixel is 1 / (width - 1) of it, so scale = (n - 1) (width - 1) / (width_px - inner_px) and
+        offset = -inner_px (n - 1) / (width_px - inner_px), whatever the span and the supersampling factor."""
+        if not width_px > inner_px >= 0.0:
+            raise ValueError("0 <= inner_px < width_px")
+        if view.width > 1:
+            per_px = float(view.width - 1)
+        else:   # a single column: the rows' pitch, in units of span_r
+            per_px = max(view.height - 1, 1) * (view.span_r / view.span_i)
+        span = float(width_px) - float(inner_px)
+        return Palette(self.entries, self.inside, (len(self) - 1) * per_px / span, -float(inner_px) * (len(self) - 1) / span)
+
+    @staticmethod
+    def deep_distance(view, width_px: float = 8.0, *, inner_px: float = 0.0, near=(0, 0, 0), far=(255, 255, 255), n: int = 256,
+                      inside=(0, 0, 0, 255)) -> "Palette":
+        """Palette.distance for a DeepView and source "distance_rel"."""
+        return Palette(Palette._ramp(near, far, n), inside=inside).for_deep_distance(view, width_px, inner_px=inner_px)
+
+    @staticmethod
+    def _ramp(near, far, n: int) -> np.ndarray:
         x = np.arange(n, dtype=np.float64)[:, None] / (n - 1)
         rgb = (1.0 - x) * np.asarray(near, np.float64)[None, :] + x * np.asarray(far, np.float64)[None, :]
         e = np.empty((n, 4), np.uint8)
         e[:, :3] = np.floor(rgb + 0.5).astype(np.uint8)
         e[:, 3] = 255
-        return Palette(e, inside=inside).for_distance(view, width_px, inner_px=inner_px)
+        return e
 
     def spec(self, source: str, supersample: int, max_band_rows: int = 0) -> L.mbk_render_spec:
         """The C struct; it points into self.entries, which the caller keeps alive for the call."""

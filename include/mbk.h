@@ -238,7 +238,8 @@ int mbk_view_compute_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, ui
  * the reference's iterations, the run-on steps are not in it).  d_counts / h_counts may be NULL.  MBK_ERR_INVALID, with nothing
  * written: NULL d_distance / h_distance, MBK_PRECISION_F32 in the flags of _launch_distance (there is no binary32 form;
  * _compute_distance ignores every flag but the kernel), MBK_KERNEL_SIMPLE and MBK_KERNEL_REFILL, mrd >= 2^31, and whatever
- * mbk_view_launch refuses in a view.  Deep views (the derivative of a perturbed orbit) are not implemented.
+ * mbk_view_launch refuses in a view.  Deep views have a form of their own, with a derivative whose exponent cannot overflow
+ * and the view's span as the unit: mbk_deep_view_launch_distance, below ("Distance estimates for deep views").
  */
 int mbk_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
                              int32_t *d_counts, double *d_distance, void *hip_stream);
@@ -362,6 +363,56 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes);
 
 /*
+ * Distance estimates for deep views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes, and
+ * the plain-view contract above keeps its rule (dmag = |d|^2 overflows once |d| passes 1e154 and de is then 0).  |dz/dc| at
+ * escape is of the order of 1 / (distance to the set): a view 1e-200 wide has |d| ~ 1e200 on every escaped pixel.  So the
+ * derivative is carried as d = D 2^e with an integer e per pixel, and the value is reported as a fraction of the view's span.
+ *
+ * Contract (tests/deep_distance_model.py restates it in numpy; tests/test_gpu_deep_distance.py holds the GPU to it).
+ * Everything of "Deep-zoom views" stands: orbit table, offsets dc, the step, rebasing, the count.  Added per pixel, binary64,
+ * every operation rounded on its own:
+ *   state     zp = the pixel's full z of the previous step, (Dr, Di) and an integer e with d = D 2^e.
+ *             Start: zp = (fl(Z_1.r + dc.r), fl(Z_1.i + dc.i)) (z_0 = c), D = (1, 0), e = 0 -- the plain contract's d_0 = 1.
+ *   step i    before the z step of the deep contract:
+ *               u = fl(fl(zp.r Dr) - fl(zp.i Di)), v = fl(fl(zp.r Di) + fl(zp.i Dr)), Dr = fl(2u + one), Di = 2v,
+ *               one = ldexp(1, -e) as a binary64 (subnormal, then 0, once e passes 1022);
+ *             then, if max(|Dr|, |Di|) >= 2^256: Dr = fl(Dr 2^-256), Di = fl(Di 2^-256) (exact unless the smaller component
+ *             turns subnormal), e = min(e + 256, 2^30).  Tested on EVERY step.  e never decreases; the cap only keeps the
+ *             integer from wrapping (rel is 0 from e ~ 2200 on, with or without it).
+ *             Then the deep step unchanged; zp becomes the z = fl(Z_m + dz) that step computes for its bailout test (after a
+ *             rebase dz = z, so zp is the same value either way).  |D| < 2^256 and |zp| < 2^16.5: nothing overflows.
+ *   count     n is exactly the count of mbk_deep_view_launch.
+ *   run-on    a pixel with n > 0 first applies the deep step's rebase rule to the escaping step's state (mag < |dz|^2 or
+ *             m == M: dz = z, m = 0 -- the count loop stops before it), then goes on, uncounted, with the same two recurrences
+ *             (rebasing included, m == M included: m < M at the top of every step) until mag >= 2^32 or 64 further steps have
+ *             run, as for plain views and for the reason given there.  mag is then at most ~2^64.
+ *   output    the distance as a FRACTION OF THE VIEW'S REAL SPAN, rel = de / range_r, not a length in the plane (a length at
+ *             span 2^-960 is near the bottom of binary64, and a render's scale, <= 2^80 per unit, could not reach it).  With
+ *             range_r = f 2^k, 0.5 <= f < 1 (frexp), and dmagD = fl(fl(Dr^2) + fl(Di^2)) (below 2^513: no overflow),
+ *               rel = ldexp(fl(fl(fl(sqrt(fl(mag / dmagD))) fl(ln mag)) / f), -(e + k)),
+ *             ldexp rounding once where the result is subnormal.  0 if n = 0; never NaN (0 instead); dmagD = 0 gives +inf.
+ *             ln is the device's (ocml), division and square root the correctly rounded ones.  The unit is the same for every
+ *             window of a view and for every supersampling factor of a render (the sample view has the same range_r).
+ *   mrd       0 and 1 run no step: every count and value is 0.
+ * Windows of a view are bit-identical to the whole view.
+ * Known limit: centres within ~1e-16 of -2 stay wrong, as their counts are ("Deep-zoom views", above).
+ *
+ * One pass: the derivative rides in the deep loop (csrc/mbk_deep_distance.h).  _launch_distance: DEVICE pointers on the caller's
+ * stream (window-sized buffers, nothing is written outside them; no statistics).  _compute_distance: synchronous into HOST
+ * buffers on slot 0 (the slot-0 rule applies), stats as for mbk_deep_view_compute (the run-on steps are not counted).
+ * d_counts / h_counts may be NULL.  MBK_ERR_INVALID, with nothing written: a NULL d_rel / h_rel, any flag (there is no kernel
+ * selection, no fp32, no MBK_LAZY_UNIFORM; MBK_WANT_* are not used either: the pointers select the outputs), and whatever
+ * mbk_deep_view_launch refuses (NULL orbit, empty or oversized window, ranges outside [2^-960, 4], mrd > the orbit's mrd).
+ */
+int mbk_deep_view_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
+int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats);
+/* "output" above on the HOST, compiled from the function the kernel uses (with the host's ln): no ctx, no device.  For the
+ * CPU tests. */
+double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count);
+
+/*
  * Rendering: a view to an RGBA8 image on the device, with a palette and supersampling.  Replaces, for a view of any kind,
  * what the reference's Viewer does on the host for a chunk (DistributedMandelbrotViewer.py:110-135, data_to_img_array: the
  * bytes through matplotlib's jet, black where the byte is 0) -- mbk_palette_viewer is that colouring as a palette.  Additive
@@ -405,7 +456,7 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
  */
 #define MBK_RENDER_BYTES 0u
 #define MBK_RENDER_SMOOTH 1u
-/* MBK_RENDER_DISTANCE (plain views only; a deep render refuses it): the samples are what mbk_view_launch_distance writes for
+/* MBK_RENDER_DISTANCE (plain views only; a deep render refuses it and takes MBK_RENDER_DISTANCE_REL): the samples are what mbk_view_launch_distance writes for
  * the sample view (12 bytes per sample, banded like MBK_RENDER_SMOOTH).  Colour of a sample: `inside` if its count is 0;
  * otherwise the MBK_RENDER_SMOOTH rule with de in place of nu -- t = fl(fl(de * scale) + offset), t = 0 unless 0 <= t --
  * except that the palette does NOT wrap: t >= n - 1 (+inf included) gives p[n - 1], otherwise k = floor(t),
@@ -413,11 +464,17 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
  * only, 0 < scale <= 2^80 (de of a view 1e-13 wide is ~1e-16: scale is in units of 1 / pitch).  mbk_render_resolve_host takes
  * the source too, reading de through its `smooth` argument. */
 #define MBK_RENDER_DISTANCE 3u
+/* MBK_RENDER_DISTANCE_REL (deep renders only; a plain render refuses it): the samples are what mbk_deep_view_launch_distance
+ * writes for the sample view (12 bytes per sample, banded like MBK_RENDER_SMOOTH): rel, the distance as a fraction of the
+ * view's real span, the same unit at every supersampling factor.  Colour: the MBK_RENDER_DISTANCE rule with rel in place of
+ * de (no wrap, `inside` for count 0, 0 < scale <= 2^80): a ramp over w output pixels of a W-wide view has
+ * scale = (n - 1)(W - 1) / w.  mbk_render_resolve_host takes the source too. */
+#define MBK_RENDER_DISTANCE_REL 4u
 /* The most sample scratch a render keeps on one stream. */
 #define MBK_RENDER_BAND_BYTES (256u << 20)
 
 typedef struct mbk_render_spec {
-    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH | MBK_RENDER_DISTANCE */
+    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH | MBK_RENDER_DISTANCE | MBK_RENDER_DISTANCE_REL */
     uint32_t supersample;   /* 1, 2, 3, 4, 8 */
     const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
     uint32_t palette_len;
