@@ -17,8 +17,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libmbk_hip.so")
 SOURCES = [os.path.join(CSRC, "mbk_api.hip")]
-DEPS = SOURCES + [os.path.join(CSRC, "mbk_kernels.h"), os.path.join(CSRC, "mbk_refill.h"), os.path.join(CSRC, "mbk_loops.inc"), os.path.join(CSRC, "mbk_persist.h"), os.path.join(CSRC, "mbk_scan.h"), os.path.join(CSRC, "mbk_units.h"), os.path.join(CSRC, "mbk_spill.h"), os.path.join(CSRC, "mbk_feeder.h"), os.path.join(CSRC, "mbk_deep_orbit.h"), os.path.join(CSRC, "mbk_deep.h"), os.path.join(CSRC, "mbk_render.h"), os.path.join(CSRC, "mbk_chunks.h"), os.path.join(CSRC, "mbk_distance.h"), os.path.join(CSRC, "mbk_deep_distance.h"),
-                  os.path.join(os.path.dirname(HERE), "include", "mbk.h")]
+DEPS = (SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
+        + [os.path.join(os.path.dirname(HERE), "include", "mbk.h")])
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
          "-fPIC", "-shared", "-Wall", "-Wno-unused-result"]
 

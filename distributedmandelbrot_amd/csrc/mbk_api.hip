@@ -1093,6 +1093,18 @@ static int launch_scan_t(mbk_ctx *ctx, TileArgs a, bool safe, hipStream_t stream
     return MBK_OK;
 }
 
+// The axes and the window of `v` in a kernel's arguments (TileArgs, DistanceArgs: the same fields)
+template <typename Args>
+static void fill_window(Args &a, const mbk_view *v)
+{
+    a.re = make_axis(v->start_r, v->range_r, v->width);
+    a.im = make_axis(v->start_i, v->range_i, v->height);
+    a.col0 = v->col0;
+    a.row0 = v->row0;
+    a.ncols = v->ncols;
+    a.nrows = v->nrows;
+}
+
 static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags,
                        int32_t *d_counts, uint8_t *d_bytes, hipStream_t stream, double *d_smooth = nullptr,
                        ReduceSlot *fuse = nullptr, bool counts_unwanted = false, bool *fused = nullptr)
@@ -1115,12 +1127,7 @@ static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t f
 
     TileArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.re = make_axis(v->start_r, v->range_r, v->width);
-    a.im = make_axis(v->start_i, v->range_i, v->height);
-    a.col0 = v->col0;
-    a.row0 = v->row0;
-    a.ncols = v->ncols;
-    a.nrows = v->nrows;
+    fill_window(a, v);
     a.out_pitch = v->ncols;
     a.out_col0 = 0;
     a.out_row0 = 0;
@@ -1181,18 +1188,31 @@ static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t f
     return MBK_OK;
 }
 
+// Grow the device buffer `p` of capacity `cap` (in the caller's unit: pixels, bytes) to `need` of them, which take `bytes`
+// bytes.  Free, clear pointer and capacity, allocate, set the capacity -- in this order, so that a failed hipMalloc leaves
+// no dangling pointer with a stale capacity.  (hipFree waits for the launches that may still read the old buffer.)
+template <typename T>
+static int grow(mbk_ctx *ctx, T *&p, size_t &cap, size_t need, size_t bytes)
+{
+    if (need <= cap) return MBK_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    MBK_HIP(ctx, hipMalloc((void **)&p, bytes));
+    cap = need;
+    return MBK_OK;
+}
+
+// counts and bytes of a slot, both under cap_px: it is zero until both exist
 static int ensure_buffers(mbk_ctx *ctx, Slot &sl, size_t px)
 {
     if (px <= sl.cap_px) return MBK_OK;
-    if (sl.d_counts) (void)hipFree(sl.d_counts);
-    if (sl.d_bytes) (void)hipFree(sl.d_bytes);
-    sl.d_counts = nullptr;
-    sl.d_bytes = nullptr;
+    size_t cap_counts = 0, cap_bytes = 0;
     sl.cap_px = 0;
-    MBK_HIP(ctx, hipMalloc((void **)&sl.d_counts, px * sizeof(int32_t)));
-    MBK_HIP(ctx, hipMalloc((void **)&sl.d_bytes, px));
-    sl.cap_px = px;
-    return MBK_OK;
+    int rc = grow(ctx, sl.d_counts, cap_counts, px, px * sizeof(int32_t));
+    if (rc == MBK_OK) rc = grow(ctx, sl.d_bytes, cap_bytes, px, px);
+    if (rc == MBK_OK) sl.cap_px = px;
+    return rc;
 }
 
 // clear = false: the partial results were zeroed earlier on this stream and a tile kernel has already added its fused
@@ -1258,9 +1278,76 @@ static void fill_stats_from_reduce(const ReduceSlot *h_red, mbk_stats *s, bool h
     s->all_bytes_one = have_bytes && t.any_byte_not_one == 0 ? 1u : 0u;
     s->rle_runs = have_bytes ? t.run_starts : 0ull;
 }
-static void fill_stats_from_reduce(const Slot &sl, mbk_stats *s, bool have_bytes)
+
+// The statistics of a finished slot (its stream has been synchronised): the times between its events and, if `reduced`,
+// the totals of its reduction scratch.
+static int slot_stats(mbk_ctx *ctx, const Slot &sl, mbk_stats *stats, bool have_bytes, bool reduced = true)
 {
-    fill_stats_from_reduce(sl.h_red, s, have_bytes);
+    std::memset(stats, 0, sizeof(*stats));
+    MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
+    MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
+    if (reduced) fill_stats_from_reduce(sl.h_red, stats, have_bytes);
+    return MBK_OK;
+}
+
+// ---- the synchronous calls (mbk_*_compute*, DESIGN.md "A synchronous call") ------------------------------------------
+// They run on slot 0 -- its stream, buffers, events and reduction scratch -- and are made of three parts: the entry point's
+// own refusals and sync_begin; an enqueue step that returns a status and never waits; sync_end on that status.
+
+static int sync_begin(mbk_ctx *ctx)
+{
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->s[0].busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    return MBK_OK;
+}
+
+// rc: what the enqueue step returned.  A failure may have left work queued that still writes into the slot's and the ctx'
+// buffers: the stream is drained before the status goes back (the error text is already in place).  Otherwise wait and
+// fill `stats` (may be NULL); have_bytes / reduced as for slot_stats.
+static int sync_end(mbk_ctx *ctx, int rc, mbk_stats *stats, bool have_bytes, bool reduced = true)
+{
+    Slot &sl = ctx->s[0];
+    if (rc != MBK_OK) {
+        (void)hipStreamSynchronize(sl.stream);
+        return rc;
+    }
+    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    return stats ? slot_stats(ctx, sl, stats, have_bytes, reduced) : MBK_OK;
+}
+
+// The calls that return one binary64 value per pixel (smooth, distance, deep distance) between sync_begin and the return:
+// launch(d_counts, d_values, stream) enqueues the kernels that write both.
+template <typename Launch>
+static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch)
+{
+    Slot &sl = ctx->s[0];
+    auto enqueue = [&]() -> int {
+        int rc = ensure_buffers(ctx, sl, px);
+        if (rc != MBK_OK) return rc;
+        rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, px, px * sizeof(double));
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+        rc = launch(sl.d_counts, ctx->d_smooth, sl.stream);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+        rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        ctx->last_px = 0;   // (no bytes on the device: mbk_serialize_last has nothing to read)
+        return MBK_OK;
+    };
+    return sync_end(ctx, enqueue(), stats, false);
+}
+
+// MBK_WANT_* flags need the pointers they fill
+static int check_wanted(mbk_ctx *ctx, uint32_t flags, const void *counts, const void *bytes)
+{
+    if ((flags & MBK_WANT_COUNTS) && !counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
+    if ((flags & MBK_WANT_BYTES) && !bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    return MBK_OK;
 }
 
 // ------------------------------------- C ABI ---------------------------------------------------
@@ -1479,12 +1566,7 @@ static TileArgs view_window_args(const mbk_view *v)
 {
     TileArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.re = make_axis(v->start_r, v->range_r, v->width);
-    a.im = make_axis(v->start_i, v->range_i, v->height);
-    a.col0 = v->col0;
-    a.row0 = v->row0;
-    a.ncols = v->ncols;
-    a.nrows = v->nrows;
+    fill_window(a, v);
     return a;
 }
 
@@ -1511,10 +1593,10 @@ static int submit_view(mbk_ctx *ctx, Slot &sl, const mbk_view *view, uint32_t mr
 {
     if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
     const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    if (wc && !h_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
-    if (wb && !h_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    int rc = check_wanted(ctx, flags, h_counts, h_bytes);
+    if (rc != MBK_OK) return rc;
     bool dummy;
-    int rc = validate_view(ctx, view, &dummy, (flags & MBK_PRECISION_F32) != 0);
+    rc = validate_view(ctx, view, &dummy, (flags & MBK_PRECISION_F32) != 0);
     if (rc != MBK_OK) return rc;
     const size_t px = (size_t)view->ncols * view->nrows;
     const bool lazy = wb && (flags & MBK_LAZY_UNIFORM) != 0;
@@ -1597,13 +1679,7 @@ static int wait_slot(mbk_ctx *ctx, Slot &sl, mbk_stats *stats)
             MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
         }
     }
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-        fill_stats_from_reduce(sl, stats, sl.with_bytes);
-    }
-    return MBK_OK;
+    return stats ? slot_stats(ctx, sl, stats, sl.with_bytes) : MBK_OK;
 }
 
 static void datachunk_view(mbk_view *v, double sr, double si, double range)
@@ -1712,43 +1788,15 @@ int mbk_view_compute_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, ui
                             int32_t *h_counts, double *h_smooth, mbk_stats *stats)
 {
     if (!ctx || !view || !h_smooth) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    // the synchronous calls run on slot 0: its buffers, events and reduction scratch belong to a tile in flight
-    if (ctx->s[0].busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    int rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
     bool dummy;
-    int rc = validate_view(ctx, view, &dummy);
+    rc = validate_view(ctx, view, &dummy);
     if (rc != MBK_OK) return rc;
-    const size_t px = (size_t)view->ncols * view->nrows;
-    rc = ensure_buffers(ctx, ctx->s[0], px);
-    if (rc != MBK_OK) return rc;
-    if (px > ctx->smooth_cap_px) {
-        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
-        ctx->d_smooth = nullptr;
-        ctx->smooth_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
-        ctx->smooth_cap_px = px;
-    }
-    MBK_HIP(ctx, hipEventRecord(ctx->s[0].ev_k0, ctx->s[0].stream));
-    rc = launch_tile(ctx, view, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, ctx->s[0].d_counts, nullptr,
-                     ctx->s[0].stream, ctx->d_smooth);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(ctx->s[0].ev_k1, ctx->s[0].stream));
-    rc = launch_reduce(ctx, ctx->s[0], ctx->s[0].d_counts, nullptr, px, mrd, ctx->s[0].stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(ctx->s[0].ev_c0, ctx->s[0].stream));
-    MBK_HIP(ctx, hipMemcpyAsync(h_smooth, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, ctx->s[0].stream));
-    if (h_counts)
-        MBK_HIP(ctx, hipMemcpyAsync(h_counts, ctx->s[0].d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->s[0].stream));
-    MBK_HIP(ctx, hipEventRecord(ctx->s[0].ev_c1, ctx->s[0].stream));
-    MBK_HIP(ctx, hipStreamSynchronize(ctx->s[0].stream));
-    ctx->last_px = 0;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, ctx->s[0].ev_k0, ctx->s[0].ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, ctx->s[0].ev_c0, ctx->s[0].ev_c1));
-        fill_stats_from_reduce(ctx->s[0], stats, false);
-    }
-    return MBK_OK;
+    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_smooth, stats,
+                          [&](int32_t *d_counts, double *d_smooth, hipStream_t stream) {
+                              return launch_tile(ctx, view, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, d_counts, nullptr, stream, d_smooth);
+                          });
 }
 
 // ---- distance estimates (mbk_distance.h; mbk.h "Distance estimates") ---------------------------------------------------
@@ -1779,14 +1827,8 @@ static int launch_distance(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32
         if (!d_counts) {
             StreamScratch *sc = nullptr;
             int rc = get_scratch(ctx, stream, &sc);
+            if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
             if (rc != MBK_OK) return rc;
-            if (px > sc->dist_cap_px) {
-                if (sc->d_dist_counts) (void)hipFree(sc->d_dist_counts);   // (hipFree waits for the launches that may still read it)
-                sc->d_dist_counts = nullptr;
-                sc->dist_cap_px = 0;
-                MBK_HIP(ctx, hipMalloc((void **)&sc->d_dist_counts, px * sizeof(int32_t)));
-                sc->dist_cap_px = px;
-            }
             d_counts = sc->d_dist_counts;
         }
         int rc = launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
@@ -1794,12 +1836,7 @@ static int launch_distance(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32
     }
     mbk::DistanceArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.re = make_axis(v->start_r, v->range_r, v->width);
-    a.im = make_axis(v->start_i, v->range_i, v->height);
-    a.col0 = v->col0;
-    a.row0 = v->row0;
-    a.ncols = v->ncols;
-    a.nrows = v->nrows;
+    fill_window(a, v);
     a.blocks_x = (v->ncols + 7u) / 8u;
     a.mrd = (int32_t)mrd;
     a.counts_in = one_pass ? nullptr : d_counts;
@@ -1835,39 +1872,12 @@ int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, 
     bool safe = false;
     int rc = distance_check(ctx, view, mrd, flags & MBK_KERNEL_MASK, &safe);
     if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    // the synchronous calls run on slot 0: its buffers, events and reduction scratch belong to a tile in flight
-    Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
-    const size_t px = (size_t)view->ncols * view->nrows;
-    rc = ensure_buffers(ctx, sl, px);
+    rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
-    if (px > ctx->smooth_cap_px) {
-        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
-        ctx->d_smooth = nullptr;
-        ctx->smooth_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
-        ctx->smooth_cap_px = px;
-    }
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-    rc = launch_distance(ctx, view, mrd, flags & MBK_KERNEL_MASK, safe, sl.d_counts, ctx->d_smooth, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-    rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    MBK_HIP(ctx, hipMemcpyAsync(h_distance, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-    if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
-    ctx->last_px = 0;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-        fill_stats_from_reduce(sl, stats, false);
-    }
-    return MBK_OK;
+    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_distance, stats,
+                          [&](int32_t *d_counts, double *d_distance, hipStream_t stream) {
+                              return launch_distance(ctx, view, mrd, flags & MBK_KERNEL_MASK, safe, d_counts, d_distance, stream);
+                          });
 }
 
 double mbk_distance_value_host(double mag, double dmag, int32_t count)
@@ -1878,8 +1888,8 @@ double mbk_distance_value_host(double mag, double dmag, int32_t count)
 int mbk_serialize_last(mbk_ctx *ctx, uint8_t *h_out, uint64_t cap, uint64_t *size, uint32_t *codec)
 {
     if (!ctx || !h_out || !size || !codec) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->s[0].busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
+    int rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
     const size_t n = ctx->last_px;
     if (n == 0) return fail(ctx, MBK_ERR_INVALID, "no tile with quantised bytes has been computed on this ctx");
     const uint32_t nblocks = (uint32_t)((n + mbk::kRleBlock - 1) / mbk::kRleBlock);
@@ -1890,13 +1900,8 @@ int mbk_serialize_last(mbk_ctx *ctx, uint8_t *h_out, uint64_t cap, uint64_t *siz
     const size_t off_cnt = 0, off_tot = align(off_cnt + (size_t)nblocks * 4), off_start = align(off_tot + 8),
                  off_val = align(off_start + max_runs * 4), off_out = align(off_val + max_runs),
                  total_bytes = off_out + 1 + n;
-    if (n > ctx->rle_cap_px) {
-        if (ctx->d_rle) (void)hipFree(ctx->d_rle);
-        ctx->d_rle = nullptr;
-        ctx->rle_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_rle, total_bytes));
-        ctx->rle_cap_px = n;
-    }
+    rc = grow(ctx, ctx->d_rle, ctx->rle_cap_px, n, total_bytes);
+    if (rc != MBK_OK) return rc;
     uint32_t *d_cnt = (uint32_t *)(ctx->d_rle + off_cnt);
     unsigned long long *d_tot = (unsigned long long *)(ctx->d_rle + off_tot);
     uint32_t *d_start = (uint32_t *)(ctx->d_rle + off_start);
@@ -2051,10 +2056,10 @@ int mbk_quantise_counts(mbk_ctx *ctx, const int32_t *h_counts, uint64_t n, uint3
     if (mrd == 0 || mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must be in [1, 2^31)");
     if (n == 0) return MBK_OK;
     if (n > (1ull << 31)) return fail(ctx, MBK_ERR_INVALID, "more than 2^31 counts");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
-    int rc = ensure_buffers(ctx, sl, (size_t)n);
+    rc = ensure_buffers(ctx, sl, (size_t)n);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipMemcpyAsync(sl.d_counts, h_counts, n * sizeof(int32_t), hipMemcpyHostToDevice, sl.stream));
     hipLaunchKernelGGL(mbk::quantise_kernel, dim3(2048), dim3(256), 0, sl.stream, sl.d_counts, sl.d_bytes, n,
@@ -2193,14 +2198,9 @@ static double deep_step(double range, uint32_t n)
     return s;
 }
 
-// the deep kernel on device pointers (validated by the caller), on `stream`
-static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
-                       int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+// what the deep kernels share: the orbit, the view's geometry and window, mrd (every other field zero)
+static void fill_deep_args(mbk::DeepArgs &a, const double4 *d_orbit, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd)
 {
-    const double4 *d_orbit = nullptr;
-    int rc = deep_copy(ctx, orbit, &d_orbit);
-    if (rc != MBK_OK) return rc;
-    mbk::DeepArgs a;
     std::memset(&a, 0, sizeof(a));
     const std::vector<double> &t = orbit->o.table;
     a.orbit = d_orbit;
@@ -2216,6 +2216,17 @@ static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep
     a.nrows = v->nrows;
     a.blocks_x = (v->ncols + 7u) / 8u;
     a.mrd = (int32_t)mrd;
+}
+
+// the deep kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
+                       int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+{
+    const double4 *d_orbit = nullptr;
+    int rc = deep_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepArgs a;
+    fill_deep_args(a, d_orbit, orbit, v, mrd);
     a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
     a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
     a.counts = d_counts;
@@ -2235,36 +2246,23 @@ int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_de
     if (rc != MBK_OK) return rc;
     const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
     if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
-    if (wc && !d_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
-    if (wb && !d_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    rc = check_wanted(ctx, flags, d_counts, d_bytes);
+    if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     return launch_deep(ctx, orbit, view, mrd, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
                        (hipStream_t)hip_stream);
 }
 
-int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
-                          int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+// enqueue kernel + reduction + D2H of a checked deep view on a slot's stream (no host synchronisation); h_smooth (may be
+// NULL) is the synchronous form's
+static int deep_enqueue(mbk_ctx *ctx, Slot &sl, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                        int32_t *h_counts, uint8_t *h_bytes, double *h_smooth)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_deep(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
     const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    if (!wc && !wb && !h_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and h_smooth select no output");
-    if (wc && !h_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
-    if (wb && !h_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
     const size_t px = (size_t)view->ncols * view->nrows;
-    rc = ensure_buffers(ctx, sl, px);
+    int rc = ensure_buffers(ctx, sl, px);
+    if (rc == MBK_OK && h_smooth) rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, px, px * sizeof(double));
     if (rc != MBK_OK) return rc;
-    if (h_smooth && px > ctx->smooth_cap_px) {
-        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
-        ctx->d_smooth = nullptr;
-        ctx->smooth_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
-        ctx->smooth_cap_px = px;
-    }
     // counts always go to the device: they feed the statistics
     MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
     rc = launch_deep(ctx, orbit, view, mrd, sl.d_counts, wb ? sl.d_bytes : nullptr, h_smooth ? ctx->d_smooth : nullptr, sl.stream);
@@ -2277,15 +2275,23 @@ int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_d
     if (wb) MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sl.d_bytes, px, hipMemcpyDeviceToHost, sl.stream));
     if (h_smooth) MBK_HIP(ctx, hipMemcpyAsync(h_smooth, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
     MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
-    ctx->last_px = wb ? px : 0;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-        fill_stats_from_reduce(sl, stats, wb);
-    }
+    if (&sl == &ctx->s[0]) ctx->last_px = wb ? px : 0;
     return MBK_OK;
+}
+
+int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                          int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_deep(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    if (!wc && !wb && !h_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and h_smooth select no output");
+    rc = check_wanted(ctx, flags, h_counts, h_bytes);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    return sync_end(ctx, deep_enqueue(ctx, ctx->s[0], orbit, view, mrd, flags, h_counts, h_bytes, h_smooth), stats, wb);
 }
 
 int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
@@ -2297,52 +2303,21 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
     if (rc != MBK_OK) return rc;
     const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
     if (!wc && !wb) return fail(ctx, MBK_ERR_INVALID, "flags select no output");
-    if (wc && !h_counts) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_COUNTS with NULL counts pointer");
-    if (wb && !h_bytes) return fail(ctx, MBK_ERR_INVALID, "MBK_WANT_BYTES with NULL bytes pointer");
+    rc = check_wanted(ctx, flags, h_counts, h_bytes);
+    if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     Slot &sl = ctx->s[slot];
     if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
-    const size_t px = (size_t)view->ncols * view->nrows;
-    rc = ensure_buffers(ctx, sl, px);
+    rc = deep_enqueue(ctx, sl, orbit, view, mrd, flags, h_counts, h_bytes, nullptr);
     if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-    rc = launch_deep(ctx, orbit, view, mrd, sl.d_counts, wb ? sl.d_bytes : nullptr, nullptr, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-    rc = launch_reduce(ctx, sl, sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    if (wc) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-    if (wb) MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sl.d_bytes, px, hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
     sl.immediate = false;
     sl.lazy_h_bytes = nullptr;
     sl.busy = true;
     sl.with_bytes = wb;
-    if (&sl == &ctx->s[0]) ctx->last_px = wb ? px : 0;
     return MBK_OK;
 }
 
 // ---- distance estimates for deep views (mbk_deep_distance.h; mbk.h "Distance estimates for deep views") ----------------
-
-static void fill_deep_args(mbk::DeepArgs &a, const double4 *d_orbit, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd)
-{
-    std::memset(&a, 0, sizeof(a));
-    const std::vector<double> &t = orbit->o.table;
-    a.orbit = d_orbit;
-    a.z1 = make_double4(t[4], t[5], t[6], t[7]);
-    a.M = orbit->o.length;
-    a.half_r = (double)(v->width - 1u) * 0.5;
-    a.half_i = (double)(v->height - 1u) * 0.5;
-    a.step_r = deep_step(v->range_r, v->width);
-    a.step_i = deep_step(v->range_i, v->height);
-    a.col0 = v->col0;
-    a.row0 = v->row0;
-    a.ncols = v->ncols;
-    a.nrows = v->nrows;
-    a.blocks_x = (v->ncols + 7u) / 8u;
-    a.mrd = (int32_t)mrd;
-}
 
 // the deep distance kernel on device pointers (validated by the caller), on `stream`
 static int launch_deep_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
@@ -2383,39 +2358,12 @@ int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, co
     if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
     int rc = validate_deep(ctx, orbit, view, mrd, 0u);
     if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
-    const size_t px = (size_t)view->ncols * view->nrows;
-    rc = ensure_buffers(ctx, sl, px);
+    rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
-    if (px > ctx->smooth_cap_px) {
-        if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
-        ctx->d_smooth = nullptr;
-        ctx->smooth_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_smooth, px * sizeof(double)));
-        ctx->smooth_cap_px = px;
-    }
-    // counts always go to the device: they feed the statistics
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-    rc = launch_deep_distance(ctx, orbit, view, mrd, sl.d_counts, ctx->d_smooth, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-    rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    MBK_HIP(ctx, hipMemcpyAsync(h_rel, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-    if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
-    ctx->last_px = 0;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-        fill_stats_from_reduce(sl, stats, false);
-    }
-    return MBK_OK;
+    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_rel, stats,
+                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
+                              return launch_deep_distance(ctx, orbit, view, mrd, d_counts, d_rel, stream);
+                          });
 }
 
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count)
@@ -2489,6 +2437,18 @@ struct RenderTarget {
     uint32_t width, height, col0, row0, ncols, nrows;   // of the OUTPUT
 };
 
+// The targets of the two kinds of view.  A NULL view makes a target of neither kind, which render_check refuses in its turn.
+static RenderTarget view_target(const mbk_view *v)
+{
+    if (!v) return RenderTarget{};
+    return RenderTarget{v, nullptr, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows};
+}
+static RenderTarget deep_target(const mbk_deep_orbit *orbit, const mbk_deep_view *v)
+{
+    if (!v) return RenderTarget{};
+    return RenderTarget{nullptr, orbit, v, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows};
+}
+
 // The sample view / window of the output window (col0, row0, ncols, nrows) of `t`
 static void sample_window(const RenderTarget &t, uint32_t s, uint32_t col0, uint32_t row0, uint32_t ncols, uint32_t nrows,
                           mbk_view *v, mbk_deep_view *d)
@@ -2513,37 +2473,28 @@ static void sample_window(const RenderTarget &t, uint32_t s, uint32_t col0, uint
 }
 
 // Everything a render can refuse, before anything is allocated, enqueued or written.
-static int render_check(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit *orbit, const mbk_deep_view *deep, bool is_deep,
-                        uint32_t mrd, uint32_t flags, const mbk_render_spec *spec, const void *out, RenderTarget *t)
+static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                        const void *out)
 {
     int rc = validate_render_spec(ctx, spec);
     if (rc != MBK_OK) return rc;
     if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (is_deep ? !deep : !view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    t->view = is_deep ? nullptr : view;
-    t->orbit = orbit;
-    t->deep = is_deep ? deep : nullptr;
-    t->width = is_deep ? deep->width : view->width;
-    t->height = is_deep ? deep->height : view->height;
-    t->col0 = is_deep ? deep->col0 : view->col0;
-    t->row0 = is_deep ? deep->row0 : view->row0;
-    t->ncols = is_deep ? deep->ncols : view->ncols;
-    t->nrows = is_deep ? deep->nrows : view->nrows;
+    if (!t.view && !t.deep) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     const uint32_t s = spec->supersample;
-    if ((uint64_t)t->width * s > 0xffffffffull || (uint64_t)t->height * s > 0xffffffffull)
+    if ((uint64_t)t.width * s > 0xffffffffull || (uint64_t)t.height * s > 0xffffffffull)
         return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t->col0 + t->ncols > t->width || (uint64_t)t->row0 + t->nrows > t->height)
+    if ((uint64_t)t.col0 + t.ncols > t.width || (uint64_t)t.row0 + t.nrows > t.height)
         return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
     const bool dist = spec->source == MBK_RENDER_DISTANCE;
     const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;
     const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel;   // (the distance samples obey the smooth launch's rules)
     mbk_view sv;
     mbk_deep_view sd;
-    sample_window(*t, s, t->col0, t->row0, t->ncols, t->nrows, &sv, &sd);
-    if (is_deep) {
+    sample_window(t, s, t.col0, t.row0, t.ncols, t.nrows, &sv, &sd);
+    if (t.deep) {
         if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)");
         if (flags) return fail(ctx, MBK_ERR_INVALID, "deep renders take no flags (no kernel selection, no fp32)");
-        return validate_deep(ctx, orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
+        return validate_deep(ctx, t.orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
     }
     if (rel) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)");
     if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
@@ -2596,13 +2547,8 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     // layout: SMOOTH nu | counts; BYTES counts (statistics only) | bytes
     const size_t off2 = smooth ? round_up_256(cap_samples * 8u) : (stat ? round_up_256(cap_samples * 4u) : 0u);
     const size_t need = off2 + (smooth ? cap_samples * 4u : cap_samples);
-    if (need > sc->render_cap) {
-        if (sc->d_render) (void)hipFree(sc->d_render);   // (hipFree waits for the launches that may still read it)
-        sc->d_render = nullptr;
-        sc->render_cap = 0;
-        MBK_HIP(ctx, hipMalloc(&sc->d_render, need));
-        sc->render_cap = need;
-    }
+    rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
+    if (rc != MBK_OK) return rc;
     uint8_t *base = (uint8_t *)sc->d_render;
     double *d_nu = smooth ? (double *)base : nullptr;
     int32_t *d_counts = smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr);
@@ -2665,78 +2611,65 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     return MBK_OK;
 }
 
-static int render_launch(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit *orbit, const mbk_deep_view *deep, bool is_deep,
-                         uint32_t mrd, uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+static int render_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                         uint8_t *d_rgba, void *hip_stream)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    RenderTarget t;
-    int rc = render_check(ctx, view, orbit, deep, is_deep, mrd, flags, spec, d_rgba, &t);
+    int rc = render_check(ctx, t, mrd, flags, spec, d_rgba);
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
 }
 
-static int render_compute(mbk_ctx *ctx, const mbk_view *view, const mbk_deep_orbit *orbit, const mbk_deep_view *deep, bool is_deep,
-                          uint32_t mrd, uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+static int render_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                          uint8_t *h_rgba, mbk_stats *stats)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    RenderTarget t;
-    int rc = render_check(ctx, view, orbit, deep, is_deep, mrd, flags, spec, h_rgba, &t);
+    int rc = render_check(ctx, t, mrd, flags, spec, h_rgba);
     if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
     const size_t px = (size_t)t.ncols * t.nrows;
-    if (px > ctx->rgba_cap_px) {
-        if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
-        ctx->d_rgba = nullptr;
-        ctx->rgba_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_rgba, px * sizeof(uint32_t)));
-        ctx->rgba_cap_px = px;
-    }
-    MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-    rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl);
-    if (rc != MBK_OK) {
-        (void)hipStreamSynchronize(sl.stream);   // nothing of a failed render stays queued on the slot
-        return rc;
-    }
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-        fill_stats_from_reduce(sl, stats, false);
-    }
-    return MBK_OK;
+    auto enqueue = [&]() -> int {
+        int rc = grow(ctx, ctx->d_rgba, ctx->rgba_cap_px, px, px * sizeof(uint32_t));
+        if (rc != MBK_OK) return rc;
+        // the bands add their statistics up in the slot's reduction scratch: cleared once, here
+        MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    return sync_end(ctx, enqueue(), stats, false);
 }
 
 int mbk_view_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                            uint8_t *d_rgba, void *hip_stream)
 {
-    return render_launch(ctx, view, nullptr, nullptr, false, mrd, flags, spec, d_rgba, hip_stream);
+    return render_launch(ctx, view_target(view), mrd, flags, spec, d_rgba, hip_stream);
 }
 
 int mbk_view_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                             uint8_t *h_rgba, mbk_stats *stats)
 {
-    return render_compute(ctx, view, nullptr, nullptr, false, mrd, flags, spec, h_rgba, stats);
+    return render_compute(ctx, view_target(view), mrd, flags, spec, h_rgba, stats);
 }
 
 int mbk_deep_view_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
 {
-    return render_launch(ctx, nullptr, orbit, view, true, mrd, flags, spec, d_rgba, hip_stream);
+    return render_launch(ctx, deep_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream);
 }
 
 int mbk_deep_view_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
 {
-    return render_compute(ctx, nullptr, orbit, view, true, mrd, flags, spec, h_rgba, stats);
+    return render_compute(ctx, deep_target(orbit, view), mrd, flags, spec, h_rgba, stats);
 }
 
 // jet as matplotlib defines it (a public piecewise-linear colour map; the reference's Viewer looks colours up in its 256-entry
@@ -3033,37 +2966,32 @@ int mbk_chunk_decode_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t siz
     uint64_t runs;
     const uint32_t why = stream_precheck(h_stream, size, n, &codec, &runs);
     if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
-    StreamScratch *sc = nullptr;
-    int rc = get_scratch(ctx, sl.stream, &sc);
+    int rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
-    if (!sc->h_chunk_status) MBK_HIP(ctx, hipHostMalloc((void **)&sc->h_chunk_status, sizeof(uint32_t), hipHostMallocDefault));
-    // the decoded bytes live in the stream's scratch, not in the slot's tile buffer: mbk_serialize_last is not affected
-    if (!sc->d_chunk_bytes) MBK_HIP(ctx, hipMalloc((void **)&sc->d_chunk_bytes, MBK_CHUNK_BYTES));
-    rc = chunk_decode_run(ctx, sc, h_stream, size, n, codec, runs, sc->d_chunk_bytes, nullptr, sc->h_chunk_status, sl.ev_k0, sl.stream);
-    if (rc == MBK_OK) {
+    Slot &sl = ctx->s[0];
+    StreamScratch *sc = nullptr;
+    auto decode = [&]() -> int {
+        int rc = get_scratch(ctx, sl.stream, &sc);
+        if (rc != MBK_OK) return rc;
+        if (!sc->h_chunk_status) MBK_HIP(ctx, hipHostMalloc((void **)&sc->h_chunk_status, sizeof(uint32_t), hipHostMallocDefault));
+        // the decoded bytes live in the stream's scratch, not in the slot's tile buffer: mbk_serialize_last is not affected
+        if (!sc->d_chunk_bytes) MBK_HIP(ctx, hipMalloc((void **)&sc->d_chunk_bytes, MBK_CHUNK_BYTES));
+        rc = chunk_decode_run(ctx, sc, h_stream, size, n, codec, runs, sc->d_chunk_bytes, nullptr, sc->h_chunk_status, sl.ev_k0, sl.stream);
+        if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-        rc = launch_reduce(ctx, sl, nullptr, sc->d_chunk_bytes, n, 0u, sl.stream);
-    }
-    if (rc != MBK_OK) {
-        (void)hipStreamSynchronize(sl.stream);
-        return rc;
-    }
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+        return launch_reduce(ctx, sl, nullptr, sc->d_chunk_bytes, n, 0u, sl.stream);
+    };
+    // the verdict on the stream first: a bad one leaves h_bytes untouched
+    rc = sync_end(ctx, decode(), nullptr, false);
+    if (rc != MBK_OK) return rc;
     if (*sc->h_chunk_status != MBK_STREAM_OK) return fail_stream(ctx, *sc->h_chunk_status);
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sc->d_chunk_bytes, n, hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-        fill_stats_from_reduce(sl, stats, true);
-    }
-    return MBK_OK;
+    auto copy = [&]() -> int {
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sc->d_chunk_bytes, n, hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    return sync_end(ctx, copy(), stats, true);
 }
 
 int mbk_chunk_render_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size, const mbk_chunk_spec *spec, uint8_t *h_rgba,
@@ -3077,41 +3005,35 @@ int mbk_chunk_render_compute(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t siz
     uint64_t runs;
     const uint32_t why = stream_precheck(h_stream, size, MBK_CHUNK_BYTES, &codec, &runs);
     if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot 0 has a tile in flight: call mbk_wait first");
     const uint32_t w = MBK_CHUNK_DEFINITION >> lk;
     const size_t px = (size_t)w * w;
-    if (px > ctx->rgba_cap_px) {
-        if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
-        ctx->d_rgba = nullptr;
-        ctx->rgba_cap_px = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&ctx->d_rgba, px * sizeof(uint32_t)));
-        ctx->rgba_cap_px = px;
-    }
     uint32_t *h_status = nullptr;
-    rc = chunk_render_run(ctx, h_stream, size, codec, runs, spec, lk, ctx->d_rgba, w, nullptr, true, &h_status, sl.ev_k0, sl.stream);
-    if (rc != MBK_OK) {
-        (void)hipStreamSynchronize(sl.stream);   // nothing of a failed render stays queued on the slot
-        return rc;
-    }
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
+    auto render = [&]() -> int {
+        int rc = grow(ctx, ctx->d_rgba, ctx->rgba_cap_px, px, px * sizeof(uint32_t));
+        if (rc != MBK_OK) return rc;
+        rc = chunk_render_run(ctx, h_stream, size, codec, runs, spec, lk, ctx->d_rgba, w, nullptr, true, &h_status, sl.ev_k0, sl.stream);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+        return MBK_OK;
+    };
+    // the verdict on the stream first: a bad one leaves h_rgba untouched
+    rc = sync_end(ctx, render(), nullptr, false);
+    if (rc != MBK_OK) return rc;
     if (*h_status != MBK_STREAM_OK) return fail_stream(ctx, *h_status);
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    if (pitch_px == w)
-        MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
-    else
-        MBK_HIP(ctx, hipMemcpy2DAsync(h_rgba, pitch_px * sizeof(uint32_t), ctx->d_rgba, (size_t)w * sizeof(uint32_t),
-                                      (size_t)w * sizeof(uint32_t), w, hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    MBK_HIP(ctx, hipStreamSynchronize(sl.stream));
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->kernel_ms, sl.ev_k0, sl.ev_k1));
-        MBK_HIP(ctx, hipEventElapsedTime(&stats->d2h_ms, sl.ev_c0, sl.ev_c1));
-    }
-    return MBK_OK;
+    auto copy = [&]() -> int {
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        if (pitch_px == w)
+            MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+        else
+            MBK_HIP(ctx, hipMemcpy2DAsync(h_rgba, pitch_px * sizeof(uint32_t), ctx->d_rgba, (size_t)w * sizeof(uint32_t),
+                                          (size_t)w * sizeof(uint32_t), w, hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    return sync_end(ctx, copy(), stats, false, false);   // (no statistics of the bytes: nothing was reduced)
 }
 
 static int ctx_submit(void *user, int slot, uint32_t level, uint32_t mrd, uint32_t ir, uint32_t ii, uint8_t *h_bytes)

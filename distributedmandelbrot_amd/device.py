@@ -24,6 +24,31 @@ class MbkError(RuntimeError):
         self.status = status
 
 
+def _error_text(lib, ctx=None) -> str:
+    """The library's last error text: that of `ctx`, or (None) of the calling thread."""
+    return (lib.mbk_last_error(ctx) or b"").decode()
+
+
+def _check(lib, st: int, ctx=None) -> None:
+    if st != L.MBK_OK:
+        raise MbkError(st, _error_text(lib, ctx))
+
+
+def _out_array(out: Optional[np.ndarray], shape, dtype) -> np.ndarray:
+    """`out`, or a new array: C-contiguous, of this dtype and of the shape's size."""
+    if out is None:
+        return np.empty(shape, dtype)
+    assert out.dtype == dtype and out.size == int(np.prod(shape)) and out.flags.c_contiguous
+    return out
+
+
+def _wanted(shape, counts: Optional[np.ndarray], byts: Optional[np.ndarray]):
+    """(MBK_WANT_* flags, counts pointer, bytes pointer) of the host outputs that are not None, each checked as _out_array does."""
+    flags = (L.MBK_WANT_COUNTS if counts is not None else 0) | (L.MBK_WANT_BYTES if byts is not None else 0)
+    return (flags, None if counts is None else _out_array(counts, shape, np.int32).ctypes.data,
+            None if byts is None else _out_array(byts, shape, np.uint8).ctypes.data)
+
+
 @dataclass(frozen=True)
 class View:
     """width x height samples of [start_r, start_r+range_r] x [start_i, start_i+range_i], endpoints
@@ -107,16 +132,14 @@ class DeepOrbit:
         self.center = (_decimal_string(center_r, bits), _decimal_string(center_i, bits))
         h = C.c_void_p()
         st = self._lib.mbk_deep_orbit_create(self.center[0].encode(), self.center[1].encode(), bits, int(mrd), C.byref(h))
-        if st != L.MBK_OK:
-            raise MbkError(st, (self._lib.mbk_last_error(None) or b"").decode())
+        _check(self._lib, st)
         self._h = h
         n, esc, p, m = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._check(self._lib.mbk_deep_orbit_info(h, C.byref(n), C.byref(esc), C.byref(p), C.byref(m)))
         self.length, self.escaped, self.precision_bits, self.mrd = int(n.value), bool(esc.value), int(p.value), int(m.value)
 
     def _check(self, st: int) -> None:
-        if st != L.MBK_OK:
-            raise MbkError(st, (self._lib.mbk_last_error(None) or b"").decode())
+        _check(self._lib, st)
 
     def table(self) -> Tuple[np.ndarray, np.ndarray]:
         """(Zr, Zi): Z_0 .. Z_M as float64."""
@@ -161,9 +184,7 @@ def datachunk_geometry(level: int, index_real: int, index_imag: int) -> Tuple[fl
     """(start_r, start_i, range) of a DataChunk tile: WorkerCUDA.py:75-78 == DataChunk.cs:32-33,59-66."""
     lib = L.load()
     a, b, c = C.c_double(), C.c_double(), C.c_double()
-    st = lib.mbk_datachunk_geometry(level, index_real, index_imag, C.byref(a), C.byref(b), C.byref(c))
-    if st != L.MBK_OK:
-        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    _check(lib, lib.mbk_datachunk_geometry(level, index_real, index_imag, C.byref(a), C.byref(b), C.byref(c)))
     return a.value, b.value, c.value
 
 
@@ -174,6 +195,13 @@ def _stream_array(stream) -> np.ndarray:
     else:
         a = np.frombuffer(stream, np.uint8)
     return a
+
+
+_EMPTY_STREAM = (C.c_uint8 * 1)()   # what the pointer of an empty stream points to: never read, alive with the module
+
+
+def _stream_ptr(a: np.ndarray) -> int:
+    return a.ctypes.data if a.size else C.addressof(_EMPTY_STREAM)
 
 
 class ChunkStreamError(MbkError):
@@ -189,10 +217,9 @@ def chunk_stream_check(stream, n: int = L.MBK_CHUNK_BYTES) -> Tuple[int, int]:
     lib = L.load()
     a = _stream_array(stream)
     codec, runs, reason = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
-    st = lib.mbk_chunk_stream_check(a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size, n, C.byref(codec),
-                                    C.byref(runs), C.byref(reason))
+    st = lib.mbk_chunk_stream_check(_stream_ptr(a), a.size, n, C.byref(codec), C.byref(runs), C.byref(reason))
     if st != L.MBK_OK:
-        raise ChunkStreamError(int(reason.value), (lib.mbk_last_error(None) or b"").decode())
+        raise ChunkStreamError(int(reason.value), _error_text(lib))
     return int(codec.value), int(runs.value)
 
 
@@ -201,12 +228,8 @@ def decode_chunk_host(stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarr
     `out` is left untouched when the stream is invalid (MbkError)."""
     lib = L.load()
     a = _stream_array(stream)
-    if out is None:
-        out = np.empty(n, np.uint8)
-    assert out.dtype == np.uint8 and out.size == n and out.flags.c_contiguous
-    st = lib.mbk_chunk_decode_host(a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size, n, out.ctypes.data)
-    if st != L.MBK_OK:
-        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    out = _out_array(out, n, np.uint8)
+    _check(lib, lib.mbk_chunk_decode_host(_stream_ptr(a), a.size, n, out.ctypes.data))
     return out
 
 
@@ -219,9 +242,7 @@ class MandelbrotDevice:
     def __init__(self, device: int = 0):
         self._lib = L.load()
         h = C.c_void_p()
-        st = self._lib.mbk_create(device, C.byref(h))
-        if st != L.MBK_OK:
-            raise MbkError(st, (self._lib.mbk_last_error(None) or b"").decode())
+        _check(self._lib, self._lib.mbk_create(device, C.byref(h)))
         self._h = h
         self.device = device
         self._pinned = []
@@ -249,8 +270,7 @@ class MandelbrotDevice:
             pass
 
     def _check(self, st: int) -> None:
-        if st != L.MBK_OK:
-            raise MbkError(st, (self._lib.mbk_last_error(self._h) or b"").decode())
+        _check(self._lib, st, self._h)
 
     # -- queries ---------------------------------------------------------------------------
     def info(self) -> dict:
@@ -332,29 +352,19 @@ class MandelbrotDevice:
         """Synchronous: returns (counts int32[nrows,ncols] | None, bytes uint8[nrows,ncols] | None, TileStats)."""
         cv = self._cview(view, window)
         shape = (cv.nrows, cv.ncols)
-        flags = L.KERNELS[kernel] | L.PRECISIONS[precision]
-        counts = byts = None
-        if want_counts:
-            counts = out_counts if out_counts is not None else np.empty(shape, np.int32)
-            assert counts.dtype == np.int32 and counts.size == shape[0] * shape[1] and counts.flags.c_contiguous
-            flags |= L.MBK_WANT_COUNTS
-        if want_bytes:
-            byts = out_bytes if out_bytes is not None else np.empty(shape, np.uint8)
-            assert byts.dtype == np.uint8 and byts.size == shape[0] * shape[1] and byts.flags.c_contiguous
-            flags |= L.MBK_WANT_BYTES
+        counts = _out_array(out_counts, shape, np.int32) if want_counts else None
+        byts = _out_array(out_bytes, shape, np.uint8) if want_bytes else None
+        flags, p_counts, p_bytes = _wanted(shape, counts, byts)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_view_compute(
-            self._h, C.byref(cv), mrd, flags,
-            counts.ctypes.data if counts is not None else None,
-            byts.ctypes.data if byts is not None else None, C.byref(st)))
+        self._check(self._lib.mbk_view_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel] | L.PRECISIONS[precision] | flags,
+                                               p_counts, p_bytes, C.byref(st)))
         return counts, byts, _stats(st)
 
     def datachunk(self, level: int, mrd: int, index_real: int, index_imag: int, *,
                   want_counts: bool = False, out_bytes: Optional[np.ndarray] = None):
         """The reference's process_workload (WorkerCUDA.py:70-100): uint8[16777216] for one tile.
         Returns (bytes uint8[16777216], counts int32[16777216] | None, TileStats)."""
-        byts = out_bytes if out_bytes is not None else np.empty(L.MBK_CHUNK_BYTES, np.uint8)
-        assert byts.dtype == np.uint8 and byts.size == L.MBK_CHUNK_BYTES and byts.flags.c_contiguous
+        byts = _out_array(out_bytes, L.MBK_CHUNK_BYTES, np.uint8)
         counts = np.empty(L.MBK_CHUNK_BYTES, np.int32) if want_counts else None
         st = L.mbk_stats()
         self._check(self._lib.mbk_datachunk(
@@ -435,16 +445,9 @@ class MandelbrotDevice:
         """Enqueue a view / window on `slot` and return at once; the given host arrays (C-contiguous, sized
         for the window; slices of a larger image are fine) are valid after wait(slot)."""
         cv = self._cview(view, window)
-        n = cv.nrows * cv.ncols
-        flags = L.KERNELS[kernel] | L.PRECISIONS[precision]
-        for arr, dt, flag in ((out_counts, np.int32, L.MBK_WANT_COUNTS), (out_bytes, np.uint8, L.MBK_WANT_BYTES)):
-            if arr is not None:
-                assert arr.dtype == dt and arr.size == n and arr.flags.c_contiguous
-                flags |= flag
-        self._check(self._lib.mbk_view_submit(
-            self._h, slot, C.byref(cv), mrd, flags,
-            out_counts.ctypes.data if out_counts is not None else None,
-            out_bytes.ctypes.data if out_bytes is not None else None))
+        flags, p_counts, p_bytes = _wanted((cv.nrows, cv.ncols), out_counts, out_bytes)
+        self._check(self._lib.mbk_view_submit(self._h, slot, C.byref(cv), mrd, L.KERNELS[kernel] | L.PRECISIONS[precision] | flags,
+                                              p_counts, p_bytes))
 
     def wait(self, slot: int) -> TileStats:
         st = L.mbk_stats()
@@ -473,39 +476,21 @@ class MandelbrotDevice:
         """Synchronous: (counts int32 | None, bytes uint8 | None, smooth float64 | None, TileStats), each [nrows, ncols]."""
         cv = self._cdeep(view, window)
         shape = (cv.nrows, cv.ncols)
-        flags = 0
-        counts = byts = smooth = None
-        if want_counts:
-            counts = out_counts if out_counts is not None else np.empty(shape, np.int32)
-            assert counts.dtype == np.int32 and counts.size == shape[0] * shape[1] and counts.flags.c_contiguous
-            flags |= L.MBK_WANT_COUNTS
-        if want_bytes:
-            byts = out_bytes if out_bytes is not None else np.empty(shape, np.uint8)
-            assert byts.dtype == np.uint8 and byts.size == shape[0] * shape[1] and byts.flags.c_contiguous
-            flags |= L.MBK_WANT_BYTES
-        if want_smooth:
-            smooth = np.empty(shape, np.float64)
+        counts = _out_array(out_counts, shape, np.int32) if want_counts else None
+        byts = _out_array(out_bytes, shape, np.uint8) if want_bytes else None
+        smooth = np.empty(shape, np.float64) if want_smooth else None
+        flags, p_counts, p_bytes = _wanted(shape, counts, byts)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_compute(
-            self._h, orbit._h, C.byref(cv), mrd, flags,
-            counts.ctypes.data if counts is not None else None, byts.ctypes.data if byts is not None else None,
-            smooth.ctypes.data if smooth is not None else None, C.byref(st)))
+        self._check(self._lib.mbk_deep_view_compute(self._h, orbit._h, C.byref(cv), mrd, flags, p_counts, p_bytes,
+                                                    smooth.ctypes.data if smooth is not None else None, C.byref(st)))
         return counts, byts, smooth, _stats(st)
 
     def submit_deep_view(self, slot: int, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None,
                          out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None) -> None:
         """Enqueue a deep view / window on `slot`; the host arrays are valid after wait(slot)."""
         cv = self._cdeep(view, window)
-        n = cv.nrows * cv.ncols
-        flags = 0
-        for arr, dt, flag in ((out_counts, np.int32, L.MBK_WANT_COUNTS), (out_bytes, np.uint8, L.MBK_WANT_BYTES)):
-            if arr is not None:
-                assert arr.dtype == dt and arr.size == n and arr.flags.c_contiguous
-                flags |= flag
-        self._check(self._lib.mbk_deep_view_submit(
-            self._h, slot, orbit._h, C.byref(cv), mrd, flags,
-            out_counts.ctypes.data if out_counts is not None else None,
-            out_bytes.ctypes.data if out_bytes is not None else None))
+        flags, p_counts, p_bytes = _wanted((cv.nrows, cv.ncols), out_counts, out_bytes)
+        self._check(self._lib.mbk_deep_view_submit(self._h, slot, orbit._h, C.byref(cv), mrd, flags, p_counts, p_bytes))
 
     def launch_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_counts: int = 0, d_bytes: int = 0,
                          d_smooth: int = 0, stream: int = 0, window=None) -> None:
@@ -539,10 +524,7 @@ class MandelbrotDevice:
     # -- rendering (include/mbk.h, "Rendering") ---------------------------------------------------
     def _render_out(self, cv, out):
         shape = (cv.nrows, cv.ncols, 4)
-        if out is None:
-            return np.empty(shape, np.uint8)
-        assert out.dtype == np.uint8 and out.size == shape[0] * shape[1] * 4 and out.flags.c_contiguous
-        return out.reshape(shape)
+        return _out_array(out, shape, np.uint8).reshape(shape)
 
     def render_view(self, view: View, mrd: int, *, palette, source: str = "smooth", supersample: int = 1, window=None,
                     kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None):
@@ -595,11 +577,9 @@ class MandelbrotDevice:
         The statistics are those of the decoded bytes (all_bytes_zero / all_bytes_one, rle_runs).  MbkError for an invalid
         stream, with `out` untouched."""
         a = _stream_array(stream)
-        if out is None:
-            out = np.empty(n, np.uint8)
-        assert out.dtype == np.uint8 and out.size == n and out.flags.c_contiguous
+        out = _out_array(out, n, np.uint8)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_chunk_decode_compute(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size,
+        self._check(self._lib.mbk_chunk_decode_compute(self._h, _stream_ptr(a), a.size,
                                                        n, out.ctypes.data, C.byref(st)))
         return out, _stats(st)
 
@@ -628,7 +608,7 @@ class MandelbrotDevice:
                 raise ValueError("out must be uint8 rows of 4-byte pixels, `pitch` pixels apart")
         spec = self._chunk_spec(palette, scale)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_chunk_render_compute(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size,
+        self._check(self._lib.mbk_chunk_render_compute(self._h, _stream_ptr(a), a.size,
                                                        C.byref(spec), out.ctypes.data, pitch, C.byref(st)))
         return out, _stats(st)
 
@@ -638,7 +618,7 @@ class MandelbrotDevice:
         to the device word d_status.  `stream` must stay alive until the HIP stream has passed the copy; a uint8 array over
         pinned memory (`pinned_empty`) makes the copy asynchronous."""
         a = _stream_array(stream)
-        self._check(self._lib.mbk_chunk_decode_launch(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size, n,
+        self._check(self._lib.mbk_chunk_decode_launch(self._h, _stream_ptr(a), a.size, n,
                                                       d_bytes or None, d_status or None, hip_stream or None))
 
     def launch_render_chunk(self, stream, *, d_rgba: int, palette=None, scale: int = 1, pitch: Optional[int] = None,
@@ -649,7 +629,7 @@ class MandelbrotDevice:
         a = _stream_array(stream)
         spec = self._chunk_spec(palette, scale)
         w = L.MBK_CHUNK_DEFINITION // int(scale) if scale in L.CHUNK_SCALES else 0
-        self._check(self._lib.mbk_chunk_render_launch(self._h, a.ctypes.data if a.size else C.addressof(C.c_uint8(0)), a.size,
+        self._check(self._lib.mbk_chunk_render_launch(self._h, _stream_ptr(a), a.size,
                                                       C.byref(spec), d_rgba or None, w if pitch is None else int(pitch),
                                                       d_status or None, hip_stream or None))
 
