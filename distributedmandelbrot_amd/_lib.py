@@ -46,8 +46,10 @@ MBK_RENDER_BYTES = 0
 MBK_RENDER_SMOOTH = 1
 MBK_RENDER_DISTANCE = 3
 MBK_RENDER_DISTANCE_REL = 4
+MBK_RENDER_EQUALIZED = 5
 RENDER_SOURCES = {"bytes": MBK_RENDER_BYTES, "smooth": MBK_RENDER_SMOOTH, "distance": MBK_RENDER_DISTANCE,
-                  "distance_rel": MBK_RENDER_DISTANCE_REL}
+                  "distance_rel": MBK_RENDER_DISTANCE_REL, "equalized": MBK_RENDER_EQUALIZED}
+MBK_HISTOGRAM_MAX_MRD = 1 << 20
 RENDER_SUPERSAMPLES = (1, 2, 3, 4, 8)
 MBK_RENDER_BAND_BYTES = 256 << 20
 # reason codes of an invalid chunk stream (include/mbk.h, "Stored chunks")
@@ -199,6 +201,30 @@ SIGNATURES = {
     "mbk_palette_viewer": (C.c_int, [C.c_void_p]),
     "mbk_render_resolve_host": (C.c_int, [C.POINTER(mbk_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "mbk_counts_histogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mbk_view_histogram_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_histogram_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p]),
+    "mbk_view_histogram_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.POINTER(mbk_stats)]),
+    "mbk_deep_view_histogram_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_counts_histogram_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mbk_equalize_lut_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mbk_equalize_value_host": (C.c_double, [C.c_void_p, C.c_uint32, C.c_double]),
+    "mbk_view_render_equalized_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                   C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mbk_view_render_equalized_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                    C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                    C.POINTER(mbk_stats)]),
+    "mbk_deep_view_render_equalized_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                        C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                        C.c_void_p]),
+    "mbk_deep_view_render_equalized_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                         C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                         C.POINTER(mbk_stats)]),
+    "mbk_render_resolve_equalized_host": (C.c_int, [C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mbk_chunk_stream_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]),
     "mbk_chunk_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -26,6 +26,7 @@
 #include "mbk_feeder.h"
 #include "mbk_deep_orbit.h"
 #include "mbk_deep.h"
+#include "mbk_histogram.h"
 #include "mbk_render.h"
 #include "mbk_chunks.h"
 #include "mbk_distance.h"
@@ -101,6 +102,10 @@ struct StreamScratch {
     // distance estimates (mbk_distance.h): the counts of a two-pass launch whose caller wants none
     int32_t *d_dist_counts = nullptr;
     size_t dist_cap_px = 0;
+    // equalised renders (mbk_histogram.h): the table of the last one, kept like the palette
+    double *d_lut = nullptr;
+    size_t lut_cap = 0;               // entries
+    std::vector<double> lut;          // what d_lut holds
 };
 static const size_t kMaxStreamScratch = 64;
 static const uint32_t kStampSlots = 16, kShareRing = 64;
@@ -132,6 +137,8 @@ struct mbk_ctx {
     size_t smooth_cap_px = 0;
     uint32_t *d_rgba = nullptr;      // the image of the synchronous renders (mbk_*_render_compute)
     size_t rgba_cap_px = 0;
+    unsigned long long *d_hist = nullptr;   // the table of the synchronous histograms (mbk_*_histogram_compute)
+    size_t hist_cap = 0;             // bins
     uint8_t *d_rle = nullptr;        // RLE scratch: block counts | run starts | run values | output stream
     size_t rle_cap_px = 0;
     uint32_t opt[MBK_OPT_COUNT_];    // tuning options (mbk_set_option); every value is bit-exact
@@ -339,6 +346,7 @@ static void free_scratch(StreamScratch &sc)
     if (sc.d_chunk_bytes) (void)hipFree(sc.d_chunk_bytes);
     if (sc.h_chunk_status) (void)hipHostFree(sc.h_chunk_status);
     if (sc.d_dist_counts) (void)hipFree(sc.d_dist_counts);
+    if (sc.d_lut) (void)hipFree(sc.d_lut);
     sc = StreamScratch();
 }
 
@@ -1494,6 +1502,7 @@ void mbk_destroy(mbk_ctx *ctx)
     if (ctx->d_rle) (void)hipFree(ctx->d_rle);
     if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
     if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
+    if (ctx->d_hist) (void)hipFree(ctx->d_hist);
     delete ctx;
 }
 
@@ -2373,17 +2382,22 @@ double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double 
 
 // ---- rendering (mbk_render.h; mbk.h "Rendering") -----------------------------------------------------------
 
-static int validate_render_spec(mbk_ctx *ctx, const mbk_render_spec *spec)
+// equalized: the call carries a table (mbk_*_render_equalized_*, mbk_render_resolve_equalized_host): it takes
+// MBK_RENDER_EQUALIZED and nothing else; the calls without a table refuse that source.
+static int validate_render_spec(mbk_ctx *ctx, const mbk_render_spec *spec, bool equalized = false)
 {
     if (!spec) return fail(ctx, MBK_ERR_INVALID, "render spec is NULL");
     if (!spec->palette) return fail(ctx, MBK_ERR_INVALID, "palette is NULL");
     const uint32_t s = spec->supersample;
     if (s != 1u && s != 2u && s != 3u && s != 4u && s != 8u) return fail(ctx, MBK_ERR_INVALID, "supersample must be 1, 2, 3, 4 or 8");
+    if (equalized != (spec->source == MBK_RENDER_EQUALIZED))
+        return fail(ctx, MBK_ERR_INVALID, equalized ? "the equalized calls take MBK_RENDER_EQUALIZED only"
+                                                    : "MBK_RENDER_EQUALIZED needs a table: use the equalized calls");
     if (spec->source == MBK_RENDER_BYTES) {
         if (spec->palette_len != 256u) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_BYTES takes a palette of 256 entries");
-    } else if (spec->source == MBK_RENDER_SMOOTH) {
+    } else if (spec->source == MBK_RENDER_SMOOTH || spec->source == MBK_RENDER_EQUALIZED) {
         if (spec->palette_len < 2u || spec->palette_len > 65536u)
-            return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_SMOOTH takes a palette of 2 .. 65536 entries");
+            return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_SMOOTH / _EQUALIZED take a palette of 2 .. 65536 entries");
         if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^20]");
         if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
     } else if (spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL) {
@@ -2411,6 +2425,8 @@ static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint
     p.inside = pack_rgba(spec->inside);
     p.scale = spec->scale;
     p.offset = spec->offset;
+    p.lut = nullptr;
+    p.lut_mrd = 0u;
     return p;
 }
 
@@ -2426,6 +2442,31 @@ static int stream_palette(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, c
         MBK_HIP(ctx, hipMemcpy(sc->d_palette, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         sc->palette = words;
     }
+    return MBK_OK;
+}
+
+// The equalisation table a call carries: lut_len == mrd + 2 entries, each finite and in [0, 1].
+static int validate_lut(mbk_ctx *ctx, const double *h_lut, uint32_t lut_len, uint64_t mrd)
+{
+    if (!h_lut) return fail(ctx, MBK_ERR_INVALID, "equalisation table is NULL");
+    if (mrd > MBK_HISTOGRAM_MAX_MRD) return fail(ctx, MBK_ERR_INVALID, "mrd exceeds MBK_HISTOGRAM_MAX_MRD");
+    if ((uint64_t)lut_len != mrd + 2u) return fail(ctx, MBK_ERR_INVALID, "lut_len must equal mrd + 2");
+    for (uint32_t k = 0; k < lut_len; ++k)
+        if (!(h_lut[k] >= 0.0 && h_lut[k] <= 1.0))
+            return fail(ctx, MBK_ERR_INVALID, "equalisation table entries must be finite and lie in [0, 1]");
+    return MBK_OK;
+}
+
+// The stream's device copy of the table, under the palette's rule: uploaded when it differs, after the launches that read it.
+static int stream_lut(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const double *h_lut, uint32_t lut_len)
+{
+    if (sc->lut.size() == lut_len && std::memcmp(sc->lut.data(), h_lut, (size_t)lut_len * sizeof(double)) == 0) return MBK_OK;
+    MBK_HIP(ctx, hipStreamSynchronize(stream));
+    sc->lut.clear();
+    int rc = grow(ctx, sc->d_lut, sc->lut_cap, lut_len, (size_t)lut_len * sizeof(double));
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipMemcpy(sc->d_lut, h_lut, (size_t)lut_len * sizeof(double), hipMemcpyHostToDevice));
+    sc->lut.assign(h_lut, h_lut + lut_len);
     return MBK_OK;
 }
 
@@ -2474,9 +2515,9 @@ static void sample_window(const RenderTarget &t, uint32_t s, uint32_t col0, uint
 
 // Everything a render can refuse, before anything is allocated, enqueued or written.
 static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                        const void *out)
+                        const void *out, bool equalized = false, const double *h_lut = nullptr, uint32_t lut_len = 0u)
 {
-    int rc = validate_render_spec(ctx, spec);
+    int rc = validate_render_spec(ctx, spec, equalized);
     if (rc != MBK_OK) return rc;
     if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
     if (!t.view && !t.deep) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
@@ -2487,14 +2528,16 @@ static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint3
         return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
     const bool dist = spec->source == MBK_RENDER_DISTANCE;
     const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;
-    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel;   // (the distance samples obey the smooth launch's rules)
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel || equalized;   // (the distance samples obey the smooth launch's rules)
     mbk_view sv;
     mbk_deep_view sd;
     sample_window(t, s, t.col0, t.row0, t.ncols, t.nrows, &sv, &sd);
     if (t.deep) {
         if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)");
         if (flags) return fail(ctx, MBK_ERR_INVALID, "deep renders take no flags (no kernel selection, no fp32)");
-        return validate_deep(ctx, t.orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
+        rc = validate_deep(ctx, t.orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
+        if (rc != MBK_OK || !equalized) return rc;
+        return validate_lut(ctx, h_lut, lut_len, mrd);
     }
     if (rel) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)");
     if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
@@ -2510,7 +2553,7 @@ static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint3
     if ((smooth || f32) && (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL))
         return fail(ctx, MBK_ERR_INVALID, "smooth colouring and MBK_PRECISION_F32 are implemented by the scan / asm / group kernels only");
     if (smooth && f32) return fail(ctx, MBK_ERR_INVALID, "smooth colouring is implemented in binary64 only");
-    return MBK_OK;
+    return equalized ? validate_lut(ctx, h_lut, lut_len, mrd) : MBK_OK;
 }
 
 static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
@@ -2518,12 +2561,13 @@ static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 // A checked render (render_check) onto the device image d_out (ncols x nrows words), on `stream`.  stat: the slot whose
 // reduction scratch adds up the statistics of the samples and whose ev_k1 marks the last resolve kernel (_compute), or NULL.
 static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                      uint32_t *d_out, hipStream_t stream, Slot *stat)
+                      uint32_t *d_out, hipStream_t stream, Slot *stat, const double *h_lut = nullptr, uint32_t lut_len = 0u)
 {
     const uint32_t s = spec->supersample;
     const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;              // (deep views: rel in place of de, the same colour rule)
     const bool dist = spec->source == MBK_RENDER_DISTANCE || rel;
-    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist;   // (same sample layout: binary64 value | counts)
+    const bool eq = spec->source == MBK_RENDER_EQUALIZED;                  // (the smooth samples, coloured through the table)
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || eq;   // (same sample layout: binary64 value | counts)
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
@@ -2531,6 +2575,10 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     // the palette: uploaded when it differs from what this stream's device copy holds, after the launches that read that
     rc = stream_palette(ctx, sc, stream, spec->palette, spec->palette_len);
     if (rc != MBK_OK) return rc;
+    if (eq) {
+        rc = stream_lut(ctx, sc, stream, h_lut, lut_len);
+        if (rc != MBK_OK) return rc;
+    }
 
     // bands: rows of the output window whose samples fit the budget, and pieces of columns if one row's do not
     const uint64_t per_px = (uint64_t)s * s * (smooth ? 12u : (stat ? 5u : 1u));
@@ -2553,6 +2601,7 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     double *d_nu = smooth ? (double *)base : nullptr;
     int32_t *d_counts = smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr);
     uint8_t *d_bytes = smooth ? nullptr : base + off2;
+    const double *d_lut = eq ? sc->d_lut : nullptr;
     const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
 
     const size_t lds = (size_t)spec->palette_len * sizeof(uint32_t);
@@ -2592,10 +2641,14 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             a.chunks_x = (nc + px_per_wg - 1u) / px_per_wg;
             a.lds_palette = use_lds ? 1u : 0u;
             a.pal = render_palette(spec, d_palette);
+            a.pal.lut = d_lut;
+            a.pal.lut_mrd = eq ? lut_len - 2u : 0u;
             const uint64_t pieces = (uint64_t)a.chunks_x * nr;
             const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
             if (dist)
-                mbk::launch_resolve<true, true>(s, grid, use_lds ? lds : 0u, stream, a);
+                mbk::launch_resolve<true, mbk::kRuleDistance>(s, grid, use_lds ? lds : 0u, stream, a);
+            else if (eq)
+                mbk::launch_resolve<true, mbk::kRuleEqualized>(s, grid, use_lds ? lds : 0u, stream, a);
             else if (smooth)
                 mbk::launch_resolve<true>(s, grid, use_lds ? lds : 0u, stream, a);
             else
@@ -2611,22 +2664,25 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     return MBK_OK;
 }
 
+// equalized (here and in render_compute): the call carries the table h_lut[lut_len] and takes MBK_RENDER_EQUALIZED only
 static int render_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                         uint8_t *d_rgba, void *hip_stream)
+                         uint8_t *d_rgba, void *hip_stream, bool equalized = false, const double *h_lut = nullptr,
+                         uint32_t lut_len = 0u)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = render_check(ctx, t, mrd, flags, spec, d_rgba);
+    int rc = render_check(ctx, t, mrd, flags, spec, d_rgba, equalized, h_lut, lut_len);
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, h_lut, lut_len);
 }
 
 static int render_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                          uint8_t *h_rgba, mbk_stats *stats)
+                          uint8_t *h_rgba, mbk_stats *stats, bool equalized = false, const double *h_lut = nullptr,
+                          uint32_t lut_len = 0u)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = render_check(ctx, t, mrd, flags, spec, h_rgba);
+    int rc = render_check(ctx, t, mrd, flags, spec, h_rgba, equalized, h_lut, lut_len);
     if (rc != MBK_OK) return rc;
     rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
@@ -2638,7 +2694,7 @@ static int render_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uin
         // the bands add their statistics up in the slot's reduction scratch: cleared once, here
         MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl);
+        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
@@ -2670,6 +2726,32 @@ int mbk_deep_view_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, cons
                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
 {
     return render_compute(ctx, deep_target(orbit, view), mrd, flags, spec, h_rgba, stats);
+}
+
+int mbk_view_render_equalized_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                     const double *h_lut, uint32_t lut_len, uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, view_target(view), mrd, flags, spec, d_rgba, hip_stream, true, h_lut, lut_len);
+}
+
+int mbk_view_render_equalized_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                      const double *h_lut, uint32_t lut_len, uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, view_target(view), mrd, flags, spec, h_rgba, stats, true, h_lut, lut_len);
+}
+
+int mbk_deep_view_render_equalized_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                          uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, deep_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream, true, h_lut, lut_len);
+}
+
+int mbk_deep_view_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                           uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, deep_target(orbit, view), mrd, flags, spec, h_rgba, stats, true, h_lut, lut_len);
 }
 
 // jet as matplotlib defines it (a public piecewise-linear colour map; the reference's Viewer looks colours up in its 256-entry
@@ -2709,22 +2791,221 @@ int mbk_palette_viewer(uint8_t out[1024])
     return MBK_OK;
 }
 
-int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
-                            const uint8_t *bytes, const double *smooth, uint8_t *rgba)
+// mbk_render_resolve_host, and with a table (equalized) mbk_render_resolve_equalized_host
+static int resolve_host(const mbk_render_spec *spec, bool equalized, const double *h_lut, uint32_t lut_len, uint32_t width,
+                        uint32_t height, const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba)
 {
-    int rc = validate_render_spec(nullptr, spec);
+    int rc = validate_render_spec(nullptr, spec, equalized);
     if (rc != MBK_OK) return rc;
+    if (equalized) {
+        if (lut_len < 2u) return fail(nullptr, MBK_ERR_INVALID, "lut_len must be mrd + 2");
+        rc = validate_lut(nullptr, h_lut, lut_len, (uint64_t)lut_len - 2u);
+        if (rc != MBK_OK) return rc;
+    }
     if (!rgba) return fail(nullptr, MBK_ERR_INVALID, "output pointer is NULL");
     const uint32_t s = spec->supersample;
     if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
         return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
     const bool dist = spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL;
-    const bool sm = spec->source == MBK_RENDER_SMOOTH || dist;
+    const bool sm = spec->source == MBK_RENDER_SMOOTH || dist || equalized;
     if (sm ? (!counts || !smooth) : !bytes) return fail(nullptr, MBK_ERR_INVALID, "the source's sample arrays are NULL");
     std::vector<uint32_t> words(spec->palette_len);
     for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
-    mbk::render_resolve_host(render_palette(spec, words.data()), sm, s, width, height, counts, bytes, smooth, rgba, dist);
+    mbk::RenderPalette pal = render_palette(spec, words.data());
+    pal.lut = h_lut;
+    pal.lut_mrd = equalized ? lut_len - 2u : 0u;
+    mbk::render_resolve_host(pal, sm, s, width, height, counts, bytes, smooth, rgba,
+                             dist ? mbk::kRuleDistance : (equalized ? mbk::kRuleEqualized : mbk::kRuleSmooth));
     return MBK_OK;
+}
+
+int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                            const uint8_t *bytes, const double *smooth, uint8_t *rgba)
+{
+    return resolve_host(spec, false, nullptr, 0u, width, height, counts, bytes, smooth, rgba);
+}
+
+int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint32_t width,
+                                      uint32_t height, const int32_t *counts, const double *smooth, uint8_t *rgba)
+{
+    return resolve_host(spec, true, h_lut, lut_len, width, height, counts, nullptr, smooth, rgba);
+}
+
+// ---- count histograms and the equalisation table (mbk_histogram.h; mbk.h "Count histograms") ------------------------------
+
+static int check_hist_mrd(mbk_ctx *ctx, uint32_t mrd)
+{
+    if (mrd == 0u || mrd > MBK_HISTOGRAM_MAX_MRD) return fail(ctx, MBK_ERR_INVALID, "mrd must lie in [1, MBK_HISTOGRAM_MAX_MRD]");
+    return MBK_OK;
+}
+
+int mbk_counts_histogram_host(const int32_t *counts, uint64_t n, uint32_t mrd, uint64_t *hist)
+{
+    if (!hist || (!counts && n)) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = check_hist_mrd(nullptr, mrd);
+    if (rc != MBK_OK) return rc;
+    mbk::counts_histogram_host(counts, n, mrd, hist);
+    return MBK_OK;
+}
+
+int mbk_equalize_lut_host(const uint64_t *hist, uint32_t mrd, double *lut)
+{
+    if (!hist || !lut) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = check_hist_mrd(nullptr, mrd);
+    if (rc != MBK_OK) return rc;
+    if (!mbk::equalize_lut_host(hist, mrd, lut))
+        return fail(nullptr, MBK_ERR_INVALID, "twice the number of escaped samples must stay below 2^53");
+    return MBK_OK;
+}
+
+double mbk_equalize_value_host(const double *lut, uint32_t mrd, double nu)
+{
+    if (!lut || mrd > MBK_HISTOGRAM_MAX_MRD) return 0.0;
+    return mbk::equalize_value(lut, mrd, nu);
+}
+
+int mbk_counts_histogram(mbk_ctx *ctx, const int32_t *d_counts, uint64_t n, uint32_t mrd, uint64_t *d_hist, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!d_hist || (!d_counts && n)) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    int rc = check_hist_mrd(ctx, mrd);
+    if (rc != MBK_OK) return rc;
+    if (((uintptr_t)d_counts & 3u) || ((uintptr_t)d_hist & 7u))
+        return fail(ctx, MBK_ERR_INVALID, "d_counts must be 4-byte and d_hist 8-byte aligned");
+    if (n == 0) return MBK_OK;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    mbk::launch_counts_histogram(d_counts, n, mrd, (unsigned long long *)d_hist, (uint32_t)std::max(ctx->prop.multiProcessorCount, 1),
+                                 (hipStream_t)hip_stream);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// Everything a view histogram can refuse, before anything is allocated, enqueued or written: the sample launch's own rules.
+static int hist_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const void *out)
+{
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "histogram pointer is NULL");
+    if (!t.view && !t.deep) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    int rc = check_hist_mrd(ctx, mrd);
+    if (rc != MBK_OK) return rc;
+    if (t.deep) {
+        if (flags) return fail(ctx, MBK_ERR_INVALID, "deep histograms take no flags (no kernel selection, no fp32)");
+        return validate_deep(ctx, t.orbit, t.deep, mrd, MBK_WANT_COUNTS);
+    }
+    if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
+        return fail(ctx, MBK_ERR_INVALID, "histogram flags carry kernel selection and MBK_PRECISION_F32 only");
+    const bool f32 = (flags & MBK_PRECISION_F32) != 0;
+    bool dummy;
+    rc = validate_view(ctx, t.view, &dummy, f32);
+    if (rc != MBK_OK) return rc;
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
+    if (f32 && (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL))
+        return fail(ctx, MBK_ERR_INVALID, "MBK_PRECISION_F32 is implemented by the scan / asm / group kernels only");
+    return MBK_OK;
+}
+
+// A checked histogram (hist_check) added into the device table d_hist, on `stream`: the window's counts band by band through
+// the stream's render scratch (4 bytes per sample, at most MBK_RENDER_BAND_BYTES: the bands of render_run).  stat as for
+// render_run: its reduction scratch adds up the statistics, its ev_k1 marks the last histogram kernel.
+static int hist_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, unsigned long long *d_hist,
+                    hipStream_t stream, Slot *stat)
+{
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    const uint64_t per_px = 4u;
+    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;
+    uint32_t tile_cols = t.ncols, band_rows;
+    if ((uint64_t)t.ncols * per_px <= budget) {
+        band_rows = (uint32_t)std::min<uint64_t>(t.nrows, budget / ((uint64_t)t.ncols * per_px));
+    } else {
+        band_rows = 1u;
+        tile_cols = (uint32_t)(budget / per_px);
+    }
+    const size_t need = (size_t)tile_cols * band_rows * per_px;
+    rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
+    if (rc != MBK_OK) return rc;
+    int32_t *d_counts = (int32_t *)sc->d_render;   // (sc may move when a launch below adds a stream's scratch: not used past here)
+    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
+    for (uint32_t r = 0; r < t.nrows; r += band_rows) {
+        const uint32_t nr = std::min(band_rows, t.nrows - r);
+        for (uint32_t c = 0; c < t.ncols; c += tile_cols) {
+            const uint32_t nc = std::min(tile_cols, t.ncols - c);
+            mbk_view sv;
+            mbk_deep_view sd;
+            sample_window(t, 1u, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
+            if (t.deep)
+                rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, nullptr, nullptr, stream);
+            else
+                rc = launch_tile(ctx, &sv, mrd, flags | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+            if (rc != MBK_OK) return rc;
+            const uint64_t n = (uint64_t)nc * nr;
+            mbk::launch_counts_histogram(d_counts, n, mrd, d_hist, cus, stream);
+            MBK_HIP(ctx, hipGetLastError());
+            if (stat) {
+                if (r + nr == t.nrows && c + nc == t.ncols) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
+                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, n, mrd, stream, false);
+                if (rc != MBK_OK) return rc;
+            }
+        }
+    }
+    return MBK_OK;
+}
+
+static int hist_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, uint64_t *d_hist, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = hist_check(ctx, t, mrd, flags, d_hist);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_hist & 7u) return fail(ctx, MBK_ERR_INVALID, "d_hist must be 8-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return hist_run(ctx, t, mrd, flags, (unsigned long long *)d_hist, (hipStream_t)hip_stream, nullptr);
+}
+
+static int hist_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = hist_check(ctx, t, mrd, flags, h_hist);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    Slot &sl = ctx->s[0];
+    auto enqueue = [&]() -> int {
+        int rc = grow(ctx, ctx->d_hist, ctx->hist_cap, mrd, (size_t)mrd * sizeof(uint64_t));
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipMemsetAsync(ctx->d_hist, 0, (size_t)mrd * sizeof(uint64_t), sl.stream));
+        MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+        rc = hist_run(ctx, t, mrd, flags, ctx->d_hist, sl.stream, &sl);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_hist, ctx->d_hist, (size_t)mrd * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    return sync_end(ctx, enqueue(), stats, false);
+}
+
+int mbk_view_histogram_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint64_t *d_hist, void *hip_stream)
+{
+    return hist_launch(ctx, view_target(view), mrd, flags, d_hist, hip_stream);
+}
+
+int mbk_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
+{
+    return hist_compute(ctx, view_target(view), mrd, flags, h_hist, stats);
+}
+
+int mbk_deep_view_histogram_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                   uint32_t flags, uint64_t *d_hist, void *hip_stream)
+{
+    return hist_launch(ctx, deep_target(orbit, view), mrd, flags, d_hist, hip_stream);
+}
+
+int mbk_deep_view_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                    uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
+{
+    return hist_compute(ctx, deep_target(orbit, view), mrd, flags, h_hist, stats);
 }
 
 // ---- the native worker loop (mbk_feeder.h) ----------------------------------------------------------------

@@ -1,6 +1,6 @@
 // mbk_render.h -- views to RGBA8 images (include/mbk.h, "Rendering"): the colour of one sample and the resolve of a pixel's
 // s x s samples, written once as __host__ __device__ functions that the resolve kernel and mbk_render_resolve_host share, and
-// the kernel itself.  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
+// the kernel itself (three rules for the binary64 samples: smooth, distance, equalised).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
 //
 // Everything after the samples is integer arithmetic or exact binary64: t = fl(fl(nu * scale) + offset) are two rounded
 // operations (the translation unit is compiled with -ffp-contract=off), floor(t) and (t - floor(t)) * 256 are exact for
@@ -12,6 +12,8 @@
 #include <cstring>
 #include <hip/hip_runtime.h>
 
+#include "mbk_histogram.h"
+
 namespace mbk {
 
 // A palette as the kernel sees it: n RGBA8 entries packed into little-endian words (R in bits 0..7, A in 24..31).
@@ -21,7 +23,12 @@ struct RenderPalette {
     double n_rcp;      // fl(1 / n): the quotient estimate of index_mod
     uint32_t inside;   // MBK_RENDER_SMOOTH: the colour of a sample whose count is 0
     double scale, offset;
+    const double *lut;   // MBK_RENDER_EQUALIZED: the equalisation table, lut_mrd + 2 entries
+    uint32_t lut_mrd;
 };
+
+// How a binary64 sample becomes a colour: the three rules of the sources that share the (count, value) sample layout.
+enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2 };
 
 // Two colour channels at a time: a word holds channels 0 and 2 (or 1 and 3) in its 16-bit halves.
 __host__ __device__ inline uint32_t render_even(uint32_t c) { return c & 0x00ff00ffu; }
@@ -76,6 +83,26 @@ __host__ __device__ inline uint32_t render_colour_distance(const RenderPalette &
     const uint32_t f = (uint32_t)((t - k) * 256.0);
     const uint32_t i0 = (uint32_t)k;
     return render_blend(entries[i0], entries[i0 + 1u], f);
+}
+
+// The colour of one MBK_RENDER_EQUALIZED sample: nu through the equalisation table (mbk_histogram.h), then the distance rule
+// with that value in place of de.  The table is read from global memory: up to 8 MiB does not fit LDS, and its accesses are
+// as coherent as the image.
+__host__ __device__ inline uint32_t render_colour_equalized(const RenderPalette &p, const uint32_t *entries, int32_t count, double nu)
+{
+    if (count == 0) return p.inside;
+    return render_colour_distance(p, entries, count, equalize_value(p.lut, p.lut_mrd, nu));
+}
+
+template <int RULE>
+__host__ __device__ inline uint32_t render_colour(const RenderPalette &p, const uint32_t *entries, int32_t count, double value)
+{
+    if constexpr (RULE == kRuleDistance)
+        return render_colour_distance(p, entries, count, value);
+    else if constexpr (RULE == kRuleEqualized)
+        return render_colour_equalized(p, entries, count, value);
+    else
+        return render_colour_smooth(p, entries, count, value);
 }
 
 // The sum of a pixel's sample colours, two channels to a word (8 x 8 x 255 < 2^16), and its rounded mean
@@ -144,8 +171,9 @@ __device__ inline void render_load_smooth(const RenderArgs &a, uint64_t at, doub
 // lane) adjacent output pixels, so that a wave's loads cover one contiguous stretch of each sample row and its stores one
 // contiguous stretch of the image.  The grid is sized to the chip and every workgroup takes pieces in turn, which is what
 // makes staging the palette in LDS worth its loads.  Pure streaming: s^2 x (12 | 1) bytes in, 4 bytes out per pixel.
-// DIST (with SMOOTH): the samples are distance estimates (render_colour_distance); same loads, same layout.
-template <bool SMOOTH, int S, bool DIST = false>
+// RULE (with SMOOTH): what the binary64 samples are -- nu, distance estimates (render_colour_distance) or nu for the
+// equalisation table (render_colour_equalized); same loads, same layout.
+template <bool SMOOTH, int S, int RULE = kRuleSmooth>
 __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const RenderArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_palette[];
@@ -170,8 +198,7 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
                 render_load_smooth<S>(a, ((uint64_t)row * S + sy) * a.pitch + (uint64_t)col * S, nu, cnt);
 #pragma unroll
                 for (int sx = 0; sx < S; ++sx)
-                    sum.add(DIST ? render_colour_distance(a.pal, entries, cnt[sx], nu[sx])
-                                 : render_colour_smooth(a.pal, entries, cnt[sx], nu[sx]));
+                    sum.add(render_colour<RULE>(a.pal, entries, cnt[sx], nu[sx]));
             }
             out_row[col] = sum.mean(S * S);
         } else {
@@ -210,23 +237,23 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
     }
 }
 
-template <bool SMOOTH, bool DIST = false>
+template <bool SMOOTH, int RULE = kRuleSmooth>
 inline void launch_resolve(uint32_t s, dim3 grid, size_t lds, hipStream_t stream, const RenderArgs &a)
 {
     const dim3 block(kRenderThreads);
     switch (s) {
-        case 1: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 1, DIST>), grid, block, lds, stream, a); break;
-        case 2: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 2, DIST>), grid, block, lds, stream, a); break;
-        case 3: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 3, DIST>), grid, block, lds, stream, a); break;
-        case 4: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 4, DIST>), grid, block, lds, stream, a); break;
-        default: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 8, DIST>), grid, block, lds, stream, a); break;
+        case 1: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 1, RULE>), grid, block, lds, stream, a); break;
+        case 2: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 2, RULE>), grid, block, lds, stream, a); break;
+        case 3: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 3, RULE>), grid, block, lds, stream, a); break;
+        case 4: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 4, RULE>), grid, block, lds, stream, a); break;
+        default: hipLaunchKernelGGL((render_resolve_kernel<SMOOTH, 8, RULE>), grid, block, lds, stream, a); break;
     }
 }
 
 // The same rule on the host, for caller-supplied samples of (width * s) x (height * s): mbk_render_resolve_host.
 inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, uint32_t s, uint32_t width, uint32_t height,
                                 const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba,
-                                bool distance = false)
+                                int rule = kRuleSmooth)
 {
     const uint64_t pitch = (uint64_t)width * s;
     for (uint32_t y = 0; y < height; ++y)
@@ -235,9 +262,10 @@ inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, ui
             for (uint32_t sy = 0; sy < s; ++sy)
                 for (uint32_t sx = 0; sx < s; ++sx) {
                     const uint64_t at = ((uint64_t)y * s + sy) * pitch + (uint64_t)x * s + sx;
-                    sum.add(!smooth_source ? pal.entries[bytes[at]]
-                            : distance     ? render_colour_distance(pal, pal.entries, counts[at], smooth[at])
-                                           : render_colour_smooth(pal, pal.entries, counts[at], smooth[at]));
+                    sum.add(!smooth_source            ? pal.entries[bytes[at]]
+                            : rule == kRuleDistance  ? render_colour_distance(pal, pal.entries, counts[at], smooth[at])
+                            : rule == kRuleEqualized ? render_colour_equalized(pal, pal.entries, counts[at], smooth[at])
+                                                     : render_colour_smooth(pal, pal.entries, counts[at], smooth[at]));
                 }
             const uint32_t c = sum.mean(s * s);
             uint8_t *o = rgba + ((uint64_t)y * width + x) * 4u;

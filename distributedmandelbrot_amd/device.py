@@ -527,49 +527,124 @@ class MandelbrotDevice:
         return _out_array(out, shape, np.uint8).reshape(shape)
 
     def render_view(self, view: View, mrd: int, *, palette, source: str = "smooth", supersample: int = 1, window=None,
-                    kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+                    kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None):
         """The view as an RGBA8 image, coloured and anti-aliased on the GPU: (width * s) x (height * s) samples of the
         same rectangle, each through `palette` (image.Palette; source "smooth": nu, "bytes": the quantised byte,
         "distance": the exterior distance estimate, palette not cyclic -- Palette.distance), s x s of them averaged per pixel.  Only the image crosses PCIe.  `window` is in output pixels; `out` may be a
         (pinned) uint8 array of the window's size.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples);
-        row 0 is the lowest imaginary part."""
+        row 0 is the lowest imaginary part.
+        Source "equalized" colours nu through an equalisation table (image.equalize_lut; Palette.for_equalized): `lut`, or
+        with lut=None the table of the histogram of the WHOLE view at output resolution (view_histogram: s = 1, `window`
+        ignored, so that every band of an image, on any GPU, uses one table); 8 * mrd bytes and the image cross PCIe."""
         cv = self._cview(view, window)
         rgba = self._render_out(cv, out)
         spec = palette.spec(source, supersample, max_band_rows)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_view_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
-                                                      rgba.ctypes.data, C.byref(st)))
+        if source == "equalized":
+            lut = self._lut(lut, lambda: self.view_histogram(view, mrd, kernel=kernel))
+            self._check(self._lib.mbk_view_render_equalized_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                                    lut.ctypes.data, lut.size, rgba.ctypes.data, C.byref(st)))
+        else:
+            self._check(self._lib.mbk_view_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                          rgba.ctypes.data, C.byref(st)))
         return rgba, _stats(st)
 
+    @staticmethod
+    def _lut(lut, histogram) -> np.ndarray:
+        """The caller's equalisation table as a contiguous float64 array, or the table of histogram()."""
+        if lut is None:
+            from .image import equalize_lut
+            return equalize_lut(histogram())
+        return np.ascontiguousarray(lut, dtype=np.float64).ravel()
+
     def render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, source: str = "smooth",
-                         supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+                         supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None):
         """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height.
         Source "distance_rel" colours the deep distance estimate (compute_deep_view_distance; Palette.deep_distance); source
-        "distance", the plain views' estimate in plane units, is refused (MbkError)."""
+        "distance", the plain views' estimate in plane units, is refused (MbkError).  Source "equalized" and `lut` as for
+        render_view (the table of deep_view_histogram of the whole view when lut is None)."""
         cv = self._cdeep(view, window)
         rgba = self._render_out(cv, out)
         spec = palette.spec(source, supersample, max_band_rows)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                           rgba.ctypes.data, C.byref(st)))
+        if source == "equalized":
+            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd))
+            self._check(self._lib.mbk_deep_view_render_equalized_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                                         lut.ctypes.data, lut.size, rgba.ctypes.data, C.byref(st)))
+        else:
+            self._check(self._lib.mbk_deep_view_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                               rgba.ctypes.data, C.byref(st)))
         return rgba, _stats(st)
 
     def launch_render_view(self, view: View, mrd: int, *, palette, d_rgba: int, source: str = "smooth", supersample: int = 1,
-                           stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0) -> None:
+                           stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0, lut=None) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes (e.g. a torch tensor's data_ptr()) on
-        ``stream`` (0 = HIP's null stream)."""
+        ``stream`` (0 = HIP's null stream).  Source "equalized" with lut=None first takes the whole view's histogram
+        synchronously (view_histogram), as render_view does."""
         cv = self._cview(view, window)
         spec = palette.spec(source, supersample, max_band_rows)
+        if source == "equalized":
+            lut = self._lut(lut, lambda: self.view_histogram(view, mrd, kernel=kernel))
+            self._check(self._lib.mbk_view_render_equalized_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                                   lut.ctypes.data, lut.size, d_rgba or None, stream or None))
+            return
         self._check(self._lib.mbk_view_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
                                                      d_rgba or None, stream or None))
 
     def launch_render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, d_rgba: int,
                                 source: str = "smooth", supersample: int = 1, stream: int = 0, window=None,
-                                max_band_rows: int = 0) -> None:
+                                max_band_rows: int = 0, lut=None) -> None:
         cv = self._cdeep(view, window)
         spec = palette.spec(source, supersample, max_band_rows)
+        if source == "equalized":
+            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd))
+            self._check(self._lib.mbk_deep_view_render_equalized_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                                        lut.ctypes.data, lut.size, d_rgba or None,
+                                                                        stream or None))
+            return
         self._check(self._lib.mbk_deep_view_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
                                                           d_rgba or None, stream or None))
+
+    # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
+    def view_histogram(self, view: View, mrd: int, *, window=None, kernel: str = "default", precision: str = "f64",
+                       want_stats: bool = False):
+        """The histogram of the window's escape counts, built on the GPU: uint64[mrd], hist[c] the number of samples whose
+        count is c.  Only 8 * mrd bytes cross PCIe.  want_stats: (hist, TileStats) -- never_pixels and pixel_iterations from
+        the reduction over the same counts, hist[0] and sum c hist[c] + (mrd - 1) hist[0]."""
+        cv = self._cview(view, window)
+        hist = np.empty(max(int(mrd), 0), np.uint64)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_histogram_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel] | L.PRECISIONS[precision],
+                                                         hist.ctypes.data if hist.size else None, C.byref(st)))
+        return (hist, _stats(st)) if want_stats else hist
+
+    def deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_stats: bool = False):
+        """view_histogram for a deep view."""
+        cv = self._cdeep(view, window)
+        hist = np.empty(max(int(mrd), 0), np.uint64)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_view_histogram_compute(self._h, orbit._h, C.byref(cv), mrd, 0,
+                                                              hist.ctypes.data if hist.size else None, C.byref(st)))
+        return (hist, _stats(st)) if want_stats else hist
+
+    def launch_view_histogram(self, view: View, mrd: int, *, d_hist: int, stream: int = 0, window=None, kernel: str = "default",
+                              precision: str = "f64") -> None:
+        """Asynchronous form: the window's histogram is ADDED into the DEVICE table d_hist (uint64[mrd]; the caller clears it)
+        on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_view_histogram_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel] | L.PRECISIONS[precision],
+                                                        d_hist or None, stream or None))
+
+    def launch_deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_hist: int, stream: int = 0,
+                                   window=None) -> None:
+        cv = self._cdeep(view, window)
+        self._check(self._lib.mbk_deep_view_histogram_launch(self._h, orbit._h, C.byref(cv), mrd, 0, d_hist or None,
+                                                             stream or None))
+
+    def counts_histogram(self, d_counts: int, n: int, mrd: int, d_hist: int, stream: int = 0) -> None:
+        """Asynchronous: the histogram of n int32 counts in DEVICE memory is ADDED into the DEVICE table d_hist (uint64[mrd])
+        on ``stream``; counts outside [0, mrd - 1] are skipped.  The sibling of reduce_counts."""
+        self._check(self._lib.mbk_counts_histogram(self._h, d_counts or None, n, mrd, d_hist or None, stream or None))
 
     # -- stored chunks (include/mbk.h, "Stored chunks") ---------------------------------------------
     def decode_chunk(self, stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None):

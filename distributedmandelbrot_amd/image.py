@@ -22,7 +22,9 @@ class Palette:
     Source "bytes" takes 256 entries, indexed by the quantised byte; `inside`, `scale` and `offset` are not used there.
     Source "distance" maps the distance estimate de the same way, t = de * scale + offset, but the palette does not wrap:
     t >= n - 1 is the last entry (Palette.distance / for_distance set scale from a view's pixel pitch).  Source "distance_rel"
-    (deep views) does the same with the distance as a fraction of the view's span (Palette.deep_distance / for_deep_distance)."""
+    (deep views) does the same with the distance as a fraction of the view's span (Palette.deep_distance / for_deep_distance).
+    Source "equalized" maps v in [0, 1], nu sent through an equalisation table (equalize_lut), without a wrap as well
+    (Palette.for_equalized spreads the whole palette over it)."""
     entries: np.ndarray
     inside: Tuple[int, int, int, int] = (0, 0, 0, 255)
     scale: float = 1.0
@@ -112,6 +114,11 @@ class Palette:
         """Palette.distance for a DeepView and source "distance_rel"."""
         return Palette(Palette._ramp(near, far, n), inside=inside).for_deep_distance(view, width_px, inner_px=inner_px)
 
+    def for_equalized(self) -> "Palette":
+        """This palette spread over the equalised value v in [0, 1] of source "equalized": scale = n - 1, offset = 0, so that
+        equal shares of the escaped samples take equal stretches of the palette."""
+        return Palette(self.entries, self.inside, float(len(self) - 1), 0.0)
+
     @staticmethod
     def _ramp(near, far, n: int) -> np.ndarray:
         x = np.arange(n, dtype=np.float64)[:, None] / (n - 1)
@@ -127,10 +134,44 @@ class Palette:
                                  (C.c_uint8 * 4)(*self.inside), float(self.scale), float(self.offset), int(max_band_rows))
 
 
+def equalize_lut(hist) -> np.ndarray:
+    """mbk_equalize_lut_host: the equalisation table, float64[mrd + 2], of a histogram of counts (uint64[mrd]; what
+    MandelbrotDevice.view_histogram returns).  lut[k] is the share of escaped samples whose count is below k - 1 plus half the
+    share with count k - 1; count 0 takes no part."""
+    lib = L.load()
+    h = np.ascontiguousarray(hist, dtype=np.uint64).ravel()
+    lut = np.empty(h.size + 2, np.float64)
+    st = lib.mbk_equalize_lut_host(h.ctypes.data if h.size else None, h.size, lut.ctypes.data)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return lut
+
+
+def equalize_value(lut, nu: float) -> float:
+    """mbk_equalize_value_host: the equalised value of one sample."""
+    t = np.ascontiguousarray(lut, dtype=np.float64).ravel()
+    return float(L.load().mbk_equalize_value_host(t.ctypes.data, t.size - 2, float(nu)))
+
+
+def counts_histogram_host(counts, mrd: int, hist=None) -> np.ndarray:
+    """mbk_counts_histogram_host: the histogram of int32 counts on the host, ADDED into `hist` (uint64[mrd]; None: zeros)."""
+    lib = L.load()
+    c = np.ascontiguousarray(counts, dtype=np.int32).ravel()
+    hist = np.zeros(max(int(mrd), 0), np.uint64) if hist is None else hist
+    assert hist.dtype == np.uint64 and hist.size == mrd and hist.flags.c_contiguous
+    st = lib.mbk_counts_histogram_host(c.ctypes.data if c.size else None, c.size, mrd, hist.ctypes.data if hist.size else None)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return hist
+
+
 def resolve_host(palette: Palette, source: str, supersample: int, width: int, height: int, *, counts=None, bytes_=None,
-                 smooth=None) -> np.ndarray:
+                 smooth=None, lut=None) -> np.ndarray:
     """mbk_render_resolve_host: colour and resolve caller-supplied samples of (height s, width s) on the host -- the same
-    code the kernel is compiled from, without a device."""
+    code the kernel is compiled from, without a device.  Source "equalized" takes the table `lut`
+    (mbk_render_resolve_equalized_host)."""
     lib = L.load()
     out = np.empty((height, width, 4), np.uint8)
     arrs = []
@@ -140,8 +181,13 @@ def resolve_host(palette: Palette, source: str, supersample: int, width: int, he
         if a is not None and a.size != width * height * supersample * supersample:
             raise ValueError("sample arrays must hold (height * s) x (width * s) elements")
     spec = palette.spec(source, supersample)
-    st = lib.mbk_render_resolve_host(C.byref(spec), width, height, *[a.ctypes.data if a is not None else None for a in arrs],
-                                     out.ctypes.data)
+    ptrs = [a.ctypes.data if a is not None else None for a in arrs]
+    if lut is not None:
+        t = np.ascontiguousarray(lut, dtype=np.float64).ravel()
+        st = lib.mbk_render_resolve_equalized_host(C.byref(spec), t.ctypes.data, t.size, width, height, ptrs[0], ptrs[2],
+                                                   out.ctypes.data)
+    else:
+        st = lib.mbk_render_resolve_host(C.byref(spec), width, height, *ptrs, out.ctypes.data)
     if st != L.MBK_OK:
         from .device import MbkError
         raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())

@@ -470,11 +470,15 @@ double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double 
  * de (no wrap, `inside` for count 0, 0 < scale <= 2^80): a ramp over w output pixels of a W-wide view has
  * scale = (n - 1)(W - 1) / w.  mbk_render_resolve_host takes the source too. */
 #define MBK_RENDER_DISTANCE_REL 4u
+/* MBK_RENDER_EQUALIZED (plain and deep views, through the mbk_*_render_equalized_* calls only: the four calls below have no
+ * table and refuse it): the samples are those of MBK_RENDER_SMOOTH, coloured through an equalisation table -- "Count histograms
+ * and histogram-equalised colouring", below. */
+#define MBK_RENDER_EQUALIZED 5u
 /* The most sample scratch a render keeps on one stream. */
 #define MBK_RENDER_BAND_BYTES (256u << 20)
 
 typedef struct mbk_render_spec {
-    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH | MBK_RENDER_DISTANCE | MBK_RENDER_DISTANCE_REL */
+    uint32_t source;        /* MBK_RENDER_BYTES | MBK_RENDER_SMOOTH | MBK_RENDER_DISTANCE | MBK_RENDER_DISTANCE_REL | MBK_RENDER_EQUALIZED */
     uint32_t supersample;   /* 1, 2, 3, 4, 8 */
     const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
     uint32_t palette_len;
@@ -513,6 +517,92 @@ int mbk_palette_viewer(uint8_t out[1024]);
  * a width or height of 0 or width s, height s >= 2^31. */
 int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
                             const uint8_t *bytes, const double *smooth, uint8_t *rgba);
+
+/*
+ * Count histograms and histogram-equalised colouring.  NOT in the reference; additive (the ABI version stays 5): no existing
+ * call changes.  Every colouring above maps a sample to a palette position through a scale and an offset the caller must
+ * already know; a deep view's escaped counts lie in a narrow, unknown interval far from 0.  A histogram of the view's counts,
+ * built on the device, tells the caller the range (8 mrd bytes cross PCIe instead of 12 per pixel), and a cumulative table
+ * made from it spreads the palette evenly over the samples that are there.
+ *
+ * Contract (exact; tests/histogram_model.py restates it in numpy, tests/test_histogram.py and tests/test_gpu_histogram.py hold
+ * the host and the GPU to it):
+ *   histogram  hist is uint64[mrd], 1 <= mrd <= MBK_HISTOGRAM_MAX_MRD (an 8 MiB table); hist[c] is the number of samples whose
+ *              count is c (counts lie in {0} U [1, mrd - 1]).  A count outside [0, mrd - 1] is skipped, and nothing is ever
+ *              written outside the mrd bins.  hist[0] is mbk_stats.never_pixels, and sum c hist[c] + (mrd - 1) hist[0] is
+ *              mbk_stats.pixel_iterations.  Integer sums: exact whatever the schedule.
+ *   table      lut is double[mrd + 2].  With E = sum_{c >= 1} hist[c], cum(k) = sum_{1 <= c < min(k, mrd)} hist[c] and
+ *              h(k) = hist[k] for 1 <= k < mrd, else 0:  lut[0] = 0, and for k >= 1
+ *                lut[k] = fl((2 cum(k - 1) + h(k - 1)) / (2 E)),
+ *              the share of escaped samples with a lower count plus half the share with count k - 1 (nu of a count-n sample
+ *              lies in about (n + 0.16, n + 1.53]).  Monotone, lut[1] = 0, lut[mrd + 1] = 1.  E = 0 gives all zeros.  2 E must
+ *              be below 2^53, so that the conversions are exact and there is one correctly rounded division.  Count 0, the
+ *              interior, takes no part.
+ *   value      of a sample with smooth value nu, every operation rounded on its own: x = nu, or 0 unless 0 <= x (negative,
+ *              -inf, NaN).  If x >= mrd + 1: v = lut[mrd + 1].  Otherwise k = floor(x), f = x - k (exact) and
+ *              v = fl(lut[k] + fl(f fl(lut[k + 1] - lut[k]))).
+ *   colour     MBK_RENDER_EQUALIZED: `inside` if the sample's count is 0; otherwise v as above, then the MBK_RENDER_DISTANCE
+ *              rule with v in place of de: t = fl(fl(v scale) + offset), no wrap, t >= n - 1 gives the last entry.
+ *              2 <= palette_len <= 65536; scale and offset take the MBK_RENDER_SMOOTH ranges (scale = n - 1, offset = 0
+ *              spreads the whole palette).  Samples, banding, flags and resolve are those of MBK_RENDER_SMOOTH.
+ *
+ * mbk_counts_histogram: asynchronous, over counts already in HBM (the sibling of mbk_reduce_counts), on the caller's stream.
+ * It ADDS into d_hist (8-byte aligned; d_counts 4-byte aligned): the caller clears it, so that windows, bands and GPUs can
+ * accumulate into one table.  n == 0 is a no-op.
+ * mbk_view_histogram_launch / mbk_deep_view_histogram_launch: the window's counts are produced by mbk_view_launch /
+ * mbk_deep_view_launch into scratch the ctx keeps per stream (the renders' sample scratch), with the same kernel selection and
+ * refusal rules: `flags` carries kernel selection and MBK_PRECISION_F32 for a plain view, nothing for a deep one.  4 bytes per
+ * sample, banded under MBK_RENDER_BAND_BYTES exactly as a render bands, so no view size needs more scratch.  Each band's
+ * counts are ADDED into d_hist.
+ * _compute: synchronous on slot 0 (the slot-0 rule applies); h_hist is OVERWRITTEN, not accumulated; stats as for
+ * mbk_view_compute without bytes (kernel_ms from the first sample kernel to the last histogram kernel, d2h_ms the copy of the
+ * table, pixel_iterations and never_pixels from the existing reduction over the same counts -- not from the table).
+ * The _host forms need no ctx and no device.  mbk_counts_histogram_host ADDS, like the device call.  mbk_equalize_value_host
+ * returns 0 for a NULL table or an mrd above the limit.
+ * MBK_ERR_INVALID, with nothing written: NULL pointers, mrd == 0 or above MBK_HISTOGRAM_MAX_MRD, misaligned device pointers,
+ * a total at or above 2^52 escaped samples (mbk_equalize_lut_host), and whatever the sample launches refuse.
+ *
+ * mbk_*_render_equalized_*: the arguments of the four render calls plus the table.  h_lut is a HOST pointer to lut_len entries,
+ * copied during the call into scratch the ctx keeps per stream, under the palette's wait-on-change rule.  They accept
+ * MBK_RENDER_EQUALIZED only.  MBK_ERR_INVALID, with nothing written: whatever the render calls refuse for MBK_RENDER_SMOOTH,
+ * any other source, a NULL h_lut, lut_len != mrd + 2 (so mrd <= MBK_HISTOGRAM_MAX_MRD), an entry that is not finite or lies
+ * outside [0, 1].  mbk_render_resolve_equalized_host is the host twin of the resolve (mrd = lut_len - 2), compiled from the
+ * same colour function as the kernel.
+ *
+ * The histogram kernel (csrc/mbk_histogram.h has the design and what was measured): zeros are counted in registers, a
+ * workgroup keeps a window of bins in LDS where its first samples say the counts lie, equal values are folded within a wave
+ * before any atomic, and what falls outside the window goes to the table with 64-bit global atomics.
+ *
+ * Out of scope: fusing the histogram into the escape kernels; histograms of nu itself or of distance values; byte histograms
+ * of stored chunks (render_level); a sharding form (the additive d_hist makes one easy); slot / submit forms.
+ */
+#define MBK_HISTOGRAM_MAX_MRD (1u << 20)
+int mbk_counts_histogram(mbk_ctx *ctx, const int32_t *d_counts, uint64_t n, uint32_t mrd, uint64_t *d_hist, void *hip_stream);
+int mbk_view_histogram_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint64_t *d_hist,
+                              void *hip_stream);
+int mbk_deep_view_histogram_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                   uint32_t flags, uint64_t *d_hist, void *hip_stream);
+int mbk_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint64_t *h_hist,
+                               mbk_stats *stats);
+int mbk_deep_view_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                    uint32_t flags, uint64_t *h_hist, mbk_stats *stats);
+int mbk_counts_histogram_host(const int32_t *counts, uint64_t n, uint32_t mrd, uint64_t *hist);
+int mbk_equalize_lut_host(const uint64_t *hist, uint32_t mrd, double *lut);
+double mbk_equalize_value_host(const double *lut, uint32_t mrd, double nu);
+int mbk_view_render_equalized_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                                     const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint8_t *d_rgba,
+                                     void *hip_stream);
+int mbk_view_render_equalized_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                                      const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint8_t *h_rgba,
+                                      mbk_stats *stats);
+int mbk_deep_view_render_equalized_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                          uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_view_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                           uint8_t *h_rgba, mbk_stats *stats);
+int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint32_t width,
+                                      uint32_t height, const int32_t *counts, const double *smooth, uint8_t *rgba);
 
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
