@@ -225,6 +225,28 @@ SIGNATURES = {
                                                          C.POINTER(mbk_stats)]),
     "mbk_render_resolve_equalized_host": (C.c_int, [C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_julia_view_submit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                               C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                                C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_julia_view_render_equalized_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32,
+                                                         C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32,
+                                                         C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_render_equalized_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32,
+                                                          C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32,
+                                                          C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_julia_view_histogram_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_histogram_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                                   C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_julia_count_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double)]),
     "mbk_chunk_stream_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]),
     "mbk_chunk_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

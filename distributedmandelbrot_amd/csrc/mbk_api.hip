@@ -31,6 +31,7 @@
 #include "mbk_chunks.h"
 #include "mbk_distance.h"
 #include "mbk_deep_distance.h"
+#include "mbk_julia.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -1358,6 +1359,66 @@ static int check_wanted(mbk_ctx *ctx, uint32_t flags, const void *counts, const 
     return MBK_OK;
 }
 
+// enqueue kernel + reduction + D2H of a checked view on a slot's stream (no host synchronisation): the enqueue step of the deep
+// and the Julia views, synchronous (h_smooth may be given) and slot forms alike.  launch(d_counts, d_bytes, d_smooth, stream)
+// enqueues the kernel; counts always go to the device, they feed the statistics.
+template <typename Launch>
+static int view_enqueue(mbk_ctx *ctx, Slot &sl, size_t px, uint32_t mrd, uint32_t flags, int32_t *h_counts, uint8_t *h_bytes,
+                        double *h_smooth, Launch launch)
+{
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    int rc = ensure_buffers(ctx, sl, px);
+    if (rc == MBK_OK && h_smooth) rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, px, px * sizeof(double));
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+    rc = launch(sl.d_counts, wb ? sl.d_bytes : nullptr, h_smooth ? ctx->d_smooth : nullptr, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+    rc = launch_reduce(ctx, sl, sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+    if (wc) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+    if (wb) MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sl.d_bytes, px, hipMemcpyDeviceToHost, sl.stream));
+    if (h_smooth) MBK_HIP(ctx, hipMemcpyAsync(h_smooth, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+    if (&sl == &ctx->s[0]) ctx->last_px = wb ? px : 0;
+    return MBK_OK;
+}
+
+// The slot form of such a view behind its own refusals: slot range, output selection, pointers, a free slot; then the enqueue
+// step and the slot's bookkeeping.
+template <typename Launch>
+static int view_submit(mbk_ctx *ctx, int slot, size_t px, uint32_t mrd, uint32_t flags, int32_t *h_counts, uint8_t *h_bytes, Launch launch)
+{
+    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
+    if (!(flags & (MBK_WANT_COUNTS | MBK_WANT_BYTES))) return fail(ctx, MBK_ERR_INVALID, "flags select no output");
+    int rc = check_wanted(ctx, flags, h_counts, h_bytes);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    Slot &sl = ctx->s[slot];
+    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
+    rc = view_enqueue(ctx, sl, px, mrd, flags, h_counts, h_bytes, nullptr, launch);
+    if (rc != MBK_OK) return rc;
+    sl.immediate = false;
+    sl.lazy_h_bytes = nullptr;
+    sl.busy = true;
+    sl.with_bytes = (flags & MBK_WANT_BYTES) != 0;
+    return MBK_OK;
+}
+
+// The synchronous form behind its own refusals: output selection, pointers; sync_begin, the enqueue step, sync_end.
+template <typename Launch>
+static int view_compute(mbk_ctx *ctx, size_t px, uint32_t mrd, uint32_t flags, int32_t *h_counts, uint8_t *h_bytes, double *h_smooth,
+                        mbk_stats *stats, Launch launch)
+{
+    if (!(flags & (MBK_WANT_COUNTS | MBK_WANT_BYTES)) && !h_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and h_smooth select no output");
+    int rc = check_wanted(ctx, flags, h_counts, h_bytes);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    return sync_end(ctx, view_enqueue(ctx, ctx->s[0], px, mrd, flags, h_counts, h_bytes, h_smooth, launch), stats, (flags & MBK_WANT_BYTES) != 0);
+}
+
 // ------------------------------------- C ABI ---------------------------------------------------
 
 extern "C" {
@@ -2262,45 +2323,16 @@ int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_de
                        (hipStream_t)hip_stream);
 }
 
-// enqueue kernel + reduction + D2H of a checked deep view on a slot's stream (no host synchronisation); h_smooth (may be
-// NULL) is the synchronous form's
-static int deep_enqueue(mbk_ctx *ctx, Slot &sl, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
-                        int32_t *h_counts, uint8_t *h_bytes, double *h_smooth)
-{
-    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    const size_t px = (size_t)view->ncols * view->nrows;
-    int rc = ensure_buffers(ctx, sl, px);
-    if (rc == MBK_OK && h_smooth) rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, px, px * sizeof(double));
-    if (rc != MBK_OK) return rc;
-    // counts always go to the device: they feed the statistics
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-    rc = launch_deep(ctx, orbit, view, mrd, sl.d_counts, wb ? sl.d_bytes : nullptr, h_smooth ? ctx->d_smooth : nullptr, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-    rc = launch_reduce(ctx, sl, sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-    if (wc) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-    if (wb) MBK_HIP(ctx, hipMemcpyAsync(h_bytes, sl.d_bytes, px, hipMemcpyDeviceToHost, sl.stream));
-    if (h_smooth) MBK_HIP(ctx, hipMemcpyAsync(h_smooth, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-    MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
-    if (&sl == &ctx->s[0]) ctx->last_px = wb ? px : 0;
-    return MBK_OK;
-}
-
 int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
     int rc = validate_deep(ctx, orbit, view, mrd, flags);
     if (rc != MBK_OK) return rc;
-    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    if (!wc && !wb && !h_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and h_smooth select no output");
-    rc = check_wanted(ctx, flags, h_counts, h_bytes);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    return sync_end(ctx, deep_enqueue(ctx, ctx->s[0], orbit, view, mrd, flags, h_counts, h_bytes, h_smooth), stats, wb);
+    return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
+                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                            return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
+                        });
 }
 
 int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
@@ -2310,20 +2342,10 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
     if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
     int rc = validate_deep(ctx, orbit, view, mrd, flags);
     if (rc != MBK_OK) return rc;
-    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    if (!wc && !wb) return fail(ctx, MBK_ERR_INVALID, "flags select no output");
-    rc = check_wanted(ctx, flags, h_counts, h_bytes);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    Slot &sl = ctx->s[slot];
-    if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
-    rc = deep_enqueue(ctx, sl, orbit, view, mrd, flags, h_counts, h_bytes, nullptr);
-    if (rc != MBK_OK) return rc;
-    sl.immediate = false;
-    sl.lazy_h_bytes = nullptr;
-    sl.busy = true;
-    sl.with_bytes = wb;
-    return MBK_OK;
+    return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
+                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                           return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
+                       });
 }
 
 // ---- distance estimates for deep views (mbk_deep_distance.h; mbk.h "Distance estimates for deep views") ----------------
@@ -2378,6 +2400,131 @@ int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, co
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count)
 {
     return mbk::deep_distance_value(mag, dmagD, e, range_r, count);
+}
+
+// ---- Julia views (mbk_julia.h; mbk.h "Julia views") ----------------------------------------------------------
+
+// Everything a Julia launch can refuse, before anything is allocated, enqueued or written.  flags: MBK_WANT_* and kernel
+// selection; quantised: the launch produces bytes.
+static int julia_check(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags, bool quantised)
+{
+    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_KERNEL_MASK))
+        return fail(ctx, MBK_ERR_INVALID, "Julia views take MBK_WANT_COUNTS / MBK_WANT_BYTES and kernel selection only (no fp32, no MBK_LAZY_UNIFORM)");
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel != MBK_KERNEL_DEFAULT && kernel != MBK_KERNEL_ASM && kernel != MBK_KERNEL_GROUP)
+        return fail(ctx, MBK_ERR_INVALID, "Julia views are implemented by MBK_KERNEL_DEFAULT / _ASM / _GROUP only");
+    if (!std::isfinite(c_r) || !std::isfinite(c_i)) return fail(ctx, MBK_ERR_INVALID, "the Julia parameter must be finite");
+    bool dummy;
+    int rc = validate_view(ctx, v, &dummy);
+    if (rc != MBK_OK) return rc;
+    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (quantised && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    return MBK_OK;
+}
+
+// the Julia kernel on device pointers (checked by the caller: julia_check), on `stream`.  The parameter is uniform, so the two
+// exactness rules (mbk_julia.h) pick the instantiation here, once per launch.
+static int launch_julia(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                        int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+{
+    mbk::JuliaArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_window(a, v);
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.cr = c_r;
+    a.ci = c_i;
+    a.mrd = (int32_t)mrd;
+    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
+    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
+    a.exact_steps = ctx->opt[MBK_OPT_EXACT_STEPS];
+    a.cyc_window = ctx->opt[MBK_OPT_CYCLE_WINDOW];
+    a.counts = d_counts;
+    a.bytes = d_bytes;
+    a.smooth = d_smooth;
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    const bool literal = mbk::julia_needs_literal(c_i);
+    const bool per_step = kernel == MBK_KERNEL_ASM || literal || !mbk::julia_grouped_ok(c_r, c_i);
+    const bool cyc = ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u;
+    const uint32_t gs = ctx->opt[MBK_OPT_GROUP_STEPS];
+    const dim3 grid(a.blocks_x * ((v->nrows + 7u) / 8u)), block(64);
+    // MBK_OPT_WAVE_LIMIT: unused dynamic LDS per workgroup.  The sizes were found on tile_asm_kernel, but a cap through LDS is a
+    // property of the size alone: it admits at most 4 k workgroups per CU to any kernel, and this one's registers (at most 42
+    // VGPRs: 8 waves per SIMD, 32 per CU) never bind before it.
+    const uint32_t lds = ctx->wave_limit_lds[ctx->opt[MBK_OPT_WAVE_LIMIT] & 7u];
+    if (literal)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<false, 0, false>), grid, block, lds, stream, a);
+    else if (per_step)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 0, false>), grid, block, lds, stream, a);
+    else if (gs == 32u && !cyc)   // (with the cycle test 32 means 16: mbk_loops.inc)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 32, false>), grid, block, lds, stream, a);
+    else if (gs >= 16u && cyc)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 16, true>), grid, block, lds, stream, a);
+    else if (gs >= 16u)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 16, false>), grid, block, lds, stream, a);
+    else if (gs == 8u && cyc)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 8, true>), grid, block, lds, stream, a);
+    else if (gs == 8u)
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 8, false>), grid, block, lds, stream, a);
+    else
+        hipLaunchKernelGGL((mbk::julia_view_kernel<true, 4, false>), grid, block, lds, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_julia_view_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    int rc = julia_check(ctx, view, c_r, c_i, mrd, flags, wb);
+    if (rc != MBK_OK) return rc;
+    if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
+    rc = check_wanted(ctx, flags, d_counts, d_bytes);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_julia(ctx, view, c_r, c_i, mrd, flags, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
+                        (hipStream_t)hip_stream);
+}
+
+int mbk_julia_view_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = julia_check(ctx, view, c_r, c_i, mrd, flags, (flags & MBK_WANT_BYTES) != 0);
+    if (rc != MBK_OK) return rc;
+    return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
+                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                            return launch_julia(ctx, view, c_r, c_i, mrd, flags, d_counts, d_bytes, d_smooth, stream);
+                        });
+}
+
+int mbk_julia_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                          int32_t *h_counts, uint8_t *h_bytes)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
+    int rc = julia_check(ctx, view, c_r, c_i, mrd, flags, (flags & MBK_WANT_BYTES) != 0);
+    if (rc != MBK_OK) return rc;
+    return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
+                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                           return launch_julia(ctx, view, c_r, c_i, mrd, flags, d_counts, d_bytes, d_smooth, stream);
+                       });
+}
+
+int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, double *mag)
+{
+    if (!count) return fail(nullptr, MBK_ERR_INVALID, "count is NULL");
+    if (!std::isfinite(c_r) || !std::isfinite(c_i)) return fail(nullptr, MBK_ERR_INVALID, "the Julia parameter must be finite");
+    if (mrd > 0x7fffffffu) return fail(nullptr, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    double m = 0.0;
+    // the doubling a launch with this parameter would use (mbk_julia.h): both forms must give the contract's count.  A z_r beyond
+    // what a view may hold (validate_view: 2^500) takes the literal form: fl(2 z_r) may overflow there, and with z_i = 0 the
+    // literal inf * 0 is NaN where the fused form returns c_i.  Only z_0 can do that: a later |zr| >= 2^512 has mag = inf, escaped.
+    const bool literal = mbk::julia_needs_literal(c_i) || !(std::fabs(z_r) <= kMaxCoord);
+    *count = literal ? mbk::julia_count<false>(z_r, z_i, c_r, c_i, (int32_t)mrd, &m)
+                     : mbk::julia_count<true>(z_r, z_i, c_r, c_i, (int32_t)mrd, &m);
+    if (mag) *mag = m;
+    return MBK_OK;
 }
 
 // ---- rendering (mbk_render.h; mbk.h "Rendering") -----------------------------------------------------------
@@ -2470,24 +2617,34 @@ static int stream_lut(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const
     return MBK_OK;
 }
 
-// What a render renders: a view (deep == nullptr) or a deep view on its orbit.
+// What a render renders: a view (deep == nullptr), a deep view on its orbit, or the Julia set of (c_r, c_i) on a view (julia).
 struct RenderTarget {
     const mbk_view *view;
     const mbk_deep_orbit *orbit;
     const mbk_deep_view *deep;
     uint32_t width, height, col0, row0, ncols, nrows;   // of the OUTPUT
+    bool julia;
+    double c_r, c_i;
 };
 
-// The targets of the two kinds of view.  A NULL view makes a target of neither kind, which render_check refuses in its turn.
+// The targets of the three kinds of view.  A NULL view makes a target of neither kind, which render_check refuses in its turn.
 static RenderTarget view_target(const mbk_view *v)
 {
     if (!v) return RenderTarget{};
-    return RenderTarget{v, nullptr, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows};
+    return RenderTarget{v, nullptr, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0};
 }
 static RenderTarget deep_target(const mbk_deep_orbit *orbit, const mbk_deep_view *v)
 {
     if (!v) return RenderTarget{};
-    return RenderTarget{nullptr, orbit, v, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows};
+    return RenderTarget{nullptr, orbit, v, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0};
+}
+static RenderTarget julia_target(const mbk_view *v, double c_r, double c_i)
+{
+    RenderTarget t = view_target(v);
+    t.julia = true;
+    t.c_r = c_r;
+    t.c_i = c_i;
+    return t;
 }
 
 // The sample view / window of the output window (col0, row0, ncols, nrows) of `t`
@@ -2540,6 +2697,13 @@ static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint3
         return validate_lut(ctx, h_lut, lut_len, mrd);
     }
     if (rel) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)");
+    if (t.julia) {
+        if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for Mandelbrot views only (no Julia renders)");
+        if (flags & ~MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "Julia render flags carry kernel selection only");
+        rc = julia_check(ctx, &sv, t.c_r, t.c_i, mrd, flags, !smooth);
+        if (rc != MBK_OK || !equalized) return rc;
+        return validate_lut(ctx, h_lut, lut_len, mrd);
+    }
     if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
         return fail(ctx, MBK_ERR_INVALID, "render flags carry kernel selection (and MBK_PRECISION_F32) only");
     const bool f32 = (flags & MBK_PRECISION_F32) != 0;
@@ -2619,6 +2783,8 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             if (t.deep) {
                 rc = rel ? launch_deep_distance(ctx, t.orbit, &sd, mrd, d_counts, d_nu, stream)
                          : launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream);
+            } else if (t.julia) {
+                rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, d_bytes, d_nu, stream);
             } else if (dist) {
                 bool safe = false;
                 rc = distance_check(ctx, &sv, mrd, flags, &safe);
@@ -2752,6 +2918,32 @@ int mbk_deep_view_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *o
                                            uint8_t *h_rgba, mbk_stats *stats)
 {
     return render_compute(ctx, deep_target(orbit, view), mrd, flags, spec, h_rgba, stats, true, h_lut, lut_len);
+}
+
+int mbk_julia_view_render_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                 const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, julia_target(view, c_r, c_i), mrd, flags, spec, d_rgba, hip_stream);
+}
+
+int mbk_julia_view_render_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                  const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, julia_target(view, c_r, c_i), mrd, flags, spec, h_rgba, stats);
+}
+
+int mbk_julia_view_render_equalized_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                           const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint8_t *d_rgba,
+                                           void *hip_stream)
+{
+    return render_launch(ctx, julia_target(view, c_r, c_i), mrd, flags, spec, d_rgba, hip_stream, true, h_lut, lut_len);
+}
+
+int mbk_julia_view_render_equalized_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                            const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint8_t *h_rgba,
+                                            mbk_stats *stats)
+{
+    return render_compute(ctx, julia_target(view, c_r, c_i), mrd, flags, spec, h_rgba, stats, true, h_lut, lut_len);
 }
 
 // jet as matplotlib defines it (a public piecewise-linear colour map; the reference's Viewer looks colours up in its 256-entry
@@ -2891,6 +3083,10 @@ static int hist_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
         if (flags) return fail(ctx, MBK_ERR_INVALID, "deep histograms take no flags (no kernel selection, no fp32)");
         return validate_deep(ctx, t.orbit, t.deep, mrd, MBK_WANT_COUNTS);
     }
+    if (t.julia) {
+        if (flags & ~MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "Julia histogram flags carry kernel selection only");
+        return julia_check(ctx, t.view, t.c_r, t.c_i, mrd, flags, false);
+    }
     if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
         return fail(ctx, MBK_ERR_INVALID, "histogram flags carry kernel selection and MBK_PRECISION_F32 only");
     const bool f32 = (flags & MBK_PRECISION_F32) != 0;
@@ -2936,6 +3132,8 @@ static int hist_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t 
             sample_window(t, 1u, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
             if (t.deep)
                 rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, nullptr, nullptr, stream);
+            else if (t.julia)
+                rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, nullptr, nullptr, stream);
             else
                 rc = launch_tile(ctx, &sv, mrd, flags | MBK_WANT_COUNTS, d_counts, nullptr, stream);
             if (rc != MBK_OK) return rc;
@@ -3006,6 +3204,18 @@ int mbk_deep_view_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, c
                                     uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
 {
     return hist_compute(ctx, deep_target(orbit, view), mrd, flags, h_hist, stats);
+}
+
+int mbk_julia_view_histogram_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                    uint64_t *d_hist, void *hip_stream)
+{
+    return hist_launch(ctx, julia_target(view, c_r, c_i), mrd, flags, d_hist, hip_stream);
+}
+
+int mbk_julia_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                     uint64_t *h_hist, mbk_stats *stats)
+{
+    return hist_compute(ctx, julia_target(view, c_r, c_i), mrd, flags, h_hist, stats);
 }
 
 // ---- the native worker loop (mbk_feeder.h) ----------------------------------------------------------------

@@ -623,6 +623,36 @@ __device__ __forceinline__ int32_t escape_count_group(MBK_T cr, MBK_T ci, int32_
     return kCycle && cnt < 0 ? 0 : cnt;   // -1: retired by the cycle test = never escapes
 }
 
+// The same two routines for an orbit that starts at z0 = (z0r, z0i) instead of c: the Julia set of the parameter c (mbk_julia.h).
+// The step loops above keep state and parameter apart; only the seed differs.  z0 is never tested, as c is not above.  What the
+// grouped test and the cycle test rest on carries over: ">= 4 stays >= 4" needs |c| <= 2 - 1e-9 and nothing of z (the caller
+// sends every other c to the per-step loop), and the step map is a function of the state alone once c is fixed.
+template <bool kFmaDouble>
+__device__ __forceinline__ int32_t escape_count_asm_from(MBK_T z0r, MBK_T z0i, MBK_T cr, MBK_T ci, int32_t mrd, MBK_T *m_out = nullptr)
+{
+    MBK_T zr = z0r, zi = z0i;
+    MBK_T a = zr * zr, b = zi * zi, m = 0;
+    int32_t cnt = 0;
+    escape_steps_asm<kFmaDouble>(cr, ci, zr, zi, a, b, m, cnt, 0u, mrd > 1 ? (uint32_t)mrd - 1u : 0u);
+    if (m_out) *m_out = m;
+    return cnt;
+}
+
+template <int kGroup = 8, bool kCycle = false>
+__device__ __forceinline__ int32_t escape_count_group_from(MBK_T z0r, MBK_T z0i, MBK_T cr, MBK_T ci, int32_t mrd, MBK_T *m_out = nullptr,
+                                                           uint32_t kExactSteps = 8, uint32_t cyc_wcap = 32u)
+{
+    MBK_T zr = z0r, zi = z0i;
+    MBK_T a = zr * zr, b = zi * zi, m = 0;
+    int32_t cnt = 0;
+    const uint32_t total = mrd > 1 ? (uint32_t)mrd - 1u : 0u;
+    const uint32_t first = total < kExactSteps ? total : kExactSteps;
+    escape_steps_asm<true>(cr, ci, zr, zi, a, b, m, cnt, 0u, first);
+    if (cnt == 0 && total > first) escape_steps_tail<kGroup, kCycle>(cr, ci, zr, zi, a, b, m, cnt, first, total, cyc_wcap);
+    if (m_out) *m_out = m;
+    return kCycle && cnt < 0 ? 0 : cnt;   // -1: retired by the cycle test = never escapes
+}
+
 // ---------------------------------------------------------------------------------------------
 // The light path of pass 1 (kernel "scan") for a RUN of interior 8x8 blocks, in one asm loop: block k of the run lies
 // `rowinc` rows below block k-1 in the same block column (the wave's stride), so per block only the imaginary

@@ -188,6 +188,15 @@ def datachunk_geometry(level: int, index_real: int, index_imag: int) -> Tuple[fl
     return a.value, b.value, c.value
 
 
+def julia_count_host(z, c, mrd: int) -> Tuple[int, float]:
+    """mbk_julia_count_host: (n, mag) of one Julia orbit -- z -> z^2 + c from z_0 = z -- on the host, without a device: the
+    contract's loop (include/mbk.h, "Julia views") with the doubling a launch with this c would use."""
+    lib = L.load()
+    n, mag = C.c_int32(0), C.c_double(0.0)
+    _check(lib, lib.mbk_julia_count_host(float(z[0]), float(z[1]), float(c[0]), float(c[1]), mrd, C.byref(n), C.byref(mag)))
+    return int(n.value), float(mag.value)
+
+
 def _stream_array(stream) -> np.ndarray:
     """A chunk stream (bytes, bytearray, memoryview or uint8 array) as a contiguous uint8 array, without a copy where possible."""
     if isinstance(stream, np.ndarray):
@@ -645,6 +654,91 @@ class MandelbrotDevice:
         """Asynchronous: the histogram of n int32 counts in DEVICE memory is ADDED into the DEVICE table d_hist (uint64[mrd])
         on ``stream``; counts outside [0, mrd - 1] are skipped.  The sibling of reduce_counts."""
         self._check(self._lib.mbk_counts_histogram(self._h, d_counts or None, n, mrd, d_hist or None, stream or None))
+
+    # -- Julia views (include/mbk.h, "Julia views") ---------------------------------------------------
+    def compute_julia_view(self, view: View, c, mrd: int, *, window=None, want_counts: bool = True, want_bytes: bool = True,
+                           want_smooth: bool = False, kernel: str = "default", out_counts: Optional[np.ndarray] = None,
+                           out_bytes: Optional[np.ndarray] = None):
+        """The Julia set of the parameter c = (c_r, c_i) on `view`: z -> z^2 + c from z_0 = the pixel's coordinate.
+        Synchronous: (counts int32 | None, bytes uint8 | None, smooth float64 | None, TileStats), each [nrows, ncols].
+        kernel: "default", "asm" (the per-step loop) or "group"."""
+        cv = self._cview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        counts = _out_array(out_counts, shape, np.int32) if want_counts else None
+        byts = _out_array(out_bytes, shape, np.uint8) if want_bytes else None
+        smooth = np.empty(shape, np.float64) if want_smooth else None
+        flags, p_counts, p_bytes = _wanted(shape, counts, byts)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_julia_view_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel] | flags,
+                                                     p_counts, p_bytes, smooth.ctypes.data if smooth is not None else None,
+                                                     C.byref(st)))
+        return counts, byts, smooth, _stats(st)
+
+    def submit_julia_view(self, slot: int, view: View, c, mrd: int, *, window=None, out_counts: Optional[np.ndarray] = None,
+                          out_bytes: Optional[np.ndarray] = None, kernel: str = "default") -> None:
+        """Enqueue a Julia view / window on `slot`; the host arrays are valid after wait(slot)."""
+        cv = self._cview(view, window)
+        flags, p_counts, p_bytes = _wanted((cv.nrows, cv.ncols), out_counts, out_bytes)
+        self._check(self._lib.mbk_julia_view_submit(self._h, slot, C.byref(cv), float(c[0]), float(c[1]), mrd,
+                                                    L.KERNELS[kernel] | flags, p_counts, p_bytes))
+
+    def launch_julia_view(self, view: View, c, mrd: int, *, d_counts: int = 0, d_bytes: int = 0, d_smooth: int = 0,
+                          stream: int = 0, window=None, kernel: str = "default") -> None:
+        """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        flags = L.KERNELS[kernel] | (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0)
+        self._check(self._lib.mbk_julia_view_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, flags, d_counts or None,
+                                                    d_bytes or None, d_smooth or None, stream or None))
+
+    def render_julia_view(self, view: View, c, mrd: int, *, palette, source: str = "smooth", supersample: int = 1, window=None,
+                          kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None):
+        """render_view for the Julia set of c: source "bytes", "smooth" or "equalized" (`lut` as for render_view: None takes
+        the table of julia_view_histogram of the whole view); the distance sources are refused (MbkError)."""
+        cv = self._cview(view, window)
+        rgba = self._render_out(cv, out)
+        spec = palette.spec(source, supersample, max_band_rows)
+        st = L.mbk_stats()
+        if source == "equalized":
+            lut = self._lut(lut, lambda: self.julia_view_histogram(view, c, mrd, kernel=kernel))
+            self._check(self._lib.mbk_julia_view_render_equalized_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
+                                                                          L.KERNELS[kernel], C.byref(spec), lut.ctypes.data, lut.size,
+                                                                          rgba.ctypes.data, C.byref(st)))
+        else:
+            self._check(self._lib.mbk_julia_view_render_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
+                                                                L.KERNELS[kernel], C.byref(spec), rgba.ctypes.data, C.byref(st)))
+        return rgba, _stats(st)
+
+    def launch_render_julia_view(self, view: View, c, mrd: int, *, palette, d_rgba: int, source: str = "smooth",
+                                 supersample: int = 1, stream: int = 0, window=None, kernel: str = "default",
+                                 max_band_rows: int = 0, lut=None) -> None:
+        """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream``; "equalized" with lut=None first
+        takes the whole view's histogram synchronously, as render_julia_view does."""
+        cv = self._cview(view, window)
+        spec = palette.spec(source, supersample, max_band_rows)
+        if source == "equalized":
+            lut = self._lut(lut, lambda: self.julia_view_histogram(view, c, mrd, kernel=kernel))
+            self._check(self._lib.mbk_julia_view_render_equalized_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
+                                                                         L.KERNELS[kernel], C.byref(spec), lut.ctypes.data, lut.size,
+                                                                         d_rgba or None, stream or None))
+            return
+        self._check(self._lib.mbk_julia_view_render_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
+                                                           C.byref(spec), d_rgba or None, stream or None))
+
+    def julia_view_histogram(self, view: View, c, mrd: int, *, window=None, kernel: str = "default", want_stats: bool = False):
+        """view_histogram for the Julia set of c."""
+        cv = self._cview(view, window)
+        hist = np.empty(max(int(mrd), 0), np.uint64)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_julia_view_histogram_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
+                                                               hist.ctypes.data if hist.size else None, C.byref(st)))
+        return (hist, _stats(st)) if want_stats else hist
+
+    def launch_julia_view_histogram(self, view: View, c, mrd: int, *, d_hist: int, stream: int = 0, window=None,
+                                    kernel: str = "default") -> None:
+        """Asynchronous form: the window's histogram is ADDED into the DEVICE table d_hist (uint64[mrd]) on ``stream``."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_julia_view_histogram_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
+                                                              d_hist or None, stream or None))
 
     # -- stored chunks (include/mbk.h, "Stored chunks") ---------------------------------------------
     def decode_chunk(self, stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None):

@@ -168,9 +168,26 @@ def render_deep_view(devices: Sequence, orbit, view, mrd: int, *, band_rows: int
                          submit, compute, "submit_deep_view")
 
 
+def render_julia_view(devices: Sequence, view, c, mrd: int, *, band_rows: int = 128, want_counts: bool = True,
+                      want_bytes: bool = True, kernel: str = "default", out_counts: Optional[np.ndarray] = None,
+                      out_bytes: Optional[np.ndarray] = None
+                      ) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], List[dict]]:
+    """render_view for the Julia set of the parameter c = (c_r, c_i) on `view` (submit_julia_view / wait); the image is
+    bit-identical to compute_julia_view's."""
+    def submit(dev, s, window, oc, ob):
+        dev.submit_julia_view(s, view, c, mrd, window=window, out_counts=oc, out_bytes=ob, kernel=kernel)
+
+    def compute(dev, window, oc, ob):
+        return dev.compute_julia_view(view, c, mrd, window=window, want_counts=want_counts, want_bytes=want_bytes, kernel=kernel,
+                                      out_counts=oc, out_bytes=ob)[3]
+
+    return _render_bands(devices, view.width, view.height, band_rows, want_counts, want_bytes, out_counts, out_bytes,
+                         submit, compute, "submit_julia_view")
+
+
 def _render_bands(devices, width, height, band_rows, want_counts, want_bytes, out_counts, out_bytes, submit, compute,
                   submit_name):
-    """The feeder loop of render_view / render_deep_view: submit(dev, slot, window, out_counts, out_bytes) + dev.wait(slot)
+    """The feeder loop of render_view / render_deep_view / render_julia_view: submit(dev, slot, window, out_counts, out_bytes) + dev.wait(slot)
     on devices that have `submit_name`, compute(dev, window, out_counts, out_bytes) -> stats on the others."""
     bands = make_bands(height, band_rows)
     queue = WorkQueue(bands)

@@ -604,6 +604,85 @@ int mbk_deep_view_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *o
 int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint32_t width,
                                       uint32_t height, const int32_t *counts, const double *smooth, uint8_t *rgba);
 
+/*
+ * Julia views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes.  Every view above iterates
+ * z -> z^2 + c with the pixel as c.  A Julia view fixes c = (c_r, c_i) and takes the pixel as the starting point: "the Julia set
+ * of the point I am looking at".  A Julia view is an mbk_view plus the parameter; coordinates (np.linspace), window rule,
+ * layout and row order are those of every view.
+ *
+ * Contract (exact; tests/julia_model.py restates it in numpy, tests/test_julia.py and tests/test_gpu_julia.py hold the host
+ * and the GPU to it):
+ *   state     for the pixel with coordinate p, z_0 = p.  z_0 is never tested (as calc_mb_value never tests its z_0 = c).
+ *   step      z_(k+1) = z_k^2 + c in binary64, every operation rounded on its own, in the reference's order:
+ *               zr' = fl(fl(fl(zr zr) - fl(zi zi)) + c_r),  zi' = fl(fl(fl(2 zr) zi) + c_i);   at most mrd - 1 updates;
+ *               mag_k = fl(fl(zr^2) + fl(zi^2)).
+ *   count     n = the first k >= 1 with mag_k >= 4 (false for NaN), 0 if there is none.  mrd 0 and 1 run no step.
+ *   outputs   bytes: the quantiser of every view, of n.  smooth: nu = n + 1 - log2(0.5 ln mag_n), the function and the
+ *             allowance of mbk_view_launch_smooth (2.57 ulp(nu) + 3.38 x 2^-52 around the correctly rounded value at mag_n).
+ *             mbk_stats means what it means for mbk_view_compute.
+ *   identity  at a pixel whose coordinate equals c bit for bit, n is the Mandelbrot count of c (the same orbit).
+ *   windows   a window of a view is bit-identical to that part of the whole view.
+ *   odd input coordinates whose squares overflow or turn NaN store whatever this strict evaluation stores.
+ *
+ * Two exactness rules, both decided on the host once per launch (c is uniform):
+ *   doubling  The kernels form zi' as fma(2, fl(zr zi), c_i), which equals the literal form unless zr zi is a non-zero
+ *             subnormal (2 fl(zr zi) then carries a rounding that fl(fl(2 zr) zi) does not).  For a Mandelbrot view that
+ *             hazard sits on rows with a tiny c_i.  For a Julia view zi is NOT tied to c_i: with c_i = 0 (c = -1, -0.75,
+ *             0.25 ...) a row whose z0_i is tiny keeps zi tiny for many steps.  |c_i| >= 2^-900 makes the rewrite safe for
+ *             every z: both candidate addends are below 2^-1021, less than a quarter ulp of c_i, and round away alike.  So
+ *             every launch with |c_i| < 2^-900, c_i = 0 included, takes the literal 8-operation per-step loop.  (The two forms
+ *             also part where fl(2 zr) overflows and zi = 0: NaN against c_i.  Only z_0 can do that -- a later |zr| >= 2^512 has
+ *             mag = inf and has escaped --, and a view's coordinates are bounded by 2^500; mbk_julia_count_host, which takes any
+ *             z, uses the literal form beyond that bound.)
+ *   grouping  The grouped bailout test (MBK_KERNEL_GROUP) relies on "|z|^2 >= 4 stays >= 4", which holds for
+ *             |c|^2 < 4 - 1e-9 whatever z is (|z'| >= |z|^2 - |c| > 2 + 2e-10) and fails above: for |c| > 2 a |z| >= 2
+ *             that is below |c| can come back inside.  A launch whose fl(fl(c_r^2) + fl(c_i^2)) is not below 4 - 1e-9 takes
+ *             the per-step loop throughout.  The cycle test needs only that the step is a function of the state, which a
+ *             fixed c gives it.
+ *
+ * flags: MBK_WANT_COUNTS | MBK_WANT_BYTES on the three view calls, plus kernel selection: MBK_KERNEL_DEFAULT (the library's
+ * choice: the grouped test with the cycle test where the two rules allow it), MBK_KERNEL_ASM (the per-step loop, every
+ * iteration executed: the witness), MBK_KERNEL_GROUP (grouped test + cycle test under MBK_OPT_GROUP_STEPS, _EXACT_STEPS,
+ * _CYCLE_DETECT, _CYCLE_WINDOW and _WAVE_LIMIT; no other option is consulted; _WAVE_LIMIT's cap, unused LDS per workgroup,
+ * holds for this kernel as for any: its registers allow 8 waves per SIMD, so they never bind before it).  Every accepted value gives identical output.
+ * MBK_ERR_INVALID, with nothing written: MBK_KERNEL_SIMPLE / _REFILL / _SCAN, MBK_PRECISION_F32, MBK_LAZY_UNIFORM, any other
+ * flag bit, a non-finite c, mrd >= 2^31, mrd == 0 with bytes, no output selected, a wanted output with a NULL pointer, and
+ * whatever mbk_view_launch refuses of a view.
+ *
+ * mbk_julia_view_launch: asynchronous, device pointers, the caller's stream; d_smooth may be NULL.  _compute: synchronous on
+ * slot 0, host pointers, h_smooth may be NULL.  _submit: on a slot, completed by mbk_wait.
+ * mbk_julia_view_render_* / _render_equalized_* / _histogram_*: the calls of the same names without "julia_", on the Julia
+ * samples: banding, palettes, supersampling, tables and statistics are the same code.  flags carry kernel selection only;
+ * sources MBK_RENDER_BYTES, _SMOOTH and (equalized calls) _EQUALIZED; the distance sources are refused.
+ * mbk_julia_count_host: one orbit on the host, no ctx, no device -- the contract's loop as the kernels restate it, with the
+ * doubling a launch with this c would use.  *mag (may be NULL) is the mag of the last step run (mag_n if n > 0; 0 if no step
+ * ran).  MBK_ERR_INVALID for a NULL count, a non-finite c, mrd >= 2^31; z may be anything.
+ *
+ * Out of scope: distance estimates and deep (perturbation) Julia views, an fp32 form, the scan / refill / units machinery,
+ * the z -> -z symmetry.
+ */
+int mbk_julia_view_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream);
+int mbk_julia_view_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats);
+int mbk_julia_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                          int32_t *h_counts, uint8_t *h_bytes);
+int mbk_julia_view_render_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                 const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_julia_view_render_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                  const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+int mbk_julia_view_render_equalized_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                           uint8_t *d_rgba, void *hip_stream);
+int mbk_julia_view_render_equalized_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd,
+                                            uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                            uint8_t *h_rgba, mbk_stats *stats);
+int mbk_julia_view_histogram_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                    uint64_t *d_hist, void *hip_stream);
+int mbk_julia_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                     uint64_t *h_hist, mbk_stats *stats);
+int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, double *mag);
+
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
 #define MBK_CODEC_RLE 0x01u
