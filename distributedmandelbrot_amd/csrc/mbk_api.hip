@@ -39,10 +39,6 @@ using mbk::ReduceSlot;
 using mbk::TileArgs;
 using mbk::WorkQueues;
 
-// Scratch that helper kernels of a launch use (dispatch-order list, work-queue cursors, the scan
-// kernel's deferred-block lists).  It is keyed by the HIP stream the launch goes to: launches on one
-// stream are ordered, so one set per stream can never be rewritten while a kernel still reads it,
-// however many streams the caller uses (round 1 shared a ring of 8 across all streams).
 // Dispatch lists per stream, used in turn.  Two were enough to let the pre-pass of launch L + 1 run beside the tile kernel of
 // launch L -- but a second queue gets no wave slot on a chip full of single-wave workgroups until the tile kernel's grid is
 // dealt (measured, profiles/r05/gaps_*.txt: the pre-pass starts 200 us into a 275 us launch and ends after it), which did not
@@ -50,11 +46,10 @@ using mbk::WorkQueues;
 // of launch L + 1 may start one launch earlier and is done long before its list is needed.
 static const int kOrderRing = 3;
 
-struct StreamScratch {
-    hipStream_t stream = nullptr;
-    // heavy-first dispatch order of kernels "asm"/"group": kOrderRing lists (list | 3 counters | middle-class list) used
-    // in turn, so that the pre-pass of a later launch (memset + classify, on the aux stream) can run while the tile
-    // kernels of the launches before it still read the others
+// The dispatch-list ring of one stream: the heavy-first dispatch order of kernels "asm"/"group", kOrderRing lists
+// (list | 3 counters | middle-class list) used in turn, so that the pre-pass of a later launch (memset + classify, on the aux
+// stream) can run while the tile kernels of the launches before it still read the others
+struct OrderRing {
     uint32_t *d_order[kOrderRing] = {};
     uint32_t *d_ctl = nullptr;    // 8 words per list: the units pre-pass' counters (H, V, M | late M, settled H, ticket), zero between launches
     bool ctl_dirty = true;        // the counters must be cleared (on the pre-pass' own stream) before the next pre-pass: never used
@@ -67,6 +62,60 @@ struct StreamScratch {
     hipEvent_t ev_cls[kOrderRing] = {};   // pre-pass into list k finished
     hipEvent_t ev_done[kOrderRing] = {};  // the tile kernel that read list k finished
     bool done_valid[kOrderRing] = {};
+
+    void drop_lists()   // (the callers of this and the next have drained whatever may still use what goes)
+    {
+        for (int k = 0; k < kOrderRing; ++k) {
+            if (d_order[k]) (void)hipFree(d_order[k]);
+            d_order[k] = nullptr;
+            done_valid[k] = false;
+        }
+        order_cap = 0;
+    }
+    void drop_aux()   // the stream and the events that tie it to the caller's
+    {
+        if (aux) (void)hipStreamDestroy(aux);
+        aux = nullptr;
+        for (int k = 0; k < kOrderRing; ++k) {
+            if (ev_cls[k]) (void)hipEventDestroy(ev_cls[k]);
+            if (ev_done[k]) (void)hipEventDestroy(ev_done[k]);
+            ev_cls[k] = ev_done[k] = nullptr;
+            done_valid[k] = false;
+        }
+    }
+    void release()
+    {
+        if (aux) (void)hipStreamSynchronize(aux);
+        drop_lists();
+        drop_aux();
+        if (d_ctl) (void)hipFree(d_ctl);
+        *this = OrderRing();
+    }
+};
+
+// SPILL (mbk_spill.h): the slots of the spilled lanes (state, meta), the per-block counts, the chunk sums / offsets and the
+// total of the prefix sum, the compacted list of slots
+struct SpillBuffers {
+    void *d_z = nullptr;
+    uint32_t *d_meta = nullptr, *d_cnt = nullptr, *d_chunks = nullptr, *d_src = nullptr;
+    unsigned long long *d_total = nullptr;
+    size_t cap_slots = 0, cap_blocks = 0;   // capacities (slots of 16 bytes of state; blocks)
+
+    void release()
+    {
+        for (void *q : {d_z, (void *)d_meta, (void *)d_cnt, (void *)d_chunks, (void *)d_src, (void *)d_total})
+            if (q) (void)hipFree(q);
+        *this = SpillBuffers();
+    }
+};
+
+// Scratch that helper kernels of a launch use (dispatch-order list, work-queue cursors, the scan
+// kernel's deferred-block lists).  It is keyed by the HIP stream the launch goes to: launches on one
+// stream are ordered, so one set per stream can never be rewritten while a kernel still reads it,
+// however many streams the caller uses (round 1 shared a ring of 8 across all streams).
+struct StreamScratch {
+    hipStream_t stream = nullptr;
+    OrderRing ring;
     WorkQueues *d_queues = nullptr;  // kernel "refill"
     mbk::ScanCursors *d_cursors = nullptr;  // kernel "scan": two sets, used alternately
     uint32_t *d_entries = nullptr;   // kernel "scan": the 64 todo lists (block ids)
@@ -75,12 +124,7 @@ struct StreamScratch {
     bool cursors_dirty = false;      // a scan launch failed after its cursor sets were assigned: clear both next time
     uint32_t *h_hint = nullptr;   // pinned, written by the kernels of the last launch on this stream:
                                   // [0] longest deferred list (scan pass 2), [1] share of heavy blocks x 65536
-    // SPILL (mbk_spill.h): the slots of the spilled lanes (state, meta), the per-block counts, the chunk sums / offsets and the
-    // total of the prefix sum, the compacted list of slots
-    void *d_spill_z = nullptr;
-    uint32_t *d_spill_meta = nullptr, *d_spill_cnt = nullptr, *d_spill_chunks = nullptr, *d_spill_src = nullptr;
-    unsigned long long *d_spill_total = nullptr;
-    size_t spill_cap_slots = 0, spill_cap_blocks = 0;   // capacities (slots of 16 bytes of state; blocks)
+    SpillBuffers spill;
     ReduceSlot *d_red = nullptr;  // mbk_reduce_counts on this (caller) stream: its own partial results, so that a
     ReduceSlot *h_red = nullptr;  // reduction on a caller stream never shares a buffer with a tile in flight on a slot
     // kernel "units": the shares of the eight XCDs (mbk_units.h).  Launch number c (1-based) writes its time stamps into
@@ -320,21 +364,9 @@ static int validate_view(mbk_ctx *ctx, const mbk_view *v, bool *safe_doubling, b
 
 static void free_scratch(StreamScratch &sc)
 {
-    if (sc.aux) (void)hipStreamSynchronize(sc.aux);
-    for (int k = 0; k < kOrderRing; ++k) {
-        if (sc.d_order[k]) (void)hipFree(sc.d_order[k]);
-        if (sc.ev_cls[k]) (void)hipEventDestroy(sc.ev_cls[k]);
-        if (sc.ev_done[k]) (void)hipEventDestroy(sc.ev_done[k]);
-    }
-    if (sc.aux) (void)hipStreamDestroy(sc.aux);
-    if (sc.d_ctl) (void)hipFree(sc.d_ctl);
+    sc.ring.release();
+    sc.spill.release();
     if (sc.d_queues) (void)hipFree(sc.d_queues);
-    if (sc.d_spill_z) (void)hipFree(sc.d_spill_z);
-    if (sc.d_spill_meta) (void)hipFree(sc.d_spill_meta);
-    if (sc.d_spill_cnt) (void)hipFree(sc.d_spill_cnt);
-    if (sc.d_spill_chunks) (void)hipFree(sc.d_spill_chunks);
-    if (sc.d_spill_src) (void)hipFree(sc.d_spill_src);
-    if (sc.d_spill_total) (void)hipFree(sc.d_spill_total);
     if (sc.d_cursors) (void)hipFree(sc.d_cursors);
     if (sc.d_entries) (void)hipFree(sc.d_entries);
     if (sc.h_hint) (void)hipHostFree(sc.h_hint);
@@ -440,363 +472,430 @@ static void xcd_shares_update(const mbk_ctx *ctx, StreamScratch &sc)
     }
 }
 
-// Launch the one-wave-per-block kernels ("asm" / "group", fp64 or fp32) for the window described by `a`
-// (a.col0/row0/ncols/nrows, output at a.out_*), optionally behind the heavy-first classify pre-pass.
-// fuse / counts_unwanted / fused: as for launch_scan_t -- partial-result slots (already zeroed on `stream`) to which a kernel
-// that can do so adds the tile's pixel-iterations and never-escaped count itself (the units kernel, when the int32 counts in
-// `a` exist for the statistics only: it then writes none); *fused says whether it did.
-static int launch_blocks(mbk_ctx *ctx, TileArgs a, uint32_t kernel, bool safe, bool f32, hipStream_t stream,
-                         ReduceSlot *fuse = nullptr, bool counts_unwanted = false, bool *fused = nullptr)
+// The statistics a tile kernel may add up itself: partial-result slots (already zeroed on the launch's stream) to which a
+// kernel that can do so adds the tile's pixel-iterations and never-escaped count (the units kernel and the finish-in-place
+// light pass).  counts_unwanted: the int32 counts of the launch exist for the statistics only -- a launch that fuses them
+// writes none.  fused (out): whether the kernel that served the launch did it.
+struct FuseStats { ReduceSlot *slots; bool counts_unwanted; bool fused; };
+
+// The quantised bytes of counts 1..4, packed low byte first: the table of the light paths (units kernel, scan pass 1)
+static uint32_t quant_table4(int32_t mrd, bool want_bytes)
 {
-    const uint32_t wpw = ctx->opt[MBK_OPT_WAVES_PER_WG];  // 8x8-pixel blocks (= waves) per workgroup
-    a.blocks_x = (a.ncols + 8u * wpw - 1u) / (8u * wpw);
-    const uint32_t by = (a.nrows + 7u) / 8u;
+    uint32_t qtab = 0u;
+    if (want_bytes && mrd > 0)
+        for (uint32_t c = 1; c <= 4u; ++c)
+            qtab |= (uint32_t)(((uint64_t)c * 256u + (uint32_t)mrd - 1u) / (uint32_t)mrd & 0xffu) << (8u * (c - 1u));
+    return qtab;
+}
+
+// launch_blocks, step by step.  What a launch is made of, decided once from the window and the options:
+struct BlockLaunchPlan {
+    uint32_t wpw, by;                   // 8x8-pixel blocks (= waves) per workgroup; block rows
+    dim3 grid, block;
+    uint32_t order_mode, probe_steps;   // MBK_OPT_ORDER, MBK_OPT_PROBE_STEPS
+    bool cyc, units, ordered;           // MBK_OPT_CYCLE_DETECT; the units kernel serves the launch; it follows a list built by a pre-pass
+    double unit_share;                  // with `units`: the host probe's share of the window still inside after 4 steps
+};
+
+// Step 1, the launch facts, the window facts of `a` (set_window_facts) among them.  Host arithmetic only -- no HIP call.
+static BlockLaunchPlan block_launch_plan(mbk_ctx *ctx, TileArgs &a, uint32_t kernel, bool safe, bool f32)
+{
+    BlockLaunchPlan p;
+    p.wpw = ctx->opt[MBK_OPT_WAVES_PER_WG];
+    a.blocks_x = (a.ncols + 8u * p.wpw - 1u) / (8u * p.wpw);
+    p.by = (a.nrows + 7u) / 8u;
     set_window_facts(a, f32);
-    const bool cyc = ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u;
-    const dim3 grid(a.blocks_x * by), block(64u * wpw);
-    const uint32_t order_mode = ctx->opt[MBK_OPT_ORDER], probe_steps = ctx->opt[MBK_OPT_PROBE_STEPS];
-    a.perm_mul = order_mode == 1 ? coprime_multiplier(grid.x) : 1u;
+    p.cyc = ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u;
+    p.grid = dim3(a.blocks_x * p.by);
+    p.block = dim3(64u * p.wpw);
+    p.order_mode = ctx->opt[MBK_OPT_ORDER];
+    p.probe_steps = ctx->opt[MBK_OPT_PROBE_STEPS];
+    a.perm_mul = p.order_mode == 1 ? coprime_multiplier(p.grid.x) : 1u;
     a.order = nullptr;
-    int order_slot = -1;
-    bool mid_first = false, order_overlap = false;
-    StreamScratch *order_sc = nullptr;
     // order 3 = "units" (mbk_units.h): the light blocks of eight neighbouring block columns are ONE workgroup.  Where the
     // units kernel cannot serve a launch (outputs, widths, step counts it has no form for) the launch takes order 2.
-    bool units = order_mode == 3 && wpw == 1u && kernel == MBK_KERNEL_GROUP && !safe && a.smooth == nullptr &&
-                 (a.counts || a.bytes) && !(a.bytes && a.quant_wide) && a.blocks_x % 8u == 0u && a.blocks_x <= 2048u &&
-                 a.fast_bx_end > 0u && a.fast_by_end > 0u && (f32 || ctx->opt[MBK_OPT_GROUP_STEPS] == 16u) &&
-                 grid.x >= 16384u && (uint32_t)a.mrd > 2u * probe_steps && by <= 0xffffu;
+    p.units = p.order_mode == 3 && p.wpw == 1u && kernel == MBK_KERNEL_GROUP && !safe && a.smooth == nullptr &&
+              (a.counts || a.bytes) && !(a.bytes && a.quant_wide) && a.blocks_x % 8u == 0u && a.blocks_x <= 2048u &&
+              a.fast_bx_end > 0u && a.fast_by_end > 0u && (f32 || ctx->opt[MBK_OPT_GROUP_STEPS] == 16u) &&
+              p.grid.x >= 16384u && (uint32_t)a.mrd > 2u * p.probe_steps && p.by <= 0xffffu;
     // ... and only where there is light area to batch: the share of the host's 16 x 16 probe pixels of the window that is gone
     // after 4 steps (a deterministic function of the window).  Measured (profiles/r04/units_ab.txt): cfg2 (0.64 light) strict
     // -0.3 % / cycle test +4.7 %, DataChunk (1,0,0) (0.8) +2.1 % / +9.7 %, cfg3 (none) -0.7 % / 0.
-    double unit_share = 0.0;
-    if (units) {
-        unit_share = window_heavy_share(ctx, a);
-        units = (1.0 - unit_share) * 65536.0 >= (double)ctx->opt[MBK_OPT_UNITS_MIN_LIGHT];
+    p.unit_share = 0.0;
+    if (p.units) {
+        p.unit_share = window_heavy_share(ctx, a);
+        p.units = (1.0 - p.unit_share) * 65536.0 >= (double)ctx->opt[MBK_OPT_UNITS_MIN_LIGHT];
     }
-    if (order_mode >= 2 && grid.x >= 16384u && (uint32_t)a.mrd > 2u * probe_steps && a.blocks_x <= 0xffffu && by <= 0xffffu) {
-        // (a list entry packs block row and workgroup column into 16 bits each; wider windows go in image order)
-        // heavy-first dispatch order (see classify_blocks_kernel); small launches skip it: one kernel in image
-        // order beats memset + classify + tile below ~16 k blocks (cfg1, 4096 blocks: 20 us against 27)
-        StreamScratch *sc = nullptr;
-        int rc = get_scratch(ctx, stream, &sc);
-        if (rc != MBK_OK) return rc;
-        // MBK_OPT_PREPASS_OVERLAP: 0 the pre-pass runs on the caller's stream, in order (one queue, no event: +4..5 us per cfg2
-        // launch back to back, profiles/r06/prepass_modes_ab.txt); 1 / 2 on an auxiliary stream (2: at the highest priority), tied
-        // to the tile kernel by events.  (Round 6 also tried it as an ANY-ORDER launch on the caller's stream -- an AQL packet
-        // without the barrier bit, hipExtAnyOrderLaunch, which would start in the previous tile kernel's drain -- but gfx950
-        // ignores the flag: profiles/microbench/anyorder.hip, profiles/r06/anyorder.txt.)
-        const uint32_t pp_mode = ctx->opt[MBK_OPT_PREPASS_OVERLAP];
-        const bool overlap = pp_mode != 0u;
-        // MBK_OPT_PREPASS_OVERLAP = 2: the auxiliary stream has the highest priority, so that the pre-pass of launch L + 1 gets
-        // its workgroups in while the tile kernel of launch L is in full swing instead of waiting for its drain (round 5: once
-        // the launch no longer ends in a 20 us drain, a pre-pass that waited for it sits on the critical path)
-        const uint32_t want_prio = pp_mode == 2u ? 2u : 1u;
-        if (sc->pp_last != (int)pp_mode) {
-            // the lists' hand-over differs by mode (events between two streams / the order of one queue): nothing of the old
-            // mode may be in flight when the first launch of the new one picks its list
-            if (sc->pp_last >= 0) {
-                MBK_HIP(ctx, hipStreamSynchronize(stream));
-                if (sc->aux) MBK_HIP(ctx, hipStreamSynchronize(sc->aux));
-            }
-            for (int k = 0; k < kOrderRing; ++k) sc->done_valid[k] = false;
-            sc->pp_last = (int)pp_mode;
-        }
-        if (overlap && sc->aux && sc->aux_prio != want_prio) {
+    // (a list entry packs block row and workgroup column into 16 bits each; wider windows go in image order)
+    // heavy-first dispatch order (see classify_blocks_kernel); small launches skip it: one kernel in image
+    // order beats memset + classify + tile below ~16 k blocks (cfg1, 4096 blocks: 20 us against 27)
+    p.ordered = p.order_mode >= 2 && p.grid.x >= 16384u && (uint32_t)a.mrd > 2u * p.probe_steps && a.blocks_x <= 0xffffu && p.by <= 0xffffu;
+    return p;
+}
+
+// The dispatch list a launch got from its stream's ring, and the one owner of "the launch took a list and did not get whole":
+// leaving launch_blocks before `whole` is set marks the ring's control words for clearing -- a pre-pass that did not run to its
+// last workgroup leaves its ticket behind, and no later one would clear it.  (Wider than needed -- a failure before the pre-pass
+// is enqueued, or behind the classify pre-pass, marks them too -- which costs the next units launch one drain and one memset.)
+struct OrderList {
+    StreamScratch *sc = nullptr;   // (null: the launch took no list)
+    unsigned k = 0;                // the list's place in the ring
+    uint32_t *list = nullptr;      // d_order[k]
+    hipStream_t pre = nullptr;     // the stream its pre-pass goes to
+    bool overlap = false;          // ... which is the ring's auxiliary stream, tied to the caller's by events
+    bool whole = false;
+    ~OrderList() { if (sc && !whole) sc->ring.ctl_dirty = true; }
+};
+
+// Step 2, the ring of `stream`: brings it into the state MBK_OPT_PREPASS_OVERLAP asks for (a change drains both streams), grows
+// the lists to `nblocks` entries, takes the next one in turn and makes the pre-pass stream wait for that list's last reader.
+static int acquire_order_list(mbk_ctx *ctx, hipStream_t stream, uint32_t nblocks, OrderList *out)
+{
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    OrderRing &ring = sc->ring;
+    // MBK_OPT_PREPASS_OVERLAP: 0 the pre-pass runs on the caller's stream, in order (one queue, no event: +4..5 us per cfg2
+    // launch back to back, profiles/r06/prepass_modes_ab.txt); 1 / 2 on an auxiliary stream (2: at the highest priority), tied
+    // to the tile kernel by events.  (Round 6 also tried it as an ANY-ORDER launch on the caller's stream -- an AQL packet
+    // without the barrier bit, hipExtAnyOrderLaunch, which would start in the previous tile kernel's drain -- but gfx950
+    // ignores the flag: profiles/microbench/anyorder.hip, profiles/r06/anyorder.txt.)
+    const uint32_t pp_mode = ctx->opt[MBK_OPT_PREPASS_OVERLAP];
+    const bool overlap = pp_mode != 0u;
+    // MBK_OPT_PREPASS_OVERLAP = 2: the auxiliary stream has the highest priority, so that the pre-pass of launch L + 1 gets
+    // its workgroups in while the tile kernel of launch L is in full swing instead of waiting for its drain (round 5: once
+    // the launch no longer ends in a 20 us drain, a pre-pass that waited for it sits on the critical path)
+    const uint32_t want_prio = pp_mode == 2u ? 2u : 1u;
+    if (ring.pp_last != (int)pp_mode) {
+        // the lists' hand-over differs by mode (events between two streams / the order of one queue): nothing of the old
+        // mode may be in flight when the first launch of the new one picks its list
+        if (ring.pp_last >= 0) {
             MBK_HIP(ctx, hipStreamSynchronize(stream));
-            MBK_HIP(ctx, hipStreamSynchronize(sc->aux));
-            (void)hipStreamDestroy(sc->aux);
-            sc->aux = nullptr;
-            for (int k = 0; k < kOrderRing; ++k) {
-                if (sc->ev_cls[k]) (void)hipEventDestroy(sc->ev_cls[k]);
-                if (sc->ev_done[k]) (void)hipEventDestroy(sc->ev_done[k]);
-                sc->ev_cls[k] = sc->ev_done[k] = nullptr;
-                sc->done_valid[k] = false;
-            }
+            if (ring.aux) MBK_HIP(ctx, hipStreamSynchronize(ring.aux));
         }
-        if (overlap && !sc->aux) {
-            if (want_prio == 2u) {
-                int least = 0, greatest = 0;
-                MBK_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-                MBK_HIP(ctx, hipStreamCreateWithPriority(&sc->aux, hipStreamNonBlocking, greatest));
-            } else
-            MBK_HIP(ctx, hipStreamCreateWithFlags(&sc->aux, hipStreamNonBlocking));
-            sc->aux_prio = want_prio;
-            for (int k = 0; k < kOrderRing; ++k) {
-                MBK_HIP(ctx, hipEventCreateWithFlags(&sc->ev_cls[k], hipEventDisableTiming));
-                MBK_HIP(ctx, hipEventCreateWithFlags(&sc->ev_done[k], hipEventDisableTiming));
-            }
-        }
-        if (grid.x > sc->order_cap) {
-            // the old lists may still be read / written by kernels in flight on the two streams
-            MBK_HIP(ctx, hipStreamSynchronize(stream));
-            if (sc->aux) MBK_HIP(ctx, hipStreamSynchronize(sc->aux));
-            for (int k = 0; k < kOrderRing; ++k) {
-                if (sc->d_order[k]) (void)hipFree(sc->d_order[k]);
-                sc->d_order[k] = nullptr;
-                sc->done_valid[k] = false;
-            }
-            sc->order_cap = 0;
-            // list | 3 counters | middle-class list (classify_blocks_kernel) | 2 counters, the units kernel's plan (64-byte aligned)
-            // | its settled H entries (mbk_units.h: units_settled_base)
-            for (int k = 0; k < kOrderRing; ++k)
-                MBK_HIP(ctx, hipMalloc((void **)&sc->d_order[k], mbk::units_list_words(grid.x) * sizeof(uint32_t)));
-            sc->order_cap = grid.x;
-        }
-        // Pre-pass of THIS launch on the aux stream: it depends on the window only, not on anything the caller's
-        // stream computes, so it may run while the previous launch's tile kernel is still busy (memset + classify
-        // are 13 us of a 577 us cfg2 step, with the chip nearly idle).  List k is free once the tile kernel that
-        // read it kOrderRing launches ago has finished (ev_done); the tile kernel waits for its list (ev_cls).  With
-        // prepass_overlap = 0 everything goes to the caller's stream, as in rounds 1-2.
-        const unsigned k = sc->order_turn++ % (unsigned)kOrderRing;
-        uint32_t *ord = sc->d_order[k];
-        uint32_t *cursors = ord + grid.x;   // right behind the list: the tile kernel finds them at order[gridDim.x]
-        hipStream_t pre = overlap ? sc->aux : stream;
-        if (overlap && sc->done_valid[k]) MBK_HIP(ctx, hipStreamWaitEvent(sc->aux, sc->ev_done[k], 0));
-        // (serial mode needs no wait: the list's last reader, kOrderRing launches ago, ran on this same stream)
-        if (units) {
-            // MBK_OPT_M_LATE = s > 0: M blocks whose centre pixel escapes at step >= s open the dispatch order; MBK_OPT_H_SETTLED
-            // = k > 0 (with the cycle test only): H blocks whose probe orbit is within 10^-k of settled close the front list
-            const uint32_t hs = cyc ? ctx->opt[MBK_OPT_H_SETTLED] : 0u;
-            const double settle_thr = hs ? std::pow(10.0, -(double)hs) : 0.0;
-            // the pre-pass' six counters live apart from the lists (whose layout moves with the window's size), are zeroed once
-            // here and put back to zero by the pre-pass itself (mbk_units.h: classify_units_kernel)
-            if (!sc->d_ctl) {
-                MBK_HIP(ctx, hipMalloc((void **)&sc->d_ctl, (size_t)kOrderRing * 8u * sizeof(uint32_t)));
-                sc->ctl_dirty = true;
-            }
-            if (sc->ctl_dirty) {
-                // ON the stream the pre-pass runs on (a hipMemset on the null stream does not order against a
-                // non-blocking stream -- what commit d786d61 removed for the scan cursors), and behind whatever pre-pass may
-                // still be running there and on the caller's stream; also after a failed launch (a pre-pass that did not run
-                // to its last workgroup leaves its ticket behind, and no later one would ever clear it)
-                if (sc->aux) MBK_HIP(ctx, hipStreamSynchronize(sc->aux));
-                MBK_HIP(ctx, hipStreamSynchronize(stream));
-                MBK_HIP(ctx, hipMemsetAsync(sc->d_ctl, 0, (size_t)kOrderRing * 8u * sizeof(uint32_t), pre));
-                sc->ctl_dirty = false;
-            }
-            uint32_t *ctl = sc->d_ctl + 8u * k;
-            // the shares of the eight XCDs: MBK_OPT_XCD_BALANCE 0 even, 1 following the stamps of earlier launches on this
-            // stream, 2 a fixed uneven deal (tests)
-            // (1 applies to the strict loops only: with the cycle test a launch ends with the drain of its boundary blocks, which
-            // the stamps -- when an XCD dealt its last ids -- do not see; following them cost 0.3 % there, xcd_balance_ab.txt)
-            // (and to a whole chip only: the stamps' "workgroup id mod 8 = XCD" is the dispatch order of 8 XCDs x 32 CUs -- a
-            // partitioned device, CPX / DPX modes, deals differently: ADVICE r4)
-            const uint32_t balance = ctx->opt[MBK_OPT_XCD_BALANCE] == 1u && (cyc || ctx->prop.multiProcessorCount != 256)
-                                         ? 0u : ctx->opt[MBK_OPT_XCD_BALANCE];
-            static const double kUneven[8] = {0.110, 0.140, 0.125, 0.120, 0.130, 0.125, 0.115, 0.135};
-            if (balance == 1u && !sc->h_stamps) {
-                MBK_HIP(ctx, hipHostMalloc((void **)&sc->h_stamps, (size_t)kStampSlots * mbk::kStampWords * sizeof(unsigned long long),
-                                           hipHostMallocDefault));
-                std::memset(sc->h_stamps, 0xff, (size_t)kStampSlots * mbk::kStampWords * sizeof(unsigned long long));
-            }
-            if (balance == 1u) xcd_shares_update(ctx, *sc);
-            mbk::XcdShares w;
-            double f[8];
-            const uint32_t seq = ++sc->xcd_issued;
-            StreamScratch::SharesUsed &used = sc->xcd_ring[seq % kShareRing];
-            used.seq = seq;
-            used.switches = ctx->stream_switches;
-            for (uint32_t x = 0; x < 8u; ++x) {
-                f[x] = balance == 1u ? sc->xcd_f[x] : (balance == 2u ? kUneven[x] : 0.125);
-                used.f[x] = (float)f[x];
-            }
-            shares_from_fractions(f, w.cum);
-            a.plan = ord + ((2u * (size_t)grid.x + 5u + 15u) & ~(size_t)15u);   // (ends below units_settled_base: + 16 + 40 <= + 64)
-            a.stamps = balance == 1u ? sc->h_stamps + (size_t)(seq % kStampSlots) * mbk::kStampWords : nullptr;
-            a.stamp_tag = seq & 0xffffu;
-            const uint32_t cwg = ctx->opt[MBK_OPT_CLASSIFY_WG];
-            hipLaunchKernelGGL(mbk::classify_units_kernel, dim3((grid.x + cwg - 1u) / cwg), dim3(cwg), 0, pre, a, grid.x,
-                               (int32_t)probe_steps, ord, ctl, (int32_t)ctx->opt[MBK_OPT_M_LATE], settle_thr, ctl + 3, (uint32_t *)a.plan, w,
-                               a.stamps ? 1u : 0u);
+        for (int k = 0; k < kOrderRing; ++k) ring.done_valid[k] = false;
+        ring.pp_last = (int)pp_mode;
+    }
+    if (overlap && ring.aux && ring.aux_prio != want_prio) {
+        MBK_HIP(ctx, hipStreamSynchronize(stream));
+        MBK_HIP(ctx, hipStreamSynchronize(ring.aux));
+        ring.drop_aux();
+    }
+    if (overlap && !ring.aux) {
+        if (want_prio == 2u) {
+            int least = 0, greatest = 0;
+            MBK_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+            MBK_HIP(ctx, hipStreamCreateWithPriority(&ring.aux, hipStreamNonBlocking, greatest));
         } else {
-        MBK_HIP(ctx, hipMemsetAsync(cursors, 0, 3 * sizeof(uint32_t), pre));
-        // the middle class: MBK_OPT_PROBE_MID's (dispatched between heavy and light) or, without one, MBK_OPT_M_LATE's
-        // (order 3 only: boundary blocks whose centre escapes at step >= m_late, dispatched first)
-        mid_first = order_mode == 3 && ctx->opt[MBK_OPT_PROBE_MID] > probe_steps && ctx->opt[MBK_OPT_M_LATE] >= 2u &&
-                    ctx->opt[MBK_OPT_M_LATE] <= probe_steps;
-        hipLaunchKernelGGL(mbk::classify_blocks_kernel, dim3((grid.x + 1023u) / 1024u), dim3(1024), 0, pre, a,
-                           grid.x, 8u * wpw, (int32_t)probe_steps, (int32_t)(mid_first ? ctx->opt[MBK_OPT_M_LATE] : ctx->opt[MBK_OPT_PROBE_MID]),
-                           ord, cursors);
+            MBK_HIP(ctx, hipStreamCreateWithFlags(&ring.aux, hipStreamNonBlocking));
         }
-        if (overlap) {
-            MBK_HIP(ctx, hipEventRecord(sc->ev_cls[k], sc->aux));
-            MBK_HIP(ctx, hipStreamWaitEvent(stream, sc->ev_cls[k], 0));
+        ring.aux_prio = want_prio;
+        for (int k = 0; k < kOrderRing; ++k) {
+            MBK_HIP(ctx, hipEventCreateWithFlags(&ring.ev_cls[k], hipEventDisableTiming));
+            MBK_HIP(ctx, hipEventCreateWithFlags(&ring.ev_done[k], hipEventDisableTiming));
         }
-        order_slot = (int)k;
-        order_overlap = overlap;
-        order_sc = sc;
-        a.order = ord;
-        a.ngrid = grid.x;
-        a.order_mid = mid_first ? 2u : (ctx->opt[MBK_OPT_PROBE_MID] <= probe_steps ? 1u : 0u);
     }
-    // SPILL (round 6; mbk_kernels.h: block_pixel_spill, mbk_spill.h): the launches the units kernel does not serve -- deep zooms:
-    // little light area, long orbits -- with single-wave workgroups, 16-step groups (fp64) and counts / bytes as outputs, when
-    // the depth and the size are worth a second pass and a checkpoint fits (the per-step prologue + the first checkpoint + 64 steps).
-    // The second pass lasts at least as long as ONE wave needs for the steps a never-escaping lane has left -- ~ mrd x 21 ns, a
-    // lone wave issues one dependent instruction per 8 cycles: 0.21 ms at mrd 10 000, 1.05 ms at 50 000 -- whatever the size of the
-    // launch, while what the first pass saves grows with the number of blocks: the two meet near 2^19 blocks (measured: cfg3,
-    // 2^20 blocks, +4.7 %; a 16 384 x 1 024 band of cfg4, 2^18 blocks at mrd 50 000, -4 %: profiles/r06/spill_ab.txt), hence
-    // MBK_OPT_SPILL_MIN_BLOCKS.  Slot numbers are 32 bits, a lane's step count 26.
-    StreamScratch *spill_sc = nullptr;
+    if (nblocks > ring.order_cap) {
+        // the old lists may still be read / written by kernels in flight on the two streams
+        MBK_HIP(ctx, hipStreamSynchronize(stream));
+        if (ring.aux) MBK_HIP(ctx, hipStreamSynchronize(ring.aux));
+        ring.drop_lists();
+        // list | 3 counters | middle-class list (classify_blocks_kernel) | 2 counters, the units kernel's plan (64-byte aligned)
+        // | its settled H entries (mbk_units.h: units_settled_base)
+        for (int k = 0; k < kOrderRing; ++k)
+            MBK_HIP(ctx, hipMalloc((void **)&ring.d_order[k], mbk::units_list_words(nblocks) * sizeof(uint32_t)));
+        ring.order_cap = nblocks;
+    }
+    // Pre-pass of THIS launch on the aux stream: it depends on the window only, not on anything the caller's
+    // stream computes, so it may run while the previous launch's tile kernel is still busy (memset + classify
+    // are 13 us of a 577 us cfg2 step, with the chip nearly idle).  List k is free once the tile kernel that
+    // read it kOrderRing launches ago has finished (ev_done); the tile kernel waits for its list (ev_cls).  With
+    // prepass_overlap = 0 everything goes to the caller's stream, as in rounds 1-2.
+    const unsigned k = ring.order_turn++ % (unsigned)kOrderRing;
+    if (overlap && ring.done_valid[k]) MBK_HIP(ctx, hipStreamWaitEvent(ring.aux, ring.ev_done[k], 0));
+    // (serial mode needs no wait: the list's last reader, kOrderRing launches ago, ran on this same stream)
+    out->k = k;
+    out->list = ring.d_order[k];
+    out->pre = overlap ? ring.aux : stream;
+    out->overlap = overlap;
+    out->sc = sc;   // (from here on `out` marks the ring unless the launch gets whole)
+    return MBK_OK;
+}
+
+// Step 3a, the pre-pass of the units kernel (mbk_units.h) into list `ol`: clears the ring's control words where they may be
+// stale, settles the shares of the eight XCDs and the launch's time-stamp slot (a.plan, a.stamps, a.stamp_tag), enqueues it.
+static int enqueue_units_prepass(mbk_ctx *ctx, TileArgs &a, const BlockLaunchPlan &p, const OrderList &ol, hipStream_t stream)
+{
+    StreamScratch *sc = ol.sc;
+    OrderRing &ring = sc->ring;
+    // MBK_OPT_M_LATE = s > 0: M blocks whose centre pixel escapes at step >= s open the dispatch order; MBK_OPT_H_SETTLED
+    // = k > 0 (with the cycle test only): H blocks whose probe orbit is within 10^-k of settled close the front list
+    const uint32_t hs = p.cyc ? ctx->opt[MBK_OPT_H_SETTLED] : 0u;
+    const double settle_thr = hs ? std::pow(10.0, -(double)hs) : 0.0;
+    // the pre-pass' six counters live apart from the lists (whose layout moves with the window's size), are zeroed once
+    // here and put back to zero by the pre-pass itself (mbk_units.h: classify_units_kernel)
+    if (!ring.d_ctl) {
+        MBK_HIP(ctx, hipMalloc((void **)&ring.d_ctl, (size_t)kOrderRing * 8u * sizeof(uint32_t)));
+        ring.ctl_dirty = true;
+    }
+    if (ring.ctl_dirty) {
+        // ON the stream the pre-pass runs on (a hipMemset on the null stream does not order against a
+        // non-blocking stream -- what commit d786d61 removed for the scan cursors), and behind whatever pre-pass may
+        // still be running there and on the caller's stream; also after a failed launch (OrderList)
+        if (ring.aux) MBK_HIP(ctx, hipStreamSynchronize(ring.aux));
+        MBK_HIP(ctx, hipStreamSynchronize(stream));
+        MBK_HIP(ctx, hipMemsetAsync(ring.d_ctl, 0, (size_t)kOrderRing * 8u * sizeof(uint32_t), ol.pre));
+        ring.ctl_dirty = false;
+    }
+    uint32_t *ctl = ring.d_ctl + 8u * ol.k;
+    // the shares of the eight XCDs: MBK_OPT_XCD_BALANCE 0 even, 1 following the stamps of earlier launches on this
+    // stream, 2 a fixed uneven deal (tests)
+    // (1 applies to the strict loops only: with the cycle test a launch ends with the drain of its boundary blocks, which
+    // the stamps -- when an XCD dealt its last ids -- do not see; following them cost 0.3 % there, xcd_balance_ab.txt)
+    // (and to a whole chip only: the stamps' "workgroup id mod 8 = XCD" is the dispatch order of 8 XCDs x 32 CUs -- a
+    // partitioned device, CPX / DPX modes, deals differently: ADVICE r4)
+    const uint32_t balance = ctx->opt[MBK_OPT_XCD_BALANCE] == 1u && (p.cyc || ctx->prop.multiProcessorCount != 256)
+                                 ? 0u : ctx->opt[MBK_OPT_XCD_BALANCE];
+    static const double kUneven[8] = {0.110, 0.140, 0.125, 0.120, 0.130, 0.125, 0.115, 0.135};
+    if (balance == 1u && !sc->h_stamps) {
+        MBK_HIP(ctx, hipHostMalloc((void **)&sc->h_stamps, (size_t)kStampSlots * mbk::kStampWords * sizeof(unsigned long long),
+                                   hipHostMallocDefault));
+        std::memset(sc->h_stamps, 0xff, (size_t)kStampSlots * mbk::kStampWords * sizeof(unsigned long long));
+    }
+    if (balance == 1u) xcd_shares_update(ctx, *sc);
+    mbk::XcdShares w;
+    double f[8];
+    const uint32_t seq = ++sc->xcd_issued;
+    StreamScratch::SharesUsed &used = sc->xcd_ring[seq % kShareRing];
+    used.seq = seq;
+    used.switches = ctx->stream_switches;
+    for (uint32_t x = 0; x < 8u; ++x) {
+        f[x] = balance == 1u ? sc->xcd_f[x] : (balance == 2u ? kUneven[x] : 0.125);
+        used.f[x] = (float)f[x];
+    }
+    shares_from_fractions(f, w.cum);
+    a.plan = ol.list + ((2u * (size_t)p.grid.x + 5u + 15u) & ~(size_t)15u);   // (ends below units_settled_base: + 16 + 40 <= + 64)
+    a.stamps = balance == 1u ? sc->h_stamps + (size_t)(seq % kStampSlots) * mbk::kStampWords : nullptr;
+    a.stamp_tag = seq & 0xffffu;
+    const uint32_t cwg = ctx->opt[MBK_OPT_CLASSIFY_WG];
+    hipLaunchKernelGGL(mbk::classify_units_kernel, dim3((p.grid.x + cwg - 1u) / cwg), dim3(cwg), 0, ol.pre, a, p.grid.x,
+                       (int32_t)p.probe_steps, ol.list, ctl, (int32_t)ctx->opt[MBK_OPT_M_LATE], settle_thr, ctl + 3, (uint32_t *)a.plan, w,
+                       a.stamps ? 1u : 0u);
+    return MBK_OK;
+}
+
+// Step 3b, the heavy-first pre-pass (classify_blocks_kernel) into list `ol`, behind the clearing of its cursors.
+// *mid_first: the list's middle class is MBK_OPT_M_LATE's and opens the dispatch order.
+static int enqueue_classify_prepass(mbk_ctx *ctx, const TileArgs &a, const BlockLaunchPlan &p, const OrderList &ol, bool *mid_first)
+{
+    const uint32_t nblocks = p.grid.x;
+    uint32_t *cursors = ol.list + nblocks;   // right behind the list: the tile kernel finds them at order[gridDim.x]
+    MBK_HIP(ctx, hipMemsetAsync(cursors, 0, 3 * sizeof(uint32_t), ol.pre));
+    // the middle class: MBK_OPT_PROBE_MID's (dispatched between heavy and light) or, without one, MBK_OPT_M_LATE's
+    // (order 3 only: boundary blocks whose centre escapes at step >= m_late, dispatched first)
+    *mid_first = p.order_mode == 3 && ctx->opt[MBK_OPT_PROBE_MID] > p.probe_steps && ctx->opt[MBK_OPT_M_LATE] >= 2u &&
+                 ctx->opt[MBK_OPT_M_LATE] <= p.probe_steps;
+    hipLaunchKernelGGL(mbk::classify_blocks_kernel, dim3((nblocks + 1023u) / 1024u), dim3(1024), 0, ol.pre, a,
+                       nblocks, 8u * p.wpw, (int32_t)p.probe_steps, (int32_t)(*mid_first ? ctx->opt[MBK_OPT_M_LATE] : ctx->opt[MBK_OPT_PROBE_MID]),
+                       ol.list, cursors);
+    return MBK_OK;
+}
+
+// Step 4a, does the launch run with the SPILL second pass?  SPILL (round 6; mbk_kernels.h: block_pixel_spill, mbk_spill.h): the launches the units kernel does not serve -- deep zooms:
+// little light area, long orbits -- with single-wave workgroups, 16-step groups (fp64) and counts / bytes as outputs, when
+// the depth and the size are worth a second pass and a checkpoint fits (the per-step prologue + the first checkpoint + 64 steps).
+// The second pass lasts at least as long as ONE wave needs for the steps a never-escaping lane has left -- ~ mrd x 21 ns, a
+// lone wave issues one dependent instruction per 8 cycles: 0.21 ms at mrd 10 000, 1.05 ms at 50 000 -- whatever the size of the
+// launch, while what the first pass saves grows with the number of blocks: the two meet near 2^19 blocks (measured: cfg3,
+// 2^20 blocks, +4.7 %; a 16 384 x 1 024 band of cfg4, 2^18 blocks at mrd 50 000, -4 %: profiles/r06/spill_ab.txt), hence
+// MBK_OPT_SPILL_MIN_BLOCKS.  Slot numbers are 32 bits, a lane's step count 26.
+static bool spill_wanted(const mbk_ctx *ctx, const TileArgs &a, const BlockLaunchPlan &p, uint32_t kernel, bool safe, bool f32)
+{
     const uint32_t spill_first = ctx->opt[MBK_OPT_SPILL_FIRST], spill_lanes = ctx->opt[MBK_OPT_SPILL_LANES];
-    const bool spill = !units && a.order != nullptr && order_mode >= 2u && kernel == MBK_KERNEL_GROUP && !safe && a.smooth == nullptr && wpw == 1u &&
-                       (a.counts || a.bytes) && spill_first != 0u && (f32 || ctx->opt[MBK_OPT_GROUP_STEPS] == 16u) &&
-                       (uint32_t)a.mrd >= ctx->opt[MBK_OPT_SPILL_MIN_MRD] && (uint32_t)a.mrd < (1u << 26) &&
-                       ((uint64_t)grid.x >> ctx->opt[MBK_OPT_SPILL_MIN_BLOCKS]) != 0ull &&
-                       (uint64_t)a.mrd > (uint64_t)ctx->opt[MBK_OPT_EXACT_STEPS] + spill_first + 66u &&
-                       (uint64_t)grid.x * spill_lanes < (1ull << 32) && a.fast_bx_end > 0u && a.fast_by_end > 0u;
-    if (spill) {
-        StreamScratch *sc = order_sc;
-        const size_t slots = (size_t)grid.x * spill_lanes, nchunks = (grid.x + mbk::kSpillChunk - 1u) / mbk::kSpillChunk;
-        if (slots > sc->spill_cap_slots || grid.x > sc->spill_cap_blocks) {
-            MBK_HIP(ctx, hipStreamSynchronize(stream));   // the old buffers may still be in use
-            for (void **q : {&sc->d_spill_z, (void **)&sc->d_spill_meta, (void **)&sc->d_spill_cnt, (void **)&sc->d_spill_chunks,
-                             (void **)&sc->d_spill_src, (void **)&sc->d_spill_total}) {
-                if (*q) (void)hipFree(*q);
-                *q = nullptr;
-            }
-            sc->spill_cap_slots = sc->spill_cap_blocks = 0;
-            // 24 bytes per slot (403 MB for an 8192^2 window): a device short of memory runs the launch without the second pass
-            // -- an optimisation must not turn into an error -- and the next launch that wants it tries again
-            const bool got = hipMalloc(&sc->d_spill_z, slots * 16u) == hipSuccess &&          // (zr, zi) as two doubles; two floats use half of it
-                             hipMalloc((void **)&sc->d_spill_meta, slots * sizeof(uint32_t)) == hipSuccess &&
-                             hipMalloc((void **)&sc->d_spill_src, slots * sizeof(uint32_t)) == hipSuccess &&
-                             hipMalloc((void **)&sc->d_spill_cnt, (size_t)grid.x * sizeof(uint32_t)) == hipSuccess &&
-                             hipMalloc((void **)&sc->d_spill_chunks, (nchunks * mbk::kSpillLevels + 1u) * sizeof(uint32_t)) == hipSuccess &&
-                             hipMalloc((void **)&sc->d_spill_total, sizeof(unsigned long long)) == hipSuccess;
-            if (got) {
-                sc->spill_cap_slots = slots;
-                sc->spill_cap_blocks = grid.x;
-            } else {
-                (void)hipGetLastError();   // (the failed allocation's sticky error)
-                for (void **q : {&sc->d_spill_z, (void **)&sc->d_spill_meta, (void **)&sc->d_spill_cnt, (void **)&sc->d_spill_chunks,
-                                 (void **)&sc->d_spill_src, (void **)&sc->d_spill_total}) {
-                    if (*q) (void)hipFree(*q);
-                    *q = nullptr;
-                }
-            }
+    return !p.units && a.order != nullptr && p.order_mode >= 2u && kernel == MBK_KERNEL_GROUP && !safe && a.smooth == nullptr && p.wpw == 1u &&
+           (a.counts || a.bytes) && spill_first != 0u && (f32 || ctx->opt[MBK_OPT_GROUP_STEPS] == 16u) &&
+           (uint32_t)a.mrd >= ctx->opt[MBK_OPT_SPILL_MIN_MRD] && (uint32_t)a.mrd < (1u << 26) &&
+           ((uint64_t)p.grid.x >> ctx->opt[MBK_OPT_SPILL_MIN_BLOCKS]) != 0ull &&
+           (uint64_t)a.mrd > (uint64_t)ctx->opt[MBK_OPT_EXACT_STEPS] + spill_first + 66u &&
+           (uint64_t)p.grid.x * spill_lanes < (1ull << 32) && a.fast_bx_end > 0u && a.fast_by_end > 0u;
+}
+
+// Step 4b, the SPILL buffers of the stream, grown to `nblocks` blocks, or none (*out).  Where they exist `a` is told about them
+// and the blocks' counts are cleared on `stream`.
+static int acquire_spill(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, TileArgs &a, uint32_t nblocks, SpillBuffers **out)
+{
+    SpillBuffers &sp = sc->spill;
+    const uint32_t spill_lanes = ctx->opt[MBK_OPT_SPILL_LANES];
+    const size_t slots = (size_t)nblocks * spill_lanes, nchunks = (nblocks + mbk::kSpillChunk - 1u) / mbk::kSpillChunk;
+    *out = nullptr;
+    if (slots > sp.cap_slots || nblocks > sp.cap_blocks) {
+        MBK_HIP(ctx, hipStreamSynchronize(stream));   // the old buffers may still be in use
+        sp.release();
+        // 24 bytes per slot (403 MB for an 8192^2 window): a device short of memory runs the launch without the second pass
+        // -- an optimisation must not turn into an error -- and the next launch that wants it tries again
+        const bool got = hipMalloc(&sp.d_z, slots * 16u) == hipSuccess &&          // (zr, zi) as two doubles; two floats use half of it
+                         hipMalloc((void **)&sp.d_meta, slots * sizeof(uint32_t)) == hipSuccess &&
+                         hipMalloc((void **)&sp.d_src, slots * sizeof(uint32_t)) == hipSuccess &&
+                         hipMalloc((void **)&sp.d_cnt, (size_t)nblocks * sizeof(uint32_t)) == hipSuccess &&
+                         hipMalloc((void **)&sp.d_chunks, (nchunks * mbk::kSpillLevels + 1u) * sizeof(uint32_t)) == hipSuccess &&
+                         hipMalloc((void **)&sp.d_total, sizeof(unsigned long long)) == hipSuccess;
+        if (got) {
+            sp.cap_slots = slots;
+            sp.cap_blocks = nblocks;
+        } else {
+            (void)hipGetLastError();   // (the failed allocation's sticky error)
+            sp.release();
         }
-        if (sc->spill_cap_slots >= slots && sc->spill_cap_blocks >= grid.x && sc->d_spill_z) {
-            a.spill_first = spill_first;
-            a.spill_lanes = spill_lanes;
-            a.spill_win_shift = ctx->opt[MBK_OPT_SPILL_CYC_SHIFT];
-            a.spill_z = sc->d_spill_z;
-            a.spill_meta = sc->d_spill_meta;
-            a.spill_cnt = sc->d_spill_cnt;
-            MBK_HIP(ctx, hipMemsetAsync(sc->d_spill_cnt, 0, (size_t)grid.x * sizeof(uint32_t), stream));
-            spill_sc = sc;
+    }
+    if (sp.cap_slots >= slots && sp.cap_blocks >= nblocks && sp.d_z) {
+        a.spill_first = ctx->opt[MBK_OPT_SPILL_FIRST];
+        a.spill_lanes = spill_lanes;
+        a.spill_win_shift = ctx->opt[MBK_OPT_SPILL_CYC_SHIFT];
+        a.spill_z = sp.d_z;
+        a.spill_meta = sp.d_meta;
+        a.spill_cnt = sp.d_cnt;
+        MBK_HIP(ctx, hipMemsetAsync(sp.d_cnt, 0, (size_t)nblocks * sizeof(uint32_t), stream));
+        *out = &sp;
+    }
+    return MBK_OK;
+}
+
+// Step 5, which instantiation serves a launch: a kernel as a pointer to its launch stub, so that each family has one launch site.
+typedef void (*UnitsKernel)(TileArgs, uint32_t);
+typedef void (*BlockKernel)(TileArgs);
+typedef void (*SpillKernel)(TileArgs, const uint32_t *, const unsigned long long *, uint32_t);
+
+// tile_units_kernel -- rows: number format and cycle test; columns: bytes with the statistics fused | counts and bytes | bytes | counts
+static UnitsKernel pick_units_kernel(bool f32, bool cyc, bool stats, bool counts, bool bytes)
+{
+    static const UnitsKernel forms[4][4] = {
+        {mbk::tile_units_kernel<float, 8, true, false, true, true>, mbk::tile_units_kernel<float, 8, true, true, true>,
+         mbk::tile_units_kernel<float, 8, true, false, true>, mbk::tile_units_kernel<float, 8, true, true, false>},
+        {mbk::tile_units_kernel<float, 8, false, false, true, true>, mbk::tile_units_kernel<float, 8, false, true, true>,
+         mbk::tile_units_kernel<float, 8, false, false, true>, mbk::tile_units_kernel<float, 8, false, true, false>},
+        {mbk::tile_units_kernel<double, 16, true, false, true, true>, mbk::tile_units_kernel<double, 16, true, true, true>,
+         mbk::tile_units_kernel<double, 16, true, false, true>, mbk::tile_units_kernel<double, 16, true, true, false>},
+        {mbk::tile_units_kernel<double, 16, false, false, true, true>, mbk::tile_units_kernel<double, 16, false, true, true>,
+         mbk::tile_units_kernel<double, 16, false, false, true>, mbk::tile_units_kernel<double, 16, false, true, false>},
+    };
+    return forms[(f32 ? 0 : 2) + (cyc ? 0 : 1)][stats ? 0 : (counts && bytes) ? 1 : bytes ? 2 : 3];
+}
+
+// tile_asm_kernel: the first pass of a SPILL launch, or the form the selector, the literal doubling and MBK_OPT_GROUP_STEPS ask for
+static BlockKernel pick_block_kernel(uint32_t kernel, bool safe, bool f32, bool cyc, uint32_t group_steps, bool spill)
+{
+    if (spill && f32 && cyc) return mbk::tile_asm_kernel<float, true, 8, true, true>;
+    if (spill && f32) return mbk::tile_asm_kernel<float, true, 8, false, true>;
+    if (spill && cyc) return mbk::tile_asm_kernel<double, true, 16, true, true>;
+    if (spill) return mbk::tile_asm_kernel<double, true, 16, false, true>;
+    if (f32 && safe) return mbk::tile_asm_kernel<float, false, 0>;
+    if (f32 && kernel == MBK_KERNEL_ASM) return mbk::tile_asm_kernel<float, true, 0>;
+    if (f32 && cyc) return mbk::tile_asm_kernel<float, true, 8, true>;
+    if (f32) return mbk::tile_asm_kernel<float, true, 8>;
+    if (safe) return mbk::tile_asm_kernel<double, false, 0>;
+    if (kernel == MBK_KERNEL_ASM) return mbk::tile_asm_kernel<double, true, 0>;
+    if (group_steps == 32 && !cyc) return mbk::tile_asm_kernel<double, true, 32>;   // (with the cycle test 32 means 16: mbk_loops.inc)
+    if (group_steps >= 16 && cyc) return mbk::tile_asm_kernel<double, true, 16, true>;
+    if (group_steps >= 16) return mbk::tile_asm_kernel<double, true, 16>;
+    if (group_steps == 8 && cyc) return mbk::tile_asm_kernel<double, true, 8, true>;
+    if (group_steps == 8) return mbk::tile_asm_kernel<double, true, 8>;
+    return mbk::tile_asm_kernel<double, true, 4>;
+}
+
+// tile_spill_kernel (mbk_spill.h): the second pass of a SPILL launch
+static SpillKernel pick_spill_kernels(bool f32, bool cyc)
+{
+    if (f32 && cyc) return mbk::tile_spill_kernel<float, true>;
+    if (f32) return mbk::tile_spill_kernel<float, false>;
+    if (cyc) return mbk::tile_spill_kernel<double, true>;
+    return mbk::tile_spill_kernel<double, false>;
+}
+
+// ... and the units kernel's launch: its grid, its table of small bytes, and the statistics where the caller takes them from it.
+static void enqueue_units_tile(mbk_ctx *ctx, TileArgs &a, const BlockLaunchPlan &p, bool f32, uint32_t lds, hipStream_t stream, FuseStats *fuse)
+{
+    // Grid: the host cannot know how many units the probe makes of this window, so it estimates them from its own
+    // 16 x 16 probe (share of the pixels still inside after 4 steps ~ the H and M blocks; the rest, eight to a unit)
+    // and the kernel strides: a deterministic function of the window, no hint from earlier launches.
+    const double est = (double)p.grid.x * (p.unit_share + (1.0 - p.unit_share) / 8.0);
+    const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
+    uint32_t g = (uint32_t)std::min<double>((double)p.grid.x, est * 1.15 + 2048.0);
+    // a multiple of 8: id mod 8 = workgroup mod 8 = the XCD; at least 2^14: bounds a wave's trips (the kernel's packed statistics)
+    g = (std::max(std::max(g, std::min(p.grid.x, cus * 64u)), 16384u) + 7u) & ~7u;
+    a.unit_stride = g;
+    const bool stats = fuse != nullptr && fuse->slots != nullptr && fuse->counts_unwanted && a.bytes != nullptr;
+    if (stats) {
+        a.stats = fuse->slots;
+        a.counts = nullptr;
+        fuse->fused = true;
+    }
+    hipLaunchKernelGGL(pick_units_kernel(f32, p.cyc, stats, a.counts != nullptr, a.bytes != nullptr), dim3(g), dim3(64), lds, stream, a,
+                       quant_table4(a.mrd, a.bytes != nullptr));
+}
+
+// Step 6, the SPILL second pass: compact the blocks' spilled lanes into one list (chunk sums, their scan, the expansion), then run them.
+static int enqueue_spill_second_pass(mbk_ctx *ctx, const TileArgs &a, const SpillBuffers &sp, uint32_t nblocks, bool f32, bool cyc, hipStream_t stream)
+{
+    const uint32_t nchunks = (nblocks + mbk::kSpillChunk - 1u) / mbk::kSpillChunk;
+    hipLaunchKernelGGL(mbk::spill_count_kernel, dim3(nchunks), dim3(mbk::kSpillChunk), 0, stream, sp.d_cnt, nblocks, nchunks, sp.d_chunks);
+    hipLaunchKernelGGL(mbk::rle_scan_kernel, dim3(1), dim3(1024), 0, stream, sp.d_chunks, nchunks * mbk::kSpillLevels, sp.d_total);
+    hipLaunchKernelGGL(mbk::spill_expand_kernel, dim3(nchunks), dim3(mbk::kSpillChunk), 0, stream, sp.d_cnt, nblocks, nchunks,
+                       sp.d_chunks, a.spill_lanes, sp.d_src);
+    // grid: an upper bound (the number of lanes is known on the device only), strided
+    const uint32_t nwg = (uint32_t)std::min<uint64_t>(((uint64_t)nblocks * a.spill_lanes + 63u) / 64u, 16384u);
+    // (fewer resident waves per SIMD for this pass -- through unused LDS, as MBK_OPT_WAVE_LIMIT -- were tried: 2 / 3 per SIMD cost
+    // 0.1 / 0.05 ms of its 0.64 ms; what halved it was the order of the list, latest checkpoint first: profiles/r06/spill_ab.txt)
+    const uint32_t lds2 = 0u;
+    hipLaunchKernelGGL(pick_spill_kernels(f32, cyc), dim3(nwg), dim3(64), lds2, stream, a, sp.d_src, sp.d_total, nwg);
+    MBK_HIP(ctx, hipGetLastError());
+    ++ctx->spill_launches;
+    ctx->last_spill_stream = stream;
+    return MBK_OK;
+}
+
+// Launch the one-wave-per-block kernels ("asm" / "group", fp64 or fp32) for the window described by `a`
+// (a.col0/row0/ncols/nrows, output at a.out_*), optionally behind the heavy-first classify pre-pass: the steps above, in order.
+static int launch_blocks(mbk_ctx *ctx, TileArgs a, uint32_t kernel, bool safe, bool f32, hipStream_t stream, FuseStats *fuse = nullptr)
+{
+    const BlockLaunchPlan p = block_launch_plan(ctx, a, kernel, safe, f32);
+    OrderList ol;   // (once it holds a list, a failing return leaves the ring marked: ctl_dirty)
+    if (p.ordered) {
+        int rc = acquire_order_list(ctx, stream, p.grid.x, &ol);
+        if (rc != MBK_OK) return rc;
+        OrderRing &ring = ol.sc->ring;
+        bool mid_first = false;
+        rc = p.units ? enqueue_units_prepass(ctx, a, p, ol, stream) : enqueue_classify_prepass(ctx, a, p, ol, &mid_first);
+        if (rc != MBK_OK) return rc;
+        if (ol.overlap) {
+            MBK_HIP(ctx, hipEventRecord(ring.ev_cls[ol.k], ring.aux));
+            MBK_HIP(ctx, hipStreamWaitEvent(stream, ring.ev_cls[ol.k], 0));
         }
+        a.order = ol.list;
+        a.ngrid = p.grid.x;
+        a.order_mid = mid_first ? 2u : (ctx->opt[MBK_OPT_PROBE_MID] <= p.probe_steps ? 1u : 0u);
+    }
+    SpillBuffers *spill = nullptr;
+    if (spill_wanted(ctx, a, p, kernel, safe, f32)) {
+        const int rc = acquire_spill(ctx, ol.sc, stream, a, p.grid.x, &spill);
+        if (rc != MBK_OK) return rc;
     }
     // MBK_OPT_WAVE_LIMIT: unused dynamic LDS caps the resident waves per SIMD (single-wave workgroups only)
-    const uint32_t lds = wpw == 1u ? ctx->wave_limit_lds[ctx->opt[MBK_OPT_WAVE_LIMIT] & 7u] : 0u;
-    if (units && a.order) {
-        // Grid: the host cannot know how many units the probe makes of this window, so it estimates them from its own
-        // 16 x 16 probe (share of the pixels still inside after 4 steps ~ the H and M blocks; the rest, eight to a unit)
-        // and the kernel strides: a deterministic function of the window, no hint from earlier launches.
-        const double share = unit_share;
-        const double est = (double)grid.x * (share + (1.0 - share) / 8.0);
-        const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-        uint32_t g = (uint32_t)std::min<double>((double)grid.x, est * 1.15 + 2048.0);
-        // a multiple of 8: id mod 8 = workgroup mod 8 = the XCD; at least 2^14: bounds a wave's trips (the kernel's packed statistics)
-        g = (std::max(std::max(g, std::min(grid.x, cus * 64u)), 16384u) + 7u) & ~7u;
-        a.unit_stride = g;
-        uint32_t qtab = 0u;   // quantised bytes of counts 1..4, packed (the light path's table)
-        if (a.bytes && a.mrd > 0)
-            for (uint32_t c = 1; c <= 4u; ++c)
-                qtab |= (uint32_t)(((uint64_t)c * 256u + (uint32_t)a.mrd - 1u) / (uint32_t)a.mrd & 0xffu) << (8u * (c - 1u));
-        const bool stats = fuse != nullptr && counts_unwanted && a.bytes != nullptr;
-        if (stats) {
-            a.stats = fuse;
-            a.counts = nullptr;
-            if (fused) *fused = true;
-        }
-#define MBK_LAUNCH_UNITS(T, G, CYC)                                                                                         \
-    do {                                                                                                                   \
-        if (stats)                                                                                                         \
-            hipLaunchKernelGGL((mbk::tile_units_kernel<T, G, CYC, false, true, true>), dim3(g), dim3(64), lds, stream, a, qtab); \
-        else if (a.counts && a.bytes)                                                                                      \
-            hipLaunchKernelGGL((mbk::tile_units_kernel<T, G, CYC, true, true>), dim3(g), dim3(64), lds, stream, a, qtab);   \
-        else if (a.bytes)                                                                                                  \
-            hipLaunchKernelGGL((mbk::tile_units_kernel<T, G, CYC, false, true>), dim3(g), dim3(64), lds, stream, a, qtab);  \
-        else                                                                                                               \
-            hipLaunchKernelGGL((mbk::tile_units_kernel<T, G, CYC, true, false>), dim3(g), dim3(64), lds, stream, a, qtab);  \
-    } while (0)
-        if (f32 && cyc) MBK_LAUNCH_UNITS(float, 8, true);
-        else if (f32) MBK_LAUNCH_UNITS(float, 8, false);
-        else if (cyc) MBK_LAUNCH_UNITS(double, 16, true);
-        else MBK_LAUNCH_UNITS(double, 16, false);
-#undef MBK_LAUNCH_UNITS
-    } else
-    if (spill_sc && f32 && cyc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<float, true, 8, true, true>), grid, block, lds, stream, a);
-    else if (spill_sc && f32)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<float, true, 8, false, true>), grid, block, lds, stream, a);
-    else if (spill_sc && cyc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 16, true, true>), grid, block, lds, stream, a);
-    else if (spill_sc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 16, false, true>), grid, block, lds, stream, a);
+    const uint32_t lds = p.wpw == 1u ? ctx->wave_limit_lds[ctx->opt[MBK_OPT_WAVE_LIMIT] & 7u] : 0u;
+    if (p.units && a.order)
+        enqueue_units_tile(ctx, a, p, f32, lds, stream, fuse);
     else
-    if (f32 && safe)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<float, false, 0>), grid, block, lds, stream, a);
-    else if (f32 && kernel == MBK_KERNEL_ASM)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<float, true, 0>), grid, block, lds, stream, a);
-    else if (f32 && cyc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<float, true, 8, true>), grid, block, lds, stream, a);
-    else if (f32)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<float, true, 8>), grid, block, lds, stream, a);
-    else if (safe)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, false, 0>), grid, block, lds, stream, a);
-    else if (kernel == MBK_KERNEL_ASM)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 0>), grid, block, lds, stream, a);
-    else if (ctx->opt[MBK_OPT_GROUP_STEPS] == 32 && !cyc)   // (with the cycle test 32 means 16: mbk_loops.inc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 32>), grid, block, lds, stream, a);
-    else if (ctx->opt[MBK_OPT_GROUP_STEPS] >= 16 && cyc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 16, true>), grid, block, lds, stream, a);
-    else if (ctx->opt[MBK_OPT_GROUP_STEPS] >= 16)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 16>), grid, block, lds, stream, a);
-    else if (ctx->opt[MBK_OPT_GROUP_STEPS] == 8 && cyc)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 8, true>), grid, block, lds, stream, a);
-    else if (ctx->opt[MBK_OPT_GROUP_STEPS] == 8)
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 8>), grid, block, lds, stream, a);
-    else
-        hipLaunchKernelGGL((mbk::tile_asm_kernel<double, true, 4>), grid, block, lds, stream, a);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            if (order_sc) order_sc->ctl_dirty = true;   // a pre-pass may be stuck half-way: clear its counters before the next one
-            return fail(ctx, MBK_ERR_HIP, std::string("tile launch: ") + hipGetErrorString(e));
-        }
+        hipLaunchKernelGGL(pick_block_kernel(kernel, safe, f32, p.cyc, ctx->opt[MBK_OPT_GROUP_STEPS], spill != nullptr), p.grid, p.block, lds, stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(ctx, MBK_ERR_HIP, std::string("tile launch: ") + hipGetErrorString(e));
+    if (ol.overlap) {   // list `ol.k` is busy until this tile kernel has finished
+        MBK_HIP(ctx, hipEventRecord(ol.sc->ring.ev_done[ol.k], stream));
+        ol.sc->ring.done_valid[ol.k] = true;
     }
-    if (order_slot >= 0 && order_overlap) {   // list `order_slot` is busy until this tile kernel has finished
-        MBK_HIP(ctx, hipEventRecord(order_sc->ev_done[order_slot], stream));
-        order_sc->done_valid[order_slot] = true;
+    if (spill) {
+        const int rc = enqueue_spill_second_pass(ctx, a, *spill, p.grid.x, f32, p.cyc, stream);
+        if (rc != MBK_OK) return rc;
     }
-    if (spill_sc) {
-        // the second pass: compact the blocks' spilled lanes into one list (chunk sums, their scan, the expansion), then run them
-        StreamScratch *sc = spill_sc;
-        const uint32_t nchunks = (grid.x + mbk::kSpillChunk - 1u) / mbk::kSpillChunk;
-        hipLaunchKernelGGL(mbk::spill_count_kernel, dim3(nchunks), dim3(mbk::kSpillChunk), 0, stream, sc->d_spill_cnt, grid.x, nchunks, sc->d_spill_chunks);
-        hipLaunchKernelGGL(mbk::rle_scan_kernel, dim3(1), dim3(1024), 0, stream, sc->d_spill_chunks, nchunks * mbk::kSpillLevels, sc->d_spill_total);
-        hipLaunchKernelGGL(mbk::spill_expand_kernel, dim3(nchunks), dim3(mbk::kSpillChunk), 0, stream, sc->d_spill_cnt, grid.x, nchunks,
-                           sc->d_spill_chunks, spill_lanes, sc->d_spill_src);
-        // grid: an upper bound (the number of lanes is known on the device only), strided
-        const uint32_t nwg = (uint32_t)std::min<uint64_t>(((uint64_t)grid.x * spill_lanes + 63u) / 64u, 16384u);
-        // (fewer resident waves per SIMD for this pass -- through unused LDS, as MBK_OPT_WAVE_LIMIT -- were tried: 2 / 3 per SIMD cost
-        // 0.1 / 0.05 ms of its 0.64 ms; what halved it was the order of the list, latest checkpoint first: profiles/r06/spill_ab.txt)
-        const uint32_t lds2 = 0u;
-        if (f32 && cyc)
-            hipLaunchKernelGGL((mbk::tile_spill_kernel<float, true>), dim3(nwg), dim3(64), lds2, stream, a, sc->d_spill_src, sc->d_spill_total, nwg);
-        else if (f32)
-            hipLaunchKernelGGL((mbk::tile_spill_kernel<float, false>), dim3(nwg), dim3(64), lds2, stream, a, sc->d_spill_src, sc->d_spill_total, nwg);
-        else if (cyc)
-            hipLaunchKernelGGL((mbk::tile_spill_kernel<double, true>), dim3(nwg), dim3(64), lds2, stream, a, sc->d_spill_src, sc->d_spill_total, nwg);
-        else
-            hipLaunchKernelGGL((mbk::tile_spill_kernel<double, false>), dim3(nwg), dim3(64), lds2, stream, a, sc->d_spill_src, sc->d_spill_total, nwg);
-        MBK_HIP(ctx, hipGetLastError());
-        ++ctx->spill_launches;
-        ctx->last_spill_stream = stream;
-    }
+    ol.whole = true;
     return MBK_OK;
 }
 
@@ -938,16 +1037,85 @@ static double window_heavy_share(mbk_ctx *ctx, const TileArgs &a)
     return ctx->probe_share;
 }
 
+// The kernels of "scan" (mbk_scan.h), as for launch_blocks.  tile_light_kernel -- rows: finish in place with the statistics fused,
+// cycle test / strict | finish in place, cycle test / strict | listing what it cannot finish; columns: counts and bytes | bytes | counts
+typedef void (*ScanKernel)(TileArgs, mbk::ScanArgs);
+template <typename T>
+static ScanKernel pick_light_kernel(int inl, bool stats, bool counts, bool bytes)
+{
+    static const ScanKernel forms[5][3] = {
+        {mbk::tile_light_kernel<T, true, true, 2, true>, mbk::tile_light_kernel<T, false, true, 2, true>, mbk::tile_light_kernel<T, true, false, 2, true>},
+        {mbk::tile_light_kernel<T, true, true, 1, true>, mbk::tile_light_kernel<T, false, true, 1, true>, mbk::tile_light_kernel<T, true, false, 1, true>},
+        {mbk::tile_light_kernel<T, true, true, 2>, mbk::tile_light_kernel<T, false, true, 2>, mbk::tile_light_kernel<T, true, false, 2>},
+        {mbk::tile_light_kernel<T, true, true, 1>, mbk::tile_light_kernel<T, false, true, 1>, mbk::tile_light_kernel<T, true, false, 1>},
+        {mbk::tile_light_kernel<T, true, true, 0>, mbk::tile_light_kernel<T, false, true, 0>, mbk::tile_light_kernel<T, true, false, 0>},
+    };
+    return forms[inl == 0 ? 4 : (stats ? 0 : 2) + (inl == 2 ? 0 : 1)][(counts && bytes) ? 0 : bytes ? 1 : 2];
+}
+
+template <typename T>
+static ScanKernel pick_todo_kernel(bool cyc) { return cyc ? mbk::tile_todo_kernel<T, true> : mbk::tile_todo_kernel<T, false>; }
+
+// The two-pass form's scratch on `stream`: the cursor set of this launch and the one its pass 1 clears for the next, the 64
+// todo lists (`qcap` ids each) and the size of pass 2, into `s`.
+static int acquire_scan_lists(mbk_ctx *ctx, hipStream_t stream, uint32_t qcap, double probe_share, mbk::ScanArgs &s, StreamScratch **out)
+{
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    if (!sc->d_cursors || sc->cursors_dirty) {
+        if (!sc->d_cursors) MBK_HIP(ctx, hipMalloc((void **)&sc->d_cursors, 2 * sizeof(mbk::ScanCursors)));
+        // once per stream, ON that stream: hipMemset on the null stream does not order against a
+        // non-blocking stream (the first launch on a new stream raced with it and lost listed blocks).
+        // Also after a failed launch: pass 1 of launch L is what clears the set of launch L+1, so a launch that
+        // failed after taking its sets would leave the next one appending behind stale tails.
+        MBK_HIP(ctx, hipMemsetAsync(sc->d_cursors, 0, 2 * sizeof(mbk::ScanCursors), stream));
+        sc->scan_turn = 0;
+        sc->cursors_dirty = false;
+    }
+    const size_t need = (size_t)qcap * mbk::kScanQueues;
+    if (need > sc->scan_cap_blocks) {
+        if (sc->d_entries) {
+            MBK_HIP(ctx, hipStreamSynchronize(stream));  // may still be in use
+            (void)hipFree(sc->d_entries);
+        }
+        sc->d_entries = nullptr;
+        sc->scan_cap_blocks = 0;
+        MBK_HIP(ctx, hipMalloc((void **)&sc->d_entries, need * sizeof(uint32_t)));
+        sc->scan_cap_blocks = need;
+    }
+    s.cur = sc->d_cursors + (sc->scan_turn & 1u);
+    s.cur_next = sc->d_cursors + ((sc->scan_turn + 1u) & 1u);
+    ++sc->scan_turn;
+    s.entries = sc->d_entries;
+    s.qcap = qcap;
+    // pass 2: 64 lists x (hint = longest list of the previous launch on this stream + 25 %).  Never fewer
+    // workgroups than fill the chip (when the tile has that many blocks): a hint from a light tile followed by
+    // a heavy one would otherwise leave a few waves looping over whole lists.
+    // When the host probe of THIS window (window_heavy_share) found no pixel that outlives the light pass and the
+    // finish-in-place form is switched off, pass 2 is launched as one workgroup per CU (its stride loop keeps it correct
+    // if the probe missed a thin feature) instead of the chip-filling floor.
+    const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
+    const uint32_t hint = sc->h_hint[0];
+    if (probe_share == 0.0) {
+        s.ranks2 = std::min(qcap, (cus + mbk::kScanQueues - 1u) / mbk::kScanQueues);
+    } else {
+        s.ranks2 = hint == 0xffffffffu ? qcap : (uint32_t)std::min<uint64_t>(qcap, (uint64_t)hint + hint / 4u + 2u);
+        s.ranks2 = std::max(s.ranks2, std::min(qcap, (cus * 32u + mbk::kScanQueues - 1u) / mbk::kScanQueues));
+    }
+    if (s.ranks2 == 0u) s.ranks2 = 1u;
+    s.hint_out = sc->h_hint;
+    *out = sc;
+    return MBK_OK;
+}
+
 // Kernel "scan": a persistent light pass over every 8x8 block, then one workgroup per block it listed as
 // unfinished (mbk_scan.h).  Launches the light pass cannot serve go to launch_blocks ("group").
 template <typename T>
-// fuse: partial-result slots (already zeroed on `stream`) to which the finish-in-place form adds the tile's
-// pixel-iterations and never-escaped count itself; *fused says whether it did.  counts_unwanted: the int32 counts in
-// `a` exist for the statistics only -- a launch that fuses them does not write them.
-static int launch_scan_t(mbk_ctx *ctx, TileArgs a, bool safe, hipStream_t stream, double probe_share,
-                         ReduceSlot *fuse = nullptr, bool counts_unwanted = false, bool *fused = nullptr)
+static int launch_scan_t(mbk_ctx *ctx, TileArgs a, bool safe, hipStream_t stream, double probe_share, FuseStats *fuse = nullptr)
 {
     const bool f32 = sizeof(T) == 4;
+    const bool cyc = ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u;
     a.blocks_x = (a.ncols + 7u) / 8u;
     const uint32_t nby = (a.nrows + 7u) / 8u;
     const uint32_t nblocks = a.blocks_x * nby;  // <= 2^31 / 64 (validate_view)
@@ -997,107 +1165,34 @@ static int launch_scan_t(mbk_ctx *ctx, TileArgs a, bool safe, hipStream_t stream
     // block rows (strips: rows) whose imaginary coordinates all come from the regular formula (the asm computes them that way)
     const uint32_t im_n = a.im.n - (axis_end_is_regular(a.im) ? 0u : 1u);
     s.fast_by_end = std::min(a.nrows / region_h, im_n > a.row0 ? (im_n - a.row0) / region_h : 0u);
-    s.qtab = 0u;
-    if (a.bytes && a.mrd > 0)
-        for (uint32_t k = 1; k <= 4u; ++k)
-            s.qtab |= (uint32_t)(((uint64_t)k * 256u + (uint32_t)a.mrd - 1u) / (uint32_t)a.mrd & 0xffu) << (8u * (k - 1u));
+    s.qtab = quant_table4(a.mrd, a.bytes != nullptr);
     s.long_groups = ctx->opt[MBK_OPT_GROUP_STEPS] >= 16u ? 1u : 0u;   // (the scan path has no 32-step form: 32 means 16)
     set_window_facts(a, f32);
-#define MBK_LAUNCH_LIGHT(INL)                                                                                              \
-    do {                                                                                                                   \
-        if (a.counts && a.bytes)                                                                                           \
-            hipLaunchKernelGGL((mbk::tile_light_kernel<T, true, true, INL>), dim3(w1), dim3(64), 0, stream, a, s);         \
-        else if (a.bytes)                                                                                                  \
-            hipLaunchKernelGGL((mbk::tile_light_kernel<T, false, true, INL>), dim3(w1), dim3(64), 0, stream, a, s);        \
-        else                                                                                                               \
-            hipLaunchKernelGGL((mbk::tile_light_kernel<T, true, false, INL>), dim3(w1), dim3(64), 0, stream, a, s);        \
-    } while (0)
     if (inline_todo) {
         // one launch, no lists, no scratch: a block the light path cannot finish is finished where it is found
-        if (fuse && (a.bytes || !counts_unwanted)) {
-            a.stats = fuse;
-            if (counts_unwanted) a.counts = nullptr;
-#define MBK_LAUNCH_LIGHT_STATS(INL)                                                                                        \
-    do {                                                                                                                   \
-        if (a.counts && a.bytes)                                                                                           \
-            hipLaunchKernelGGL((mbk::tile_light_kernel<T, true, true, INL, true>), dim3(w1), dim3(64), 0, stream, a, s);   \
-        else if (a.bytes)                                                                                                  \
-            hipLaunchKernelGGL((mbk::tile_light_kernel<T, false, true, INL, true>), dim3(w1), dim3(64), 0, stream, a, s);  \
-        else                                                                                                               \
-            hipLaunchKernelGGL((mbk::tile_light_kernel<T, true, false, INL, true>), dim3(w1), dim3(64), 0, stream, a, s);  \
-    } while (0)
-            if (ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u) MBK_LAUNCH_LIGHT_STATS(2);
-            else MBK_LAUNCH_LIGHT_STATS(1);
-#undef MBK_LAUNCH_LIGHT_STATS
-            MBK_HIP(ctx, hipGetLastError());
-            if (fused) *fused = true;
-            return MBK_OK;
+        const bool stats = fuse != nullptr && fuse->slots != nullptr && (a.bytes || !fuse->counts_unwanted);
+        if (stats) {
+            a.stats = fuse->slots;
+            if (fuse->counts_unwanted) a.counts = nullptr;
         }
-        if (ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u) MBK_LAUNCH_LIGHT(2);
-        else MBK_LAUNCH_LIGHT(1);
+        hipLaunchKernelGGL(pick_light_kernel<T>(cyc ? 2 : 1, stats, a.counts != nullptr, a.bytes != nullptr), dim3(w1), dim3(64), 0, stream, a, s);
         MBK_HIP(ctx, hipGetLastError());
+        if (stats) fuse->fused = true;
         return MBK_OK;
     }
 
     // every list is fed by the waves with its index mod 64; a wave lists at most its own blocks
     const uint32_t qcap = ((w1 + mbk::kScanQueues - 1u) / mbk::kScanQueues) * ((nby + s.stride_by - 1u) / s.stride_by);
     StreamScratch *sc = nullptr;
-    int rc = get_scratch(ctx, stream, &sc);
+    const int rc = acquire_scan_lists(ctx, stream, qcap, probe_share, s, &sc);
     if (rc != MBK_OK) return rc;
-    if (!sc->d_cursors || sc->cursors_dirty) {
-        if (!sc->d_cursors) MBK_HIP(ctx, hipMalloc((void **)&sc->d_cursors, 2 * sizeof(mbk::ScanCursors)));
-        // once per stream, ON that stream: hipMemset on the null stream does not order against a
-        // non-blocking stream (the first launch on a new stream raced with it and lost listed blocks).
-        // Also after a failed launch: pass 1 of launch L is what clears the set of launch L+1, so a launch that
-        // failed after taking its sets would leave the next one appending behind stale tails.
-        MBK_HIP(ctx, hipMemsetAsync(sc->d_cursors, 0, 2 * sizeof(mbk::ScanCursors), stream));
-        sc->scan_turn = 0;
-        sc->cursors_dirty = false;
-    }
-    const size_t need = (size_t)qcap * mbk::kScanQueues;
-    if (need > sc->scan_cap_blocks) {
-        if (sc->d_entries) {
-            MBK_HIP(ctx, hipStreamSynchronize(stream));  // may still be in use
-            (void)hipFree(sc->d_entries);
-        }
-        sc->d_entries = nullptr;
-        sc->scan_cap_blocks = 0;
-        MBK_HIP(ctx, hipMalloc((void **)&sc->d_entries, need * sizeof(uint32_t)));
-        sc->scan_cap_blocks = need;
-    }
-    s.cur = sc->d_cursors + (sc->scan_turn & 1u);
-    s.cur_next = sc->d_cursors + ((sc->scan_turn + 1u) & 1u);
-    ++sc->scan_turn;
-    s.entries = sc->d_entries;
-    s.qcap = qcap;
-    // pass 2: 64 lists x (hint = longest list of the previous launch on this stream + 25 %).  Never fewer
-    // workgroups than fill the chip (when the tile has that many blocks): a hint from a light tile followed by
-    // a heavy one would otherwise leave a few waves looping over whole lists.
-    // When the host probe of THIS window (window_heavy_share) found no pixel that outlives the light pass and the
-    // finish-in-place form is switched off, pass 2 is launched as one workgroup per CU (its stride loop keeps it correct
-    // if the probe missed a thin feature) instead of the chip-filling floor.
-    const uint32_t hint = sc->h_hint[0];
-    if (probe_share == 0.0) {
-        s.ranks2 = std::min(qcap, (cus + mbk::kScanQueues - 1u) / mbk::kScanQueues);
-    } else {
-        s.ranks2 = hint == 0xffffffffu ? qcap : (uint32_t)std::min<uint64_t>(qcap, (uint64_t)hint + hint / 4u + 2u);
-        s.ranks2 = std::max(s.ranks2, std::min(qcap, (cus * 32u + mbk::kScanQueues - 1u) / mbk::kScanQueues));
-    }
-    if (s.ranks2 == 0u) s.ranks2 = 1u;
-    s.hint_out = sc->h_hint;
-    MBK_LAUNCH_LIGHT(0);
-#undef MBK_LAUNCH_LIGHT
+    hipLaunchKernelGGL(pick_light_kernel<T>(0, false, a.counts != nullptr, a.bytes != nullptr), dim3(w1), dim3(64), 0, stream, a, s);
     const uint32_t lds2 = ctx->wave_limit_lds[ctx->opt[MBK_OPT_WAVE_LIMIT] & 7u];
-    if (ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u)
-        hipLaunchKernelGGL((mbk::tile_todo_kernel<T, true>), dim3(mbk::kScanQueues * s.ranks2), dim3(64), lds2, stream, a, s);
-    else
-        hipLaunchKernelGGL((mbk::tile_todo_kernel<T, false>), dim3(mbk::kScanQueues * s.ranks2), dim3(64), lds2, stream, a, s);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            sc->cursors_dirty = true;
-            return fail(ctx, MBK_ERR_HIP, std::string("scan launch: ") + hipGetErrorString(e));
-        }
+    hipLaunchKernelGGL(pick_todo_kernel<T>(cyc), dim3(mbk::kScanQueues * s.ranks2), dim3(64), lds2, stream, a, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        sc->cursors_dirty = true;
+        return fail(ctx, MBK_ERR_HIP, std::string("scan launch: ") + hipGetErrorString(e));
     }
     return MBK_OK;
 }
@@ -1115,10 +1210,9 @@ static void fill_window(Args &a, const mbk_view *v)
 }
 
 static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags,
-                       int32_t *d_counts, uint8_t *d_bytes, hipStream_t stream, double *d_smooth = nullptr,
-                       ReduceSlot *fuse = nullptr, bool counts_unwanted = false, bool *fused = nullptr)
+                       int32_t *d_counts, uint8_t *d_bytes, hipStream_t stream, double *d_smooth = nullptr, FuseStats *fuse = nullptr)
 {
-    if (fused) *fused = false;
+    if (fuse) fuse->fused = false;
     if (stream != ctx->last_tile_stream) {
         ctx->last_tile_stream = stream;
         ++ctx->stream_switches;
@@ -1174,13 +1268,12 @@ static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t f
             const double share = window_heavy_share(ctx, a);
             if (kernel == MBK_KERNEL_DEFAULT &&
                 (share * 65536.0 > (double)ctx->opt[MBK_OPT_HEAVY_SHARE] || ctx->opt[MBK_OPT_HEAVY_SHARE] == 0u))
-                return launch_blocks(ctx, a, MBK_KERNEL_GROUP, safe, f32, stream, fuse, counts_unwanted, fused);
-            return f32 ? launch_scan_t<float>(ctx, a, safe, stream, share, fuse, counts_unwanted, fused)
-                       : launch_scan_t<double>(ctx, a, safe, stream, share, fuse, counts_unwanted, fused);
+                return launch_blocks(ctx, a, MBK_KERNEL_GROUP, safe, f32, stream, fuse);
+            return f32 ? launch_scan_t<float>(ctx, a, safe, stream, share, fuse) : launch_scan_t<double>(ctx, a, safe, stream, share, fuse);
         }
         case MBK_KERNEL_GROUP:
         case MBK_KERNEL_ASM:
-            return launch_blocks(ctx, a, kernel, safe, f32, stream, fuse, counts_unwanted, fused);
+            return launch_blocks(ctx, a, kernel, safe, f32, stream, fuse);
         case MBK_KERNEL_REFILL:
             return launch_refill(ctx, a, safe, stream);
         case MBK_KERNEL_SIMPLE: {
@@ -1700,12 +1793,12 @@ static int submit_view(mbk_ctx *ctx, Slot &sl, const mbk_view *view, uint32_t mr
     // of a pyramid level).  Then no int32 count is written unless the caller asked for counts, and the pass reads the
     // bytes only (all-0 / all-1 flags, run count): 16 MiB instead of 80 for a DataChunk.
     MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
-    bool fused = false;
+    FuseStats fuse = {sl.d_red, !wc, false};
     MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-    rc = launch_tile(ctx, view, mrd, dev_flags, sl.d_counts, sl.d_bytes, sl.stream, nullptr, sl.d_red, !wc, &fused);
+    rc = launch_tile(ctx, view, mrd, dev_flags, sl.d_counts, sl.d_bytes, sl.stream, nullptr, &fuse);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
-    rc = launch_reduce(ctx, sl, fused ? nullptr : sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream, false);
+    rc = launch_reduce(ctx, sl, fuse.fused ? nullptr : sl.d_counts, wb ? sl.d_bytes : nullptr, px, mrd, sl.stream, false);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
     // MBK_LAZY_UNIFORM: whether the tile is uniform is known only when its statistics are -- deciding the copy then costs a
@@ -2069,11 +2162,11 @@ int mbk_get_option(mbk_ctx *ctx, int option, uint32_t *value)
         if (option == MBK_INFO_SPILL) {   // lanes the last such launch handed to its second pass (waits for that launch)
             *value = 0u;
             for (const StreamScratch &sc : ctx->scratch)
-                if (sc.stream == ctx->last_spill_stream && sc.d_spill_total && ctx->spill_launches) {
+                if (sc.stream == ctx->last_spill_stream && sc.spill.d_total && ctx->spill_launches) {
                     unsigned long long t = 0;
                     MBK_HIP(ctx, hipSetDevice(ctx->device));
                     MBK_HIP(ctx, hipStreamSynchronize(sc.stream));
-                    MBK_HIP(ctx, hipMemcpy(&t, sc.d_spill_total, sizeof(t), hipMemcpyDeviceToHost));
+                    MBK_HIP(ctx, hipMemcpy(&t, sc.spill.d_total, sizeof(t), hipMemcpyDeviceToHost));
                     *value = (uint32_t)std::min<unsigned long long>(t, 0xffffffffull);
                 }
         }

@@ -38,6 +38,8 @@ struct Axis {
 
 struct ReduceSlot;   // (below: partial results of the statistics reduction)
 
+constexpr uint32_t kSpillLevels = 12;    // SPILL: checkpoints told apart in the list's order (a block's count word: lanes | level << 8; mbk_spill.h)
+
 struct TileArgs {
     Axis re, im;
     uint32_t col0, row0, ncols, nrows;
@@ -369,7 +371,7 @@ __device__ __forceinline__ void block_pixel_spill(const TileArgs &p, uint32_t uc
                     z.y = zi;
                     reinterpret_cast<typename SpillPair<T>::type *>(p.spill_z)[slot] = z;
                     p.spill_meta[slot] = (ly * 8u + lx) | (n << 6);
-                    if (rank == 0u) p.spill_cnt[block_index] = k | ((level < 11u ? level : 11u) << 8);   // (11 = kSpillLevels - 1)
+                    if (rank == 0u) p.spill_cnt[block_index] = k | ((level < kSpillLevels - 1u ? level : kSpillLevels - 1u) << 8);
                     spilled = true;
                 }
                 break;

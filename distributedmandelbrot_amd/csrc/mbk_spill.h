@@ -12,7 +12,7 @@
 namespace mbk {
 
 constexpr uint32_t kSpillChunk = 1024;   // blocks per workgroup of the two list kernels
-constexpr uint32_t kSpillLevels = 12;    // checkpoints told apart in the list's order (a block's count word: lanes | level << 8)
+// (kSpillLevels, the checkpoints told apart in the list's order, is in mbk_kernels.h: the first pass clamps to it)
 
 // The list is ordered by checkpoint, LATEST FIRST, blocks in image order within one: a lane that has outlived more steps is
 // likelier to outlive the rest (the pixels of the set end up in the late checkpoints), and the second pass lasts as long as
