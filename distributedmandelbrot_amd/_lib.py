@@ -31,6 +31,7 @@ OPTIONS = {name: i for i, name in enumerate(
      "rf_livemin", "rf_patience", "rf_batch", "rf_waves", "cycle_detect", "probe_mid", "prepass_overlap", "exact_long", "scan_inline", "wave_limit", "units_min_light", "xcd_balance", "m_late", "h_settled", "classify_wg", "scan_strip", "cycle_window", "spill_first", "spill_lanes", "spill_min_mrd", "spill_min_blocks", "spill_cyc_shift"])}
 MBK_PRECISION_F32 = 0x1000
 MBK_LAZY_UNIFORM = 0x2000
+MBK_DEEP_BLA = 0x8000   # deep count / render / histogram calls only
 PRECISIONS = {"f64": 0, "f32": MBK_PRECISION_F32}
 MBK_SLOTS = 4
 MBK_WORKER_DEPTH = 3
@@ -190,6 +191,11 @@ SIGNATURES = {
     "mbk_deep_view_compute_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                                  C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_deep_distance_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32]),
+    "mbk_deep_bla_info": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "mbk_deep_bla_read": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mbk_deep_bla_count_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "mbk_view_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
                                          C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
     "mbk_view_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,

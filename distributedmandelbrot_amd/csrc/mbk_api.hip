@@ -26,6 +26,7 @@
 #include "mbk_feeder.h"
 #include "mbk_deep_orbit.h"
 #include "mbk_deep.h"
+#include "mbk_deep_bla.h"
 #include "mbk_histogram.h"
 #include "mbk_render.h"
 #include "mbk_chunks.h"
@@ -201,7 +202,17 @@ struct mbk_ctx {
     double probe_share = 0.0;
     bool probe_valid = false;
     // deep-zoom views: this ctx's device copies of the orbits it has used, by orbit id (deep_copy)
-    struct DeepCopy { uint64_t id; double4 *d; };
+    // beside each, the bilinear-approximation table of the last dcmax it was launched with (MBK_DEEP_BLA; bla_copy)
+    struct DeepCopy {
+        uint64_t id;
+        double4 *d;
+        bool has_bla;
+        uint64_t dcmax_bits;
+        double *d_rc;
+        double4 *d_ab;
+        uint32_t levels;
+        uint32_t off[mbk::kBlaMaxLevels];
+    };
     std::vector<DeepCopy> deep;
     hipDeviceProp_t prop;
     std::string err;
@@ -360,6 +371,14 @@ static int validate_view(mbk_ctx *ctx, const mbk_view *v, bool *safe_doubling, b
                                                   : "view coordinates must be finite and |x| <= 2^500");
     *safe_doubling = axis_has_tiny_nonzero(make_axis(v->start_i, v->range_i, v->height), v->row0, v->nrows, f32);
     return MBK_OK;
+}
+
+static void free_deep_copy(mbk_ctx::DeepCopy &c)
+{
+    if (c.d) (void)hipFree(c.d);
+    if (c.d_rc) (void)hipFree(c.d_rc);
+    if (c.d_ab) (void)hipFree(c.d_ab);
+    c = mbk_ctx::DeepCopy();
 }
 
 static void free_scratch(StreamScratch &sc)
@@ -1212,6 +1231,7 @@ static void fill_window(Args &a, const mbk_view *v)
 static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags,
                        int32_t *d_counts, uint8_t *d_bytes, hipStream_t stream, double *d_smooth = nullptr, FuseStats *fuse = nullptr)
 {
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is a flag of the deep view calls");
     if (fuse) fuse->fused = false;
     if (stream != ctx->last_tile_stream) {
         ctx->last_tile_stream = stream;
@@ -1652,7 +1672,7 @@ void mbk_destroy(mbk_ctx *ctx)
     }
     if (!ctx->scratch.empty() || !ctx->deep.empty()) (void)hipDeviceSynchronize();  // caller streams may still use them
     for (StreamScratch &sc : ctx->scratch) free_scratch(sc);
-    for (mbk_ctx::DeepCopy &c : ctx->deep) (void)hipFree(c.d);
+    for (mbk_ctx::DeepCopy &c : ctx->deep) free_deep_copy(c);
     if (ctx->d_rle) (void)hipFree(ctx->d_rle);
     if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
     if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
@@ -1756,6 +1776,7 @@ static int submit_view(mbk_ctx *ctx, Slot &sl, const mbk_view *view, uint32_t mr
 {
     if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
     const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is a flag of the deep view calls");
     int rc = check_wanted(ctx, flags, h_counts, h_bytes);
     if (rc != MBK_OK) return rc;
     bool dummy;
@@ -2319,7 +2340,7 @@ static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const double4 **
         }
     if (ctx->deep.size() >= kMaxDeepCopies) {
         MBK_HIP(ctx, hipDeviceSynchronize());
-        for (mbk_ctx::DeepCopy &c : ctx->deep) (void)hipFree(c.d);
+        for (mbk_ctx::DeepCopy &c : ctx->deep) free_deep_copy(c);
         ctx->deep.clear();
     }
     const size_t bytes = orbit->o.table.size() * sizeof(double);
@@ -2330,7 +2351,10 @@ static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const double4 **
         (void)hipFree(d);
         return fail(ctx, MBK_ERR_HIP, std::string("hipMemcpy (reference orbit): ") + hipGetErrorString(e));
     }
-    ctx->deep.push_back({orbit->o.id, d});
+    mbk_ctx::DeepCopy c = mbk_ctx::DeepCopy();
+    c.id = orbit->o.id;
+    c.d = d;
+    ctx->deep.push_back(c);
     *out = d;
     return MBK_OK;
 }
@@ -2339,8 +2363,10 @@ static int validate_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_de
 {
     if (!orbit) return fail(ctx, MBK_ERR_INVALID, "orbit is NULL");
     if (!v) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES))
-        return fail(ctx, MBK_ERR_INVALID, "deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
+    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_DEEP_BLA))
+        return fail(ctx, MBK_ERR_INVALID, "deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES / MBK_DEEP_BLA only (no kernel selection, no fp32)");
+    if ((flags & MBK_DEEP_BLA) && orbit->o.length > (1u << 31))
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA: the orbit is longer than 2^31 (the table's indices are 32 bits wide)");
     if (v->width == 0 || v->height == 0) return fail(ctx, MBK_ERR_INVALID, "empty view");
     if (v->ncols == 0 || v->nrows == 0) return fail(ctx, MBK_ERR_INVALID, "empty window");
     if ((uint64_t)v->col0 + v->ncols > v->width || (uint64_t)v->row0 + v->nrows > v->height)
@@ -2381,10 +2407,81 @@ static void fill_deep_args(mbk::DeepArgs &a, const double4 *d_orbit, const mbk_d
     a.mrd = (int32_t)mrd;
 }
 
-// the deep kernel on device pointers (validated by the caller), on `stream`
-static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
-                       int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+// dcmax of "Deep-zoom views with bilinear approximation": fl(|dc_r(column 0)| + |dc_i(row 0)|) of the FULL view
+static double deep_dcmax(const mbk_deep_view *v)
 {
+    volatile double dr = (0.0 - (double)(v->width - 1u) * 0.5) * deep_step(v->range_r, v->width);
+    volatile double di = (0.0 - (double)(v->height - 1u) * 0.5) * deep_step(v->range_i, v->height);
+    volatile double s = std::fabs(dr) + std::fabs(di);
+    return s;
+}
+
+// This ctx's device copy of `orbit` (deep_copy) with the table of `dcmax` beside it.  The table is built on the host and
+// uploaded when the copy has none or has another dcmax's: synchronously, and after the device has drained, since a launch that
+// reads the table it replaces may still be queued (mbk.h).  M >= 2.
+static int bla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, double dcmax, const mbk_ctx::DeepCopy **out)
+{
+    const double4 *d_orbit = nullptr;
+    int rc = deep_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk_ctx::DeepCopy *c = nullptr;
+    for (mbk_ctx::DeepCopy &k : ctx->deep)
+        if (k.id == orbit->o.id) c = &k;
+    uint64_t bits;
+    std::memcpy(&bits, &dcmax, sizeof(bits));
+    if (c->has_bla && c->dcmax_bits == bits) {
+        *out = c;
+        return MBK_OK;
+    }
+    mbk::BlaTable t;
+    try {
+        mbk::build_bla_table(orbit->o.table, orbit->o.length, dcmax, &t);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, MBK_ERR_NOMEM, "out of host memory for the bilinear-approximation table");
+    }
+    if (c->has_bla) MBK_HIP(ctx, hipDeviceSynchronize());
+    c->has_bla = false;
+    if (!c->d_rc) {   // the sizes depend on M alone: allocated once per copy
+        const size_t n = t.rc.size();
+        MBK_HIP(ctx, hipMalloc((void **)&c->d_rc, n * sizeof(double)));
+        MBK_HIP(ctx, hipMalloc((void **)&c->d_ab, n * sizeof(double4)));
+    }
+    MBK_HIP(ctx, hipMemcpy(c->d_rc, t.rc.data(), t.rc.size() * sizeof(double), hipMemcpyHostToDevice));
+    MBK_HIP(ctx, hipMemcpy(c->d_ab, t.ab.data(), t.ab.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->levels = t.levels;
+    std::memcpy(c->off, t.off, sizeof(c->off));
+    c->dcmax_bits = bits;
+    c->has_bla = true;
+    *out = c;
+    return MBK_OK;
+}
+
+// the deep kernel on device pointers (validated by the caller), on `stream`; bla: MBK_DEEP_BLA (an orbit of length 1 has no
+// table: the flag changes nothing)
+static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
+                       int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream, bool bla = false)
+{
+    if (bla && orbit->o.length >= 2u) {
+        const mbk_ctx::DeepCopy *c = nullptr;
+        int rc = bla_copy(ctx, orbit, deep_dcmax(v), &c);
+        if (rc != MBK_OK) return rc;
+        mbk::DeepBlaArgs a;
+        std::memset(&a, 0, sizeof(a));
+        fill_deep_args(a.v, c->d, orbit, v, mrd);
+        a.v.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
+        a.v.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
+        a.v.counts = d_counts;
+        a.v.bytes = d_bytes;
+        a.v.smooth = d_smooth;
+        a.rc = c->d_rc;
+        a.ab = c->d_ab;
+        a.levels = c->levels;
+        std::memcpy(a.off, c->off, sizeof(a.off));
+        const uint32_t blocks = a.v.blocks_x * ((v->nrows + 7u) / 8u);
+        hipLaunchKernelGGL(mbk::deep_bla_kernel, dim3(blocks), dim3(64), 0, stream, a);
+        MBK_HIP(ctx, hipGetLastError());
+        return MBK_OK;
+    }
     const double4 *d_orbit = nullptr;
     int rc = deep_copy(ctx, orbit, &d_orbit);
     if (rc != MBK_OK) return rc;
@@ -2413,7 +2510,7 @@ int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_de
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     return launch_deep(ctx, orbit, view, mrd, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
-                       (hipStream_t)hip_stream);
+                       (hipStream_t)hip_stream, (flags & MBK_DEEP_BLA) != 0);
 }
 
 int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
@@ -2424,7 +2521,7 @@ int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_d
     if (rc != MBK_OK) return rc;
     return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
                         [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                            return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
+                            return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream, (flags & MBK_DEEP_BLA) != 0);
                         });
 }
 
@@ -2437,8 +2534,70 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
     if (rc != MBK_OK) return rc;
     return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                           return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
+                           return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream, (flags & MBK_DEEP_BLA) != 0);
                        });
+}
+
+// ---- host twins of the bilinear-approximation table and step (mbk_deep_bla.h): no ctx, no device -------------------------
+
+static int bla_host_table(const mbk_deep_orbit *orbit, const mbk_deep_view *view, mbk::BlaTable *t)
+{
+    int rc = validate_deep(nullptr, orbit, view, 0u, MBK_DEEP_BLA);
+    if (rc != MBK_OK) return rc;
+    try {
+        mbk::build_bla_table(orbit->o.table, orbit->o.length, deep_dcmax(view), t);
+    } catch (const std::bad_alloc &) {
+        return fail(nullptr, MBK_ERR_NOMEM, "out of host memory for the bilinear-approximation table");
+    }
+    return MBK_OK;
+}
+
+int mbk_deep_bla_info(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t *levels, uint64_t *entries)
+{
+    int rc = validate_deep(nullptr, orbit, view, 0u, MBK_DEEP_BLA);
+    if (rc != MBK_OK) return rc;
+    const uint32_t n = mbk::bla_levels(orbit->o.length);
+    uint64_t total = 0;
+    for (uint32_t l = 0; l < n; ++l) total += (orbit->o.length - 1u) >> l;
+    if (levels) *levels = n;
+    if (entries) *entries = total;
+    return MBK_OK;
+}
+
+int mbk_deep_bla_read(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t level, double *A_r, double *A_i,
+                      double *B_r, double *B_i, double *rc_out, uint64_t n)
+{
+    if (!A_r || !A_i || !B_r || !B_i || !rc_out) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::BlaTable t;
+    int rc = bla_host_table(orbit, view, &t);
+    if (rc != MBK_OK) return rc;
+    if (level >= t.levels) return fail(nullptr, MBK_ERR_INVALID, "the table has no such level");
+    const uint32_t cnt = t.count(level);
+    if (n < cnt) return fail(nullptr, MBK_ERR_INVALID, "the outputs hold fewer than the level's entries");
+    for (uint32_t j = 0; j < cnt; ++j) {
+        const size_t e = (size_t)t.off[level] + j;
+        A_r[j] = t.ab[4 * e];
+        A_i[j] = t.ab[4 * e + 1];
+        B_r[j] = t.ab[4 * e + 2];
+        B_i[j] = t.ab[4 * e + 3];
+        rc_out[j] = t.rc[e];
+    }
+    return MBK_OK;
+}
+
+int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                            int32_t *count, double *mag, uint64_t *steps_executed)
+{
+    if (!count || !mag || !steps_executed) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::BlaTable t;
+    int rc = bla_host_table(orbit, view, &t);
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    volatile double dcr = ((double)col - (double)(view->width - 1u) * 0.5) * deep_step(view->range_r, view->width);
+    volatile double dci = ((double)row - (double)(view->height - 1u) * 0.5) * deep_step(view->range_i, view->height);
+    mbk::bla_count_host(orbit->o.table, orbit->o.length, t, dcr, dci, (int64_t)mrd, count, mag, steps_executed);
+    return MBK_OK;
 }
 
 // ---- distance estimates for deep views (mbk_deep_distance.h; mbk.h "Distance estimates for deep views") ----------------
@@ -2784,8 +2943,9 @@ static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint3
     sample_window(t, s, t.col0, t.row0, t.ncols, t.nrows, &sv, &sd);
     if (t.deep) {
         if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)");
-        if (flags) return fail(ctx, MBK_ERR_INVALID, "deep renders take no flags (no kernel selection, no fp32)");
-        rc = validate_deep(ctx, t.orbit, &sd, mrd, smooth ? 0u : MBK_WANT_BYTES);
+        if (flags & ~MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep renders take MBK_DEEP_BLA only (no kernel selection, no fp32)");
+        if (flags && rel) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for deep distance estimates");
+        rc = validate_deep(ctx, t.orbit, &sd, mrd, (smooth ? 0u : MBK_WANT_BYTES) | flags);
         if (rc != MBK_OK || !equalized) return rc;
         return validate_lut(ctx, h_lut, lut_len, mrd);
     }
@@ -2875,7 +3035,7 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
             if (t.deep) {
                 rc = rel ? launch_deep_distance(ctx, t.orbit, &sd, mrd, d_counts, d_nu, stream)
-                         : launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream);
+                         : launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream, (flags & MBK_DEEP_BLA) != 0);
             } else if (t.julia) {
                 rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, d_bytes, d_nu, stream);
             } else if (dist) {
@@ -3173,8 +3333,8 @@ static int hist_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     int rc = check_hist_mrd(ctx, mrd);
     if (rc != MBK_OK) return rc;
     if (t.deep) {
-        if (flags) return fail(ctx, MBK_ERR_INVALID, "deep histograms take no flags (no kernel selection, no fp32)");
-        return validate_deep(ctx, t.orbit, t.deep, mrd, MBK_WANT_COUNTS);
+        if (flags & ~MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep histograms take MBK_DEEP_BLA only (no kernel selection, no fp32)");
+        return validate_deep(ctx, t.orbit, t.deep, mrd, MBK_WANT_COUNTS | flags);
     }
     if (t.julia) {
         if (flags & ~MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "Julia histogram flags carry kernel selection only");
@@ -3224,7 +3384,7 @@ static int hist_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t 
             mbk_deep_view sd;
             sample_window(t, 1u, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
             if (t.deep)
-                rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, nullptr, nullptr, stream);
+                rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, nullptr, nullptr, stream, (flags & MBK_DEEP_BLA) != 0);
             else if (t.julia)
                 rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, nullptr, nullptr, stream);
             else

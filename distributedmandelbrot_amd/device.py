@@ -481,31 +481,38 @@ class MandelbrotDevice:
 
     def compute_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_counts: bool = True,
                           want_bytes: bool = True, want_smooth: bool = False, out_counts: Optional[np.ndarray] = None,
-                          out_bytes: Optional[np.ndarray] = None):
-        """Synchronous: (counts int32 | None, bytes uint8 | None, smooth float64 | None, TileStats), each [nrows, ncols]."""
+                          out_bytes: Optional[np.ndarray] = None, bla: bool = False):
+        """Synchronous: (counts int32 | None, bytes uint8 | None, smooth float64 | None, TileStats), each [nrows, ncols].
+        bla: step with bilinear approximation (MBK_DEEP_BLA; include/mbk.h, "Deep-zoom views with bilinear approximation"):
+        runs of steps collapse into one linear map while the pixel's offset is tiny against the reference orbit -- several
+        times fewer steps on a deep view, counts that equal the exact rule's on all but a fraction of a percent of pixels."""
         cv = self._cdeep(view, window)
         shape = (cv.nrows, cv.ncols)
         counts = _out_array(out_counts, shape, np.int32) if want_counts else None
         byts = _out_array(out_bytes, shape, np.uint8) if want_bytes else None
         smooth = np.empty(shape, np.float64) if want_smooth else None
         flags, p_counts, p_bytes = _wanted(shape, counts, byts)
+        flags |= L.MBK_DEEP_BLA if bla else 0
         st = L.mbk_stats()
         self._check(self._lib.mbk_deep_view_compute(self._h, orbit._h, C.byref(cv), mrd, flags, p_counts, p_bytes,
                                                     smooth.ctypes.data if smooth is not None else None, C.byref(st)))
         return counts, byts, smooth, _stats(st)
 
     def submit_deep_view(self, slot: int, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None,
-                         out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None) -> None:
+                         out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None,
+                         bla: bool = False) -> None:
         """Enqueue a deep view / window on `slot`; the host arrays are valid after wait(slot)."""
         cv = self._cdeep(view, window)
         flags, p_counts, p_bytes = _wanted((cv.nrows, cv.ncols), out_counts, out_bytes)
+        flags |= L.MBK_DEEP_BLA if bla else 0
         self._check(self._lib.mbk_deep_view_submit(self._h, slot, orbit._h, C.byref(cv), mrd, flags, p_counts, p_bytes))
 
     def launch_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_counts: int = 0, d_bytes: int = 0,
-                         d_smooth: int = 0, stream: int = 0, window=None) -> None:
-        """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream)."""
+                         d_smooth: int = 0, stream: int = 0, window=None, bla: bool = False) -> None:
+        """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream).  With bla the first launch of a
+        view's spans on an orbit builds and uploads the table synchronously."""
         cv = self._cdeep(view, window)
-        flags = (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0)
+        flags = (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0) | (L.MBK_DEEP_BLA if bla else 0)
         self._check(self._lib.mbk_deep_view_launch(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None,
                                                    d_bytes or None, d_smooth or None, stream or None))
 
@@ -567,21 +574,24 @@ class MandelbrotDevice:
         return np.ascontiguousarray(lut, dtype=np.float64).ravel()
 
     def render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, source: str = "smooth",
-                         supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None):
+                         supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None,
+                         bla: bool = False):
         """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height.
         Source "distance_rel" colours the deep distance estimate (compute_deep_view_distance; Palette.deep_distance); source
         "distance", the plain views' estimate in plane units, is refused (MbkError).  Source "equalized" and `lut` as for
-        render_view (the table of deep_view_histogram of the whole view when lut is None)."""
+        render_view (the table of deep_view_histogram of the whole view when lut is None).  bla: the samples (and that
+        histogram) are those of compute_deep_view(bla=True); refused with source "distance_rel"."""
         cv = self._cdeep(view, window)
         rgba = self._render_out(cv, out)
         spec = palette.spec(source, supersample, max_band_rows)
         st = L.mbk_stats()
+        flags = L.MBK_DEEP_BLA if bla else 0
         if source == "equalized":
-            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd))
-            self._check(self._lib.mbk_deep_view_render_equalized_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla))
+            self._check(self._lib.mbk_deep_view_render_equalized_compute(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
                                                                          lut.ctypes.data, lut.size, rgba.ctypes.data, C.byref(st)))
         else:
-            self._check(self._lib.mbk_deep_view_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+            self._check(self._lib.mbk_deep_view_render_compute(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
                                                                rgba.ctypes.data, C.byref(st)))
         return rgba, _stats(st)
 
@@ -602,16 +612,17 @@ class MandelbrotDevice:
 
     def launch_render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, d_rgba: int,
                                 source: str = "smooth", supersample: int = 1, stream: int = 0, window=None,
-                                max_band_rows: int = 0, lut=None) -> None:
+                                max_band_rows: int = 0, lut=None, bla: bool = False) -> None:
         cv = self._cdeep(view, window)
         spec = palette.spec(source, supersample, max_band_rows)
+        flags = L.MBK_DEEP_BLA if bla else 0
         if source == "equalized":
-            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd))
-            self._check(self._lib.mbk_deep_view_render_equalized_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla))
+            self._check(self._lib.mbk_deep_view_render_equalized_launch(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
                                                                         lut.ctypes.data, lut.size, d_rgba or None,
                                                                         stream or None))
             return
-        self._check(self._lib.mbk_deep_view_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+        self._check(self._lib.mbk_deep_view_render_launch(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
                                                           d_rgba or None, stream or None))
 
     # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
@@ -627,12 +638,13 @@ class MandelbrotDevice:
                                                          hist.ctypes.data if hist.size else None, C.byref(st)))
         return (hist, _stats(st)) if want_stats else hist
 
-    def deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_stats: bool = False):
-        """view_histogram for a deep view."""
+    def deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_stats: bool = False,
+                            bla: bool = False):
+        """view_histogram for a deep view (bla: of the counts of compute_deep_view(bla=True))."""
         cv = self._cdeep(view, window)
         hist = np.empty(max(int(mrd), 0), np.uint64)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_histogram_compute(self._h, orbit._h, C.byref(cv), mrd, 0,
+        self._check(self._lib.mbk_deep_view_histogram_compute(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_BLA if bla else 0,
                                                               hist.ctypes.data if hist.size else None, C.byref(st)))
         return (hist, _stats(st)) if want_stats else hist
 
@@ -645,9 +657,9 @@ class MandelbrotDevice:
                                                         d_hist or None, stream or None))
 
     def launch_deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_hist: int, stream: int = 0,
-                                   window=None) -> None:
+                                   window=None, bla: bool = False) -> None:
         cv = self._cdeep(view, window)
-        self._check(self._lib.mbk_deep_view_histogram_launch(self._h, orbit._h, C.byref(cv), mrd, 0, d_hist or None,
+        self._check(self._lib.mbk_deep_view_histogram_launch(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_BLA if bla else 0, d_hist or None,
                                                              stream or None))
 
     def counts_histogram(self, d_counts: int, n: int, mrd: int, d_hist: int, stream: int = 0) -> None:

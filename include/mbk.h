@@ -319,7 +319,8 @@ int mbk_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, uint32_t mrd, 
  *                    so bytes are the usual quantiser of the count and smooth = n + 1 - log2(0.5 ln mag) as for mbk_view.
  * Limits: spans (range_r, range_i) in [2^-960, 4] (binary64 offsets stay normal); P <= 4096 (spans below 2^(64-P) resolve the
  * centre more finely than the orbit does: Python's DeepOrbit picks P = 64 + ceil(-log2 min_span) by default); a launch's mrd
- * <= the orbit's mrd.  Extended-exponent offsets (spans below 2^-960) and series approximation are not implemented.
+ * <= the orbit's mrd.  Extended-exponent offsets (spans below 2^-960) are not implemented; series approximation is a flag
+ * (MBK_DEEP_BLA, "Deep-zoom views with bilinear approximation" below), off by default.
  * Centres within ~1e-16 of -2 render wrong below spans of ~1e-15: the real orbit stays just inside |z| = 2, the binary64 table
  * holds 2.0, and every pixel retires at count 1 (tests/test_deep_truth.py, the strict xfail cases).
  *
@@ -350,8 +351,8 @@ int mbk_deep_orbit_info(const mbk_deep_orbit *orbit, uint32_t *length, uint32_t 
                         uint32_t *mrd);
 /* Z_0 .. Z_M as binary64 into zr[0..M], zi[0..M]; n is their capacity (MBK_ERR_INVALID below M + 1). */
 int mbk_deep_orbit_read(const mbk_deep_orbit *orbit, double *zr, double *zi, uint64_t n);
-/* The three forms of the view calls.  flags: MBK_WANT_COUNTS | MBK_WANT_BYTES only (kernel selection, MBK_PRECISION_F32 and
- * MBK_LAZY_UNIFORM are MBK_ERR_INVALID), as are a NULL orbit, a view without output, ranges outside [2^-960, 4] and
+/* The three forms of the view calls.  flags: MBK_WANT_COUNTS | MBK_WANT_BYTES, and MBK_DEEP_BLA ("Deep-zoom views with
+ * bilinear approximation", below), only (kernel selection, MBK_PRECISION_F32 and MBK_LAZY_UNIFORM are MBK_ERR_INVALID), as are a NULL orbit, a view without output, ranges outside [2^-960, 4] and
  * mrd > the orbit's mrd.  _launch: DEVICE pointers on the caller's stream (d_smooth may be NULL; no statistics).  _compute:
  * synchronous into HOST buffers on slot 0 (h_smooth may be NULL), stats as for mbk_view_compute -- pixel_iterations counts
  * the reference's iterations (count, or mrd - 1 for 0).  _submit: on `slot`, completed by mbk_wait. */
@@ -361,6 +362,74 @@ int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_d
                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats);
 int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes);
+
+/*
+ * Deep-zoom views with bilinear approximation.  NOT in the reference; additive (the ABI version stays 5): without the flag
+ * every call stores what it stored before.  While a pixel's offset dz is tiny against the reference orbit, the step
+ * dz -> 2 Z_m dz + dz^2 + dc is linear in (dz, dc) to working precision, and a run of 2^l such steps collapses into one map
+ * dz -> A dz + B dc whose coefficients come from a table merged pairwise over the orbit (BLA, the modern form of series
+ * approximation).  A deep pixel then executes a fraction of its steps (scripts/deep_bla_rate.py, profiles/deep_bla/).
+ *
+ * MBK_DEEP_BLA is a flag of mbk_deep_view_launch / _compute / _submit, of mbk_deep_view_render_launch / _compute and their
+ * _equalized_ forms (every source but MBK_RENDER_DISTANCE_REL) and of mbk_deep_view_histogram_launch / _compute.  Every other
+ * call refuses it with MBK_ERR_INVALID: the deep distance calls (their derivative would need coefficients of its own), every
+ * plain view call and every Julia call.
+ *
+ * Contract (tests/deep_bla_model.py restates it in numpy; tests/test_deep_bla.py holds the host twins below to it and it to
+ * the truth, tests/test_gpu_deep_bla.py holds the GPU to it, bit for bit).  Everything of "Deep-zoom views" stands: orbit
+ * table, offsets dc, the step, the rebase rule, counts, bytes, smooth, statistics (pixel_iterations counts the reference's
+ * iterations -- count, or mrd - 1 for 0 -- not the steps executed).  Binary64 throughout, every operation rounded on its own,
+ * no contraction.
+ *   table     built on the host from the orbit's binary64 table Z_0 .. Z_M and one number per view,
+ *               dcmax = fl(|dc_r(column 0)| + |dc_i(row 0)|) of the FULL view, not the window
+ *             (a 1-norm: nothing is squared, so it cannot underflow at span 2^-960; windows and bands share one table and stay
+ *             bit-identical to the whole view), with eps = 2^-40.  Level l has n_l = floor((M - 1) / 2^l) entries, for
+ *             l = 0 .. while n_l >= 1; entry j covers the 2^l steps that start at m = 1 + j 2^l.  With M <= 1 there is no
+ *             table and the flag changes nothing.
+ *             Level 0: A = (2 Z_m.r, 2 Z_m.i), B = (1, 0), r = fl(eps fl(sqrt(fl(fl(A_r^2) + fl(A_i^2))))).
+ *             Level l + 1, entry j, from x = entry 2j and y = entry 2j + 1 of level l:
+ *               A = A_y A_x;  B = A_y B_x + B_y
+ *               (complex products are (fl(fl(ac) - fl(bd)), fl(fl(ad) + fl(bc))) with (a, b) the left factor; the sum is
+ *               rounded per component; |A_x| and |B_x| are fl(sqrt(fl(fl(.^2) + fl(.^2)))))
+ *               t = fl(fl(r_y - fl(|B_x| dcmax)) / |A_x|);  r = min(r_x, max(t, 0))
+ *               r = 0 whenever |A_x| = 0 or any component of the merged A, of the merged B, or t is not finite.  High levels
+ *               overflow (|A| grows like 4^(2^l)); such an entry is simply never taken.  Its A and B are stored as computed
+ *               (infinities, NaNs of the host's own sign and payload).
+ *             r is non-increasing in l at a fixed starting m.  Stored per entry: A, B and rc = fl(r 0.7071067811865476).
+ *   step      state (dz, m, i), i the index of the step about to run.  Take the highest level l with ALL of
+ *               m >= 1;  (m - 1) mod 2^l = 0;  (m - 1) >> l < n_l;  i + 2^l <= mrd;  max(|dz.r|, |dz.i|) < rc
+ *             (each is monotone in l: a search upward from level 0 that stops at the first failure finds the same level).
+ *             If there is one:
+ *               dz = (fl(fl(fl(A_r dz.r) - fl(A_i dz.i)) + fl(fl(B_r dc.r) - fl(B_i dc.i))),
+ *                     fl(fl(fl(A_r dz.i) + fl(A_i dz.r)) + fl(fl(B_r dc.i) + fl(B_i dc.r))));  m += 2^l
+ *               and the step index becomes i + 2^l - 1.  If there is none, the plain step runs.  After either, exactly as in
+ *             "Deep-zoom views": z = fl(Z_m + dz) and mag are formed; mag >= 4 stores that step index as the count (its mag
+ *             feeds smooth); then the rebase rule applies (mag < |dz|^2 or m == M).  The steps inside a skip are not tested.
+ *             m = 0, the state right after a rebase, always takes the plain step.
+ *   eps       2^-40, a constant of the contract (it changes output, so it is not an mbk_option).  Against direct iteration at
+ *             P + 128 bits it equals the truth on every sampled pixel of the catalogue of tests/test_deep_truth.py and of the
+ *             seahorse view at span 1e-20, mrd 30000; the 2^-24 the literature suggests for binary64 reaches 88.75 % there, off
+ *             by up to 140 (tests/test_deep_bla.py keeps that test).  The same cap as the plain contract: >= 99 % of pixels.
+ *
+ * The ctx keeps the device copy of one table beside each orbit copy, keyed by the orbit's id and the bits of dcmax: 40 bytes
+ * per entry, fewer than 2 (M - 1) entries.  It is built on the host and uploaded on the first MBK_DEEP_BLA launch of the orbit
+ * on the ctx, and REBUILT whenever a launch brings another dcmax (another span or aspect of the full view) -- synchronously, and
+ * the rebuild first synchronises the device, since a queued launch may still read the table it replaces.  So the orbit's
+ * "first launch" rule covers it: launch once per (orbit, spans) before capturing, and expect alternating spans on one orbit to
+ * serialise.  The table is freed with the orbit copies.
+ */
+#define MBK_DEEP_BLA 0x8000u
+/* Host twins for the CPU tests, compiled from the functions the builder and the kernel use: no ctx, no device.  `view` gives
+ * dcmax (its window is not used); MBK_ERR_INVALID for what mbk_deep_view_launch refuses in a view.
+ * _info: the number of levels (0 for M <= 1) and of entries over all levels.  _read: level `level` into five arrays of
+ * capacity n (MBK_ERR_INVALID below n_level, or for a level the table does not have).  _count_host: the pixel (col, row) of
+ * the full view under the rule above -- its count, the mag of the escaping step (0 for count 0) and the number of steps
+ * executed, a skip counting as one. */
+int mbk_deep_bla_info(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t *levels, uint64_t *entries);
+int mbk_deep_bla_read(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t level, double *A_r, double *A_i,
+                      double *B_r, double *B_i, double *rc, uint64_t n);
+int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                            int32_t *count, double *mag, uint64_t *steps_executed);
 
 /*
  * Distance estimates for deep views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes, and
@@ -490,7 +559,7 @@ typedef struct mbk_render_spec {
 /* Asynchronous, on the caller's stream: d_rgba is a DEVICE buffer of ncols * nrows * 4 bytes, and nothing is written outside
  * it.  `flags` carries kernel selection (and MBK_PRECISION_F32 for MBK_RENDER_BYTES) only, under the rules of the call that
  * makes the samples: MBK_RENDER_SMOOTH refuses MBK_KERNEL_SIMPLE / _REFILL / MBK_PRECISION_F32, a deep render refuses every
- * flag.  MBK_ERR_INVALID, with nothing written: a NULL spec / palette / output, an unknown source, s outside the set,
+ * flag but MBK_DEEP_BLA.  MBK_ERR_INVALID, with nothing written: a NULL spec / palette / output, an unknown source, s outside the set,
  * palette_len wrong for the source, scale / offset outside their ranges or not finite, W s or H s beyond what the sample call
  * accepts (the whole sample window is validated as one), any other flag, and whatever the sample call refuses.
  * _compute: synchronous into a HOST buffer on slot 0 (the slot-0 rule above applies); stats as for mbk_view_compute, over the
@@ -551,7 +620,7 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
  * accumulate into one table.  n == 0 is a no-op.
  * mbk_view_histogram_launch / mbk_deep_view_histogram_launch: the window's counts are produced by mbk_view_launch /
  * mbk_deep_view_launch into scratch the ctx keeps per stream (the renders' sample scratch), with the same kernel selection and
- * refusal rules: `flags` carries kernel selection and MBK_PRECISION_F32 for a plain view, nothing for a deep one.  4 bytes per
+ * refusal rules: `flags` carries kernel selection and MBK_PRECISION_F32 for a plain view, MBK_DEEP_BLA alone for a deep one.  4 bytes per
  * sample, banded under MBK_RENDER_BAND_BYTES exactly as a render bands, so no view size needs more scratch.  Each band's
  * counts are ADDED into d_hist.
  * _compute: synchronous on slot 0 (the slot-0 rule applies); h_hist is OVERWRITTEN, not accumulated; stats as for
