@@ -59,6 +59,12 @@ STREAM_REASONS = {MBK_STREAM_OK: "MBK_STREAM_OK", MBK_STREAM_BAD_CODEC: "MBK_STR
                   MBK_STREAM_ZERO_RUN: "MBK_STREAM_ZERO_RUN", MBK_STREAM_TOO_LONG: "MBK_STREAM_TOO_LONG",
                   MBK_STREAM_TOO_SHORT: "MBK_STREAM_TOO_SHORT"}
 CHUNK_SCALES = (1, 2, 4, 8, 16, 32, 64)
+# density views (include/mbk.h, "Density views")
+MBK_DENSITY_MAX_CELLS = 1 << 28
+MBK_DENSITY_LINEAR = 0
+MBK_DENSITY_SQRT = 1
+DENSITY_MODES = {"linear": MBK_DENSITY_LINEAR, "sqrt": MBK_DENSITY_SQRT}
+DENSITY_FACTORS = (1, 2, 4, 8)
 
 
 class mbk_view(C.Structure):
@@ -84,6 +90,20 @@ class mbk_render_spec(C.Structure):
 
 class mbk_chunk_spec(C.Structure):
     _fields_ = [("palette", C.c_void_p), ("scale", C.c_uint32)]
+
+
+class mbk_density_target(C.Structure):
+    _fields_ = [("start_r", C.c_double), ("start_i", C.c_double), ("range_r", C.c_double), ("range_i", C.c_double),
+                ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class mbk_density_stats(C.Structure):
+    _fields_ = [("deposits", C.c_uint64), ("dropped", C.c_uint64)]
+
+
+class mbk_density_render_spec(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("factor", C.c_uint32), ("palette", C.c_void_p), ("palette_len", C.c_uint32),
+                ("scale", C.c_double), ("offset", C.c_double)]
 
 
 class mbk_stats(C.Structure):
@@ -253,6 +273,21 @@ SIGNATURES = {
                                                    C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_julia_count_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double)]),
+    "mbk_view_density_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,
+                                          C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mbk_view_density_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(mbk_stats),
+                                           C.POINTER(mbk_density_stats)]),
+    "mbk_density_max": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]),
+    "mbk_density_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(mbk_density_render_spec),
+                                            C.c_void_p, C.c_void_p]),
+    "mbk_density_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(mbk_density_render_spec),
+                                             C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_density_cell_host": (C.c_int, [C.POINTER(mbk_density_target), C.c_double, C.c_double, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "mbk_density_accumulate_host": (C.c_int, [C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_void_p, C.POINTER(mbk_density_stats)]),
+    "mbk_density_resolve_host": (C.c_int, [C.POINTER(mbk_density_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_chunk_stream_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]),
     "mbk_chunk_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -33,6 +33,7 @@
 #include "mbk_distance.h"
 #include "mbk_deep_distance.h"
 #include "mbk_julia.h"
+#include "mbk_density.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -152,6 +153,9 @@ struct StreamScratch {
     double *d_lut = nullptr;
     size_t lut_cap = 0;               // entries
     std::vector<double> lut;          // what d_lut holds
+    // density views (mbk_density.h): the band totals and cursors of the compacted list (64 words), and mbk_density_max's result
+    uint32_t *d_density_bands = nullptr;
+    mbk::DensityMax *d_density_max = nullptr;
 };
 static const size_t kMaxStreamScratch = 64;
 static const uint32_t kStampSlots = 16, kShareRing = 64;
@@ -185,6 +189,9 @@ struct mbk_ctx {
     size_t rgba_cap_px = 0;
     unsigned long long *d_hist = nullptr;   // the table of the synchronous histograms (mbk_*_histogram_compute)
     size_t hist_cap = 0;             // bins
+    uint32_t *d_density = nullptr;   // the table of the synchronous density calls (mbk_view_density_compute, mbk_density_render_compute)
+    size_t density_cap = 0;          // cells
+    unsigned long long *d_density_stat = nullptr;   // ... and their deposits / dropped points (two words)
     uint8_t *d_rle = nullptr;        // RLE scratch: block counts | run starts | run values | output stream
     size_t rle_cap_px = 0;
     uint32_t opt[MBK_OPT_COUNT_];    // tuning options (mbk_set_option); every value is bit-exact
@@ -399,6 +406,8 @@ static void free_scratch(StreamScratch &sc)
     if (sc.h_chunk_status) (void)hipHostFree(sc.h_chunk_status);
     if (sc.d_dist_counts) (void)hipFree(sc.d_dist_counts);
     if (sc.d_lut) (void)hipFree(sc.d_lut);
+    if (sc.d_density_bands) (void)hipFree(sc.d_density_bands);
+    if (sc.d_density_max) (void)hipFree(sc.d_density_max);
     sc = StreamScratch();
 }
 
@@ -1677,6 +1686,8 @@ void mbk_destroy(mbk_ctx *ctx)
     if (ctx->d_smooth) (void)hipFree(ctx->d_smooth);
     if (ctx->d_rgba) (void)hipFree(ctx->d_rgba);
     if (ctx->d_hist) (void)hipFree(ctx->d_hist);
+    if (ctx->d_density) (void)hipFree(ctx->d_density);
+    if (ctx->d_density_stat) (void)hipFree(ctx->d_density_stat);
     delete ctx;
 }
 
@@ -3469,6 +3480,346 @@ int mbk_julia_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, double 
                                      uint64_t *h_hist, mbk_stats *stats)
 {
     return hist_compute(ctx, julia_target(view, c_r, c_i), mrd, flags, h_hist, stats);
+}
+
+// ---- density views (mbk_density.h; mbk.h "Density views") ------------------------------------------------------------
+
+// The target as the kernels take it, or what is wrong with it.  inv_* are the contract's fl(W / range_r), fl(H / range_i).
+static int density_target_check(mbk_ctx *ctx, const mbk_density_target *t, mbk::DensityTarget *out)
+{
+    if (!t) return fail(ctx, MBK_ERR_INVALID, "density target is NULL");
+    if (t->width == 0u || t->height == 0u || (uint64_t)t->width * t->height > MBK_DENSITY_MAX_CELLS)
+        return fail(ctx, MBK_ERR_INVALID, "density target must hold 1 .. 2^28 cells");
+    if (!std::isfinite(t->start_r) || !std::isfinite(t->start_i))
+        return fail(ctx, MBK_ERR_INVALID, "density target start must be finite");
+    if (!(t->range_r > 0.0) || !(t->range_i > 0.0) || !std::isfinite(t->range_r) || !std::isfinite(t->range_i))
+        return fail(ctx, MBK_ERR_INVALID, "density target ranges must be finite and > 0");
+    volatile double inv_r = (double)t->width / t->range_r;
+    volatile double inv_i = (double)t->height / t->range_i;
+    out->start_r = t->start_r;
+    out->start_i = t->start_i;
+    out->inv_r = inv_r;
+    out->inv_i = inv_i;
+    out->w = (double)t->width;
+    out->h = (double)t->height;
+    out->width = t->width;
+    out->height = t->height;
+    return MBK_OK;
+}
+
+// Everything a density launch can refuse, before anything is allocated, enqueued or written.  *minc .. *maxc: the counts that
+// qualify, after the max_count == 0 substitution (with mrd < 2 no count is above 0 and the interval does not matter).
+static int density_check(mbk_ctx *ctx, const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                         uint32_t max_count, uint32_t flags, mbk::DensityTarget *dt, int32_t *minc, int32_t *maxc)
+{
+    if (flags & ~MBK_KERNEL_MASK)
+        return fail(ctx, MBK_ERR_INVALID, "density flags carry kernel selection only (no fp32, no MBK_LAZY_UNIFORM, no MBK_DEEP_BLA)");
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
+    if (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL)
+        return fail(ctx, MBK_ERR_INVALID, "density views take their counts from the scan / asm / group kernels only");
+    bool dummy;
+    int rc = validate_view(ctx, view, &dummy);
+    if (rc != MBK_OK) return rc;
+    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (min_count == 0u) return fail(ctx, MBK_ERR_INVALID, "min_count must be at least 1 (a sample that never escapes deposits nothing)");
+    uint32_t hi = max_count;
+    if (mrd >= 2u) {
+        if (max_count >= mrd) return fail(ctx, MBK_ERR_INVALID, "max_count must be below mrd");
+        if (hi == 0u) hi = mrd - 1u;
+    }
+    if (hi != 0u && min_count > hi) return fail(ctx, MBK_ERR_INVALID, "min_count exceeds max_count");
+    rc = density_target_check(ctx, target, dt);
+    if (rc != MBK_OK) return rc;
+    *minc = (int32_t)std::min<uint32_t>(min_count, 0x7fffffffu);
+    *maxc = (int32_t)std::min<uint32_t>(hi ? hi : 0x7fffffffu, 0x7fffffffu);
+    return MBK_OK;
+}
+
+// A checked density launch (density_check) added into the device table, on `stream`: the window's counts band by band through
+// the stream's render scratch (4 bytes per sample, 8 with the compacted list; at most MBK_RENDER_BAND_BYTES: the bands of
+// hist_run), each band replayed into the table.  d_stat: two device words for deposits / dropped points, or NULL.  stat as for
+// render_run: its reduction scratch adds up the statistics of the samples, its ev_k1 marks the last replay kernel.
+static int density_run(mbk_ctx *ctx, const mbk_view *v, const mbk::DensityTarget &dt, uint32_t mrd, int32_t minc, int32_t maxc,
+                       uint32_t kernel, uint32_t *d_table, unsigned long long *d_stat, hipStream_t stream, Slot *stat)
+{
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    const uint64_t per_px = mbk::kDensityCompact ? 8u : 4u;
+    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;
+    uint32_t tile_cols = v->ncols, band_rows;
+    if ((uint64_t)v->ncols * per_px <= budget) {
+        band_rows = (uint32_t)std::min<uint64_t>(v->nrows, budget / ((uint64_t)v->ncols * per_px));
+    } else {
+        band_rows = 1u;
+        tile_cols = (uint32_t)(budget / per_px);
+    }
+    const size_t cap = (size_t)tile_cols * band_rows;
+    const size_t off2 = round_up_256(cap * 4u);
+    const size_t need = mbk::kDensityCompact ? off2 + cap * 4u : cap * 4u;
+    rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
+    if (rc != MBK_OK) return rc;
+    if (mbk::kDensityCompact && !sc->d_density_bands)
+        MBK_HIP(ctx, hipMalloc((void **)&sc->d_density_bands, 2u * mbk::kDensityBands * sizeof(uint32_t)));
+    // (sc may move when a launch below adds a stream's scratch: not used past here)
+    int32_t *d_counts = (int32_t *)sc->d_render;
+    uint32_t *d_list = mbk::kDensityCompact ? (uint32_t *)((uint8_t *)sc->d_render + off2) : nullptr;
+    uint32_t *d_bands = sc->d_density_bands;
+    for (uint32_t r = 0; r < v->nrows; r += band_rows) {
+        const uint32_t nr = std::min(band_rows, v->nrows - r);
+        for (uint32_t c = 0; c < v->ncols; c += tile_cols) {
+            const uint32_t nc = std::min(tile_cols, v->ncols - c);
+            mbk_view sv = *v;
+            sv.col0 = v->col0 + c;
+            sv.row0 = v->row0 + r;
+            sv.ncols = nc;
+            sv.nrows = nr;
+            rc = launch_tile(ctx, &sv, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+            if (rc != MBK_OK) return rc;
+            if (mbk::kDensityCompact) MBK_HIP(ctx, hipMemsetAsync(d_bands, 0, 2u * mbk::kDensityBands * sizeof(uint32_t), stream));
+            mbk::DensityArgs a;
+            std::memset(&a, 0, sizeof(a));
+            fill_window(a, &sv);
+            a.min_count = minc;
+            a.max_count = maxc;
+            a.t = dt;
+            a.counts = d_counts;
+            a.table = d_table;
+            a.stat = d_stat;
+            a.list = d_list;
+            a.bands = d_bands;
+            mbk::launch_density_replay(a, stream);
+            MBK_HIP(ctx, hipGetLastError());
+            if (stat) {
+                if (r + nr == v->nrows && c + nc == v->ncols) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
+                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, (uint64_t)nc * nr, mrd, stream, false);
+                if (rc != MBK_OK) return rc;
+            }
+        }
+    }
+    return MBK_OK;
+}
+
+int mbk_view_density_launch(mbk_ctx *ctx, const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                            uint32_t max_count, uint32_t flags, uint32_t *d_density, void *hip_stream)
+{
+    if (!ctx || !d_density) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    mbk::DensityTarget dt;
+    int32_t minc, maxc;
+    int rc = density_check(ctx, view, target, mrd, min_count, max_count, flags, &dt, &minc, &maxc);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_density & 3u) return fail(ctx, MBK_ERR_INVALID, "d_density must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return density_run(ctx, view, dt, mrd, minc, maxc, flags & MBK_KERNEL_MASK, d_density, nullptr, (hipStream_t)hip_stream, nullptr);
+}
+
+int mbk_view_density_compute(mbk_ctx *ctx, const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                             uint32_t max_count, uint32_t flags, uint32_t *h_density, mbk_stats *stats, mbk_density_stats *dstats)
+{
+    if (!ctx || !h_density) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    mbk::DensityTarget dt;
+    int32_t minc, maxc;
+    int rc = density_check(ctx, view, target, mrd, min_count, max_count, flags, &dt, &minc, &maxc);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    Slot &sl = ctx->s[0];
+    const size_t cells = (size_t)dt.width * dt.height;
+    unsigned long long h_stat[2] = {0ull, 0ull};
+    auto enqueue = [&]() -> int {
+        int rc = grow(ctx, ctx->d_density, ctx->density_cap, cells, cells * sizeof(uint32_t));
+        if (rc != MBK_OK) return rc;
+        if (!ctx->d_density_stat) MBK_HIP(ctx, hipMalloc((void **)&ctx->d_density_stat, 2u * sizeof(unsigned long long)));
+        MBK_HIP(ctx, hipMemsetAsync(ctx->d_density, 0, cells * sizeof(uint32_t), sl.stream));
+        MBK_HIP(ctx, hipMemsetAsync(ctx->d_density_stat, 0, 2u * sizeof(unsigned long long), sl.stream));
+        MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+        rc = density_run(ctx, view, dt, mrd, minc, maxc, flags & MBK_KERNEL_MASK, ctx->d_density, ctx->d_density_stat, sl.stream, &sl);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_density, ctx->d_density, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_stat, ctx->d_density_stat, sizeof(h_stat), hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    rc = sync_end(ctx, enqueue(), stats, false);
+    if (rc == MBK_OK && dstats) {
+        dstats->deposits = h_stat[0];
+        dstats->dropped = h_stat[1];
+    }
+    return rc;
+}
+
+int mbk_density_max(mbk_ctx *ctx, const uint32_t *d_density, uint64_t n, uint32_t *max, uint64_t *total, void *hip_stream)
+{
+    if (!ctx || !max || !total || (!d_density && n)) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    if ((uintptr_t)d_density & 3u) return fail(ctx, MBK_ERR_INVALID, "d_density must be 4-byte aligned");
+    *max = 0u;
+    *total = 0ull;
+    if (n == 0) return MBK_OK;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, s, &sc);
+    if (rc != MBK_OK) return rc;
+    if (!sc->d_density_max) MBK_HIP(ctx, hipMalloc((void **)&sc->d_density_max, sizeof(mbk::DensityMax)));
+    MBK_HIP(ctx, hipMemsetAsync(sc->d_density_max, 0, sizeof(mbk::DensityMax), s));
+    const uint64_t blocks = std::min<uint64_t>((n + mbk::kDensityThreads - 1u) / mbk::kDensityThreads,
+                                               (uint64_t)std::max(ctx->prop.multiProcessorCount, 1) * 8u);
+    hipLaunchKernelGGL(mbk::density_max_kernel, dim3((uint32_t)blocks), dim3(mbk::kDensityThreads), 0, s, d_density, n, sc->d_density_max);
+    MBK_HIP(ctx, hipGetLastError());
+    mbk::DensityMax h = {};
+    MBK_HIP(ctx, hipMemcpyAsync(&h, sc->d_density_max, sizeof(h), hipMemcpyDeviceToHost, s));
+    MBK_HIP(ctx, hipStreamSynchronize(s));
+    *max = h.max;
+    *total = h.total;
+    return MBK_OK;
+}
+
+// Everything a density render can refuse, before anything is allocated, enqueued or written.
+static int density_render_check(mbk_ctx *ctx, const mbk_density_render_spec *spec, uint32_t width, uint32_t height, const void *table,
+                                const void *out)
+{
+    if (!spec) return fail(ctx, MBK_ERR_INVALID, "density render spec is NULL");
+    if (!spec->palette) return fail(ctx, MBK_ERR_INVALID, "palette is NULL");
+    if (!table || !out) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    if (spec->mode != MBK_DENSITY_LINEAR && spec->mode != MBK_DENSITY_SQRT) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_DENSITY_* mode");
+    const uint32_t k = spec->factor;
+    if (k != 1u && k != 2u && k != 4u && k != 8u) return fail(ctx, MBK_ERR_INVALID, "factor must be 1, 2, 4 or 8");
+    if (spec->palette_len < 2u || spec->palette_len > 65536u) return fail(ctx, MBK_ERR_INVALID, "a density render takes a palette of 2 .. 65536 entries");
+    if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p80)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^80]");
+    if (!(std::fabs(spec->offset) <= 0x1p20)) return fail(ctx, MBK_ERR_INVALID, "offset must lie in [-2^20, 2^20]");
+    if (width == 0u || height == 0u || (uint64_t)width * height > MBK_DENSITY_MAX_CELLS)
+        return fail(ctx, MBK_ERR_INVALID, "a density table holds 1 .. 2^28 cells");
+    if (width % k || height % k) return fail(ctx, MBK_ERR_INVALID, "width and height must be multiples of factor");
+    return MBK_OK;
+}
+
+static mbk::RenderPalette density_palette(const mbk_density_render_spec *spec, const uint32_t *entries)
+{
+    mbk::RenderPalette p;
+    std::memset(&p, 0, sizeof(p));
+    p.entries = entries;
+    p.n = spec->palette_len;
+    p.n_rcp = 1.0 / (double)spec->palette_len;
+    p.scale = spec->scale;
+    p.offset = spec->offset;
+    return p;
+}
+
+// A checked density render of the device table onto the device image d_out ((height / k) x (width / k) words), on `stream`.
+static int density_render_run(mbk_ctx *ctx, const uint32_t *d_table, uint32_t width, uint32_t height, const mbk_density_render_spec *spec,
+                              uint32_t *d_out, hipStream_t stream)
+{
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    rc = stream_palette(ctx, sc, stream, spec->palette, spec->palette_len);
+    if (rc != MBK_OK) return rc;
+    mbk::DensityResolveArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.table = d_table;
+    a.out = d_out;
+    a.width = width;
+    a.out_w = width / spec->factor;
+    a.out_h = height / spec->factor;
+    a.root = spec->mode == MBK_DENSITY_SQRT ? 1u : 0u;
+    a.pal = density_palette(spec, sc->d_palette);
+    const uint64_t px = (uint64_t)a.out_w * a.out_h;
+    const uint64_t blocks = std::min<uint64_t>((px + mbk::kDensityThreads - 1u) / mbk::kDensityThreads,
+                                               (uint64_t)std::max(ctx->prop.multiProcessorCount, 1) * 8u);
+    mbk::launch_density_resolve(spec->factor, dim3((uint32_t)blocks), stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_density_render_launch(mbk_ctx *ctx, const uint32_t *d_density, uint32_t width, uint32_t height,
+                              const mbk_density_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = density_render_check(ctx, spec, width, height, d_density, d_rgba);
+    if (rc != MBK_OK) return rc;
+    if (((uintptr_t)d_density & 3u) || ((uintptr_t)d_rgba & 3u)) return fail(ctx, MBK_ERR_INVALID, "d_density and d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return density_render_run(ctx, d_density, width, height, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream);
+}
+
+int mbk_density_render_compute(mbk_ctx *ctx, const uint32_t *h_density, uint32_t width, uint32_t height,
+                               const mbk_density_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = density_render_check(ctx, spec, width, height, h_density, h_rgba);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    Slot &sl = ctx->s[0];
+    const size_t cells = (size_t)width * height, px = cells / ((size_t)spec->factor * spec->factor);
+    auto enqueue = [&]() -> int {
+        int rc = grow(ctx, ctx->d_density, ctx->density_cap, cells, cells * sizeof(uint32_t));
+        if (rc == MBK_OK) rc = grow(ctx, ctx->d_rgba, ctx->rgba_cap_px, px, px * sizeof(uint32_t));
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipMemcpyAsync(ctx->d_density, h_density, cells * sizeof(uint32_t), hipMemcpyHostToDevice, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+        rc = density_render_run(ctx, ctx->d_density, width, height, spec, ctx->d_rgba, sl.stream);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k1, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    return sync_end(ctx, enqueue(), stats, false, false);
+}
+
+int mbk_density_cell_host(const mbk_density_target *target, double z_r, double z_i, uint32_t *cell_x, uint32_t *cell_y, int *inside)
+{
+    if (!cell_x || !cell_y || !inside) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::DensityTarget dt;
+    int rc = density_target_check(nullptr, target, &dt);
+    if (rc != MBK_OK) return rc;
+    uint32_t cx = 0u, cy = 0u;
+    *inside = mbk::density_cell(dt, z_r, z_i, &cx, &cy) ? 1 : 0;
+    *cell_x = cx;
+    *cell_y = cy;
+    return MBK_OK;
+}
+
+int mbk_density_accumulate_host(const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                                uint32_t max_count, uint32_t *density, mbk_density_stats *dstats)
+{
+    if (!density) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::DensityTarget dt;
+    int32_t minc, maxc;
+    int rc = density_check(nullptr, view, target, mrd, min_count, max_count, 0u, &dt, &minc, &maxc);
+    if (rc != MBK_OK) return rc;
+    const Axis re = make_axis(view->start_r, view->range_r, view->width), im = make_axis(view->start_i, view->range_i, view->height);
+    std::vector<double> cr(view->ncols), ci(view->nrows);
+    for (uint32_t c = 0; c < view->ncols; ++c) cr[c] = axis_value_host(re, view->col0 + c);
+    for (uint32_t r = 0; r < view->nrows; ++r) ci[r] = axis_value_host(im, view->row0 + r);
+    std::vector<int32_t> counts((size_t)view->ncols * view->nrows);
+    for (uint32_t r = 0; r < view->nrows; ++r)
+        for (uint32_t c = 0; c < view->ncols; ++c) {
+            double m;
+            counts[(size_t)r * view->ncols + c] = mbk::julia_count<false>(cr[c], ci[r], cr[c], ci[r], (int32_t)mrd, &m);
+        }
+    uint64_t deposits = 0, dropped = 0;
+    mbk::density_accumulate_host(cr.data(), ci.data(), view->ncols, view->nrows, counts.data(), minc, maxc, dt, density, &deposits, &dropped);
+    if (dstats) {
+        dstats->deposits = deposits;
+        dstats->dropped = dropped;
+    }
+    return MBK_OK;
+}
+
+int mbk_density_resolve_host(const mbk_density_render_spec *spec, uint32_t width, uint32_t height, const uint32_t *density, uint8_t *rgba)
+{
+    int rc = density_render_check(nullptr, spec, width, height, density, rgba);
+    if (rc != MBK_OK) return rc;
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    mbk::density_resolve_host(density_palette(spec, words.data()), spec->mode == MBK_DENSITY_SQRT, spec->factor, width, height, density, rgba);
+    return MBK_OK;
 }
 
 // ---- the native worker loop (mbk_feeder.h) ----------------------------------------------------------------

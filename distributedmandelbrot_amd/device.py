@@ -83,6 +83,28 @@ class DeepView:
             object.__setattr__(self, "span_i", float(si))
 
 
+@dataclass(frozen=True)
+class DensityTarget:
+    """The target of a density view (include/mbk.h, "Density views"): the rectangle [start_r, start_r + range_r) x
+    [start_i, start_i + range_i) cut into width x height half-open cells; the table is uint32[height, width], row 0 the
+    lowest imaginary part."""
+    start_r: float
+    start_i: float
+    range_r: float
+    range_i: float
+    width: int
+    height: int
+
+    def ctarget(self) -> L.mbk_density_target:
+        return L.mbk_density_target(self.start_r, self.start_i, self.range_r, self.range_i, self.width, self.height)
+
+
+@dataclass
+class DensityStats:
+    deposits: int   # orbit points that landed in a cell
+    dropped: int    # orbit points of qualifying samples that fell outside the target
+
+
 def _decimal_string(x, precision_bits: int) -> str:
     """An exact decimal for str / Decimal / int / float; for a Fraction with no finite decimal form, enough digits that
     the truncation to precision_bits fraction bits is the same as that of the Fraction itself."""
@@ -195,6 +217,31 @@ def julia_count_host(z, c, mrd: int) -> Tuple[int, float]:
     n, mag = C.c_int32(0), C.c_double(0.0)
     _check(lib, lib.mbk_julia_count_host(float(z[0]), float(z[1]), float(c[0]), float(c[1]), mrd, C.byref(n), C.byref(mag)))
     return int(n.value), float(mag.value)
+
+
+def density_cell_host(target: DensityTarget, z) -> Optional[Tuple[int, int]]:
+    """mbk_density_cell_host: the cell (x, y) of the point z = (z_r, z_i) in `target`, or None when it falls outside."""
+    lib = L.load()
+    ct = target.ctarget()
+    cx, cy, inside = C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+    _check(lib, lib.mbk_density_cell_host(C.byref(ct), float(z[0]), float(z[1]), C.byref(cx), C.byref(cy), C.byref(inside)))
+    return (int(cx.value), int(cy.value)) if inside.value else None
+
+
+def density_host(view: View, target: DensityTarget, mrd: int, *, min_count: int = 1, max_count: int = 0, window=None,
+                 out: Optional[np.ndarray] = None):
+    """mbk_density_accumulate_host: the density table of a view / window on the host, one orbit at a time, without a device --
+    the functions the kernels are compiled from.  ADDED into `out` (uint32[height, width]; None: zeros).
+    Returns (table, DensityStats)."""
+    lib = L.load()
+    cv = MandelbrotDevice._cview(view, window)
+    ct = target.ctarget()
+    shape = (max(int(target.height), 0), max(int(target.width), 0))
+    table = np.zeros(shape, np.uint32) if out is None else _out_array(out, shape, np.uint32)
+    ds = L.mbk_density_stats()
+    _check(lib, lib.mbk_density_accumulate_host(C.byref(cv), C.byref(ct), mrd, min_count, max_count,
+                                                table.ctypes.data if table.size else None, C.byref(ds)))
+    return table.reshape(shape), DensityStats(int(ds.deposits), int(ds.dropped))
 
 
 def _stream_array(stream) -> np.ndarray:
@@ -666,6 +713,61 @@ class MandelbrotDevice:
         """Asynchronous: the histogram of n int32 counts in DEVICE memory is ADDED into the DEVICE table d_hist (uint64[mrd])
         on ``stream``; counts outside [0, mrd - 1] are skipped.  The sibling of reduce_counts."""
         self._check(self._lib.mbk_counts_histogram(self._h, d_counts or None, n, mrd, d_hist or None, stream or None))
+
+    # -- density views (include/mbk.h, "Density views") -------------------------------------------------
+    def compute_view_density(self, view: View, target: DensityTarget, mrd: int, *, min_count: int = 1, max_count: int = 0,
+                             window=None, kernel: str = "default", out: Optional[np.ndarray] = None):
+        """The Buddhabrot density of the view's samples: every sample whose count n lies in [min_count, max_count]
+        (max_count 0: mrd - 1) deposits its n orbit points z_0 .. z_(n-1) into the cells of `target`.  Synchronous; only the
+        table crosses PCIe.  Returns (table uint32[height, width] -- overwritten, not accumulated --, TileStats over the
+        samples, DensityStats)."""
+        cv = self._cview(view, window)
+        ct = target.ctarget()
+        shape = (max(int(target.height), 0), max(int(target.width), 0))
+        table = _out_array(out, shape, np.uint32)
+        st, ds = L.mbk_stats(), L.mbk_density_stats()
+        self._check(self._lib.mbk_view_density_compute(self._h, C.byref(cv), C.byref(ct), mrd, min_count, max_count, L.KERNELS[kernel],
+                                                       table.ctypes.data if table.size else None, C.byref(st), C.byref(ds)))
+        return table.reshape(shape), _stats(st), DensityStats(int(ds.deposits), int(ds.dropped))
+
+    def launch_view_density(self, view: View, target: DensityTarget, mrd: int, *, d_density: int, min_count: int = 1,
+                            max_count: int = 0, stream: int = 0, window=None, kernel: str = "default") -> None:
+        """Asynchronous form: the window's deposits are ADDED into the DEVICE table d_density (uint32[height * width]; the
+        caller clears it) on ``stream`` (0 = HIP's null stream), so that windows, bands and launches accumulate."""
+        cv = self._cview(view, window)
+        ct = target.ctarget()
+        self._check(self._lib.mbk_view_density_launch(self._h, C.byref(cv), C.byref(ct), mrd, min_count, max_count, L.KERNELS[kernel],
+                                                      d_density or None, stream or None))
+
+    def density_max(self, d_density: int, n: int, stream: int = 0) -> Tuple[int, int]:
+        """(max, total) of n cells of a DEVICE table, reduced on the GPU on ``stream`` (the call waits for that stream)."""
+        mx, total = C.c_uint32(0), C.c_uint64(0)
+        self._check(self._lib.mbk_density_max(self._h, d_density or None, n, C.byref(mx), C.byref(total), stream or None))
+        return int(mx.value), int(total.value)
+
+    def render_density(self, table: np.ndarray, *, palette, mode: str = "sqrt", factor: int = 1, out: Optional[np.ndarray] = None):
+        """A HOST density table (uint32[height, width]) as an RGBA8 image of (height / factor, width / factor) pixels, coloured
+        (image.Palette.for_density) and box-filtered on the GPU.  Returns (rgba uint8[h, w, 4], TileStats)."""
+        t = np.ascontiguousarray(table, dtype=np.uint32)
+        if t.ndim != 2:
+            raise ValueError("a density table is a (height, width) uint32 array")
+        h, w = t.shape
+        k = int(factor) if factor in L.DENSITY_FACTORS else 1   # (a bad factor is refused by the library)
+        shape = (h // k, w // k, 4)
+        rgba = _out_array(out, shape, np.uint8).reshape(shape)
+        spec = palette.density_spec(mode, factor)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_density_render_compute(self._h, t.ctypes.data if t.size else None, w, h, C.byref(spec),
+                                                         rgba.ctypes.data if rgba.size else None, C.byref(st)))
+        return rgba, _stats(st)
+
+    def launch_render_density(self, d_density: int, width: int, height: int, *, palette, d_rgba: int, mode: str = "sqrt",
+                              factor: int = 1, stream: int = 0) -> None:
+        """Asynchronous render of a DEVICE table into a DEVICE image of (height / factor) * (width / factor) * 4 bytes on
+        ``stream`` (0 = HIP's null stream)."""
+        spec = palette.density_spec(mode, factor)
+        self._check(self._lib.mbk_density_render_launch(self._h, d_density or None, width, height, C.byref(spec), d_rgba or None,
+                                                        stream or None))
 
     # -- Julia views (include/mbk.h, "Julia views") ---------------------------------------------------
     def compute_julia_view(self, view: View, c, mrd: int, *, window=None, want_counts: bool = True, want_bytes: bool = True,

@@ -119,6 +119,27 @@ class Palette:
         equal shares of the escaped samples take equal stretches of the palette."""
         return Palette(self.entries, self.inside, float(len(self) - 1), 0.0)
 
+    def for_density(self, max_value: float, mode: str = "sqrt") -> "Palette":
+        """This palette stretched over a density table whose largest cell is `max_value` (MandelbrotDevice.density_max), for
+        render_density with the same `mode`: scale = (n - 1) / g(max_value), offset = 0, so that g(max_value) reaches the last
+        entry (g(v) = sqrt(v) for "sqrt", v for "linear").  The scale is nudged up by ulps where rounding would leave
+        fl(g scale) just below n - 1."""
+        if mode not in L.DENSITY_MODES:
+            raise ValueError("mode must be 'sqrt' or 'linear'")
+        if not max_value >= 1:
+            raise ValueError("max_value must be at least 1")
+        g = float(np.sqrt(np.float64(max_value))) if mode == "sqrt" else float(max_value)
+        last = float(len(self) - 1)
+        scale = last / g
+        while g * scale < last:
+            scale = float(np.nextafter(scale, np.inf))
+        return Palette(self.entries, self.inside, scale, 0.0)
+
+    def density_spec(self, mode: str, factor: int) -> L.mbk_density_render_spec:
+        """The C struct of a density render; it points into self.entries, which the caller keeps alive for the call."""
+        return L.mbk_density_render_spec(L.DENSITY_MODES[mode], int(factor), self.entries.ctypes.data, len(self),
+                                         float(self.scale), float(self.offset))
+
     @staticmethod
     def _ramp(near, far, n: int) -> np.ndarray:
         x = np.arange(n, dtype=np.float64)[:, None] / (n - 1)
@@ -188,6 +209,24 @@ def resolve_host(palette: Palette, source: str, supersample: int, width: int, he
                                                    out.ctypes.data)
     else:
         st = lib.mbk_render_resolve_host(C.byref(spec), width, height, *ptrs, out.ctypes.data)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return out
+
+
+def resolve_density_host(palette: Palette, table, *, mode: str = "sqrt", factor: int = 1) -> np.ndarray:
+    """mbk_density_resolve_host: a density table (uint32[height, width]) coloured and box-filtered on the host -- the same code
+    the kernel is compiled from, without a device."""
+    lib = L.load()
+    t = np.ascontiguousarray(table, dtype=np.uint32)
+    if t.ndim != 2:
+        raise ValueError("a density table is a (height, width) uint32 array")
+    h, w = t.shape
+    k = int(factor) if factor in L.DENSITY_FACTORS else 1
+    out = np.empty((h // k, w // k, 4), np.uint8)
+    spec = palette.density_spec(mode, factor)
+    st = lib.mbk_density_resolve_host(C.byref(spec), w, h, t.ctypes.data if t.size else None, out.ctypes.data if out.size else None)
     if st != L.MBK_OK:
         from .device import MbkError
         raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())

@@ -185,6 +185,55 @@ def render_julia_view(devices: Sequence, view, c, mrd: int, *, band_rows: int = 
                          submit, compute, "submit_julia_view")
 
 
+def accumulate_view_density(devices: Sequence, view, target, mrd: int, *, min_count: int = 1, max_count: int = 0,
+                            band_rows: int = 128, kernel: str = "default") -> Tuple[np.ndarray, List[dict]]:
+    """The density table (include/mbk.h, "Density views") of a whole sample view on several GPUs of this process: one host
+    thread per device pulls row bands of the SAMPLE view from a shared WorkQueue and adds each band's table
+    (compute_view_density on the band's window) to that device's own uint64 table; the per-device tables are then summed on
+    the host in uint64 and checked against 2^32 -- tables add, so bands, launches and GPUs sum to the whole view's table.
+    Returns (table uint32[height, width], per-device stats with deposits and dropped points).  OverflowError if a cell of
+    the sum does not fit 32 bits (a single GPU would have wrapped it silently)."""
+    queue = WorkQueue(make_bands(view.height, band_rows))
+    shape = (target.height, target.width)
+    tables = [np.zeros(shape, np.uint64) for _ in devices]
+    per_dev = [{"bands": 0, "pixel_iterations": 0, "kernel_ms": 0.0, "deposits": 0, "dropped": 0} for _ in devices]
+    errors: List[BaseException] = []
+
+    def feeder(slot: int) -> None:
+        dev = devices[slot]
+        try:
+            scratch = np.empty(shape, np.uint32)
+            while True:
+                band = queue.pop()
+                if band is None:
+                    return
+                table, st, ds = dev.compute_view_density(view, target, mrd, min_count=min_count, max_count=max_count,
+                                                         window=(0, band.row0, view.width, band.nrows), kernel=kernel, out=scratch)
+                tables[slot] += table
+                d = per_dev[slot]
+                d["bands"] += 1
+                d["pixel_iterations"] += st.pixel_iterations
+                d["kernel_ms"] += st.kernel_ms
+                d["deposits"] += ds.deposits
+                d["dropped"] += ds.dropped
+        except BaseException as e:
+            errors.append(e)
+
+    threads = [threading.Thread(target=feeder, args=(i,), daemon=True) for i in range(len(devices))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        raise errors[0]
+    total = np.zeros(shape, np.uint64)
+    for t in tables:
+        total += t
+    if total.size and int(total.max()) >= 1 << 32:
+        raise OverflowError("a cell of the summed density table does not fit 32 bits")
+    return total.astype(np.uint32), per_dev
+
+
 def _render_bands(devices, width, height, band_rows, want_counts, want_bytes, out_counts, out_bytes, submit, compute,
                   submit_name):
     """The feeder loop of render_view / render_deep_view / render_julia_view: submit(dev, slot, window, out_counts, out_bytes) + dev.wait(slot)

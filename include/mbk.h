@@ -752,6 +752,105 @@ int mbk_julia_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, double 
                                      uint64_t *h_hist, mbk_stats *stats);
 int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, double *mag);
 
+/*
+ * Density views (Buddhabrot / Nebulabrot).  NOT in the reference; additive (the ABI version stays 5): no existing call changes.
+ * Every picture above colours a pixel by what happened to that pixel's own orbit.  A density view instead counts where the
+ * orbits of the escaping samples GO: each orbit point adds one to the cell of a 2-D table it falls into.  The orbit points
+ * never leave the kernels, so this is the one picture a caller cannot assemble from the other calls' outputs.
+ *
+ * Contract (exact; tests/density_model.py restates it in numpy, tests/test_density.py and tests/test_gpu_density.py hold the
+ * host twins and the GPU to it):
+ *   samples   the pixels of an mbk_view, the sample view, window semantics as everywhere: the coordinates are those of
+ *             mbk_view_launch, bit for bit, and so is the count n of each sample (mrd as usual).  A sample QUALIFIES when
+ *             min_count <= n <= max_count, with 1 <= min_count and max_count == 0 meaning mrd - 1.  n = 0 (the sample never
+ *             escapes) never qualifies.
+ *   deposits  a qualifying sample deposits its orbit points z_0 = c, z_1, ..., z_(n-1): n points, all those before the step that
+ *             tripped `>= 4`.  The points are the reference's recurrence in binary64, every operation rounded on its own, in its
+ *             literal form:  zr' = fl(fl(fl(zr zr) - fl(zi zi)) + c_r),  zi' = fl(fl(fl(2 zr) zi) + c_i).  z_0 may lie anywhere
+ *             (a sample far outside |c| = 2 has n = 1 and deposits c alone).
+ *   target    a second rectangle (start_r, start_i, range_r, range_i) cut into width x height CELLS, W, H >= 1,
+ *             W H <= MBK_DENSITY_MAX_CELLS, starts finite, ranges finite and > 0.  Cells are half-open; they are not linspace
+ *             samples.  With inv_r = fl(W / range_r) and inv_i = fl(H / range_i), computed once, the cell of a point is, in
+ *             binary64 with every operation rounded on its own:
+ *               tx = fl(fl(zr - start_r) inv_r),  ty = fl(fl(zi - start_i) inv_i);
+ *               the point lands in cell (floor(tx), floor(ty)) iff 0 <= tx < W and 0 <= ty < H, otherwise it is DROPPED.
+ *             The comparisons are false for NaN (and an inv_* that overflowed drops or keeps a point as IEEE arithmetic says).
+ *             A point exactly on the right or the top edge is outside.  Row 0 is the lowest imaginary part.
+ *   table     uint32[H][W] on the device, cell (x, y) at word y W + x.  A launch ADDS to it, modulo 2^32; the caller clears it,
+ *             as for mbk_counts_histogram.  Integer sums: the table is exact whatever the schedule, and windows and bands of the
+ *             sample view, several launches and several GPUs sum to the whole view's table.  Nothing is ever written outside
+ *             the W H words.
+ *   mrd       0 and 1 run no step: nothing is deposited (max_count == 0 is accepted and stands for "every escaped sample").
+ *
+ * mbk_view_density_launch: asynchronous, on the caller's stream; d_density is a DEVICE table, 4-byte aligned.  `flags` carries
+ * kernel selection for the count pass only.  Two passes, like the default distance path: the window's counts come from
+ * mbk_view_launch with that selector, cycle test and all (for a density view the interior samples are pure waste, and the count
+ * kernels retire them for nearly nothing), into the sample scratch the ctx keeps per stream -- 4 bytes per sample, banded under
+ * MBK_RENDER_BAND_BYTES exactly as a histogram bands; then a replay kernel (csrc/mbk_density.h) runs each qualifying sample for
+ * exactly n steps without a bailout test and issues one 32-bit global atomic add per point inside the target.
+ * mbk_view_density_compute: synchronous on slot 0 (the slot-0 rule applies); h_density (W H words) is OVERWRITTEN, not accumulated;
+ * stats (may be NULL) as for mbk_view_compute without bytes, over the samples (kernel_ms from the first count kernel to the last
+ * replay kernel, d2h_ms the copy of the table); dstats (may be NULL): the points deposited and the points dropped, which add up
+ * to the sum of n over the qualifying samples -- when every escaped sample qualifies,
+ * pixel_iterations - (mrd - 1) never_pixels.
+ * mbk_density_max: a device reduction over n cells of a DEVICE table on the caller's stream, then a wait for that stream: the
+ * largest cell and the sum of all cells, so that a caller can choose a scale without copying the table.  n == 0 gives 0, 0.
+ * mbk_density_render_launch / _compute: a table of width x height cells as an RGBA8 image of (width / k) x (height / k) pixels
+ * through the caller's palette.  A cell v becomes g(v) = v (MBK_DENSITY_LINEAR) or g(v) = fl(sqrt(v)) (MBK_DENSITY_SQRT; v is
+ * exact in binary64 and the square root correctly rounded, so g is the same on the host and on the device), then
+ * t = fl(fl(g scale) + offset) and a colour by the MBK_RENDER_DISTANCE rule: no wrap, the last entry from t >= n - 1 up, t = 0
+ * unless 0 <= t; 2 <= palette_len <= 65536, 0 < scale <= 2^80, |offset| <= 2^20.  factor k in {1, 2, 4, 8} is a box filter over
+ * k x k cells, applied to the colours with the "resolve" rule of the Rendering section; width and height must be multiples of k.
+ * _launch reads a DEVICE table and writes a DEVICE image on the caller's stream (both 4-byte aligned); the palette upload
+ * follows the renders' wait-on-change rule.  _compute takes a HOST table, uploads it, and returns the image in a HOST buffer,
+ * synchronously on slot 0; stats: kernel_ms of the resolve, d2h_ms of the image, the other fields 0.
+ * The _host forms need no ctx and no device; they are compiled from the functions the kernels use.  mbk_density_cell_host: one
+ * point -> *inside = 1 and its cell, or *inside = 0.  mbk_density_accumulate_host: the whole contract for a view / window, ADDED
+ * into density (one orbit at a time: for the CPU tests, small views only).  mbk_density_resolve_host: the render.
+ * MBK_ERR_INVALID, with nothing written: NULL pointers (stats and dstats excepted); a misaligned device table or image;
+ * min_count == 0; min_count > max_count after the max_count == 0 substitution; max_count >= mrd when mrd >= 2; mrd >= 2^31; a
+ * target or a render spec outside the limits above; any flag but kernel selection (MBK_PRECISION_F32, MBK_LAZY_UNIFORM,
+ * MBK_DEEP_BLA, MBK_WANT_*); the kernels mbk_view_launch_smooth refuses (MBK_KERNEL_SIMPLE, MBK_KERNEL_REFILL); and whatever
+ * mbk_view_launch refuses in a view.
+ *
+ * Out of scope: deep, Julia and fp32 forms; the anti-Buddhabrot (orbits of the samples that never escape); random or jittered
+ * sampling; the z -> conj(z) symmetry; fusing the deposits into the count kernels; 64-bit tables; an equalised colouring of
+ * densities.
+ */
+#define MBK_DENSITY_MAX_CELLS (1u << 28)
+#define MBK_DENSITY_LINEAR 0u
+#define MBK_DENSITY_SQRT 1u
+typedef struct mbk_density_target {
+    double start_r, start_i;
+    double range_r, range_i;
+    uint32_t width, height;
+} mbk_density_target;
+typedef struct mbk_density_stats {
+    uint64_t deposits; /* orbit points that landed in a cell */
+    uint64_t dropped;  /* orbit points of qualifying samples that fell outside the target */
+} mbk_density_stats;
+typedef struct mbk_density_render_spec {
+    uint32_t mode;          /* MBK_DENSITY_LINEAR | MBK_DENSITY_SQRT */
+    uint32_t factor;        /* k: 1, 2, 4, 8 */
+    const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
+    uint32_t palette_len;
+    double scale, offset;
+} mbk_density_render_spec;
+int mbk_view_density_launch(mbk_ctx *ctx, const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                            uint32_t max_count, uint32_t flags, uint32_t *d_density, void *hip_stream);
+int mbk_view_density_compute(mbk_ctx *ctx, const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                             uint32_t max_count, uint32_t flags, uint32_t *h_density, mbk_stats *stats, mbk_density_stats *dstats);
+int mbk_density_max(mbk_ctx *ctx, const uint32_t *d_density, uint64_t n, uint32_t *max, uint64_t *total, void *hip_stream);
+int mbk_density_render_launch(mbk_ctx *ctx, const uint32_t *d_density, uint32_t width, uint32_t height,
+                              const mbk_density_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_density_render_compute(mbk_ctx *ctx, const uint32_t *h_density, uint32_t width, uint32_t height,
+                               const mbk_density_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+int mbk_density_cell_host(const mbk_density_target *target, double z_r, double z_i, uint32_t *cell_x, uint32_t *cell_y, int *inside);
+int mbk_density_accumulate_host(const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,
+                                uint32_t max_count, uint32_t *density, mbk_density_stats *dstats);
+int mbk_density_resolve_host(const mbk_density_render_spec *spec, uint32_t width, uint32_t height, const uint32_t *density,
+                             uint8_t *rgba);
+
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
 #define MBK_CODEC_RLE 0x01u
