@@ -82,6 +82,13 @@ class mbk_deep_view(C.Structure):
                 ("ncols", C.c_uint32), ("nrows", C.c_uint32)]
 
 
+class mbk_deep_xview(C.Structure):
+    _fields_ = [("range_r", C.c_double), ("range_i", C.c_double), ("exp2", C.c_int32),
+                ("width", C.c_uint32), ("height", C.c_uint32),
+                ("col0", C.c_uint32), ("row0", C.c_uint32),
+                ("ncols", C.c_uint32), ("nrows", C.c_uint32)]
+
+
 class mbk_render_spec(C.Structure):
     _fields_ = [("source", C.c_uint32), ("supersample", C.c_uint32), ("palette", C.c_void_p),
                 ("palette_len", C.c_uint32), ("inside", C.c_uint8 * 4),
@@ -216,6 +223,29 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_uint64]),
     "mbk_deep_bla_count_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "mbk_deep_orbit_read_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mbk_deep_xview_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_submit": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                        C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_count_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "mbk_deep_xview_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                               C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_render_equalized_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                         C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32, C.c_void_p,
+                                                         C.c_void_p]),
+    "mbk_deep_xview_render_equalized_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32,
+                                                          C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p, C.c_uint32,
+                                                          C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_histogram_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_histogram_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                   C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_view_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
                                          C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
     "mbk_view_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,

@@ -27,6 +27,7 @@
 #include "mbk_deep_orbit.h"
 #include "mbk_deep.h"
 #include "mbk_deep_bla.h"
+#include "mbk_deep_wide.h"
 #include "mbk_histogram.h"
 #include "mbk_render.h"
 #include "mbk_chunks.h"
@@ -209,10 +210,12 @@ struct mbk_ctx {
     double probe_share = 0.0;
     bool probe_valid = false;
     // deep-zoom views: this ctx's device copies of the orbits it has used, by orbit id (deep_copy)
-    // beside each, the bilinear-approximation table of the last dcmax it was launched with (MBK_DEEP_BLA; bla_copy)
+    // beside each, the bilinear-approximation table of the last dcmax it was launched with (MBK_DEEP_BLA; bla_copy) and the
+    // wide table, once a wide view has been launched on the orbit (wide_copy)
     struct DeepCopy {
         uint64_t id;
         double4 *d;
+        mbk::WideEntry *d_wide;
         bool has_bla;
         uint64_t dcmax_bits;
         double *d_rc;
@@ -385,6 +388,7 @@ static void free_deep_copy(mbk_ctx::DeepCopy &c)
     if (c.d) (void)hipFree(c.d);
     if (c.d_rc) (void)hipFree(c.d_rc);
     if (c.d_ab) (void)hipFree(c.d_ab);
+    if (c.d_wide) (void)hipFree(c.d_wide);
     c = mbk_ctx::DeepCopy();
 }
 
@@ -2338,6 +2342,19 @@ int mbk_deep_orbit_read(const mbk_deep_orbit *orbit, double *zr, double *zi, uin
     return MBK_OK;
 }
 
+int mbk_deep_orbit_read_wide(const mbk_deep_orbit *orbit, double *xr, double *xi, int32_t *xe, uint64_t n)
+{
+    if (!orbit || !xr || !xi || !xe) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    const uint64_t entries = (uint64_t)orbit->o.length + 1u;
+    if (n < entries) return fail(nullptr, MBK_ERR_INVALID, "the output holds fewer than length + 1 entries");
+    for (uint64_t k = 0; k < entries; ++k) {
+        xr[k] = orbit->o.wide[k].xr;
+        xi[k] = orbit->o.wide[k].xi;
+        xe[k] = orbit->o.wide[k].xe;
+    }
+    return MBK_OK;
+}
+
 static const size_t kMaxDeepCopies = 8;
 
 // This ctx's device copy of `orbit`, uploaded on first use.  A copy is never overwritten, and none is freed while a launch
@@ -2611,6 +2628,142 @@ int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *vi
     return MBK_OK;
 }
 
+// ---- extended-range deep views (mbk_deep_wide.h; mbk.h "Extended-range deep views") ----------------------------------------
+
+// This ctx's device copy of `orbit` (deep_copy) with the wide table beside it, uploaded on the orbit's first wide launch here.
+// Like the copy itself it is never overwritten and is freed with it.
+static int wide_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideEntry **out)
+{
+    const double4 *d_orbit = nullptr;
+    int rc = deep_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk_ctx::DeepCopy *c = nullptr;
+    for (mbk_ctx::DeepCopy &k : ctx->deep)
+        if (k.id == orbit->o.id) c = &k;
+    if (!c->d_wide) {
+        const size_t bytes = orbit->o.wide.size() * sizeof(mbk::WideEntry);
+        mbk::WideEntry *d = nullptr;
+        MBK_HIP(ctx, hipMalloc((void **)&d, bytes));
+        const hipError_t e = hipMemcpy(d, orbit->o.wide.data(), bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return fail(ctx, MBK_ERR_HIP, std::string("hipMemcpy (wide reference orbit): ") + hipGetErrorString(e));
+        }
+        c->d_wide = d;
+    }
+    *out = c->d_wide;
+    return MBK_OK;
+}
+
+static int validate_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd, uint32_t flags)
+{
+    if (!orbit) return fail(ctx, MBK_ERR_INVALID, "orbit is NULL");
+    if (!v) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
+    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES))
+        return fail(ctx, MBK_ERR_INVALID, "extended-range deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
+    if (v->width == 0 || v->height == 0) return fail(ctx, MBK_ERR_INVALID, "empty view");
+    if (v->ncols == 0 || v->nrows == 0) return fail(ctx, MBK_ERR_INVALID, "empty window");
+    if ((uint64_t)v->col0 + v->ncols > v->width || (uint64_t)v->row0 + v->nrows > v->height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    if ((uint64_t)v->ncols * v->nrows > (1ull << 31)) return fail(ctx, MBK_ERR_INVALID, "window larger than 2^31 pixels");
+    for (double r : {v->range_r, v->range_i})
+        if (!std::isfinite(r) || !(r >= 0x1p-64) || !(r <= 4.0))
+            return fail(ctx, MBK_ERR_INVALID, "extended-range deep view ranges must be finite and lie in [2^-64, 4]");
+    if (v->exp2 > 0 || v->exp2 < -8192) return fail(ctx, MBK_ERR_INVALID, "extended-range deep view exp2 must lie in [-8192, 0]");
+    if (mrd > orbit->o.mrd) return fail(ctx, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    return MBK_OK;
+}
+
+// the wide kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd,
+                            int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+{
+    const mbk::WideEntry *d_orbit = nullptr;
+    int rc = wide_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepWideArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.orbit = d_orbit;
+    a.z1 = orbit->o.wide[1];
+    a.M = orbit->o.length;
+    a.exp2 = v->exp2;
+    a.half_r = (double)(v->width - 1u) * 0.5;
+    a.half_i = (double)(v->height - 1u) * 0.5;
+    a.step_r = deep_step(v->range_r, v->width);
+    a.step_i = deep_step(v->range_i, v->height);
+    a.col0 = v->col0;
+    a.row0 = v->row0;
+    a.ncols = v->ncols;
+    a.nrows = v->nrows;
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
+    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
+    a.counts = d_counts;
+    a.bytes = d_bytes;
+    a.smooth = d_smooth;
+    const uint32_t blocks = a.blocks_x * ((v->nrows + 7u) / 8u);
+    hipLaunchKernelGGL(mbk::deep_wide_kernel, dim3(blocks), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_deep_xview_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_deep_wide(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
+    if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
+    rc = check_wanted(ctx, flags, d_counts, d_bytes);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_deep_wide(ctx, orbit, view, mrd, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
+                            (hipStream_t)hip_stream);
+}
+
+int mbk_deep_xview_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_deep_wide(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
+                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                            return launch_deep_wide(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
+                        });
+}
+
+int mbk_deep_xview_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
+    int rc = validate_deep_wide(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
+                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                           return launch_deep_wide(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
+                       });
+}
+
+// host twin of the wide step (mbk_deep_wide.h): no ctx, no device
+int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                              int32_t *count, double *mag)
+{
+    if (!count || !mag) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
+    if (rc != MBK_OK) return rc;
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    volatile double dcr = ((double)col - (double)(view->width - 1u) * 0.5) * deep_step(view->range_r, view->width);
+    volatile double dci = ((double)row - (double)(view->height - 1u) * 0.5) * deep_step(view->range_i, view->height);
+    mbk::wide_count_host(orbit->o.wide, orbit->o.length, dcr, dci, view->exp2, (int64_t)mrd, count, mag);
+    return MBK_OK;
+}
+
 // ---- distance estimates for deep views (mbk_deep_distance.h; mbk.h "Distance estimates for deep views") ----------------
 
 // the deep distance kernel on device pointers (validated by the caller), on `stream`
@@ -2880,7 +3033,8 @@ static int stream_lut(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const
     return MBK_OK;
 }
 
-// What a render renders: a view (deep == nullptr), a deep view on its orbit, or the Julia set of (c_r, c_i) on a view (julia).
+// What a render renders: a view (deep == nullptr), a deep view on its orbit, the Julia set of (c_r, c_i) on a view (julia), or an
+// extended-range deep view on its orbit (wide).
 struct RenderTarget {
     const mbk_view *view;
     const mbk_deep_orbit *orbit;
@@ -2888,18 +3042,24 @@ struct RenderTarget {
     uint32_t width, height, col0, row0, ncols, nrows;   // of the OUTPUT
     bool julia;
     double c_r, c_i;
+    const mbk_deep_xview *wide;   // an extended-range deep view on `orbit`
 };
 
-// The targets of the three kinds of view.  A NULL view makes a target of neither kind, which render_check refuses in its turn.
+// The targets of the four kinds of view.  A NULL view makes a target of neither kind, which render_check refuses in its turn.
 static RenderTarget view_target(const mbk_view *v)
 {
     if (!v) return RenderTarget{};
-    return RenderTarget{v, nullptr, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0};
+    return RenderTarget{v, nullptr, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0, nullptr};
 }
 static RenderTarget deep_target(const mbk_deep_orbit *orbit, const mbk_deep_view *v)
 {
     if (!v) return RenderTarget{};
-    return RenderTarget{nullptr, orbit, v, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0};
+    return RenderTarget{nullptr, orbit, v, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0, nullptr};
+}
+static RenderTarget wide_target(const mbk_deep_orbit *orbit, const mbk_deep_xview *v)
+{
+    if (!v) return RenderTarget{};
+    return RenderTarget{nullptr, orbit, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0, v};
 }
 static RenderTarget julia_target(const mbk_view *v, double c_r, double c_i)
 {
@@ -2912,9 +3072,17 @@ static RenderTarget julia_target(const mbk_view *v, double c_r, double c_i)
 
 // The sample view / window of the output window (col0, row0, ncols, nrows) of `t`
 static void sample_window(const RenderTarget &t, uint32_t s, uint32_t col0, uint32_t row0, uint32_t ncols, uint32_t nrows,
-                          mbk_view *v, mbk_deep_view *d)
+                          mbk_view *v, mbk_deep_view *d, mbk_deep_xview *x)
 {
-    if (t.deep) {
+    if (t.wide) {
+        *x = *t.wide;
+        x->width = t.width * s;
+        x->height = t.height * s;
+        x->col0 = col0 * s;
+        x->row0 = row0 * s;
+        x->ncols = ncols * s;
+        x->nrows = nrows * s;
+    } else if (t.deep) {
         *d = *t.deep;
         d->width = t.width * s;
         d->height = t.height * s;
@@ -2940,7 +3108,7 @@ static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint3
     int rc = validate_render_spec(ctx, spec, equalized);
     if (rc != MBK_OK) return rc;
     if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!t.view && !t.deep) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if (!t.view && !t.deep && !t.wide) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     const uint32_t s = spec->supersample;
     if ((uint64_t)t.width * s > 0xffffffffull || (uint64_t)t.height * s > 0xffffffffull)
         return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
@@ -2951,7 +3119,15 @@ static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint3
     const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel || equalized;   // (the distance samples obey the smooth launch's rules)
     mbk_view sv;
     mbk_deep_view sd;
-    sample_window(t, s, t.col0, t.row0, t.ncols, t.nrows, &sv, &sd);
+    mbk_deep_xview sx;
+    sample_window(t, s, t.col0, t.row0, t.ncols, t.nrows, &sv, &sd, &sx);
+    if (t.wide) {
+        if (dist || rel) return fail(ctx, MBK_ERR_INVALID, "distance estimates are not implemented for extended-range deep views");
+        if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep renders take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)");
+        rc = validate_deep_wide(ctx, t.orbit, &sx, mrd, smooth ? 0u : MBK_WANT_BYTES);
+        if (rc != MBK_OK || !equalized) return rc;
+        return validate_lut(ctx, h_lut, lut_len, mrd);
+    }
     if (t.deep) {
         if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)");
         if (flags & ~MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep renders take MBK_DEEP_BLA only (no kernel selection, no fp32)");
@@ -3043,8 +3219,11 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
             const uint32_t nc = std::min(tile_cols, t.ncols - c);
             mbk_view sv;
             mbk_deep_view sd;
-            sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
-            if (t.deep) {
+            mbk_deep_xview sx;
+            sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd, &sx);
+            if (t.wide) {
+                rc = launch_deep_wide(ctx, t.orbit, &sx, mrd, d_counts, d_bytes, d_nu, stream);
+            } else if (t.deep) {
                 rc = rel ? launch_deep_distance(ctx, t.orbit, &sd, mrd, d_counts, d_nu, stream)
                          : launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream, (flags & MBK_DEEP_BLA) != 0);
             } else if (t.julia) {
@@ -3182,6 +3361,32 @@ int mbk_deep_view_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *o
                                            uint8_t *h_rgba, mbk_stats *stats)
 {
     return render_compute(ctx, deep_target(orbit, view), mrd, flags, spec, h_rgba, stats, true, h_lut, lut_len);
+}
+
+int mbk_deep_xview_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, wide_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream);
+}
+
+int mbk_deep_xview_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, wide_target(orbit, view), mrd, flags, spec, h_rgba, stats);
+}
+
+int mbk_deep_xview_render_equalized_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                           uint8_t *d_rgba, void *hip_stream)
+{
+    return render_launch(ctx, wide_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream, true, h_lut, lut_len);
+}
+
+int mbk_deep_xview_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                            uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                            uint8_t *h_rgba, mbk_stats *stats)
+{
+    return render_compute(ctx, wide_target(orbit, view), mrd, flags, spec, h_rgba, stats, true, h_lut, lut_len);
 }
 
 int mbk_julia_view_render_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
@@ -3340,9 +3545,13 @@ int mbk_counts_histogram(mbk_ctx *ctx, const int32_t *d_counts, uint64_t n, uint
 static int hist_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const void *out)
 {
     if (!out) return fail(ctx, MBK_ERR_INVALID, "histogram pointer is NULL");
-    if (!t.view && !t.deep) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if (!t.view && !t.deep && !t.wide) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     int rc = check_hist_mrd(ctx, mrd);
     if (rc != MBK_OK) return rc;
+    if (t.wide) {
+        if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep histograms take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)");
+        return validate_deep_wide(ctx, t.orbit, t.wide, mrd, MBK_WANT_COUNTS);
+    }
     if (t.deep) {
         if (flags & ~MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep histograms take MBK_DEEP_BLA only (no kernel selection, no fp32)");
         return validate_deep(ctx, t.orbit, t.deep, mrd, MBK_WANT_COUNTS | flags);
@@ -3393,8 +3602,11 @@ static int hist_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t 
             const uint32_t nc = std::min(tile_cols, t.ncols - c);
             mbk_view sv;
             mbk_deep_view sd;
-            sample_window(t, 1u, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd);
-            if (t.deep)
+            mbk_deep_xview sx;
+            sample_window(t, 1u, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd, &sx);
+            if (t.wide)
+                rc = launch_deep_wide(ctx, t.orbit, &sx, mrd, d_counts, nullptr, nullptr, stream);
+            else if (t.deep)
                 rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, nullptr, nullptr, stream, (flags & MBK_DEEP_BLA) != 0);
             else if (t.julia)
                 rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, nullptr, nullptr, stream);
@@ -3468,6 +3680,18 @@ int mbk_deep_view_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, c
                                     uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
 {
     return hist_compute(ctx, deep_target(orbit, view), mrd, flags, h_hist, stats);
+}
+
+int mbk_deep_xview_histogram_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                    uint32_t flags, uint64_t *d_hist, void *hip_stream)
+{
+    return hist_launch(ctx, wide_target(orbit, view), mrd, flags, d_hist, hip_stream);
+}
+
+int mbk_deep_xview_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                     uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
+{
+    return hist_compute(ctx, wide_target(orbit, view), mrd, flags, h_hist, stats);
 }
 
 int mbk_julia_view_histogram_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,

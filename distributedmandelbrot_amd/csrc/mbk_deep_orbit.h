@@ -8,7 +8,8 @@
 //   product  trunc(a * b / 2^P): magnitudes multiplied, shifted right by P, sign restored (truncation toward zero)
 //   orbit    Z_0 = 0, Z_{k+1} = (sr - si + Cr, 2 t + Ci) with sr = trunc(Zr Zr), si = trunc(Zi Zi), t = trunc(Zr Zi);
 //            stop at the first M with trunc(Zr Zr) + trunc(Zi Zi) >= 4 (of Z_M), or at M = mrd; each Z_k rounded to
-//            nearest-even binary64 (subnormals included)
+//            nearest-even binary64 (subnormals included), and beside it as a binary64 mantissa pair with one int32 exponent
+//            (the wide table: no Z_k but 0 itself is lost to the exponent range)
 #pragma once
 
 #include <stdint.h>
@@ -91,13 +92,22 @@ inline bool fx_ge_int(const Fixed &a, uint64_t k)
     return a.back() >= k;   // integer part >= k, the fraction is >= 0
 }
 
+// the bit length of |X| (0 for X = 0)
+inline int fx_bit_length(const Fixed &a)
+{
+    Fixed m = a;
+    if (fx_negative(m)) fx_negate(m);
+    for (int k = (int)m.size() - 1; k >= 0; --k)
+        if (m[k]) return 64 * k + (64 - __builtin_clzll(m[k]));
+    return 0;
+}
+
 // X / 2^P rounded to nearest binary64, ties to even (a subnormal result rounds once, on its own grid)
-inline double fx_to_double(const Fixed &a)
+inline double fx_round(const Fixed &a, int P)
 {
     Fixed m = a;
     const bool neg = fx_negative(m);
     if (neg) fx_negate(m);
-    const int P = 64 * ((int)m.size() - 1);
     int h = 0;   // bit length of |X|
     for (int k = (int)m.size() - 1; k >= 0; --k)
         if (m[k]) {
@@ -124,6 +134,9 @@ inline double fx_to_double(const Fixed &a)
     const double r = std::ldexp((double)q, s - P);   // q <= 2^53 on its grid: exact
     return neg ? -r : r;
 }
+
+// the number itself: X / 2^P with P = 64 (n - 1)
+inline double fx_to_double(const Fixed &a) { return fx_round(a, 64 * ((int)a.size() - 1)); }
 
 // ---- decimal parser ----
 
@@ -220,6 +233,27 @@ inline bool fx_parse(const char *s, uint32_t P, Fixed *out, std::string *why)
 
 // ---- the orbit ----
 
+// One entry of the wide table (mbk.h, "Extended-range deep views"): Z = (xr, xi) 2^xe, the larger |component| in [0.5, 1] (1 when it
+// rounds up); a zero Z is (0, 0, kWideZeroExp).  32 bytes, the form the device reads.
+constexpr int32_t kWideZeroExp = -(1 << 24);
+struct alignas(32) WideEntry {
+    double xr, xi;
+    int32_t xe;
+    int32_t pad[3];
+};
+static_assert(sizeof(WideEntry) == 32, "the wide table is 32 bytes per entry");
+
+// xe = the bit length of the larger |component| minus P (its frexp exponent); the components over 2^(P + xe), each rounded by
+// fx_round -- the smaller one may land in the subnormal range and then rounds once, on that grid.
+inline WideEntry fx_to_wide(const Fixed &zr, const Fixed &zi)
+{
+    const int P = 64 * ((int)zr.size() - 1);
+    const int hr = fx_bit_length(zr), hi = fx_bit_length(zi);
+    const int H = hr > hi ? hr : hi;
+    if (H == 0) return WideEntry{0.0, 0.0, kWideZeroExp, {0, 0, 0}};
+    return WideEntry{fx_round(zr, H), fx_round(zi, H), H - P, {0, 0, 0}};
+}
+
 struct DeepOrbit {
     uint64_t id;                 // never reused: the key of each ctx's device copy
     uint32_t precision_bits;     // P
@@ -227,6 +261,7 @@ struct DeepOrbit {
     uint32_t length;             // M
     uint32_t escaped;            // 1 iff |Z_M|^2 >= 4
     std::vector<double> table;   // (Zr, Zi, 2 Zr, 2 Zi) for k = 0 .. M: the 32 bytes per entry the kernel reads
+    std::vector<WideEntry> wide; // Z_k = (xr, xi) 2^xe for k = 0 .. M: what the wide kernel reads (mbk_deep_wide.h)
 };
 
 inline uint64_t next_orbit_id()
@@ -253,6 +288,7 @@ inline bool build_deep_orbit(const char *cr, const char *ci, uint32_t P, uint32_
     o->mrd = mrd;
     o->escaped = 0u;
     o->table.assign(4, 0.0);   // Z_0 = 0
+    o->wide.assign(1, WideEntry{0.0, 0.0, kWideZeroExp, {0, 0, 0}});
     uint32_t k = 0;
     while (true) {
         const Fixed sr = fx_mul(zr, zr), si = fx_mul(zi, zi), t = fx_mul(zr, zi);
@@ -269,6 +305,7 @@ inline bool build_deep_orbit(const char *cr, const char *ci, uint32_t P, uint32_
         o->table.push_back(di);
         o->table.push_back(dr + dr);
         o->table.push_back(di + di);
+        o->wide.push_back(fx_to_wide(zr, zi));
     }
     o->length = k;
     o->id = next_orbit_id();

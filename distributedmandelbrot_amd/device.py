@@ -84,6 +84,44 @@ class DeepView:
 
 
 @dataclass(frozen=True)
+class WideDeepView:
+    """An extended-range deep view (include/mbk.h, "Extended-range deep views"): spans range_r 2^exp2 x range_i 2^exp2 with
+    range_* in [2^-64, 4] and exp2 in [-8192, 0], so a span far below binary64's 1e-308 can be named.  range_i defaults to
+    square pixels, as for DeepView."""
+    range_r: float
+    exp2: int
+    width: int
+    height: Optional[int] = None
+    range_i: Optional[float] = None
+
+    def __post_init__(self):
+        h = self.width if self.height is None else int(self.height)
+        object.__setattr__(self, "height", h)
+        object.__setattr__(self, "exp2", int(self.exp2))
+        if self.range_i is None:
+            ri = self.range_r if (self.width <= 1 or h <= 1 or h == self.width) else self.range_r * (h - 1) / (self.width - 1)
+            object.__setattr__(self, "range_i", float(ri))
+
+    @staticmethod
+    def from_decimal(span: Union[str, Decimal, Fraction, int, float], width: int, height: Optional[int] = None):
+        """The view whose real span is the decimal `span` ("1e-600"): converted exactly, exp2 = floor(log2 span) clamped to [-8192, 0], and
+        the mantissa span / 2^exp2 rounded once, to the nearest binary64."""
+        f = Fraction(Decimal(span)) if isinstance(span, str) else Fraction(span)
+        if f <= 0:
+            raise ValueError("the span must be > 0")
+        e = f.numerator.bit_length() - f.denominator.bit_length()      # floor(log2 f) is e or e - 1
+        if Fraction(2) ** e > f:
+            e -= 1
+        exp2 = max(min(e, 0), -8192)
+        return WideDeepView((f.numerator << -exp2) / f.denominator, exp2, width, height)
+
+    @property
+    def min_span_exp2(self) -> int:
+        """floor(log2) of the smaller span: what DeepOrbit(min_span_exp2=...) takes."""
+        return self.exp2 + math.frexp(min(self.range_r, self.range_i))[1] - 1
+
+
+@dataclass(frozen=True)
 class DensityTarget:
     """The target of a density view (include/mbk.h, "Density views"): the rectangle [start_r, start_r + range_r) x
     [start_i, start_i + range_i) cut into width x height half-open cells; the table is uint32[height, width], row 0 the
@@ -133,8 +171,13 @@ def _decimal_string(x, precision_bits: int) -> str:
     raise TypeError("a centre coordinate must be str, Decimal, Fraction, int or float")
 
 
-def default_precision_bits(min_span: Optional[float]) -> int:
-    """64 + ceil(-log2 min_span), rounded up to a multiple of 64 (min_span None: 2^-960, the deepest span a view takes)."""
+def default_precision_bits(min_span: Optional[float], min_span_exp2: Optional[int] = None) -> int:
+    """64 + ceil(-log2 min_span), rounded up to a multiple of 64 (min_span None: 2^-960, the deepest span a view takes).
+    min_span_exp2: the span as a power of two, 2^min_span_exp2, for spans a float cannot hold (WideDeepView.min_span_exp2)."""
+    if min_span_exp2 is not None:
+        if min_span is not None:
+            raise ValueError("give min_span or min_span_exp2, not both")
+        return min(4096, max(64, -(-(64 + max(0, -int(min_span_exp2))) // 64) * 64))
     span = 2.0 ** -960 if min_span is None else float(min_span)
     if not (span > 0.0 and math.isfinite(span)):
         raise ValueError("min_span must be finite and > 0")
@@ -147,10 +190,11 @@ class DeepOrbit:
     precision_bits fraction bits, up to mrd; needs no GPU.  Read-only; any MandelbrotDevice may use it."""
 
     def __init__(self, center_r: Union[str, Decimal, Fraction, int, float], center_i: Union[str, Decimal, Fraction, int, float],
-                 mrd: int, *, min_span: Optional[float] = None, precision_bits: Optional[int] = None):
+                 mrd: int, *, min_span: Optional[float] = None, precision_bits: Optional[int] = None,
+                 min_span_exp2: Optional[int] = None):
         self._lib = L.load()
         self._h = None
-        bits = int(precision_bits) if precision_bits is not None else default_precision_bits(min_span)
+        bits = int(precision_bits) if precision_bits is not None else default_precision_bits(min_span, min_span_exp2)
         self.center = (_decimal_string(center_r, bits), _decimal_string(center_i, bits))
         h = C.c_void_p()
         st = self._lib.mbk_deep_orbit_create(self.center[0].encode(), self.center[1].encode(), bits, int(mrd), C.byref(h))
@@ -169,6 +213,14 @@ class DeepOrbit:
         zi = np.empty(self.length + 1, np.float64)
         self._check(self._lib.mbk_deep_orbit_read(self._h, zr.ctypes.data, zi.ctypes.data, zr.size))
         return zr, zi
+
+    def wide_table(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(X_r float64, X_i float64, xe int32): Z_0 .. Z_M of the wide table, Z_m = X 2^xe (a zero Z: (0, 0, -2^24))."""
+        xr = np.empty(self.length + 1, np.float64)
+        xi = np.empty(self.length + 1, np.float64)
+        xe = np.empty(self.length + 1, np.int32)
+        self._check(self._lib.mbk_deep_orbit_read_wide(self._h, xr.ctypes.data, xi.ctypes.data, xe.ctypes.data, xr.size))
+        return xr, xi, xe
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -521,10 +573,24 @@ class MandelbrotDevice:
                                               d_counts or None, d_bytes or None, stream or None))
 
     # -- deep-zoom views (include/mbk.h, "Deep-zoom views") ------------------------------------
+    # Every method below takes a DeepView or a WideDeepView ("Extended-range deep views"): the wide view goes to the
+    # mbk_deep_xview_* call of the same name, which has no bilinear approximation and no distance estimate.
     @staticmethod
-    def _cdeep(view: DeepView, window) -> L.mbk_deep_view:
+    def _cdeep(view: Union[DeepView, WideDeepView], window):
         col0, row0, ncols, nrows = window if window is not None else (0, 0, view.width, view.height)
+        if isinstance(view, WideDeepView):
+            return L.mbk_deep_xview(view.range_r, view.range_i, view.exp2, view.width, view.height, col0, row0, ncols, nrows)
         return L.mbk_deep_view(view.span_r, view.span_i, view.width, view.height, col0, row0, ncols, nrows)
+
+    def _deep_fn(self, view, name: str, bla: bool = False, source: Optional[str] = None):
+        """(the C entry point `name` for this kind of deep view, its flags)"""
+        if isinstance(view, WideDeepView):
+            if bla:
+                raise ValueError("bla=True is not implemented for a WideDeepView")
+            if source in ("distance", "distance_rel"):
+                raise ValueError("distance estimates are not implemented for a WideDeepView")
+            return getattr(self._lib, "mbk_deep_xview_" + name), 0
+        return getattr(self._lib, "mbk_deep_view_" + name), (L.MBK_DEEP_BLA if bla else 0)
 
     def compute_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_counts: bool = True,
                           want_bytes: bool = True, want_smooth: bool = False, out_counts: Optional[np.ndarray] = None,
@@ -539,10 +605,10 @@ class MandelbrotDevice:
         byts = _out_array(out_bytes, shape, np.uint8) if want_bytes else None
         smooth = np.empty(shape, np.float64) if want_smooth else None
         flags, p_counts, p_bytes = _wanted(shape, counts, byts)
-        flags |= L.MBK_DEEP_BLA if bla else 0
+        fn, extra = self._deep_fn(view, "compute", bla)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_compute(self._h, orbit._h, C.byref(cv), mrd, flags, p_counts, p_bytes,
-                                                    smooth.ctypes.data if smooth is not None else None, C.byref(st)))
+        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags | extra, p_counts, p_bytes,
+                       smooth.ctypes.data if smooth is not None else None, C.byref(st)))
         return counts, byts, smooth, _stats(st)
 
     def submit_deep_view(self, slot: int, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None,
@@ -551,23 +617,25 @@ class MandelbrotDevice:
         """Enqueue a deep view / window on `slot`; the host arrays are valid after wait(slot)."""
         cv = self._cdeep(view, window)
         flags, p_counts, p_bytes = _wanted((cv.nrows, cv.ncols), out_counts, out_bytes)
-        flags |= L.MBK_DEEP_BLA if bla else 0
-        self._check(self._lib.mbk_deep_view_submit(self._h, slot, orbit._h, C.byref(cv), mrd, flags, p_counts, p_bytes))
+        fn, extra = self._deep_fn(view, "submit", bla)
+        self._check(fn(self._h, slot, orbit._h, C.byref(cv), mrd, flags | extra, p_counts, p_bytes))
 
     def launch_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_counts: int = 0, d_bytes: int = 0,
                          d_smooth: int = 0, stream: int = 0, window=None, bla: bool = False) -> None:
         """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream).  With bla the first launch of a
         view's spans on an orbit builds and uploads the table synchronously."""
         cv = self._cdeep(view, window)
-        flags = (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0) | (L.MBK_DEEP_BLA if bla else 0)
-        self._check(self._lib.mbk_deep_view_launch(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None,
-                                                   d_bytes or None, d_smooth or None, stream or None))
+        fn, extra = self._deep_fn(view, "launch", bla)
+        flags = (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0) | extra
+        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None, d_bytes or None, d_smooth or None,
+                       stream or None))
 
     def compute_deep_view_distance(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None):
         """Exterior distance estimates of a deep view (include/mbk.h, "Distance estimates for deep views"): the derivative is
         carried as D 2^e, so it cannot overflow however deep the view, and the value is rel = de / span_r, the distance as a
         fraction of the view's real span (rel * (width - 1) is the distance in pixels); 0 for never-escaped pixels.  The counts
         are those of compute_deep_view.  Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
+        self._deep_fn(view, "compute_distance", source="distance_rel")   # (a WideDeepView has no distance estimate)
         cv = self._cdeep(view, window)
         shape = (cv.nrows, cv.ncols)
         rel = np.empty(shape, np.float64)
@@ -580,6 +648,7 @@ class MandelbrotDevice:
     def launch_deep_view_distance(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
                                   stream: int = 0, window=None) -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
+        self._deep_fn(view, "launch_distance", source="distance_rel")
         cv = self._cdeep(view, window)
         self._check(self._lib.mbk_deep_view_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
                                                             d_rel or None, stream or None))
@@ -632,14 +701,14 @@ class MandelbrotDevice:
         rgba = self._render_out(cv, out)
         spec = palette.spec(source, supersample, max_band_rows)
         st = L.mbk_stats()
-        flags = L.MBK_DEEP_BLA if bla else 0
         if source == "equalized":
+            fn, flags = self._deep_fn(view, "render_equalized_compute", bla, source)
             lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla))
-            self._check(self._lib.mbk_deep_view_render_equalized_compute(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
-                                                                         lut.ctypes.data, lut.size, rgba.ctypes.data, C.byref(st)))
+            self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), lut.ctypes.data, lut.size, rgba.ctypes.data,
+                           C.byref(st)))
         else:
-            self._check(self._lib.mbk_deep_view_render_compute(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
-                                                               rgba.ctypes.data, C.byref(st)))
+            fn, flags = self._deep_fn(view, "render_compute", bla, source)
+            self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), rgba.ctypes.data, C.byref(st)))
         return rgba, _stats(st)
 
     def launch_render_view(self, view: View, mrd: int, *, palette, d_rgba: int, source: str = "smooth", supersample: int = 1,
@@ -662,15 +731,14 @@ class MandelbrotDevice:
                                 max_band_rows: int = 0, lut=None, bla: bool = False) -> None:
         cv = self._cdeep(view, window)
         spec = palette.spec(source, supersample, max_band_rows)
-        flags = L.MBK_DEEP_BLA if bla else 0
         if source == "equalized":
+            fn, flags = self._deep_fn(view, "render_equalized_launch", bla, source)
             lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla))
-            self._check(self._lib.mbk_deep_view_render_equalized_launch(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
-                                                                        lut.ctypes.data, lut.size, d_rgba or None,
-                                                                        stream or None))
+            self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), lut.ctypes.data, lut.size, d_rgba or None,
+                           stream or None))
             return
-        self._check(self._lib.mbk_deep_view_render_launch(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec),
-                                                          d_rgba or None, stream or None))
+        fn, flags = self._deep_fn(view, "render_launch", bla, source)
+        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), d_rgba or None, stream or None))
 
     # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
     def view_histogram(self, view: View, mrd: int, *, window=None, kernel: str = "default", precision: str = "f64",
@@ -691,8 +759,8 @@ class MandelbrotDevice:
         cv = self._cdeep(view, window)
         hist = np.empty(max(int(mrd), 0), np.uint64)
         st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_histogram_compute(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_BLA if bla else 0,
-                                                              hist.ctypes.data if hist.size else None, C.byref(st)))
+        fn, flags = self._deep_fn(view, "histogram_compute", bla)
+        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, hist.ctypes.data if hist.size else None, C.byref(st)))
         return (hist, _stats(st)) if want_stats else hist
 
     def launch_view_histogram(self, view: View, mrd: int, *, d_hist: int, stream: int = 0, window=None, kernel: str = "default",
@@ -706,8 +774,8 @@ class MandelbrotDevice:
     def launch_deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_hist: int, stream: int = 0,
                                    window=None, bla: bool = False) -> None:
         cv = self._cdeep(view, window)
-        self._check(self._lib.mbk_deep_view_histogram_launch(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_BLA if bla else 0, d_hist or None,
-                                                             stream or None))
+        fn, flags = self._deep_fn(view, "histogram_launch", bla)
+        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, d_hist or None, stream or None))
 
     def counts_histogram(self, d_counts: int, n: int, mrd: int, d_hist: int, stream: int = 0) -> None:
         """Asynchronous: the histogram of n int32 counts in DEVICE memory is ADDED into the DEVICE table d_hist (uint64[mrd])

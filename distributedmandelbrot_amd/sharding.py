@@ -156,7 +156,11 @@ def render_deep_view(devices: Sequence, orbit, view, mrd: int, *, band_rows: int
                      bla: bool = False) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], List[dict]]:
     """render_view for a deep-zoom view (device.DeepView) over one DeepOrbit: row bands from a shared queue, two in flight
     per device (submit_deep_view / wait).  A band's offsets come from the whole view, so the image is bit-identical to
-    compute_deep_view's -- with bla too: the table depends on the whole view, not on the band."""
+    compute_deep_view's -- with bla too: the table depends on the whole view, not on the band.  `view` may be a
+    device.WideDeepView (extended range; bla=True raises ValueError: it has no bilinear approximation)."""
+    if bla and not hasattr(view, "span_r"):
+        raise ValueError("bla=True is not implemented for a WideDeepView")
+
     def submit(dev, s, window, oc, ob):
         dev.submit_deep_view(s, orbit, view, mrd, window=window, out_counts=oc, out_bytes=ob, bla=bla)
 

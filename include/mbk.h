@@ -319,8 +319,9 @@ int mbk_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, uint32_t mrd, 
  *                    so bytes are the usual quantiser of the count and smooth = n + 1 - log2(0.5 ln mag) as for mbk_view.
  * Limits: spans (range_r, range_i) in [2^-960, 4] (binary64 offsets stay normal); P <= 4096 (spans below 2^(64-P) resolve the
  * centre more finely than the orbit does: Python's DeepOrbit picks P = 64 + ceil(-log2 min_span) by default); a launch's mrd
- * <= the orbit's mrd.  Extended-exponent offsets (spans below 2^-960) are not implemented; series approximation is a flag
- * (MBK_DEEP_BLA, "Deep-zoom views with bilinear approximation" below), off by default.
+ * <= the orbit's mrd.  Spans below 2^-960 take a view struct and a kernel of their own (mbk_deep_xview, "Extended-range deep
+ * views" below: offsets and orbit carry an int32 exponent); series approximation is a flag (MBK_DEEP_BLA, "Deep-zoom views
+ * with bilinear approximation" below), off by default.
  * Centres within ~1e-16 of -2 render wrong below spans of ~1e-15: the real orbit stays just inside |z| = 2, the binary64 table
  * holds 2.0, and every pixel retires at count 1 (tests/test_deep_truth.py, the strict xfail cases).
  *
@@ -351,6 +352,8 @@ int mbk_deep_orbit_info(const mbk_deep_orbit *orbit, uint32_t *length, uint32_t 
                         uint32_t *mrd);
 /* Z_0 .. Z_M as binary64 into zr[0..M], zi[0..M]; n is their capacity (MBK_ERR_INVALID below M + 1). */
 int mbk_deep_orbit_read(const mbk_deep_orbit *orbit, double *zr, double *zi, uint64_t n);
+/* Z_0 .. Z_M of the wide table ("Extended-range deep views", below), Z_m = (xr[m], xi[m]) 2^xe[m]; n as above. */
+int mbk_deep_orbit_read_wide(const mbk_deep_orbit *orbit, double *xr, double *xi, int32_t *xe, uint64_t n);
 /* The three forms of the view calls.  flags: MBK_WANT_COUNTS | MBK_WANT_BYTES, and MBK_DEEP_BLA ("Deep-zoom views with
  * bilinear approximation", below), only (kernel selection, MBK_PRECISION_F32 and MBK_LAZY_UNIFORM are MBK_ERR_INVALID), as are a NULL orbit, a view without output, ranges outside [2^-960, 4] and
  * mrd > the orbit's mrd.  _launch: DEVICE pointers on the caller's stream (d_smooth may be NULL; no statistics).  _compute:
@@ -430,6 +433,78 @@ int mbk_deep_bla_read(const mbk_deep_orbit *orbit, const mbk_deep_view *view, ui
                       double *B_r, double *B_i, double *rc, uint64_t n);
 int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
                             int32_t *count, double *mag, uint64_t *steps_executed);
+
+/*
+ * Extended-range deep views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes, and what
+ * the mbk_deep_view_* calls store is untouched.  A deep view above stops at spans of 2^-960 because its offsets, and the
+ * orbit table it reads, are binary64: below ~1e-308 a span cannot be named, and a reference point within 1e-308 of 0 -- every
+ * multiple of the period when the view looks at a small minibrot -- is subnormal or 0 in the table exactly where rebasing
+ * compares |Z_m + dz| with |dz|.  An extended-range view carries every number as a binary64 mantissa pair with one int32
+ * exponent, on the host (the wide table) and on the device (csrc/mbk_deep_wide.h), so spans reach as far as the fixed-point
+ * orbit does: P <= 4096 fraction bits, spans down to ~2^-4030.  It covers counts, bytes, smooth values, renders (sources
+ * bytes, smooth, equalized) and histograms; distance estimates and MBK_DEEP_BLA are not implemented for it.
+ *
+ * Contract (bit-exact; tests/deep_wide_model.py restates it in numpy; tests/test_deep_wide.py holds the host twins below to
+ * it and it to the truth, tests/test_gpu_deep_wide.py holds the GPU to it).  Binary64 mantissas, int32 exponents, every
+ * floating operation rounded on its own, no contraction.  EZ = -2^24 is the exponent of a zero.
+ *   wide table   beside the binary64 table, built once by mbk_deep_orbit_create: every Z_m of the fixed-point orbit as
+ *                (X_r, X_i, xe), Z_m = X 2^xe.  xe is the frexp exponent of the larger |component| taken from the fixed-point
+ *                value (its bit length minus P); X_r and X_i are the fixed-point components times 2^-xe, each rounded to
+ *                nearest-even binary64 (so the larger lies in [0.5, 1], 1 when it rounds up; the smaller, if it lands in the
+ *                subnormal range, rounds once on that grid).  A zero Z is (0, 0, EZ).  Wherever an entry of the binary64 table
+ *                is a normal number it equals X 2^xe bit for bit.
+ *   view         spans range_* 2^exp2 with range_* in [2^-64, 4] and exp2 in [-8192, 0].  The offsets are dc = dcm 2^exp2 with
+ *                dcm the offset formula of "Deep-zoom views" applied to range_* (column k: fl(fl(k - (W-1)/2) fl(range_r /
+ *                (W-1))), 0 for W = 1), from the full view: a window is bit-identical to the same pixels of the whole view.
+ *   helpers      sh(x, k) = ldexp(x, max(k, -1200)): exact unless the result is subnormal, and then it rounds once.
+ *                norm(v, e): with s the frexp exponent of max(|v_r|, |v_i|), (ldexp(v_r, -s), ldexp(v_i, -s), e + s); (0, 0, EZ)
+ *                when both components are 0.
+ *   step         per pixel (w, q, m), dz = w 2^q.  Start (w, q) = norm(dcm, exp2), m = 1; if M == 1 that state goes through (e)
+ *                with the entry 1 at once -- (w, q) = norm(zv, t), m = 0 -- as the plain contract's start does.
+ *                For i = 1 .. mrd-1, with (X, xe) the entry m:
+ *                  a. g = max(xe + 1, q);  A = fl(sh(X, xe + 1 - g) + sh(w, q - g)), per component
+ *                  b. p = (fl(fl(A_r w_r) - fl(A_i w_i)), fl(fl(A_r w_i) + fl(A_i w_r))), exponent g + q
+ *                  c. h = max(g + q, exp2);  N = fl(sh(p, g + q - h) + sh(dcm, exp2 - h))
+ *                  d. (w, q) = norm(N, h);  m = m + 1
+ *                  e. with (X, xe) the entry of the new m: t = max(xe, q);  zv = fl(sh(X, xe - t) + sh(w, q - t));
+ *                     mg = fl(fl(zv_r^2) + fl(zv_i^2));  mag = ldexp(mg, 2 max(t, -600))
+ *                  f. mag >= 4: count = i, stop (this mag feeds smooth as in "Deep-zoom views")
+ *                  g. dm = fl(fl(w_r^2) + fl(w_i^2));  if mg < ldexp(dm, 2 max(q - t, -600)) or m == M: (w, q) = norm(zv, t), m = 0
+ *                count 0 if the pixel never escapes; bytes are the usual quantiser; mrd 0 and 1 run no step; statistics as for
+ *                mbk_deep_view_compute (pixel_iterations counts count, or mrd - 1 for 0).
+ *   corners      The exponents are nominal: p and N are not renormalised between (b) and (c), so if A cancels to exactly 0
+ *                while g + q exceeds exp2 by more than ~1000, sh(dcm, exp2 - h) underflows and that step adds no dc (2 Z_m
+ *                = -dz exactly: no sampled pixel of the tests meets it).  A zero operand has exponent EZ, far below any other, so
+ *                it never sets g, h or t unless both are zero.  All exponents stay within +-2^26.
+ *   equals plain Scaling by a power of two is exact: wherever no value of the plain deep contract is subnormal or underflows,
+ *                an extended-range view stores the same count and the same mag, bit for bit, as the plain view of the same
+ *                spans (tests/test_deep_wide.py, on the catalogue of tests/test_deep_truth.py).
+ * Against direct iteration at P + 128 bits: >= 99 % of sampled pixels equal, the cap of the plain contract, at exp2 = -1100 and
+ * -3000 and on the centre 1e-400, whose binary64 table holds 0 in every entry.  Centres within ~1e-16 of -2 stay a known limit.
+ *
+ * Each ctx uploads its device copy of the wide table (32 bytes x (M + 1)) on the orbit's first extended-range launch there and
+ * keeps it beside the orbit's binary64 copy, under the same lifetime and eviction rule; that upload is synchronous too: launch
+ * once before capturing.
+ */
+typedef struct mbk_deep_xview {
+    double range_r, range_i;   /* in [2^-64, 4] */
+    int32_t exp2;              /* in [-8192, 0]: the spans are range_* 2^exp2 */
+    uint32_t width, height, col0, row0, ncols, nrows;
+} mbk_deep_xview;
+
+/* The three forms, as mbk_deep_view_launch / _compute / _submit: the same outputs, flags (MBK_WANT_COUNTS | MBK_WANT_BYTES
+ * only), statistics and refusals; in addition MBK_DEEP_BLA, ranges outside [2^-64, 4] and exp2 outside [-8192, 0] are
+ * MBK_ERR_INVALID. */
+int mbk_deep_xview_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream);
+int mbk_deep_xview_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats);
+int mbk_deep_xview_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes);
+/* Host twin for the CPU tests, compiled from the step functions the kernel uses: no ctx, no device.  The pixel (col, row) of
+ * the full view: its count and the mag of the escaping step (0 for count 0).  MBK_ERR_INVALID for what the launch refuses. */
+int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                              int32_t *count, double *mag);
 
 /*
  * Distance estimates for deep views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes, and
@@ -572,6 +647,12 @@ int mbk_view_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, ui
                             uint8_t *h_rgba, mbk_stats *stats);
 int mbk_deep_view_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+/* Extended-range deep views ("Extended-range deep views"): sources MBK_RENDER_BYTES / _SMOOTH (and _EQUALIZED through the
+ * _equalized_ calls below); MBK_RENDER_DISTANCE, MBK_RENDER_DISTANCE_REL and every flag are MBK_ERR_INVALID. */
+int mbk_deep_xview_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_xview_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
 int mbk_deep_view_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
 /* The reference Viewer's colouring as a 256-entry palette for MBK_RENDER_BYTES, host only: entry 0 black (0, 0, 0, 255),
@@ -655,6 +736,11 @@ int mbk_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd,
                                mbk_stats *stats);
 int mbk_deep_view_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                     uint32_t flags, uint64_t *h_hist, mbk_stats *stats);
+/* The same for an extended-range deep view (the counts of mbk_deep_xview_launch; every flag is MBK_ERR_INVALID). */
+int mbk_deep_xview_histogram_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                    uint32_t flags, uint64_t *d_hist, void *hip_stream);
+int mbk_deep_xview_histogram_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                     uint32_t flags, uint64_t *h_hist, mbk_stats *stats);
 int mbk_counts_histogram_host(const int32_t *counts, uint64_t n, uint32_t mrd, uint64_t *hist);
 int mbk_equalize_lut_host(const uint64_t *hist, uint32_t mrd, double *lut);
 double mbk_equalize_value_host(const double *lut, uint32_t mrd, double nu);
@@ -670,6 +756,12 @@ int mbk_deep_view_render_equalized_launch(mbk_ctx *ctx, const mbk_deep_orbit *or
 int mbk_deep_view_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                            uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
                                            uint8_t *h_rgba, mbk_stats *stats);
+int mbk_deep_xview_render_equalized_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                           uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_xview_render_equalized_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                            uint32_t flags, const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len,
+                                            uint8_t *h_rgba, mbk_stats *stats);
 int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double *h_lut, uint32_t lut_len, uint32_t width,
                                       uint32_t height, const int32_t *counts, const double *smooth, uint8_t *rgba);
 
