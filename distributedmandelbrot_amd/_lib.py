@@ -318,6 +318,7 @@ SIGNATURES = {
     "mbk_density_accumulate_host": (C.c_int, [C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32, C.c_uint32,
                                               C.c_void_p, C.POINTER(mbk_density_stats)]),
     "mbk_density_resolve_host": (C.c_int, [C.POINTER(mbk_density_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mbk_density_build_info": (C.c_int, []),
     "mbk_chunk_stream_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32)]),
     "mbk_chunk_decode_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -30,10 +30,10 @@ def hipcc() -> str:
     return exe
 
 
-def needs_build() -> bool:
-    if not os.path.exists(SO):
+def needs_build(so: str = SO) -> bool:
+    if not os.path.exists(so):
         return True
-    t = os.path.getmtime(SO)
+    t = os.path.getmtime(so)
     return any(os.path.getmtime(d) > t for d in DEPS if os.path.exists(d))
 
 
@@ -50,6 +50,28 @@ def build(force: bool = False, save_temps: bool = False, verbose: bool = False) 
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=cwd)
     return SO
+
+
+# Second builds of the same sources under compile-time switches, for A/B runs and for the tests of a form that does not ship.
+VARIANTS = {"density_compact": ["-DMBK_DENSITY_COMPACT=1"]}   # csrc/mbk_density.h: the compacted replay
+
+
+def variant_path(name: str) -> str:
+    return os.path.join(HERE, "build", f"libmbk_hip_{name}.so")
+
+
+def build_variant(name: str, defines, force: bool = False, verbose: bool = False) -> str:
+    """The same FLAGS and SOURCES plus `defines` (a list of -D... options) into the git-ignored build/libmbk_hip_<name>.so,
+    rebuilt under the rule of build().  The shipped library is not touched."""
+    so = variant_path(name)
+    if not force and not needs_build(so):
+        return so
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    cmd = [hipcc()] + FLAGS + list(defines) + SOURCES + ["-o", so]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd, cwd=os.path.dirname(so))
+    return so
 
 
 if __name__ == "__main__":

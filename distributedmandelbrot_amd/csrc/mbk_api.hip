@@ -4036,6 +4036,8 @@ int mbk_density_accumulate_host(const mbk_view *view, const mbk_density_target *
     return MBK_OK;
 }
 
+int mbk_density_build_info(void) { return MBK_DENSITY_COMPACT; }
+
 int mbk_density_resolve_host(const mbk_density_render_spec *spec, uint32_t width, uint32_t height, const uint32_t *density, uint8_t *rgba)
 {
     int rc = density_render_check(nullptr, spec, width, height, density, rgba);

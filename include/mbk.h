@@ -905,6 +905,10 @@ int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_
  * MBK_DEEP_BLA, MBK_WANT_*); the kernels mbk_view_launch_smooth refuses (MBK_KERNEL_SIMPLE, MBK_KERNEL_REFILL); and whatever
  * mbk_view_launch refuses in a view.
  *
+ * mbk_density_build_info: host-only, needs no ctx: which form of the replay this library was compiled with -- 0, the plain form
+ * (one lane per sample in image order; what ships), or 1, the compacted list (-DMBK_DENSITY_COMPACT=1, csrc/mbk_density.h).  The
+ * two forms compute the same tables; a test that loads a second build asks here which one it got.
+ *
  * Out of scope: deep, Julia and fp32 forms; the anti-Buddhabrot (orbits of the samples that never escape); random or jittered
  * sampling; the z -> conj(z) symmetry; fusing the deposits into the count kernels; 64-bit tables; an equalised colouring of
  * densities.
@@ -942,6 +946,7 @@ int mbk_density_accumulate_host(const mbk_view *view, const mbk_density_target *
                                 uint32_t max_count, uint32_t *density, mbk_density_stats *dstats);
 int mbk_density_resolve_host(const mbk_density_render_spec *spec, uint32_t width, uint32_t height, const uint32_t *density,
                              uint8_t *rgba);
+int mbk_density_build_info(void);
 
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u

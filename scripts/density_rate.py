@@ -37,13 +37,7 @@ RECT = (-2.0, -1.5, 3.0, 3.0)   # cfg2's view; the target is the same rectangle
 
 def build_compact() -> str:
     from distributedmandelbrot_amd import build as B
-    out_dir = os.path.join(B.HERE, "build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libmbk_hip_density_compact.so")
-    if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in B.DEPS if os.path.exists(d)):
-        return so
-    subprocess.check_call([B.hipcc()] + B.FLAGS + ["-DMBK_DENSITY_COMPACT=1"] + B.SOURCES + ["-o", so], cwd=out_dir)
-    return so
+    return B.build_variant("density_compact", B.VARIANTS["density_compact"])
 
 
 def child(args) -> int:

@@ -224,3 +224,75 @@ def test_refusals_of_the_resolve_twin():
         assert status(**kw) == bad, kw
     assert lib.mbk_density_resolve_host(None, 8, 8, table.ctypes.data, out.ctypes.data) == bad
     assert (out == 7).all()
+
+
+# ---- the case table of the GPU tests (tests/density_cases.py), checked where no GPU is needed --------------------------------
+
+def test_the_gpu_case_table_reaches_what_it_claims():
+    import density_cases as DC
+    names = {c.name for c in DC.CASES}
+    empty = {"mrd0", "mrd1", "interior", "mrd258_top", "n255_256", "n256_257", "n128"}   # ENDS has no sample with n >= 63
+    assert empty <= names
+    for case in DC.CASES:
+        want, dep, drop, nq = DC.expected(case)
+        assert (dep > 0) == (case.name not in empty), case.name
+        assert dep + drop == int(nq.sum())
+        if not case.init:
+            assert int(want.sum()) == dep
+    bands = lambda name: sorted({int(v).bit_length() - 1 for v in DC.expected(DC.BY_NAME[name])[3]})
+    for name in ("wide", "narrow", "big_rows", "t175"):
+        assert bands(name) == list(range(8)) and len(np.unique(DC.expected(DC.BY_NAME[name])[3])) >= 8
+    assert DC.expected(DC.BY_NAME["wide"])[3].size > 256                    # more than one workgroup of the list passes
+    assert DC.SMALL.width * DC.SMALL.height == 117 and 0 < DC.expected(DC.BY_NAME["partial"])[3].size % 64
+    assert bands("mrd2") == [0] and bands("mrd3") == [0, 1] and bands("mrd3_top") == [1]
+    assert bands("n7_8") == [2, 3] and bands("n15_16") == [3, 4] and bands("n31_32") == [4, 5]   # 2^k - 1 against 2^k
+    assert bands("n8_9") == [3] and bands("n16") == [4] and bands("n128_view") == [7]
+    assert 0 < DC.expected(DC.BY_NAME["sparse"])[3].size < 64
+    far = DC.expected(DC.BY_NAME["far"])
+    assert (far[3] == 1).all() and far[3].size == 256 and far[2] == 0      # the list equals the window
+    assert np.array_equal(DC.expected(DC.BY_NAME["big_rows"])[0], DC.expected(DC.BY_NAME["big_whole"])[0])
+    assert np.array_equal(DC.expected(DC.BY_NAME["big_cols"])[0], DC.expected(DC.BY_NAME["big_whole"])[0])
+    assert np.array_equal(DC.expected(DC.BY_NAME["big_twice"])[0], 2 * DC.expected(DC.BY_NAME["big_once"])[0])
+    assert DC.expected(DC.BY_NAME["one_cell"])[2] == 0 == DC.expected(DC.BY_NAME["four_cells"])[2]
+    t175 = DC.expected(DC.BY_NAME["t175"])
+    assert t175[2] > 10 * t175[1] > 0
+    # the wraps wrap: every word of wrap_all is the model's minus one, the hottest word of wrap_word passes 2^32
+    plain = DC.expected(DC.BY_NAME["partial"])[0]
+    assert np.array_equal(DC.expected(DC.BY_NAME["wrap_all"])[0], (plain.astype(np.int64) - 1) % 2 ** 32)
+    wide = DC.expected(DC.BY_NAME["wide"])[0]
+    word = DC.expected(DC.BY_NAME["wrap_word"])[0].ravel()[DC.WRAP_WORD]
+    assert int(wide.ravel()[DC.WRAP_WORD]) == int(wide.max()) > 16 and int(word) == int(wide.max()) - 16
+    # the band-loop views cross their band limit once, whichever build runs them
+    for per_sample in (4, 8):
+        (_, rows, rw), (_, cols, cw) = DC.band_views(per_sample, L.MBK_RENDER_BAND_BYTES)
+        limit = (L.MBK_RENDER_BAND_BYTES - 1024) // per_sample
+        assert limit < rows.width * rows.height <= 2 * limit and limit < cols.width <= 2 * limit and cols.height == 1
+        assert all(w[2] * w[3] <= limit for w in rw + cw)
+    assert DC.band_views(4, L.MBK_RENDER_BAND_BYTES)[0][1].height == 8200 and DC.band_views(8, L.MBK_RENDER_BAND_BYTES)[0][1].height == 4100
+
+
+def _edge_restatement(target_name):
+    """Where the 81 points z_0 = (i / 4 - 1, j / 4 - 1) of NINE fall, in integers: the cells of EDGE are 1/4 wide and start at
+    -1, so z_0 is the lower left corner of cell (i, j); HALF starts half a cell lower, so z_0 is the centre of cell (i, j).
+    Either way column 8 and row 8 are outside: on the right and the top edge of EDGE, half a cell beyond those of HALF."""
+    import density_cases as DC
+    n = DC.view_counts(DC.NINE, 2)
+    table = np.zeros((8, 8), np.uint32)
+    table[:, :] = (n[:8, :8] == 1)
+    return table, int((n == 1).sum()) - int(table.sum())
+
+
+@pytest.mark.parametrize("name", ["edge", "edge_half", "edge_orbits", "edge_half_orbits"])
+def test_table_edges_on_the_host_twin(name):
+    """A point exactly on the right or the top edge is outside; row 0 is the lowest imaginary part."""
+    import density_cases as DC
+    case = DC.BY_NAME[name]
+    want, dep, drop, _ = DC.expected(case)
+    got, ds = density_host(case.view, case.target, case.mrd, min_count=case.min_count, max_count=case.max_count)
+    assert np.array_equal(got, want) and (ds.deposits, ds.dropped) == (dep, drop)
+    if case.mrd == 2:
+        table, dropped = _edge_restatement(name)
+        assert np.array_equal(got, table) and ds.dropped == dropped > 0
+        n = DC.view_counts(DC.NINE, 2)
+        assert (n[:, 8] == 1).all() and (n[8, 6:] == 1).all()                # samples on the right and on the top edge ...
+        assert got[0, 6] == 1 and got[0, 7] == 1 and not got[7, :7].any()    # ... and row 0 holds those with c_i = -1

@@ -3,7 +3,9 @@ contract in tests/density_model.py -- and against the host twin where that is ch
 import numpy as np
 import pytest
 
+import density_cases as DC
 import density_model as M
+from density_cases import BIG, DISC, MRD, NARROW, VIEW, WIDE
 
 from distributedmandelbrot_amd import DensityTarget, MandelbrotDevice, MbkError, Palette, View
 from distributedmandelbrot_amd import _lib as L
@@ -11,14 +13,6 @@ from distributedmandelbrot_amd.device import density_host
 from distributedmandelbrot_amd.sharding import accumulate_view_density
 
 pytestmark = pytest.mark.gpu
-
-VIEW = View(-2.0, -1.25, 3.0, 2.5, 96, 64)
-MRD = 200
-WIDE = DensityTarget(-2.0, -1.5, 3.0, 3.0, 48, 40)
-NARROW = DensityTarget(-0.5, 0.5, 0.5, 0.5, 48, 40)
-DISC = DensityTarget(-2.5, -2.5, 5.0, 5.0, 40, 40)
-BIG = View(-2.0, -1.25, 3.0, 2.5, 100, 70)
-GUARD = 0xA5A5A5A5
 
 
 def _torch():
@@ -41,18 +35,67 @@ def reference():
 def _device_table(gpu, view, target, mrd, launches, guard=64, **kw):
     """The table after `launches` (a list of windows, None = the whole view) into one cleared device table with `guard`
     sentinel words on either side; the sentinels are checked."""
-    torch = _torch()
-    cells = target.width * target.height
-    host = np.full(cells + 2 * guard, GUARD, np.uint32)
-    host[guard:guard + cells] = 0
-    buf = torch.from_numpy(host.view(np.int32)).to("cuda:0")
-    torch.cuda.synchronize()
-    for window in launches:
-        gpu.launch_view_density(view, target, mrd, d_density=buf.data_ptr() + 4 * guard, window=window, **kw)
-    torch.cuda.synchronize()
-    back = buf.cpu().numpy().view(np.uint32)
-    assert (back[:guard] == GUARD).all() and (back[guard + cells:] == GUARD).all(), "a word outside the table was written"
-    return back[guard:guard + cells].reshape(target.height, target.width), buf
+    table, intact, buf = DC.device_table(gpu, view, target, mrd, launches, guard=guard, **kw)
+    assert intact, "a word outside the table was written"
+    return table, buf
+
+
+def test_this_is_the_plain_form(gpu):
+    """The library that ships replays one lane per sample (tests/test_gpu_density_compact.py runs the other form)."""
+    assert gpu._lib.mbk_density_build_info() == 0
+
+
+@pytest.mark.parametrize("name", [c.name for c in DC.CASES])
+def test_case_equals_the_model(gpu, name):
+    """Every case of tests/density_cases.py -- the shapes chosen for the list kernels of the compact form, the wrap at 2^32 and
+    the table's edges among them -- on the plain form."""
+    case = DC.BY_NAME[name]
+    DC.check_case(case, DC.run_case(gpu, case))
+
+
+def test_table_edges_against_their_integer_restatement(gpu):
+    """View (-1, -1, 2, 2, 9, 9) into 8 x 8 cells of the same square: z_0 = (i / 4 - 1, j / 4 - 1) is the lower left corner of
+    cell (i, j), column 8 and row 8 lie exactly on the right and the top edge and are dropped, and row 0 holds the samples with
+    c_i = -1.  At mrd 2 with min_count = max_count = 1 only z_0 of the n = 1 samples is deposited.  The same with the target moved
+    by half a cell, where z_0 is the centre of cell (i, j)."""
+    n = DC.view_counts(DC.NINE, 2)
+    want = (n[:8, :8] == 1).astype(np.uint32)
+    assert want[0].any() and (n[:, 8] == 1).all() and (n[8] == 1).any()
+    for name in ("edge", "edge_half"):
+        case = DC.BY_NAME[name]
+        got, _ = _device_table(gpu, case.view, case.target, 2, [None], min_count=1, max_count=1)
+        assert np.array_equal(got, want), name
+        table, _, ds = gpu.compute_view_density(case.view, case.target, 2, min_count=1, max_count=1)
+        assert np.array_equal(table, want) and (ds.deposits, ds.dropped) == (int(want.sum()), int((n == 1).sum()) - int(want.sum()))
+
+
+def test_a_launch_adds_modulo_2_to_the_32(gpu):
+    small = DC.BY_NAME["wrap_all"]
+    model = DC.expected(DC.BY_NAME["partial"])[0].astype(np.int64)
+    got, _ = _device_table(gpu, small.view, small.target, small.mrd, [None], init=DC.initial(small))
+    assert model.any() and np.array_equal(got.astype(np.int64), (model - 1) % 2 ** 32)
+    word = DC.BY_NAME["wrap_word"]
+    want = DC.expected(word)[0]
+    got, buf = _device_table(gpu, word.view, word.target, word.mrd, [None], init=DC.initial(word))
+    assert np.array_equal(got, want) and int(want.ravel()[DC.WRAP_WORD]) == int(DC.expected(DC.BY_NAME["wide"])[0].max()) - 16
+    assert gpu.density_max(buf.data_ptr() + 4 * 64, got.size) == (int(want.max()), int(want.astype(np.uint64).sum()))
+    assert int(want.max()) < 2 ** 31   # the word that passed 2^32 is small again
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["rows", "cols"])
+def test_band_loop_of_density_run(gpu, oracle, which):
+    """density_run past one band of the count scratch (MBK_RENDER_BAND_BYTES - 1024 bytes, 4 per sample): 8192 x 8200 samples are
+    two row bands of 8191 and 9 rows, a row of 67 110 000 samples two column tiles.  At mrd 8 into 512 x 512 cells that hold the
+    disc of radius 2: against the host twin's table, the C oracle's statistics, and the same view as two one-band windows."""
+    name, view, windows = DC.band_views(4, L.MBK_RENDER_BAND_BYTES)[which]
+    limit = (L.MBK_RENDER_BAND_BYTES - 1024) // 4
+    if name == "rows":
+        assert -(-view.height // (limit // view.width)) == 2
+    else:
+        assert view.width > limit and -(-view.width // limit) == 2
+    got = DC.run_band_view(gpu, view, windows)
+    print(f"plain band view {name}: kernel_ms {got['kernel_ms']:.2f}")
+    DC.check_band_view(oracle, view, got)
 
 
 @pytest.mark.parametrize("kernel", ["default", "asm", "group", "scan"])
