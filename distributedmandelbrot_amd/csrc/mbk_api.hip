@@ -1545,6 +1545,193 @@ static int view_compute(mbk_ctx *ctx, size_t px, uint32_t mrd, uint32_t flags, i
     return sync_end(ctx, view_enqueue(ctx, ctx->s[0], px, mrd, flags, h_counts, h_bytes, h_smooth, launch), stats, (flags & MBK_WANT_BYTES) != 0);
 }
 
+// ---- the four kinds of view behind one type (DESIGN.md "One target, four kinds of view") --------------------------------
+
+struct Geometry { uint32_t width, height, col0, row0, ncols, nrows; };
+
+// What a count call, a render or a histogram works on: a plain view, the Julia set of (c_r, c_i) on a view, a deep view or an
+// extended-range deep view on `orbit`.  The view struct of the kind is held by value, so a target outlives the caller's struct
+// and a piece of it (target_samples) is a target like any other.  A NULL view leaves has_view false and the kind in place:
+// the refusals of a NULL view stand at a different place in each kind's order (target_check).
+struct Target {
+    enum Kind { kPlain, kJulia, kDeep, kWide } kind;
+    bool has_view;
+    Geometry g;                    // the geometry of the view of `kind`, whichever struct holds it
+    mbk_view view;                 // kPlain, kJulia
+    mbk_deep_view deep;            // kDeep
+    mbk_deep_xview wide;           // kWide
+    const mbk_deep_orbit *orbit;   // kDeep, kWide
+    double c_r, c_i;               // kJulia
+};
+
+template <typename V>
+static Target make_target(Target::Kind kind, const V *v, V Target::*held, const mbk_deep_orbit *orbit = nullptr, double c_r = 0.0,
+                          double c_i = 0.0)
+{
+    Target t = {};
+    t.kind = kind;
+    t.orbit = orbit;
+    t.c_r = c_r;
+    t.c_i = c_i;
+    if (v) {
+        t.has_view = true;
+        t.*held = *v;
+        t.g = Geometry{v->width, v->height, v->col0, v->row0, v->ncols, v->nrows};
+    }
+    return t;
+}
+static Target view_target(const mbk_view *v) { return make_target(Target::kPlain, v, &Target::view); }
+static Target julia_target(const mbk_view *v, double c_r, double c_i) { return make_target(Target::kJulia, v, &Target::view, nullptr, c_r, c_i); }
+static Target deep_target(const mbk_deep_orbit *orbit, const mbk_deep_view *v) { return make_target(Target::kDeep, v, &Target::deep, orbit); }
+static Target wide_target(const mbk_deep_orbit *orbit, const mbk_deep_xview *v) { return make_target(Target::kWide, v, &Target::wide, orbit); }
+
+template <typename V>
+static void set_geometry(V &v, const Geometry &g)
+{
+    v.width = g.width;
+    v.height = g.height;
+    v.col0 = g.col0;
+    v.row0 = g.row0;
+    v.ncols = g.ncols;
+    v.nrows = g.nrows;
+}
+
+// The samples of the piece (col0, row0, ncols, nrows) of the OUTPUT window of `t` at supersample s: the same rectangle or
+// spans at s times the width and height.
+static Target target_samples(const Target &t, uint32_t s, uint32_t col0, uint32_t row0, uint32_t ncols, uint32_t nrows)
+{
+    Target p = t;
+    p.g = Geometry{t.g.width * s, t.g.height * s, col0 * s, row0 * s, ncols * s, nrows * s};
+    switch (t.kind) {
+        case Target::kWide: set_geometry(p.wide, p.g); break;
+        case Target::kDeep: set_geometry(p.deep, p.g); break;
+        case Target::kJulia:
+        case Target::kPlain: set_geometry(p.view, p.g); break;
+    }
+    return p;
+}
+
+// Bands (renders, histograms, density views): rows of a window whose samples fit MBK_RENDER_BAND_BYTES of scratch at
+// bytes_per_px bytes per pixel, and pieces of columns where one row's do not.  max_rows: a cap on the rows of a band, or 0.
+struct BandPlan {
+    uint32_t ncols, nrows, tile_cols, band_rows;
+    size_t cap_px() const { return (size_t)tile_cols * band_rows; }
+};
+
+static BandPlan band_plan(uint32_t ncols, uint32_t nrows, uint64_t bytes_per_px, uint32_t max_rows = 0u)
+{
+    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;   // (the parts of the scratch start on 256-byte lines)
+    BandPlan p = {ncols, nrows, ncols, 1u};
+    if ((uint64_t)ncols * bytes_per_px <= budget)
+        p.band_rows = (uint32_t)std::min<uint64_t>(nrows, budget / ((uint64_t)ncols * bytes_per_px));
+    else
+        p.tile_cols = (uint32_t)(budget / bytes_per_px);
+    if (max_rows) p.band_rows = std::min(p.band_rows, max_rows);
+    return p;
+}
+
+// piece(r, c, nr, nc, is_last) enqueues the piece at (r, c) of the window on `stream`, its counts -- samples_per_px of them per
+// pixel -- at d_counts.  stat: the slot whose reduction scratch adds up the statistics of the counts and whose ev_k1 marks the
+// last piece's last kernel (the synchronous forms), or NULL.
+template <typename Piece>
+static int for_each_band(mbk_ctx *ctx, const BandPlan &p, const int32_t *d_counts, uint64_t samples_per_px, uint32_t mrd,
+                         hipStream_t stream, Slot *stat, Piece piece)
+{
+    for (uint32_t r = 0; r < p.nrows; r += p.band_rows) {
+        const uint32_t nr = std::min(p.band_rows, p.nrows - r);
+        for (uint32_t c = 0; c < p.ncols; c += p.tile_cols) {
+            const uint32_t nc = std::min(p.tile_cols, p.ncols - c);
+            const bool is_last = r + nr == p.nrows && c + nc == p.ncols;
+            int rc = piece(r, c, nr, nc, is_last);
+            if (rc != MBK_OK) return rc;
+            if (stat) {
+                if (is_last) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
+                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, (uint64_t)nc * nr * samples_per_px, mrd, stream, false);
+                if (rc != MBK_OK) return rc;
+            }
+        }
+    }
+    return MBK_OK;
+}
+
+// ---- what deep and extended-range deep views share: mbk_deep_view and mbk_deep_xview, DeepArgs and DeepWideArgs name these
+// fields the same ----
+
+static double deep_step(double range, uint32_t n)
+{
+    if (n <= 1u) return 0.0;
+    volatile double s = range / (double)(n - 1u);
+    return s;
+}
+
+// dc of sample k of an axis of n samples over `range`: fl(fl(k - (n - 1) / 2) * step), as the kernels form it
+static double deep_dc(uint32_t k, uint32_t n, double range)
+{
+    volatile double dc = ((double)k - (double)(n - 1u) * 0.5) * deep_step(range, n);
+    return dc;
+}
+
+template <typename V>
+static bool deep_ranges_within(const V *v, double lo)
+{
+    for (double r : {v->range_r, v->range_i})
+        if (!std::isfinite(r) || !(r >= lo) || !(r <= 4.0)) return false;
+    return true;
+}
+
+// The checks of a deep view of either kind, in the order the calls report them: the pointers, the kind's flag rules
+// (flag_rules()), the geometry, the kind's ranges (range_rules()), mrd.
+template <typename V, typename FlagRules, typename RangeRules>
+static int validate_deep_view(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const V *v, uint32_t mrd, uint32_t flags, FlagRules flag_rules,
+                              RangeRules range_rules)
+{
+    if (!orbit) return fail(ctx, MBK_ERR_INVALID, "orbit is NULL");
+    if (!v) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    int rc = flag_rules();
+    if (rc != MBK_OK) return rc;
+    if (v->width == 0 || v->height == 0) return fail(ctx, MBK_ERR_INVALID, "empty view");
+    if (v->ncols == 0 || v->nrows == 0) return fail(ctx, MBK_ERR_INVALID, "empty window");
+    if ((uint64_t)v->col0 + v->ncols > v->width || (uint64_t)v->row0 + v->nrows > v->height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    if ((uint64_t)v->ncols * v->nrows > (1ull << 31)) return fail(ctx, MBK_ERR_INVALID, "window larger than 2^31 pixels");
+    rc = range_rules();
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(ctx, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    return MBK_OK;
+}
+
+// the view's geometry and window and mrd in a deep kernel's arguments
+template <typename Args, typename V>
+static void fill_deep_window(Args &a, const V *v, uint32_t mrd)
+{
+    a.half_r = (double)(v->width - 1u) * 0.5;
+    a.half_i = (double)(v->height - 1u) * 0.5;
+    a.step_r = deep_step(v->range_r, v->width);
+    a.step_i = deep_step(v->range_i, v->height);
+    a.col0 = v->col0;
+    a.row0 = v->row0;
+    a.ncols = v->ncols;
+    a.nrows = v->nrows;
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+}
+
+// the three outputs (each may be null) and the quantiser of the bytes (mbk_kernels.h: quantise) in a kernel's arguments
+template <typename Args>
+static void fill_outputs(Args &a, uint32_t mrd, int32_t *d_counts, uint8_t *d_bytes, double *d_smooth)
+{
+    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
+    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
+    a.counts = d_counts;
+    a.bytes = d_bytes;
+    a.smooth = d_smooth;
+}
+
+// one 64-lane workgroup per 8 x 8 block of the window in `a` (blocks_x set)
+template <typename Args>
+static dim3 block_grid(const Args &a) { return dim3(a.blocks_x * ((a.nrows + 7u) / 8u)); }
+
 // ------------------------------------- C ABI ---------------------------------------------------
 
 extern "C" {
@@ -2359,11 +2546,12 @@ static const size_t kMaxDeepCopies = 8;
 
 // This ctx's device copy of `orbit`, uploaded on first use.  A copy is never overwritten, and none is freed while a launch
 // that reads it may still be queued: past kMaxDeepCopies copies the device is drained and all of them go (mbk.h).
-static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const double4 **out)
+// *out points into ctx->deep: good until the next call.
+static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, mbk_ctx::DeepCopy **out)
 {
-    for (const mbk_ctx::DeepCopy &c : ctx->deep)
+    for (mbk_ctx::DeepCopy &c : ctx->deep)
         if (c.id == orbit->o.id) {
-            *out = c.d;
+            *out = &c;
             return MBK_OK;
         }
     if (ctx->deep.size() >= kMaxDeepCopies) {
@@ -2383,36 +2571,25 @@ static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const double4 **
     c.id = orbit->o.id;
     c.d = d;
     ctx->deep.push_back(c);
-    *out = d;
+    *out = &ctx->deep.back();
     return MBK_OK;
 }
 
 static int validate_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd, uint32_t flags)
 {
-    if (!orbit) return fail(ctx, MBK_ERR_INVALID, "orbit is NULL");
-    if (!v) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_DEEP_BLA))
-        return fail(ctx, MBK_ERR_INVALID, "deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES / MBK_DEEP_BLA only (no kernel selection, no fp32)");
-    if ((flags & MBK_DEEP_BLA) && orbit->o.length > (1u << 31))
-        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA: the orbit is longer than 2^31 (the table's indices are 32 bits wide)");
-    if (v->width == 0 || v->height == 0) return fail(ctx, MBK_ERR_INVALID, "empty view");
-    if (v->ncols == 0 || v->nrows == 0) return fail(ctx, MBK_ERR_INVALID, "empty window");
-    if ((uint64_t)v->col0 + v->ncols > v->width || (uint64_t)v->row0 + v->nrows > v->height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    if ((uint64_t)v->ncols * v->nrows > (1ull << 31)) return fail(ctx, MBK_ERR_INVALID, "window larger than 2^31 pixels");
-    for (double r : {v->range_r, v->range_i})
-        if (!std::isfinite(r) || !(r >= 0x1p-960) || !(r <= 4.0))
-            return fail(ctx, MBK_ERR_INVALID, "deep view ranges must be finite and lie in [2^-960, 4]");
-    if (mrd > orbit->o.mrd) return fail(ctx, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
-    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
-    return MBK_OK;
-}
-
-static double deep_step(double range, uint32_t n)
-{
-    if (n <= 1u) return 0.0;
-    volatile double s = range / (double)(n - 1u);
-    return s;
+    return validate_deep_view(
+        ctx, orbit, v, mrd, flags,
+        [&]() -> int {
+            if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_DEEP_BLA))
+                return fail(ctx, MBK_ERR_INVALID, "deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES / MBK_DEEP_BLA only (no kernel selection, no fp32)");
+            if ((flags & MBK_DEEP_BLA) && orbit->o.length > (1u << 31))
+                return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA: the orbit is longer than 2^31 (the table's indices are 32 bits wide)");
+            return MBK_OK;
+        },
+        [&]() -> int {
+            if (!deep_ranges_within(v, 0x1p-960)) return fail(ctx, MBK_ERR_INVALID, "deep view ranges must be finite and lie in [2^-960, 4]");
+            return MBK_OK;
+        });
 }
 
 // what the deep kernels share: the orbit, the view's geometry and window, mrd (every other field zero)
@@ -2423,24 +2600,13 @@ static void fill_deep_args(mbk::DeepArgs &a, const double4 *d_orbit, const mbk_d
     a.orbit = d_orbit;
     a.z1 = make_double4(t[4], t[5], t[6], t[7]);
     a.M = orbit->o.length;
-    a.half_r = (double)(v->width - 1u) * 0.5;
-    a.half_i = (double)(v->height - 1u) * 0.5;
-    a.step_r = deep_step(v->range_r, v->width);
-    a.step_i = deep_step(v->range_i, v->height);
-    a.col0 = v->col0;
-    a.row0 = v->row0;
-    a.ncols = v->ncols;
-    a.nrows = v->nrows;
-    a.blocks_x = (v->ncols + 7u) / 8u;
-    a.mrd = (int32_t)mrd;
+    fill_deep_window(a, v, mrd);
 }
 
 // dcmax of "Deep-zoom views with bilinear approximation": fl(|dc_r(column 0)| + |dc_i(row 0)|) of the FULL view
 static double deep_dcmax(const mbk_deep_view *v)
 {
-    volatile double dr = (0.0 - (double)(v->width - 1u) * 0.5) * deep_step(v->range_r, v->width);
-    volatile double di = (0.0 - (double)(v->height - 1u) * 0.5) * deep_step(v->range_i, v->height);
-    volatile double s = std::fabs(dr) + std::fabs(di);
+    volatile double s = std::fabs(deep_dc(0u, v->width, v->range_r)) + std::fabs(deep_dc(0u, v->height, v->range_i));
     return s;
 }
 
@@ -2449,18 +2615,13 @@ static double deep_dcmax(const mbk_deep_view *v)
 // reads the table it replaces may still be queued (mbk.h).  M >= 2.
 static int bla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, double dcmax, const mbk_ctx::DeepCopy **out)
 {
-    const double4 *d_orbit = nullptr;
-    int rc = deep_copy(ctx, orbit, &d_orbit);
-    if (rc != MBK_OK) return rc;
     mbk_ctx::DeepCopy *c = nullptr;
-    for (mbk_ctx::DeepCopy &k : ctx->deep)
-        if (k.id == orbit->o.id) c = &k;
+    int rc = deep_copy(ctx, orbit, &c);
+    if (rc != MBK_OK) return rc;
+    *out = c;
     uint64_t bits;
     std::memcpy(&bits, &dcmax, sizeof(bits));
-    if (c->has_bla && c->dcmax_bits == bits) {
-        *out = c;
-        return MBK_OK;
-    }
+    if (c->has_bla && c->dcmax_bits == bits) return MBK_OK;
     mbk::BlaTable t;
     try {
         mbk::build_bla_table(orbit->o.table, orbit->o.length, dcmax, &t);
@@ -2480,7 +2641,6 @@ static int bla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, double dcmax, con
     std::memcpy(c->off, t.off, sizeof(c->off));
     c->dcmax_bits = bits;
     c->has_bla = true;
-    *out = c;
     return MBK_OK;
 }
 
@@ -2496,74 +2656,24 @@ static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep
         mbk::DeepBlaArgs a;
         std::memset(&a, 0, sizeof(a));
         fill_deep_args(a.v, c->d, orbit, v, mrd);
-        a.v.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
-        a.v.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
-        a.v.counts = d_counts;
-        a.v.bytes = d_bytes;
-        a.v.smooth = d_smooth;
+        fill_outputs(a.v, mrd, d_counts, d_bytes, d_smooth);
         a.rc = c->d_rc;
         a.ab = c->d_ab;
         a.levels = c->levels;
         std::memcpy(a.off, c->off, sizeof(a.off));
-        const uint32_t blocks = a.v.blocks_x * ((v->nrows + 7u) / 8u);
-        hipLaunchKernelGGL(mbk::deep_bla_kernel, dim3(blocks), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL(mbk::deep_bla_kernel, block_grid(a.v), dim3(64), 0, stream, a);
         MBK_HIP(ctx, hipGetLastError());
         return MBK_OK;
     }
-    const double4 *d_orbit = nullptr;
-    int rc = deep_copy(ctx, orbit, &d_orbit);
+    mbk_ctx::DeepCopy *c = nullptr;
+    int rc = deep_copy(ctx, orbit, &c);
     if (rc != MBK_OK) return rc;
     mbk::DeepArgs a;
-    fill_deep_args(a, d_orbit, orbit, v, mrd);
-    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
-    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
-    a.counts = d_counts;
-    a.bytes = d_bytes;
-    a.smooth = d_smooth;
-    const uint32_t blocks = a.blocks_x * ((v->nrows + 7u) / 8u);
-    hipLaunchKernelGGL(mbk::deep_view_kernel, dim3(blocks), dim3(64), 0, stream, a);
+    fill_deep_args(a, c->d, orbit, v, mrd);
+    fill_outputs(a, mrd, d_counts, d_bytes, d_smooth);
+    hipLaunchKernelGGL(mbk::deep_view_kernel, block_grid(a), dim3(64), 0, stream, a);
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
-}
-
-int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
-                         int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_deep(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
-    rc = check_wanted(ctx, flags, d_counts, d_bytes);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_deep(ctx, orbit, view, mrd, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
-                       (hipStream_t)hip_stream, (flags & MBK_DEEP_BLA) != 0);
-}
-
-int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
-                          int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_deep(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
-                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                            return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream, (flags & MBK_DEEP_BLA) != 0);
-                        });
-}
-
-int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
-                         uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
-    int rc = validate_deep(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
-                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                           return launch_deep(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream, (flags & MBK_DEEP_BLA) != 0);
-                       });
 }
 
 // ---- host twins of the bilinear-approximation table and step (mbk_deep_bla.h): no ctx, no device -------------------------
@@ -2622,9 +2732,8 @@ int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *vi
     if (rc != MBK_OK) return rc;
     if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
     if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    volatile double dcr = ((double)col - (double)(view->width - 1u) * 0.5) * deep_step(view->range_r, view->width);
-    volatile double dci = ((double)row - (double)(view->height - 1u) * 0.5) * deep_step(view->range_i, view->height);
-    mbk::bla_count_host(orbit->o.table, orbit->o.length, t, dcr, dci, (int64_t)mrd, count, mag, steps_executed);
+    mbk::bla_count_host(orbit->o.table, orbit->o.length, t, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i),
+                        (int64_t)mrd, count, mag, steps_executed);
     return MBK_OK;
 }
 
@@ -2634,12 +2743,9 @@ int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *vi
 // Like the copy itself it is never overwritten and is freed with it.
 static int wide_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideEntry **out)
 {
-    const double4 *d_orbit = nullptr;
-    int rc = deep_copy(ctx, orbit, &d_orbit);
-    if (rc != MBK_OK) return rc;
     mbk_ctx::DeepCopy *c = nullptr;
-    for (mbk_ctx::DeepCopy &k : ctx->deep)
-        if (k.id == orbit->o.id) c = &k;
+    int rc = deep_copy(ctx, orbit, &c);
+    if (rc != MBK_OK) return rc;
     if (!c->d_wide) {
         const size_t bytes = orbit->o.wide.size() * sizeof(mbk::WideEntry);
         mbk::WideEntry *d = nullptr;
@@ -2657,23 +2763,20 @@ static int wide_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideE
 
 static int validate_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd, uint32_t flags)
 {
-    if (!orbit) return fail(ctx, MBK_ERR_INVALID, "orbit is NULL");
-    if (!v) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
-    if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES))
-        return fail(ctx, MBK_ERR_INVALID, "extended-range deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
-    if (v->width == 0 || v->height == 0) return fail(ctx, MBK_ERR_INVALID, "empty view");
-    if (v->ncols == 0 || v->nrows == 0) return fail(ctx, MBK_ERR_INVALID, "empty window");
-    if ((uint64_t)v->col0 + v->ncols > v->width || (uint64_t)v->row0 + v->nrows > v->height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    if ((uint64_t)v->ncols * v->nrows > (1ull << 31)) return fail(ctx, MBK_ERR_INVALID, "window larger than 2^31 pixels");
-    for (double r : {v->range_r, v->range_i})
-        if (!std::isfinite(r) || !(r >= 0x1p-64) || !(r <= 4.0))
-            return fail(ctx, MBK_ERR_INVALID, "extended-range deep view ranges must be finite and lie in [2^-64, 4]");
-    if (v->exp2 > 0 || v->exp2 < -8192) return fail(ctx, MBK_ERR_INVALID, "extended-range deep view exp2 must lie in [-8192, 0]");
-    if (mrd > orbit->o.mrd) return fail(ctx, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
-    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
-    return MBK_OK;
+    return validate_deep_view(
+        ctx, orbit, v, mrd, flags,
+        [&]() -> int {
+            if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
+            if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES))
+                return fail(ctx, MBK_ERR_INVALID, "extended-range deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
+            return MBK_OK;
+        },
+        [&]() -> int {
+            if (!deep_ranges_within(v, 0x1p-64))
+                return fail(ctx, MBK_ERR_INVALID, "extended-range deep view ranges must be finite and lie in [2^-64, 4]");
+            if (v->exp2 > 0 || v->exp2 < -8192) return fail(ctx, MBK_ERR_INVALID, "extended-range deep view exp2 must lie in [-8192, 0]");
+            return MBK_OK;
+        });
 }
 
 // the wide kernel on device pointers (validated by the caller), on `stream`
@@ -2689,65 +2792,11 @@ static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk
     a.z1 = orbit->o.wide[1];
     a.M = orbit->o.length;
     a.exp2 = v->exp2;
-    a.half_r = (double)(v->width - 1u) * 0.5;
-    a.half_i = (double)(v->height - 1u) * 0.5;
-    a.step_r = deep_step(v->range_r, v->width);
-    a.step_i = deep_step(v->range_i, v->height);
-    a.col0 = v->col0;
-    a.row0 = v->row0;
-    a.ncols = v->ncols;
-    a.nrows = v->nrows;
-    a.blocks_x = (v->ncols + 7u) / 8u;
-    a.mrd = (int32_t)mrd;
-    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
-    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
-    a.counts = d_counts;
-    a.bytes = d_bytes;
-    a.smooth = d_smooth;
-    const uint32_t blocks = a.blocks_x * ((v->nrows + 7u) / 8u);
-    hipLaunchKernelGGL(mbk::deep_wide_kernel, dim3(blocks), dim3(64), 0, stream, a);
+    fill_deep_window(a, v, mrd);
+    fill_outputs(a, mrd, d_counts, d_bytes, d_smooth);
+    hipLaunchKernelGGL(mbk::deep_wide_kernel, block_grid(a), dim3(64), 0, stream, a);
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
-}
-
-int mbk_deep_xview_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
-                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_deep_wide(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
-    rc = check_wanted(ctx, flags, d_counts, d_bytes);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_deep_wide(ctx, orbit, view, mrd, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
-                            (hipStream_t)hip_stream);
-}
-
-int mbk_deep_xview_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
-                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_deep_wide(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
-                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                            return launch_deep_wide(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
-                        });
-}
-
-int mbk_deep_xview_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
-    int rc = validate_deep_wide(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
-                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                           return launch_deep_wide(ctx, orbit, view, mrd, d_counts, d_bytes, d_smooth, stream);
-                       });
 }
 
 // host twin of the wide step (mbk_deep_wide.h): no ctx, no device
@@ -2758,9 +2807,8 @@ int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview 
     int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
     if (rc != MBK_OK) return rc;
     if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    volatile double dcr = ((double)col - (double)(view->width - 1u) * 0.5) * deep_step(view->range_r, view->width);
-    volatile double dci = ((double)row - (double)(view->height - 1u) * 0.5) * deep_step(view->range_i, view->height);
-    mbk::wide_count_host(orbit->o.wide, orbit->o.length, dcr, dci, view->exp2, (int64_t)mrd, count, mag);
+    mbk::wide_count_host(orbit->o.wide, orbit->o.length, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i),
+                         view->exp2, (int64_t)mrd, count, mag);
     return MBK_OK;
 }
 
@@ -2770,17 +2818,16 @@ int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview 
 static int launch_deep_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
                                 int32_t *d_counts, double *d_rel, hipStream_t stream)
 {
-    const double4 *d_orbit = nullptr;
-    int rc = deep_copy(ctx, orbit, &d_orbit);
+    mbk_ctx::DeepCopy *c = nullptr;
+    int rc = deep_copy(ctx, orbit, &c);
     if (rc != MBK_OK) return rc;
     mbk::DeepDistanceArgs a;
     std::memset(&a, 0, sizeof(a));
-    fill_deep_args(a.v, d_orbit, orbit, v, mrd);
+    fill_deep_args(a.v, c->d, orbit, v, mrd);
     a.v.counts = d_counts;
     a.range_r = v->range_r;
     a.rel = d_rel;
-    const uint32_t blocks = a.v.blocks_x * ((v->nrows + 7u) / 8u);
-    hipLaunchKernelGGL(mbk::deep_distance_kernel, dim3(blocks), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(mbk::deep_distance_kernel, block_grid(a.v), dim3(64), 0, stream, a);
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
 }
@@ -2820,9 +2867,9 @@ double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double 
 
 // ---- Julia views (mbk_julia.h; mbk.h "Julia views") ----------------------------------------------------------
 
-// Everything a Julia launch can refuse, before anything is allocated, enqueued or written.  flags: MBK_WANT_* and kernel
-// selection; quantised: the launch produces bytes.
-static int julia_check(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags, bool quantised)
+// Everything a Julia launch can refuse, before anything is allocated, enqueued or written.  flags: MBK_WANT_* (MBK_WANT_BYTES:
+// the launch produces bytes) and kernel selection.
+static int julia_check(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags)
 {
     if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_KERNEL_MASK))
         return fail(ctx, MBK_ERR_INVALID, "Julia views take MBK_WANT_COUNTS / MBK_WANT_BYTES and kernel selection only (no fp32, no MBK_LAZY_UNIFORM)");
@@ -2834,7 +2881,7 @@ static int julia_check(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, 
     int rc = validate_view(ctx, v, &dummy);
     if (rc != MBK_OK) return rc;
     if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
-    if (quantised && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
     return MBK_OK;
 }
 
@@ -2850,13 +2897,9 @@ static int launch_julia(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i,
     a.cr = c_r;
     a.ci = c_i;
     a.mrd = (int32_t)mrd;
-    a.quant_wide = (mrd >= (1u << 23)) ? 1u : 0u;
-    a.quant_rcp = mrd ? 1.0 / (double)mrd : 0.0;
+    fill_outputs(a, mrd, d_counts, d_bytes, d_smooth);
     a.exact_steps = ctx->opt[MBK_OPT_EXACT_STEPS];
     a.cyc_window = ctx->opt[MBK_OPT_CYCLE_WINDOW];
-    a.counts = d_counts;
-    a.bytes = d_bytes;
-    a.smooth = d_smooth;
     const uint32_t kernel = flags & MBK_KERNEL_MASK;
     const bool literal = mbk::julia_needs_literal(c_i);
     const bool per_step = kernel == MBK_KERNEL_ASM || literal || !mbk::julia_grouped_ok(c_r, c_i);
@@ -2887,44 +2930,150 @@ static int launch_julia(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i,
     return MBK_OK;
 }
 
-int mbk_julia_view_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
-                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+// ---- the count calls of the deep, extended-range and Julia views, and what renders and histograms share with them --------
+
+// Everything a sample launch on `t` can refuse, before anything is allocated, enqueued or written: the rules of the kind's own
+// launch.  flags: the kind's flags and MBK_WANT_* for what the launch produces (MBK_WANT_BYTES: the quantised form).  A caller
+// with flag or source rules of its own (renders, histograms) applies them first.
+static int target_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    switch (t.kind) {
+        case Target::kWide: return validate_deep_wide(ctx, t.orbit, t.has_view ? &t.wide : nullptr, mrd, flags);
+        case Target::kDeep: return validate_deep(ctx, t.orbit, t.has_view ? &t.deep : nullptr, mrd, flags);
+        case Target::kJulia: return julia_check(ctx, t.has_view ? &t.view : nullptr, t.c_r, t.c_i, mrd, flags);
+        case Target::kPlain: break;
+    }
+    bool dummy;
+    int rc = validate_view(ctx, t.has_view ? &t.view : nullptr, &dummy, (flags & MBK_PRECISION_F32) != 0);
+    if (rc != MBK_OK) return rc;
+    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if ((flags & MBK_WANT_BYTES) && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    if ((flags & MBK_KERNEL_MASK) > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
+    return MBK_OK;
+}
+
+// Where a launch writes: each pointer may be null.  values: the smooth nu, or with `distance` the distance estimate of the
+// kind (plain views: de; deep views: rel).
+struct Outputs {
+    int32_t *counts;
+    uint8_t *bytes;
+    double *values;
+    bool distance;
+};
+
+// The launch of a checked target (target_check) on device pointers, on `stream`: the one place that knows which kernels serve
+// which kind.  flags: the kind's flags; the outputs say what is wanted.
+static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const Outputs &o, hipStream_t stream)
+{
+    switch (t.kind) {
+        case Target::kWide: return launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream);
+        case Target::kDeep:
+            return o.distance ? launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
+                              : launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
+        case Target::kJulia: return launch_julia(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.bytes, o.values, stream);
+        case Target::kPlain: break;
+    }
+    if (o.distance) {
+        bool safe = false;
+        int rc = distance_check(ctx, &t.view, mrd, flags, &safe);
+        if (rc != MBK_OK) return rc;
+        return launch_distance(ctx, &t.view, mrd, flags, safe, o.counts, o.values, stream);
+    }
+    const uint32_t want = (o.counts ? MBK_WANT_COUNTS : 0u) | (o.bytes ? MBK_WANT_BYTES : 0u);
+    return launch_tile(ctx, &t.view, mrd, (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES)) | want, o.counts, o.bytes, stream, o.values);
+}
+
+// The three forms of a count call on a target: device pointers on a stream, host pointers synchronously, host pointers on a slot.
+static int target_view_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, int32_t *d_counts, uint8_t *d_bytes,
+                              double *d_smooth, void *hip_stream)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
-    int rc = julia_check(ctx, view, c_r, c_i, mrd, flags, wb);
+    int rc = target_check(ctx, t, mrd, flags);
     if (rc != MBK_OK) return rc;
+    const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
     if (!wc && !wb && !d_smooth) return fail(ctx, MBK_ERR_INVALID, "flags and d_smooth select no output");
     rc = check_wanted(ctx, flags, d_counts, d_bytes);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_julia(ctx, view, c_r, c_i, mrd, flags, wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth,
-                        (hipStream_t)hip_stream);
+    return target_launch(ctx, t, mrd, flags, Outputs{wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth, false}, (hipStream_t)hip_stream);
+}
+
+static int target_view_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, int32_t *h_counts, uint8_t *h_bytes,
+                               double *h_smooth, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = target_check(ctx, t, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    return view_compute(ctx, (size_t)t.g.ncols * t.g.nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
+                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                            return target_launch(ctx, t, mrd, flags, Outputs{d_counts, d_bytes, d_smooth, false}, stream);
+                        });
+}
+
+static int target_view_submit(mbk_ctx *ctx, int slot, const Target &t, uint32_t mrd, uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
+    int rc = target_check(ctx, t, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    return view_submit(ctx, slot, (size_t)t.g.ncols * t.g.nrows, mrd, flags, h_counts, h_bytes,
+                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
+                           return target_launch(ctx, t, mrd, flags, Outputs{d_counts, d_bytes, d_smooth, false}, stream);
+                       });
+}
+
+int mbk_deep_view_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                         int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+{
+    return target_view_launch(ctx, deep_target(orbit, view), mrd, flags, d_counts, d_bytes, d_smooth, hip_stream);
+}
+
+int mbk_deep_view_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                          int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+{
+    return target_view_compute(ctx, deep_target(orbit, view), mrd, flags, h_counts, h_bytes, h_smooth, stats);
+}
+
+int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                         uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
+{
+    return target_view_submit(ctx, slot, deep_target(orbit, view), mrd, flags, h_counts, h_bytes);
+}
+
+int mbk_deep_xview_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+{
+    return target_view_launch(ctx, wide_target(orbit, view), mrd, flags, d_counts, d_bytes, d_smooth, hip_stream);
+}
+
+int mbk_deep_xview_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                           int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
+{
+    return target_view_compute(ctx, wide_target(orbit, view), mrd, flags, h_counts, h_bytes, h_smooth, stats);
+}
+
+int mbk_deep_xview_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                          uint32_t flags, int32_t *h_counts, uint8_t *h_bytes)
+{
+    return target_view_submit(ctx, slot, wide_target(orbit, view), mrd, flags, h_counts, h_bytes);
+}
+
+int mbk_julia_view_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                          int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream)
+{
+    return target_view_launch(ctx, julia_target(view, c_r, c_i), mrd, flags, d_counts, d_bytes, d_smooth, hip_stream);
 }
 
 int mbk_julia_view_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
                            int32_t *h_counts, uint8_t *h_bytes, double *h_smooth, mbk_stats *stats)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = julia_check(ctx, view, c_r, c_i, mrd, flags, (flags & MBK_WANT_BYTES) != 0);
-    if (rc != MBK_OK) return rc;
-    return view_compute(ctx, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes, h_smooth, stats,
-                        [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                            return launch_julia(ctx, view, c_r, c_i, mrd, flags, d_counts, d_bytes, d_smooth, stream);
-                        });
+    return target_view_compute(ctx, julia_target(view, c_r, c_i), mrd, flags, h_counts, h_bytes, h_smooth, stats);
 }
 
 int mbk_julia_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
                           int32_t *h_counts, uint8_t *h_bytes)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (slot < 0 || slot >= MBK_SLOTS) return fail(ctx, MBK_ERR_INVALID, "slot out of range");
-    int rc = julia_check(ctx, view, c_r, c_i, mrd, flags, (flags & MBK_WANT_BYTES) != 0);
-    if (rc != MBK_OK) return rc;
-    return view_submit(ctx, slot, (size_t)view->ncols * view->nrows, mrd, flags, h_counts, h_bytes,
-                       [&](int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream) {
-                           return launch_julia(ctx, view, c_r, c_i, mrd, flags, d_counts, d_bytes, d_smooth, stream);
-                       });
+    return target_view_submit(ctx, slot, julia_target(view, c_r, c_i), mrd, flags, h_counts, h_bytes);
 }
 
 int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, double *mag)
@@ -3033,127 +3182,49 @@ static int stream_lut(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const
     return MBK_OK;
 }
 
-// What a render renders: a view (deep == nullptr), a deep view on its orbit, the Julia set of (c_r, c_i) on a view (julia), or an
-// extended-range deep view on its orbit (wide).
-struct RenderTarget {
-    const mbk_view *view;
-    const mbk_deep_orbit *orbit;
-    const mbk_deep_view *deep;
-    uint32_t width, height, col0, row0, ncols, nrows;   // of the OUTPUT
-    bool julia;
-    double c_r, c_i;
-    const mbk_deep_xview *wide;   // an extended-range deep view on `orbit`
+// What a render takes from each kind of view beyond the sample launch's own rules (target_check), by Target::Kind: the flags it
+// passes on, and the text that refuses MBK_RENDER_DISTANCE / MBK_RENDER_DISTANCE_REL where the kind has no such estimate.
+struct RenderRules {
+    uint32_t flags;
+    const char *bad_flags, *no_distance, *no_distance_rel;
+};
+static const RenderRules kRenderRules[4] = {
+    {MBK_KERNEL_MASK | MBK_PRECISION_F32, "render flags carry kernel selection (and MBK_PRECISION_F32) only", nullptr,
+     "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)"},
+    {MBK_KERNEL_MASK, "Julia render flags carry kernel selection only", "MBK_RENDER_DISTANCE is implemented for Mandelbrot views only (no Julia renders)",
+     "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)"},
+    {MBK_DEEP_BLA, "deep renders take MBK_DEEP_BLA only (no kernel selection, no fp32)",
+     "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)", nullptr},
+    {0u, "extended-range deep renders take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)",
+     "distance estimates are not implemented for extended-range deep views", "distance estimates are not implemented for extended-range deep views"},
 };
 
-// The targets of the four kinds of view.  A NULL view makes a target of neither kind, which render_check refuses in its turn.
-static RenderTarget view_target(const mbk_view *v)
-{
-    if (!v) return RenderTarget{};
-    return RenderTarget{v, nullptr, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0, nullptr};
-}
-static RenderTarget deep_target(const mbk_deep_orbit *orbit, const mbk_deep_view *v)
-{
-    if (!v) return RenderTarget{};
-    return RenderTarget{nullptr, orbit, v, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0, nullptr};
-}
-static RenderTarget wide_target(const mbk_deep_orbit *orbit, const mbk_deep_xview *v)
-{
-    if (!v) return RenderTarget{};
-    return RenderTarget{nullptr, orbit, nullptr, v->width, v->height, v->col0, v->row0, v->ncols, v->nrows, false, 0.0, 0.0, v};
-}
-static RenderTarget julia_target(const mbk_view *v, double c_r, double c_i)
-{
-    RenderTarget t = view_target(v);
-    t.julia = true;
-    t.c_r = c_r;
-    t.c_i = c_i;
-    return t;
-}
-
-// The sample view / window of the output window (col0, row0, ncols, nrows) of `t`
-static void sample_window(const RenderTarget &t, uint32_t s, uint32_t col0, uint32_t row0, uint32_t ncols, uint32_t nrows,
-                          mbk_view *v, mbk_deep_view *d, mbk_deep_xview *x)
-{
-    if (t.wide) {
-        *x = *t.wide;
-        x->width = t.width * s;
-        x->height = t.height * s;
-        x->col0 = col0 * s;
-        x->row0 = row0 * s;
-        x->ncols = ncols * s;
-        x->nrows = nrows * s;
-    } else if (t.deep) {
-        *d = *t.deep;
-        d->width = t.width * s;
-        d->height = t.height * s;
-        d->col0 = col0 * s;
-        d->row0 = row0 * s;
-        d->ncols = ncols * s;
-        d->nrows = nrows * s;
-    } else {
-        *v = *t.view;
-        v->width = t.width * s;
-        v->height = t.height * s;
-        v->col0 = col0 * s;
-        v->row0 = row0 * s;
-        v->ncols = ncols * s;
-        v->nrows = nrows * s;
-    }
-}
-
 // Everything a render can refuse, before anything is allocated, enqueued or written.
-static int render_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+static int render_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                         const void *out, bool equalized = false, const double *h_lut = nullptr, uint32_t lut_len = 0u)
 {
     int rc = validate_render_spec(ctx, spec, equalized);
     if (rc != MBK_OK) return rc;
     if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!t.view && !t.deep && !t.wide) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if (!t.has_view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     const uint32_t s = spec->supersample;
-    if ((uint64_t)t.width * s > 0xffffffffull || (uint64_t)t.height * s > 0xffffffffull)
+    if ((uint64_t)t.g.width * s > 0xffffffffull || (uint64_t)t.g.height * s > 0xffffffffull)
         return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t.col0 + t.ncols > t.width || (uint64_t)t.row0 + t.nrows > t.height)
+    if ((uint64_t)t.g.col0 + t.g.ncols > t.g.width || (uint64_t)t.g.row0 + t.g.nrows > t.g.height)
         return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
     const bool dist = spec->source == MBK_RENDER_DISTANCE;
     const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;
     const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel || equalized;   // (the distance samples obey the smooth launch's rules)
-    mbk_view sv;
-    mbk_deep_view sd;
-    mbk_deep_xview sx;
-    sample_window(t, s, t.col0, t.row0, t.ncols, t.nrows, &sv, &sd, &sx);
-    if (t.wide) {
-        if (dist || rel) return fail(ctx, MBK_ERR_INVALID, "distance estimates are not implemented for extended-range deep views");
-        if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep renders take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)");
-        rc = validate_deep_wide(ctx, t.orbit, &sx, mrd, smooth ? 0u : MBK_WANT_BYTES);
-        if (rc != MBK_OK || !equalized) return rc;
-        return validate_lut(ctx, h_lut, lut_len, mrd);
-    }
-    if (t.deep) {
-        if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)");
-        if (flags & ~MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep renders take MBK_DEEP_BLA only (no kernel selection, no fp32)");
-        if (flags && rel) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for deep distance estimates");
-        rc = validate_deep(ctx, t.orbit, &sd, mrd, (smooth ? 0u : MBK_WANT_BYTES) | flags);
-        if (rc != MBK_OK || !equalized) return rc;
-        return validate_lut(ctx, h_lut, lut_len, mrd);
-    }
-    if (rel) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)");
-    if (t.julia) {
-        if (dist) return fail(ctx, MBK_ERR_INVALID, "MBK_RENDER_DISTANCE is implemented for Mandelbrot views only (no Julia renders)");
-        if (flags & ~MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "Julia render flags carry kernel selection only");
-        rc = julia_check(ctx, &sv, t.c_r, t.c_i, mrd, flags, !smooth);
-        if (rc != MBK_OK || !equalized) return rc;
-        return validate_lut(ctx, h_lut, lut_len, mrd);
-    }
-    if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
-        return fail(ctx, MBK_ERR_INVALID, "render flags carry kernel selection (and MBK_PRECISION_F32) only");
-    const bool f32 = (flags & MBK_PRECISION_F32) != 0;
-    bool dummy;
-    rc = validate_view(ctx, &sv, &dummy, f32);
+    const RenderRules &rules = kRenderRules[t.kind];
+    if (dist && rules.no_distance) return fail(ctx, MBK_ERR_INVALID, rules.no_distance);
+    if (rel && rules.no_distance_rel) return fail(ctx, MBK_ERR_INVALID, rules.no_distance_rel);
+    if (flags & ~rules.flags) return fail(ctx, MBK_ERR_INVALID, rules.bad_flags);
+    if ((flags & MBK_DEEP_BLA) && rel) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for deep distance estimates");
+    rc = target_check(ctx, target_samples(t, s, t.g.col0, t.g.row0, t.g.ncols, t.g.nrows), mrd, flags | (smooth ? 0u : MBK_WANT_BYTES));
     if (rc != MBK_OK) return rc;
-    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
-    if (!smooth && mrd == 0) return fail(ctx, MBK_ERR_INVALID, "mrd == 0 has no quantised form (division by zero)");
+    // (what follows can be true of a plain view only: no other kind takes these flags)
+    const bool f32 = (flags & MBK_PRECISION_F32) != 0;
     const uint32_t kernel = flags & MBK_KERNEL_MASK;
-    if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
     if ((smooth || f32) && (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL))
         return fail(ctx, MBK_ERR_INVALID, "smooth colouring and MBK_PRECISION_F32 are implemented by the scan / asm / group kernels only");
     if (smooth && f32) return fail(ctx, MBK_ERR_INVALID, "smooth colouring is implemented in binary64 only");
@@ -3164,12 +3235,11 @@ static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
 // A checked render (render_check) onto the device image d_out (ncols x nrows words), on `stream`.  stat: the slot whose
 // reduction scratch adds up the statistics of the samples and whose ev_k1 marks the last resolve kernel (_compute), or NULL.
-static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                       uint32_t *d_out, hipStream_t stream, Slot *stat, const double *h_lut = nullptr, uint32_t lut_len = 0u)
 {
     const uint32_t s = spec->supersample;
-    const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;              // (deep views: rel in place of de, the same colour rule)
-    const bool dist = spec->source == MBK_RENDER_DISTANCE || rel;
+    const bool dist = spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL;   // (deep views: rel in place of de, the same colour rule)
     const bool eq = spec->source == MBK_RENDER_EQUALIZED;                  // (the smooth samples, coloured through the table)
     const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || eq;   // (same sample layout: binary64 value | counts)
     StreamScratch *sc = nullptr;
@@ -3184,27 +3254,16 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
         if (rc != MBK_OK) return rc;
     }
 
-    // bands: rows of the output window whose samples fit the budget, and pieces of columns if one row's do not
-    const uint64_t per_px = (uint64_t)s * s * (smooth ? 12u : (stat ? 5u : 1u));
-    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;   // (the parts of the scratch start on 256-byte lines)
-    uint32_t tile_cols = t.ncols, band_rows;
-    if ((uint64_t)t.ncols * per_px <= budget) {
-        band_rows = (uint32_t)std::min<uint64_t>(t.nrows, budget / ((uint64_t)t.ncols * per_px));
-    } else {
-        band_rows = 1u;
-        tile_cols = (uint32_t)(budget / per_px);
-    }
-    if (spec->max_band_rows) band_rows = std::min(band_rows, spec->max_band_rows);
-    const size_t cap_samples = (size_t)tile_cols * s * band_rows * s;
+    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (smooth ? 12u : (stat ? 5u : 1u)), spec->max_band_rows);
+    const size_t cap_samples = plan.cap_px() * s * s;
     // layout: SMOOTH nu | counts; BYTES counts (statistics only) | bytes
     const size_t off2 = smooth ? round_up_256(cap_samples * 8u) : (stat ? round_up_256(cap_samples * 4u) : 0u);
     const size_t need = off2 + (smooth ? cap_samples * 4u : cap_samples);
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
     if (rc != MBK_OK) return rc;
     uint8_t *base = (uint8_t *)sc->d_render;
-    double *d_nu = smooth ? (double *)base : nullptr;
-    int32_t *d_counts = smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr);
-    uint8_t *d_bytes = smooth ? nullptr : base + off2;
+    const Outputs samples = {smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr), smooth ? nullptr : base + off2,
+                             smooth ? (double *)base : nullptr, dist};
     const double *d_lut = eq ? sc->d_lut : nullptr;
     const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
 
@@ -3213,68 +3272,42 @@ static int render_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_
     const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
     const uint32_t wg_per_cu = use_lds ? (uint32_t)std::min<size_t>(8u, std::max<size_t>(1u, (160u << 10) / lds)) : 8u;
 
-    for (uint32_t r = 0; r < t.nrows; r += band_rows) {
-        const uint32_t nr = std::min(band_rows, t.nrows - r);
-        for (uint32_t c = 0; c < t.ncols; c += tile_cols) {
-            const uint32_t nc = std::min(tile_cols, t.ncols - c);
-            mbk_view sv;
-            mbk_deep_view sd;
-            mbk_deep_xview sx;
-            sample_window(t, s, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd, &sx);
-            if (t.wide) {
-                rc = launch_deep_wide(ctx, t.orbit, &sx, mrd, d_counts, d_bytes, d_nu, stream);
-            } else if (t.deep) {
-                rc = rel ? launch_deep_distance(ctx, t.orbit, &sd, mrd, d_counts, d_nu, stream)
-                         : launch_deep(ctx, t.orbit, &sd, mrd, d_counts, d_bytes, d_nu, stream, (flags & MBK_DEEP_BLA) != 0);
-            } else if (t.julia) {
-                rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, d_bytes, d_nu, stream);
-            } else if (dist) {
-                bool safe = false;
-                rc = distance_check(ctx, &sv, mrd, flags, &safe);
-                if (rc == MBK_OK) rc = launch_distance(ctx, &sv, mrd, flags, safe, d_counts, d_nu, stream);
-            } else
-                rc = launch_tile(ctx, &sv, mrd, flags | (d_counts ? MBK_WANT_COUNTS : 0u) | (d_bytes ? MBK_WANT_BYTES : 0u),
-                                 d_counts, d_bytes, stream, d_nu);
-            if (rc != MBK_OK) return rc;
-            mbk::RenderArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.counts = d_counts;
-            a.smooth = d_nu;
-            a.bytes = d_bytes;
-            a.out = d_out + (size_t)r * t.ncols + c;
-            a.pitch = (uint64_t)nc * s;
-            a.out_pitch = t.ncols;
-            a.ncols = nc;
-            a.nrows = nr;
-            const uint32_t px_per_wg = mbk::kRenderThreads * (smooth ? 1u : mbk::kRenderBytesPx);
-            a.chunks_x = (nc + px_per_wg - 1u) / px_per_wg;
-            a.lds_palette = use_lds ? 1u : 0u;
-            a.pal = render_palette(spec, d_palette);
-            a.pal.lut = d_lut;
-            a.pal.lut_mrd = eq ? lut_len - 2u : 0u;
-            const uint64_t pieces = (uint64_t)a.chunks_x * nr;
-            const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
-            if (dist)
-                mbk::launch_resolve<true, mbk::kRuleDistance>(s, grid, use_lds ? lds : 0u, stream, a);
-            else if (eq)
-                mbk::launch_resolve<true, mbk::kRuleEqualized>(s, grid, use_lds ? lds : 0u, stream, a);
-            else if (smooth)
-                mbk::launch_resolve<true>(s, grid, use_lds ? lds : 0u, stream, a);
-            else
-                mbk::launch_resolve<false>(s, grid, use_lds ? lds : 0u, stream, a);
-            MBK_HIP(ctx, hipGetLastError());
-            if (stat) {
-                if (r + nr == t.nrows && c + nc == t.ncols) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
-                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, (uint64_t)nc * s * nr * s, mrd, stream, false);
-                if (rc != MBK_OK) return rc;
-            }
-        }
-    }
-    return MBK_OK;
+    return for_each_band(ctx, plan, samples.counts, (uint64_t)s * s, mrd, stream, stat, [&](uint32_t r, uint32_t c, uint32_t nr, uint32_t nc, bool) -> int {
+        int rc = target_launch(ctx, target_samples(t, s, t.g.col0 + c, t.g.row0 + r, nc, nr), mrd, flags, samples, stream);
+        if (rc != MBK_OK) return rc;
+        mbk::RenderArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.counts = samples.counts;
+        a.smooth = samples.values;
+        a.bytes = samples.bytes;
+        a.out = d_out + (size_t)r * t.g.ncols + c;
+        a.pitch = (uint64_t)nc * s;
+        a.out_pitch = t.g.ncols;
+        a.ncols = nc;
+        a.nrows = nr;
+        const uint32_t px_per_wg = mbk::kRenderThreads * (smooth ? 1u : mbk::kRenderBytesPx);
+        a.chunks_x = (nc + px_per_wg - 1u) / px_per_wg;
+        a.lds_palette = use_lds ? 1u : 0u;
+        a.pal = render_palette(spec, d_palette);
+        a.pal.lut = d_lut;
+        a.pal.lut_mrd = eq ? lut_len - 2u : 0u;
+        const uint64_t pieces = (uint64_t)a.chunks_x * nr;
+        const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
+        if (dist)
+            mbk::launch_resolve<true, mbk::kRuleDistance>(s, grid, use_lds ? lds : 0u, stream, a);
+        else if (eq)
+            mbk::launch_resolve<true, mbk::kRuleEqualized>(s, grid, use_lds ? lds : 0u, stream, a);
+        else if (smooth)
+            mbk::launch_resolve<true>(s, grid, use_lds ? lds : 0u, stream, a);
+        else
+            mbk::launch_resolve<false>(s, grid, use_lds ? lds : 0u, stream, a);
+        MBK_HIP(ctx, hipGetLastError());
+        return MBK_OK;
+    });
 }
 
 // equalized (here and in render_compute): the call carries the table h_lut[lut_len] and takes MBK_RENDER_EQUALIZED only
-static int render_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+static int render_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                          uint8_t *d_rgba, void *hip_stream, bool equalized = false, const double *h_lut = nullptr,
                          uint32_t lut_len = 0u)
 {
@@ -3286,7 +3319,7 @@ static int render_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint
     return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, h_lut, lut_len);
 }
 
-static int render_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+static int render_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                           uint8_t *h_rgba, mbk_stats *stats, bool equalized = false, const double *h_lut = nullptr,
                           uint32_t lut_len = 0u)
 {
@@ -3296,7 +3329,7 @@ static int render_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uin
     rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
-    const size_t px = (size_t)t.ncols * t.nrows;
+    const size_t px = (size_t)t.g.ncols * t.g.nrows;
     auto enqueue = [&]() -> int {
         int rc = grow(ctx, ctx->d_rgba, ctx->rgba_cap_px, px, px * sizeof(uint32_t));
         if (rc != MBK_OK) return rc;
@@ -3541,92 +3574,60 @@ int mbk_counts_histogram(mbk_ctx *ctx, const int32_t *d_counts, uint64_t n, uint
     return MBK_OK;
 }
 
+// The flags a histogram passes on to the sample launch of each kind of view, by Target::Kind
+struct HistRules {
+    uint32_t flags;
+    const char *bad_flags;
+};
+static const HistRules kHistRules[4] = {
+    {MBK_KERNEL_MASK | MBK_PRECISION_F32, "histogram flags carry kernel selection and MBK_PRECISION_F32 only"},
+    {MBK_KERNEL_MASK, "Julia histogram flags carry kernel selection only"},
+    {MBK_DEEP_BLA, "deep histograms take MBK_DEEP_BLA only (no kernel selection, no fp32)"},
+    {0u, "extended-range deep histograms take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)"},
+};
+
 // Everything a view histogram can refuse, before anything is allocated, enqueued or written: the sample launch's own rules.
-static int hist_check(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, const void *out)
+static int hist_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const void *out)
 {
     if (!out) return fail(ctx, MBK_ERR_INVALID, "histogram pointer is NULL");
-    if (!t.view && !t.deep && !t.wide) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if (!t.has_view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     int rc = check_hist_mrd(ctx, mrd);
     if (rc != MBK_OK) return rc;
-    if (t.wide) {
-        if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep histograms take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)");
-        return validate_deep_wide(ctx, t.orbit, t.wide, mrd, MBK_WANT_COUNTS);
-    }
-    if (t.deep) {
-        if (flags & ~MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep histograms take MBK_DEEP_BLA only (no kernel selection, no fp32)");
-        return validate_deep(ctx, t.orbit, t.deep, mrd, MBK_WANT_COUNTS | flags);
-    }
-    if (t.julia) {
-        if (flags & ~MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "Julia histogram flags carry kernel selection only");
-        return julia_check(ctx, t.view, t.c_r, t.c_i, mrd, flags, false);
-    }
-    if (flags & ~(MBK_KERNEL_MASK | MBK_PRECISION_F32))
-        return fail(ctx, MBK_ERR_INVALID, "histogram flags carry kernel selection and MBK_PRECISION_F32 only");
-    const bool f32 = (flags & MBK_PRECISION_F32) != 0;
-    bool dummy;
-    rc = validate_view(ctx, t.view, &dummy, f32);
+    if (flags & ~kHistRules[t.kind].flags) return fail(ctx, MBK_ERR_INVALID, kHistRules[t.kind].bad_flags);
+    rc = target_check(ctx, t, mrd, flags | MBK_WANT_COUNTS);
     if (rc != MBK_OK) return rc;
-    const uint32_t kernel = flags & MBK_KERNEL_MASK;
-    if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
-    if (f32 && (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL))
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;   // (a plain view's only: no other kind takes MBK_PRECISION_F32)
+    if ((flags & MBK_PRECISION_F32) && (kernel == MBK_KERNEL_SIMPLE || kernel == MBK_KERNEL_REFILL))
         return fail(ctx, MBK_ERR_INVALID, "MBK_PRECISION_F32 is implemented by the scan / asm / group kernels only");
     return MBK_OK;
 }
 
 // A checked histogram (hist_check) added into the device table d_hist, on `stream`: the window's counts band by band through
-// the stream's render scratch (4 bytes per sample, at most MBK_RENDER_BAND_BYTES: the bands of render_run).  stat as for
-// render_run: its reduction scratch adds up the statistics, its ev_k1 marks the last histogram kernel.
-static int hist_run(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, unsigned long long *d_hist,
+// the stream's render scratch (4 bytes per sample: the bands of render_run).  stat as for render_run: its reduction scratch
+// adds up the statistics, its ev_k1 marks the last histogram kernel.
+static int hist_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, unsigned long long *d_hist,
                     hipStream_t stream, Slot *stat)
 {
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
-    const uint64_t per_px = 4u;
-    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;
-    uint32_t tile_cols = t.ncols, band_rows;
-    if ((uint64_t)t.ncols * per_px <= budget) {
-        band_rows = (uint32_t)std::min<uint64_t>(t.nrows, budget / ((uint64_t)t.ncols * per_px));
-    } else {
-        band_rows = 1u;
-        tile_cols = (uint32_t)(budget / per_px);
-    }
-    const size_t need = (size_t)tile_cols * band_rows * per_px;
+    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, 4u);
+    const size_t need = plan.cap_px() * 4u;
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
     if (rc != MBK_OK) return rc;
     int32_t *d_counts = (int32_t *)sc->d_render;   // (sc may move when a launch below adds a stream's scratch: not used past here)
     const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
-    for (uint32_t r = 0; r < t.nrows; r += band_rows) {
-        const uint32_t nr = std::min(band_rows, t.nrows - r);
-        for (uint32_t c = 0; c < t.ncols; c += tile_cols) {
-            const uint32_t nc = std::min(tile_cols, t.ncols - c);
-            mbk_view sv;
-            mbk_deep_view sd;
-            mbk_deep_xview sx;
-            sample_window(t, 1u, t.col0 + c, t.row0 + r, nc, nr, &sv, &sd, &sx);
-            if (t.wide)
-                rc = launch_deep_wide(ctx, t.orbit, &sx, mrd, d_counts, nullptr, nullptr, stream);
-            else if (t.deep)
-                rc = launch_deep(ctx, t.orbit, &sd, mrd, d_counts, nullptr, nullptr, stream, (flags & MBK_DEEP_BLA) != 0);
-            else if (t.julia)
-                rc = launch_julia(ctx, &sv, t.c_r, t.c_i, mrd, flags, d_counts, nullptr, nullptr, stream);
-            else
-                rc = launch_tile(ctx, &sv, mrd, flags | MBK_WANT_COUNTS, d_counts, nullptr, stream);
-            if (rc != MBK_OK) return rc;
-            const uint64_t n = (uint64_t)nc * nr;
-            mbk::launch_counts_histogram(d_counts, n, mrd, d_hist, cus, stream);
-            MBK_HIP(ctx, hipGetLastError());
-            if (stat) {
-                if (r + nr == t.nrows && c + nc == t.ncols) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
-                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, n, mrd, stream, false);
-                if (rc != MBK_OK) return rc;
-            }
-        }
-    }
-    return MBK_OK;
+    return for_each_band(ctx, plan, d_counts, 1u, mrd, stream, stat, [&](uint32_t r, uint32_t c, uint32_t nr, uint32_t nc, bool) -> int {
+        int rc = target_launch(ctx, target_samples(t, 1u, t.g.col0 + c, t.g.row0 + r, nc, nr), mrd, flags,
+                               Outputs{d_counts, nullptr, nullptr, false}, stream);
+        if (rc != MBK_OK) return rc;
+        mbk::launch_counts_histogram(d_counts, (uint64_t)nc * nr, mrd, d_hist, cus, stream);
+        MBK_HIP(ctx, hipGetLastError());
+        return MBK_OK;
+    });
 }
 
-static int hist_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, uint64_t *d_hist, void *hip_stream)
+static int hist_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, uint64_t *d_hist, void *hip_stream)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
     int rc = hist_check(ctx, t, mrd, flags, d_hist);
@@ -3636,7 +3637,7 @@ static int hist_launch(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32
     return hist_run(ctx, t, mrd, flags, (unsigned long long *)d_hist, (hipStream_t)hip_stream, nullptr);
 }
 
-static int hist_compute(mbk_ctx *ctx, const RenderTarget &t, uint32_t mrd, uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
+static int hist_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, uint64_t *h_hist, mbk_stats *stats)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
     int rc = hist_check(ctx, t, mrd, flags, h_hist);
@@ -3770,16 +3771,8 @@ static int density_run(mbk_ctx *ctx, const mbk_view *v, const mbk::DensityTarget
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
-    const uint64_t per_px = mbk::kDensityCompact ? 8u : 4u;
-    const uint64_t budget = MBK_RENDER_BAND_BYTES - 1024u;
-    uint32_t tile_cols = v->ncols, band_rows;
-    if ((uint64_t)v->ncols * per_px <= budget) {
-        band_rows = (uint32_t)std::min<uint64_t>(v->nrows, budget / ((uint64_t)v->ncols * per_px));
-    } else {
-        band_rows = 1u;
-        tile_cols = (uint32_t)(budget / per_px);
-    }
-    const size_t cap = (size_t)tile_cols * band_rows;
+    const BandPlan plan = band_plan(v->ncols, v->nrows, mbk::kDensityCompact ? 8u : 4u);
+    const size_t cap = plan.cap_px();
     const size_t off2 = round_up_256(cap * 4u);
     const size_t need = mbk::kDensityCompact ? off2 + cap * 4u : cap * 4u;
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
@@ -3790,39 +3783,30 @@ static int density_run(mbk_ctx *ctx, const mbk_view *v, const mbk::DensityTarget
     int32_t *d_counts = (int32_t *)sc->d_render;
     uint32_t *d_list = mbk::kDensityCompact ? (uint32_t *)((uint8_t *)sc->d_render + off2) : nullptr;
     uint32_t *d_bands = sc->d_density_bands;
-    for (uint32_t r = 0; r < v->nrows; r += band_rows) {
-        const uint32_t nr = std::min(band_rows, v->nrows - r);
-        for (uint32_t c = 0; c < v->ncols; c += tile_cols) {
-            const uint32_t nc = std::min(tile_cols, v->ncols - c);
-            mbk_view sv = *v;
-            sv.col0 = v->col0 + c;
-            sv.row0 = v->row0 + r;
-            sv.ncols = nc;
-            sv.nrows = nr;
-            rc = launch_tile(ctx, &sv, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
-            if (rc != MBK_OK) return rc;
-            if (mbk::kDensityCompact) MBK_HIP(ctx, hipMemsetAsync(d_bands, 0, 2u * mbk::kDensityBands * sizeof(uint32_t), stream));
-            mbk::DensityArgs a;
-            std::memset(&a, 0, sizeof(a));
-            fill_window(a, &sv);
-            a.min_count = minc;
-            a.max_count = maxc;
-            a.t = dt;
-            a.counts = d_counts;
-            a.table = d_table;
-            a.stat = d_stat;
-            a.list = d_list;
-            a.bands = d_bands;
-            mbk::launch_density_replay(a, stream);
-            MBK_HIP(ctx, hipGetLastError());
-            if (stat) {
-                if (r + nr == v->nrows && c + nc == v->ncols) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
-                rc = launch_reduce(ctx, stat->d_red, stat->h_red, d_counts, nullptr, (uint64_t)nc * nr, mrd, stream, false);
-                if (rc != MBK_OK) return rc;
-            }
-        }
-    }
-    return MBK_OK;
+    return for_each_band(ctx, plan, d_counts, 1u, mrd, stream, stat, [&](uint32_t r, uint32_t c, uint32_t nr, uint32_t nc, bool) -> int {
+        mbk_view sv = *v;
+        sv.col0 = v->col0 + c;
+        sv.row0 = v->row0 + r;
+        sv.ncols = nc;
+        sv.nrows = nr;
+        int rc = launch_tile(ctx, &sv, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+        if (rc != MBK_OK) return rc;
+        if (mbk::kDensityCompact) MBK_HIP(ctx, hipMemsetAsync(d_bands, 0, 2u * mbk::kDensityBands * sizeof(uint32_t), stream));
+        mbk::DensityArgs a;
+        std::memset(&a, 0, sizeof(a));
+        fill_window(a, &sv);
+        a.min_count = minc;
+        a.max_count = maxc;
+        a.t = dt;
+        a.counts = d_counts;
+        a.table = d_table;
+        a.stat = d_stat;
+        a.list = d_list;
+        a.bands = d_bands;
+        mbk::launch_density_replay(a, stream);
+        MBK_HIP(ctx, hipGetLastError());
+        return MBK_OK;
+    });
 }
 
 int mbk_view_density_launch(mbk_ctx *ctx, const mbk_view *view, const mbk_density_target *target, uint32_t mrd, uint32_t min_count,

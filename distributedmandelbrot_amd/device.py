@@ -592,6 +592,52 @@ class MandelbrotDevice:
             return getattr(self._lib, "mbk_deep_xview_" + name), 0
         return getattr(self._lib, "mbk_deep_view_" + name), (L.MBK_DEEP_BLA if bla else 0)
 
+    # One body per operation serves the four kinds of view.  A kind is named by keywords: orbit (a deep view, plain or wide,
+    # with bla), c (the Julia set of c on a view, with kernel), neither (a plain view, with kernel and precision).
+    def _cany(self, view, window, orbit=None, **_):
+        return self._cdeep(view, window) if orbit is not None else self._cview(view, window)
+
+    def _kind_fn(self, name: str, view, cv, *, orbit=None, c=None, kernel: str = "default", precision: str = "f64", bla: bool = False,
+                 source: Optional[str] = None):
+        """(the C entry point `name` for this kind of view, its arguments between the ctx and mrd, its flags)"""
+        if orbit is not None:
+            fn, flags = self._deep_fn(view, name, bla, source)
+            return fn, (orbit._h, C.byref(cv)), flags
+        if c is not None:
+            return getattr(self._lib, "mbk_julia_view_" + name), (C.byref(cv), float(c[0]), float(c[1])), L.KERNELS[kernel]
+        return getattr(self._lib, "mbk_view_" + name), (C.byref(cv),), L.KERNELS[kernel] | L.PRECISIONS[precision]
+
+    def _render(self, form: str, view, mrd: int, palette, source, supersample, window, max_band_rows, lut, histogram, *, out=None,
+                d_rgba: int = 0, stream: int = 0, **kind):
+        """render_* (form "compute": into the host array `out`, returns (rgba, TileStats)) and launch_render_* (form "launch":
+        into d_rgba on `stream`) of any kind of view; histogram() is the whole view's, for source "equalized" without a lut."""
+        cv = self._cany(view, window, **kind)
+        rgba = self._render_out(cv, out) if form == "compute" else None
+        spec = palette.spec(source, supersample, max_band_rows)
+        equalized = source == "equalized"
+        fn, lead, flags = self._kind_fn(("render_equalized_" if equalized else "render_") + form, view, cv, source=source, **kind)
+        table = ()
+        if equalized:
+            lut = self._lut(lut, histogram)
+            table = (lut.ctypes.data, lut.size)
+        st = L.mbk_stats()
+        tail = (rgba.ctypes.data, C.byref(st)) if form == "compute" else (d_rgba or None, stream or None)
+        self._check(fn(self._h, *lead, mrd, flags, C.byref(spec), *table, *tail))
+        return (rgba, _stats(st)) if form == "compute" else None
+
+    def _histogram(self, view, mrd: int, window, want_stats: bool, **kind):
+        cv = self._cany(view, window, **kind)
+        hist = np.empty(max(int(mrd), 0), np.uint64)
+        st = L.mbk_stats()
+        fn, lead, flags = self._kind_fn("histogram_compute", view, cv, **kind)
+        self._check(fn(self._h, *lead, mrd, flags, hist.ctypes.data if hist.size else None, C.byref(st)))
+        return (hist, _stats(st)) if want_stats else hist
+
+    def _launch_histogram(self, view, mrd: int, d_hist: int, stream: int, window, **kind) -> None:
+        cv = self._cany(view, window, **kind)
+        fn, lead, flags = self._kind_fn("histogram_launch", view, cv, **kind)
+        self._check(fn(self._h, *lead, mrd, flags, d_hist or None, stream or None))
+
     def compute_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_counts: bool = True,
                           want_bytes: bool = True, want_smooth: bool = False, out_counts: Optional[np.ndarray] = None,
                           out_bytes: Optional[np.ndarray] = None, bla: bool = False):
@@ -668,18 +714,8 @@ class MandelbrotDevice:
         Source "equalized" colours nu through an equalisation table (image.equalize_lut; Palette.for_equalized): `lut`, or
         with lut=None the table of the histogram of the WHOLE view at output resolution (view_histogram: s = 1, `window`
         ignored, so that every band of an image, on any GPU, uses one table); 8 * mrd bytes and the image cross PCIe."""
-        cv = self._cview(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec(source, supersample, max_band_rows)
-        st = L.mbk_stats()
-        if source == "equalized":
-            lut = self._lut(lut, lambda: self.view_histogram(view, mrd, kernel=kernel))
-            self._check(self._lib.mbk_view_render_equalized_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
-                                                                    lut.ctypes.data, lut.size, rgba.ctypes.data, C.byref(st)))
-        else:
-            self._check(self._lib.mbk_view_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
-                                                          rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._render("compute", view, mrd, palette, source, supersample, window, max_band_rows, lut,
+                            lambda: self.view_histogram(view, mrd, kernel=kernel), out=out, kernel=kernel)
 
     @staticmethod
     def _lut(lut, histogram) -> np.ndarray:
@@ -697,48 +733,22 @@ class MandelbrotDevice:
         "distance", the plain views' estimate in plane units, is refused (MbkError).  Source "equalized" and `lut` as for
         render_view (the table of deep_view_histogram of the whole view when lut is None).  bla: the samples (and that
         histogram) are those of compute_deep_view(bla=True); refused with source "distance_rel"."""
-        cv = self._cdeep(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec(source, supersample, max_band_rows)
-        st = L.mbk_stats()
-        if source == "equalized":
-            fn, flags = self._deep_fn(view, "render_equalized_compute", bla, source)
-            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla))
-            self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), lut.ctypes.data, lut.size, rgba.ctypes.data,
-                           C.byref(st)))
-        else:
-            fn, flags = self._deep_fn(view, "render_compute", bla, source)
-            self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._render("compute", view, mrd, palette, source, supersample, window, max_band_rows, lut,
+                            lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla), out=out, orbit=orbit, bla=bla)
 
     def launch_render_view(self, view: View, mrd: int, *, palette, d_rgba: int, source: str = "smooth", supersample: int = 1,
                            stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0, lut=None) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes (e.g. a torch tensor's data_ptr()) on
         ``stream`` (0 = HIP's null stream).  Source "equalized" with lut=None first takes the whole view's histogram
         synchronously (view_histogram), as render_view does."""
-        cv = self._cview(view, window)
-        spec = palette.spec(source, supersample, max_band_rows)
-        if source == "equalized":
-            lut = self._lut(lut, lambda: self.view_histogram(view, mrd, kernel=kernel))
-            self._check(self._lib.mbk_view_render_equalized_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
-                                                                   lut.ctypes.data, lut.size, d_rgba or None, stream or None))
-            return
-        self._check(self._lib.mbk_view_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
-                                                     d_rgba or None, stream or None))
+        self._render("launch", view, mrd, palette, source, supersample, window, max_band_rows, lut,
+                     lambda: self.view_histogram(view, mrd, kernel=kernel), d_rgba=d_rgba, stream=stream, kernel=kernel)
 
     def launch_render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, d_rgba: int,
                                 source: str = "smooth", supersample: int = 1, stream: int = 0, window=None,
                                 max_band_rows: int = 0, lut=None, bla: bool = False) -> None:
-        cv = self._cdeep(view, window)
-        spec = palette.spec(source, supersample, max_band_rows)
-        if source == "equalized":
-            fn, flags = self._deep_fn(view, "render_equalized_launch", bla, source)
-            lut = self._lut(lut, lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla))
-            self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), lut.ctypes.data, lut.size, d_rgba or None,
-                           stream or None))
-            return
-        fn, flags = self._deep_fn(view, "render_launch", bla, source)
-        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, C.byref(spec), d_rgba or None, stream or None))
+        self._render("launch", view, mrd, palette, source, supersample, window, max_band_rows, lut,
+                     lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla), d_rgba=d_rgba, stream=stream, orbit=orbit, bla=bla)
 
     # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
     def view_histogram(self, view: View, mrd: int, *, window=None, kernel: str = "default", precision: str = "f64",
@@ -746,36 +756,22 @@ class MandelbrotDevice:
         """The histogram of the window's escape counts, built on the GPU: uint64[mrd], hist[c] the number of samples whose
         count is c.  Only 8 * mrd bytes cross PCIe.  want_stats: (hist, TileStats) -- never_pixels and pixel_iterations from
         the reduction over the same counts, hist[0] and sum c hist[c] + (mrd - 1) hist[0]."""
-        cv = self._cview(view, window)
-        hist = np.empty(max(int(mrd), 0), np.uint64)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_view_histogram_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel] | L.PRECISIONS[precision],
-                                                         hist.ctypes.data if hist.size else None, C.byref(st)))
-        return (hist, _stats(st)) if want_stats else hist
+        return self._histogram(view, mrd, window, want_stats, kernel=kernel, precision=precision)
 
     def deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_stats: bool = False,
                             bla: bool = False):
         """view_histogram for a deep view (bla: of the counts of compute_deep_view(bla=True))."""
-        cv = self._cdeep(view, window)
-        hist = np.empty(max(int(mrd), 0), np.uint64)
-        st = L.mbk_stats()
-        fn, flags = self._deep_fn(view, "histogram_compute", bla)
-        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, hist.ctypes.data if hist.size else None, C.byref(st)))
-        return (hist, _stats(st)) if want_stats else hist
+        return self._histogram(view, mrd, window, want_stats, orbit=orbit, bla=bla)
 
     def launch_view_histogram(self, view: View, mrd: int, *, d_hist: int, stream: int = 0, window=None, kernel: str = "default",
                               precision: str = "f64") -> None:
         """Asynchronous form: the window's histogram is ADDED into the DEVICE table d_hist (uint64[mrd]; the caller clears it)
         on ``stream`` (0 = HIP's null stream)."""
-        cv = self._cview(view, window)
-        self._check(self._lib.mbk_view_histogram_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel] | L.PRECISIONS[precision],
-                                                        d_hist or None, stream or None))
+        self._launch_histogram(view, mrd, d_hist, stream, window, kernel=kernel, precision=precision)
 
     def launch_deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_hist: int, stream: int = 0,
                                    window=None, bla: bool = False) -> None:
-        cv = self._cdeep(view, window)
-        fn, flags = self._deep_fn(view, "histogram_launch", bla)
-        self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, d_hist or None, stream or None))
+        self._launch_histogram(view, mrd, d_hist, stream, window, orbit=orbit, bla=bla)
 
     def counts_histogram(self, d_counts: int, n: int, mrd: int, d_hist: int, stream: int = 0) -> None:
         """Asynchronous: the histogram of n int32 counts in DEVICE memory is ADDED into the DEVICE table d_hist (uint64[mrd])
@@ -876,51 +872,25 @@ class MandelbrotDevice:
                           kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None):
         """render_view for the Julia set of c: source "bytes", "smooth" or "equalized" (`lut` as for render_view: None takes
         the table of julia_view_histogram of the whole view); the distance sources are refused (MbkError)."""
-        cv = self._cview(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec(source, supersample, max_band_rows)
-        st = L.mbk_stats()
-        if source == "equalized":
-            lut = self._lut(lut, lambda: self.julia_view_histogram(view, c, mrd, kernel=kernel))
-            self._check(self._lib.mbk_julia_view_render_equalized_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
-                                                                          L.KERNELS[kernel], C.byref(spec), lut.ctypes.data, lut.size,
-                                                                          rgba.ctypes.data, C.byref(st)))
-        else:
-            self._check(self._lib.mbk_julia_view_render_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
-                                                                L.KERNELS[kernel], C.byref(spec), rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._render("compute", view, mrd, palette, source, supersample, window, max_band_rows, lut,
+                            lambda: self.julia_view_histogram(view, c, mrd, kernel=kernel), out=out, c=c, kernel=kernel)
 
     def launch_render_julia_view(self, view: View, c, mrd: int, *, palette, d_rgba: int, source: str = "smooth",
                                  supersample: int = 1, stream: int = 0, window=None, kernel: str = "default",
                                  max_band_rows: int = 0, lut=None) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream``; "equalized" with lut=None first
         takes the whole view's histogram synchronously, as render_julia_view does."""
-        cv = self._cview(view, window)
-        spec = palette.spec(source, supersample, max_band_rows)
-        if source == "equalized":
-            lut = self._lut(lut, lambda: self.julia_view_histogram(view, c, mrd, kernel=kernel))
-            self._check(self._lib.mbk_julia_view_render_equalized_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
-                                                                         L.KERNELS[kernel], C.byref(spec), lut.ctypes.data, lut.size,
-                                                                         d_rgba or None, stream or None))
-            return
-        self._check(self._lib.mbk_julia_view_render_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
-                                                           C.byref(spec), d_rgba or None, stream or None))
+        self._render("launch", view, mrd, palette, source, supersample, window, max_band_rows, lut,
+                     lambda: self.julia_view_histogram(view, c, mrd, kernel=kernel), d_rgba=d_rgba, stream=stream, c=c, kernel=kernel)
 
     def julia_view_histogram(self, view: View, c, mrd: int, *, window=None, kernel: str = "default", want_stats: bool = False):
         """view_histogram for the Julia set of c."""
-        cv = self._cview(view, window)
-        hist = np.empty(max(int(mrd), 0), np.uint64)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_julia_view_histogram_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
-                                                               hist.ctypes.data if hist.size else None, C.byref(st)))
-        return (hist, _stats(st)) if want_stats else hist
+        return self._histogram(view, mrd, window, want_stats, c=c, kernel=kernel)
 
     def launch_julia_view_histogram(self, view: View, c, mrd: int, *, d_hist: int, stream: int = 0, window=None,
                                     kernel: str = "default") -> None:
         """Asynchronous form: the window's histogram is ADDED into the DEVICE table d_hist (uint64[mrd]) on ``stream``."""
-        cv = self._cview(view, window)
-        self._check(self._lib.mbk_julia_view_histogram_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
-                                                              d_hist or None, stream or None))
+        self._launch_histogram(view, mrd, d_hist, stream, window, c=c, kernel=kernel)
 
     # -- stored chunks (include/mbk.h, "Stored chunks") ---------------------------------------------
     def decode_chunk(self, stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None):

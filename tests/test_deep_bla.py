@@ -213,3 +213,52 @@ def test_the_plain_contract_is_untouched():
     assert L.MBK_DEEP_BLA == 0x8000 and not L.MBK_DEEP_BLA & taken
     s = _case(1)
     assert np.array_equal(s["plain"], _truth(1))
+
+
+# ---- the refusals of the deep validator, line by line, through the host-only calls (no ctx: the calling thread's text) ----
+
+RANGE = "deep view ranges must be finite and lie in [2^-960, 4]"
+TOO_DEEP = "mrd exceeds the mrd the reference orbit was computed for"
+# (what differs from a served call, the message); orbit mrd 100, view 16 x 16 of span 1e-10, pixel (3, 4), mrd 50
+DEEP_REFUSALS = [
+    (dict(orbit=None), "orbit is NULL"),
+    (dict(view=None), "view is NULL"),
+    (dict(width=0), "empty view"),
+    (dict(height=0), "empty view"),
+    (dict(ncols=0), "empty window"),
+    (dict(nrows=0), "empty window"),
+    (dict(col0=10, ncols=7), "window exceeds the view"),
+    (dict(row0=16, nrows=1), "window exceeds the view"),
+    (dict(width=1 << 16, height=1 << 16, ncols=1 << 16, nrows=(1 << 15) + 1), "window larger than 2^31 pixels"),
+    (dict(range_r=2.0 ** -961), RANGE),
+    (dict(range_i=4.5), RANGE),
+    (dict(range_r=float("nan")), RANGE),
+    (dict(range_i=float("inf")), RANGE),
+    (dict(mrd=101), TOO_DEEP),
+    (dict(col=16), "pixel outside the view"),
+    (dict(row=16), "pixel outside the view"),
+    # two faults at once: the one reported
+    (dict(orbit=None, range_r=float("nan")), "orbit is NULL"),
+    (dict(width=0, mrd=101), "empty view"),
+]
+
+
+@pytest.mark.parametrize("change, message", DEEP_REFUSALS, ids=[",".join(c) for c, _ in DEEP_REFUSALS])
+def test_validator_refusals_status_and_message(change, message):
+    from distributedmandelbrot_amd import DeepOrbit
+    from distributedmandelbrot_amd.device import _error_text
+    L, lib = _lib()
+    orbit = DeepOrbit("0", "1", 100, min_span=1e-10)
+    f = dict(dict(range_r=1e-10, range_i=1e-10, width=16, height=16, col0=0, row0=0, ncols=16, nrows=16), **change)
+    cv = L.mbk_deep_view(*[f[k] for k in ("range_r", "range_i", "width", "height", "col0", "row0", "ncols", "nrows")])
+    h = orbit._h if "orbit" not in change else None
+    pv = C.byref(cv) if "view" not in change else None
+    cc, mm, ss = C.c_int32(-7), C.c_double(-7.0), C.c_uint64(7)
+    st = lib.mbk_deep_bla_count_host(h, pv, f.get("col", 3), f.get("row", 4), f.get("mrd", 50), C.byref(cc), C.byref(mm), C.byref(ss))
+    assert (st, _error_text(lib)) == (L.MBK_ERR_INVALID, message)
+    assert (cc.value, mm.value, ss.value) == (-7, -7.0, 7)
+    if message not in (TOO_DEEP, "pixel outside the view"):      # mbk_deep_bla_info runs the same validator and takes no pixel
+        levels, entries = C.c_uint32(9), C.c_uint64(9)
+        st = lib.mbk_deep_bla_info(h, pv, C.byref(levels), C.byref(entries))
+        assert (st, _error_text(lib)) == (L.MBK_ERR_INVALID, message)
+        assert (levels.value, entries.value) == (9, 9)

@@ -232,3 +232,49 @@ def test_view_refusals_write_nothing():
 def test_struct_layout():
     assert C.sizeof(L.mbk_deep_xview) == 2 * 8 + 7 * 4 + 4      # padded to the alignment of its doubles
     assert L.mbk_deep_xview.exp2.offset == 16 and L.mbk_deep_xview.width.offset == 20
+
+
+WIDE_RANGE = "extended-range deep view ranges must be finite and lie in [2^-64, 4]"
+WIDE_EXP2 = "extended-range deep view exp2 must lie in [-8192, 0]"
+# (what differs from a served call, the message); orbit mrd 100, view 16 x 16 of span 2^-50, pixel (3, 4), mrd 50
+WIDE_REFUSALS = [
+    (dict(orbit=None), "orbit is NULL"),
+    (dict(view=None), "view is NULL"),
+    (dict(width=0), "empty view"),
+    (dict(height=0), "empty view"),
+    (dict(ncols=0), "empty window"),
+    (dict(nrows=0), "empty window"),
+    (dict(col0=10, ncols=7), "window exceeds the view"),
+    (dict(row0=16, nrows=1), "window exceeds the view"),
+    (dict(width=1 << 16, height=1 << 16, ncols=1 << 16, nrows=(1 << 15) + 1), "window larger than 2^31 pixels"),
+    (dict(range_r=2.0 ** -65), WIDE_RANGE),
+    (dict(range_i=4.5), WIDE_RANGE),
+    (dict(range_r=float("nan")), WIDE_RANGE),
+    (dict(range_i=float("inf")), WIDE_RANGE),
+    (dict(exp2=1), WIDE_EXP2),
+    (dict(exp2=-8193), WIDE_EXP2),
+    (dict(mrd=101), "mrd exceeds the mrd the reference orbit was computed for"),
+    (dict(col=16), "pixel outside the view"),
+    (dict(row=16), "pixel outside the view"),
+    # two faults at once: the one reported
+    (dict(orbit=None, range_r=float("nan")), "orbit is NULL"),
+    (dict(width=0, mrd=101), "empty view"),
+    (dict(range_r=8.0, exp2=1), WIDE_RANGE),
+    (dict(exp2=1, mrd=101), WIDE_EXP2),
+    (dict(mrd=101, col=16), "mrd exceeds the mrd the reference orbit was computed for"),
+]
+
+
+@pytest.mark.parametrize("change, message", WIDE_REFUSALS, ids=[",".join(c) for c, _ in WIDE_REFUSALS])
+def test_validator_refusals_status_and_message(change, message):
+    """Every line of the wide validator through the host-only call (no ctx: the calling thread's error text)."""
+    from distributedmandelbrot_amd.device import _error_text
+    lib = L.load()
+    orbit = DeepOrbit("0", "1", 100, precision_bits=128)
+    f = dict(dict(range_r=1.0, range_i=1.0, exp2=-50, width=16, height=16, col0=0, row0=0, ncols=16, nrows=16), **change)
+    cv = L.mbk_deep_xview(*[f[k] for k in ("range_r", "range_i", "exp2", "width", "height", "col0", "row0", "ncols", "nrows")])
+    c, m = C.c_int32(-7), C.c_double(-7.0)
+    st = lib.mbk_deep_xview_count_host(orbit._h if "orbit" not in change else None, C.byref(cv) if "view" not in change else None,
+                                       f.get("col", 3), f.get("row", 4), f.get("mrd", 50), C.byref(c), C.byref(m))
+    assert (st, _error_text(lib)) == (L.MBK_ERR_INVALID, message)
+    assert (c.value, m.value) == (-7, -7.0)

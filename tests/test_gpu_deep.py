@@ -120,6 +120,44 @@ def test_submit_torch_launch_and_render_equal_compute(gpu):
     assert np.array_equal(rc, c) and np.array_equal(rb, b) and per[0]["bands"] == 3
 
 
+def test_launch_compute_and_submit_equal_the_model_on_a_ragged_window(gpu):
+    """27 x 19 view, window (3, 2, 21, 13): partial 8 x 8 blocks on both edges and a nonzero origin; the orbit escapes at M = 58,
+    so every pixel that runs on rebases (mrd 96).  The three forms, plain and with the bilinear approximation, bit for bit."""
+    import torch
+    mrd, window = 96, (3, 2, 21, 13)
+    orbit = DeepOrbit("1e-21", "1", mrd, min_span=1e-20)
+    assert orbit.escaped and orbit.length == 58
+    view = DeepView(1e-20, 27, 19)
+    mc, _ = _model(orbit, view, mrd, window)
+    assert mc.max() > orbit.length and len(np.unique(mc)) >= 8
+    exact = None
+    for bla in (False, True):
+        c, b, sm, st = gpu.compute_deep_view(orbit, view, mrd, window=window, want_smooth=True, bla=bla)
+        if not bla:
+            assert np.array_equal(c, mc) and np.array_equal(b, _bytes(mc, mrd))
+            exact = c
+        else:
+            assert (c == exact).mean() >= 0.99
+        sc, sb = np.full((13, 21), -7, np.int32), np.full((13, 21), 0xA5, np.uint8)
+        gpu.submit_deep_view(3, orbit, view, mrd, window=window, out_counts=sc, out_bytes=sb, bla=bla)
+        sst = gpu.wait(3)
+        assert np.array_equal(sc, c) and np.array_equal(sb, b)
+        assert (sst.pixel_iterations, sst.never_pixels, sst.rle_runs) == (st.pixel_iterations, st.never_pixels, st.rle_runs)
+        px = 13 * 21
+        dc = torch.full((px + 32,), -7, dtype=torch.int32, device="cuda:0")
+        db = torch.full((px + 32,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        ds = torch.full((px + 32,), -7.0, dtype=torch.float64, device="cuda:0")
+        torch.cuda.synchronize()
+        gpu.launch_deep_view(orbit, view, mrd, window=window, d_counts=dc.data_ptr() + 64, d_bytes=db.data_ptr() + 16,
+                             d_smooth=ds.data_ptr() + 128, bla=bla)
+        torch.cuda.synchronize()
+        gc, gb, gs = dc.cpu().numpy(), db.cpu().numpy(), ds.cpu().numpy()
+        assert np.array_equal(gc[16:16 + px].reshape(13, 21), c) and (gc[:16] == -7).all() and (gc[16 + px:] == -7).all()
+        assert np.array_equal(gb[16:16 + px].reshape(13, 21), b) and (gb[:16] == 0xA5).all() and (gb[16 + px:] == 0xA5).all()
+        assert np.array_equal(gs[16:16 + px].reshape(13, 21).view(np.uint64), sm.view(np.uint64))
+        assert (gs[:16] == -7.0).all() and (gs[16 + px:] == -7.0).all()
+
+
 def test_agrees_with_the_strict_path_at_1e_6(gpu):
     """Sanity: where binary64 still resolves the view, the deep path and the strict linspace path see the same picture (their
     coordinates differ by rounding only).  Measured (the numpy model and the C oracle, which the GPU equals): 99.22 % at mrd
