@@ -99,6 +99,11 @@ class mbk_chunk_spec(C.Structure):
     _fields_ = [("palette", C.c_void_p), ("scale", C.c_uint32)]
 
 
+class mbk_interior_render_spec(C.Structure):
+    _fields_ = [("supersample", C.c_uint32), ("palette", C.c_void_p), ("palette_len", C.c_uint32),
+                ("unknown", C.c_uint8 * 4), ("outside", C.c_uint8 * 4), ("scale", C.c_double), ("max_band_rows", C.c_uint32)]
+
+
 class mbk_density_target(C.Structure):
     _fields_ = [("start_r", C.c_double), ("start_i", C.c_double), ("range_r", C.c_double), ("range_i", C.c_double),
                 ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -303,6 +308,18 @@ SIGNATURES = {
                                                    C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_julia_count_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double)]),
+    "mbk_view_interior_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "mbk_view_interior_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_interior_host": (C.c_int, [C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "mbk_view_interior_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                  C.POINTER(mbk_interior_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_view_interior_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                   C.POINTER(mbk_interior_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_interior_resolve_host": (C.c_int, [C.POINTER(mbk_interior_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "mbk_view_density_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_view_density_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,

@@ -32,6 +32,7 @@
 #include "mbk_render.h"
 #include "mbk_chunks.h"
 #include "mbk_distance.h"
+#include "mbk_interior.h"
 #include "mbk_deep_distance.h"
 #include "mbk_julia.h"
 #include "mbk_density.h"
@@ -147,7 +148,7 @@ struct StreamScratch {
     size_t chunk_cap_n = 0;
     uint8_t *d_chunk_bytes = nullptr;
     uint32_t *h_chunk_status = nullptr;
-    // distance estimates (mbk_distance.h): the counts of a two-pass launch whose caller wants none
+    // distance estimates and interior views (mbk_distance.h, mbk_interior.h): the counts of a two-pass launch whose caller wants none
     int32_t *d_dist_counts = nullptr;
     size_t dist_cap_px = 0;
     // equalised renders (mbk_histogram.h): the table of the last one, kept like the palette
@@ -1450,16 +1451,20 @@ static int sync_end(mbk_ctx *ctx, int rc, mbk_stats *stats, bool have_bytes, boo
     return stats ? slot_stats(ctx, sl, stats, have_bytes, reduced) : MBK_OK;
 }
 
-// The calls that return one binary64 value per pixel (smooth, distance, deep distance) between sync_begin and the return:
-// launch(d_counts, d_values, stream) enqueues the kernels that write both.
+// The calls that return one binary64 value per pixel (smooth, distance, deep distance, interior) between sync_begin and the return:
+// launch(d_counts, d_values, stream) enqueues the kernels that write both.  with_tail (interior views): the device values are
+// followed by px int32 (the periods, at d_values + px), which the launch writes too; they go to h_tail, and h_values and h_tail
+// may each be NULL.
 template <typename Launch>
-static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch)
+static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch,
+                          bool with_tail = false, int32_t *h_tail = nullptr)
 {
     Slot &sl = ctx->s[0];
     auto enqueue = [&]() -> int {
         int rc = ensure_buffers(ctx, sl, px);
         if (rc != MBK_OK) return rc;
-        rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, px, px * sizeof(double));
+        const size_t cap = with_tail ? px + (px + 1u) / 2u : px;   // (in binary64 values)
+        rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, cap, cap * sizeof(double));
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
         rc = launch(sl.d_counts, ctx->d_smooth, sl.stream);
@@ -1468,7 +1473,8 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
         rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-        MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        if (h_values) MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        if (h_tail) MBK_HIP(ctx, hipMemcpyAsync(h_tail, ctx->d_smooth + px, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
         ctx->last_px = 0;   // (no bytes on the device: mbk_serialize_last has nothing to read)
@@ -2271,6 +2277,95 @@ double mbk_distance_value_host(double mag, double dmag, int32_t count)
     return mbk::distance_value(mag, dmag, count);
 }
 
+// ---- interior views (mbk_interior.h; mbk.h "Interior views") -----------------------------------------------------------
+
+// Everything an interior launch can refuse, before anything is allocated, enqueued or written.
+static int interior_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, bool *safe)
+{
+    int rc = validate_view(ctx, view, safe);
+    if (rc != MBK_OK) return rc;
+    if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (flags & ~(uint32_t)MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "interior views take kernel selection only (binary64, no other flag)");
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel != MBK_KERNEL_DEFAULT && kernel != MBK_KERNEL_SCAN && kernel != MBK_KERNEL_GROUP)
+        return fail(ctx, MBK_ERR_INVALID, "interior views are implemented with the default / scan / group kernels only");
+    return MBK_OK;
+}
+
+// A checked launch: the escape kernels the selector names write the counts, then the interior pass runs every count-0 pixel.
+// d_period or d_distance may be null.
+static int launch_interior(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags, bool safe, int32_t *d_counts,
+                           int32_t *d_period, double *d_distance, hipStream_t stream)
+{
+    const size_t px = (size_t)v->ncols * v->nrows;
+    if (!d_counts) {
+        StreamScratch *sc = nullptr;
+        int rc = get_scratch(ctx, stream, &sc);
+        if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
+        if (rc != MBK_OK) return rc;
+        d_counts = sc->d_dist_counts;
+    }
+    int rc = launch_tile(ctx, v, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+    if (rc != MBK_OK) return rc;
+    mbk::InteriorArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_window(a, v);
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+    a.counts_in = d_counts;
+    a.period = d_period;
+    a.distance = d_distance;
+    const dim3 grid(a.blocks_x * ((v->nrows + 7u) / 8u)), block(64);   // (at most 2^31 / 64 blocks: validate_view)
+    if (safe) hipLaunchKernelGGL(mbk::interior_kernel<false>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(mbk::interior_kernel<true>, grid, block, 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+int mbk_view_interior_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *d_counts,
+                             int32_t *d_period, double *d_distance, void *hip_stream)
+{
+    if (!ctx || (!d_period && !d_distance)) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = interior_check(ctx, view, mrd, flags, &safe);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_interior(ctx, view, mrd, flags, safe, d_counts, d_period, d_distance, (hipStream_t)hip_stream);
+}
+
+int mbk_view_interior_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *h_counts,
+                              int32_t *h_period, double *h_distance, mbk_stats *stats)
+{
+    if (!ctx || !view || (!h_period && !h_distance)) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = interior_check(ctx, view, mrd, flags, &safe);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    const size_t px = (size_t)view->ncols * view->nrows;
+    return compute_values(ctx, px, mrd, h_counts, h_distance, stats,
+                          [&](int32_t *d_counts, double *d_distance, hipStream_t stream) {
+                              return launch_interior(ctx, view, mrd, flags, safe, d_counts, h_period ? (int32_t *)(d_distance + px) : nullptr,
+                                                     h_distance ? d_distance : nullptr, stream);
+                          },
+                          true, h_period);
+}
+
+int mbk_interior_host(double c_r, double c_i, uint32_t mrd, int32_t *count, int32_t *period, int32_t *cycle_len, double *de)
+{
+    if (!count) return fail(nullptr, MBK_ERR_INVALID, "count is NULL");
+    if (mrd > 0x7fffffffu) return fail(nullptr, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    // the literal doubling throughout: the contract's step, which the fused form equals wherever a launch takes it
+    double mag = 0.0, d = 0.0;
+    int32_t L = 0, p = 0;
+    *count = mbk::julia_count<false>(c_r, c_i, c_r, c_i, (int32_t)mrd, &mag);
+    mbk::interior_pixel<false>(c_r, c_i, (int32_t)mrd, *count, L, p, d);
+    if (period) *period = p;
+    if (cycle_len) *cycle_len = L;
+    if (de) *de = d;
+    return MBK_OK;
+}
+
 int mbk_serialize_last(mbk_ctx *ctx, uint8_t *h_out, uint64_t cap, uint64_t *size, uint32_t *codec)
 {
     if (!ctx || !h_out || !size || !codec) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
@@ -2959,6 +3054,8 @@ struct Outputs {
     uint8_t *bytes;
     double *values;
     bool distance;
+    int32_t *period;   // interior views (plain views only): values is then the interior distance estimate
+    bool interior;
 };
 
 // The launch of a checked target (target_check) on device pointers, on `stream`: the one place that knows which kernels serve
@@ -2972,6 +3069,12 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
                               : launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
         case Target::kJulia: return launch_julia(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.bytes, o.values, stream);
         case Target::kPlain: break;
+    }
+    if (o.interior) {
+        bool safe = false;
+        int rc = interior_check(ctx, &t.view, mrd, flags, &safe);
+        if (rc != MBK_OK) return rc;
+        return launch_interior(ctx, &t.view, mrd, flags, safe, o.counts, o.period, o.values, stream);
     }
     if (o.distance) {
         bool safe = false;
@@ -3139,8 +3242,14 @@ static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint
     p.offset = spec->offset;
     p.lut = nullptr;
     p.lut_mrd = 0u;
+    p.unknown = p.outside = 0u;
     return p;
 }
+
+// An interior render inside the render machinery: its spec as an mbk_render_spec with a source of its own, which no public call
+// lets through (validate_render_spec), and its two extra colours.
+static const uint32_t kRenderSourceInterior = 0x100u;
+struct InteriorColours { uint32_t unknown, outside; };
 
 // The stream's device palette: uploaded when it differs from what the device copy holds, after the launches that read that.
 static int stream_palette(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const uint8_t *palette, uint32_t len)
@@ -3236,12 +3345,13 @@ static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 // A checked render (render_check) onto the device image d_out (ncols x nrows words), on `stream`.  stat: the slot whose
 // reduction scratch adds up the statistics of the samples and whose ev_k1 marks the last resolve kernel (_compute), or NULL.
 static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                      uint32_t *d_out, hipStream_t stream, Slot *stat, const double *h_lut = nullptr, uint32_t lut_len = 0u)
+                      uint32_t *d_out, hipStream_t stream, Slot *stat, const double *h_lut = nullptr, uint32_t lut_len = 0u,
+                      const InteriorColours *interior = nullptr)
 {
     const uint32_t s = spec->supersample;
     const bool dist = spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL;   // (deep views: rel in place of de, the same colour rule)
     const bool eq = spec->source == MBK_RENDER_EQUALIZED;                  // (the smooth samples, coloured through the table)
-    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || eq;   // (same sample layout: binary64 value | counts)
+    const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || eq || interior;   // (same sample layout: binary64 value | counts; interior: | periods)
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
@@ -3254,16 +3364,17 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         if (rc != MBK_OK) return rc;
     }
 
-    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (smooth ? 12u : (stat ? 5u : 1u)), spec->max_band_rows);
+    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (interior ? 16u : (smooth ? 12u : (stat ? 5u : 1u))), spec->max_band_rows);
     const size_t cap_samples = plan.cap_px() * s * s;
-    // layout: SMOOTH nu | counts; BYTES counts (statistics only) | bytes
+    // layout: SMOOTH nu | counts (interior: de | counts | periods); BYTES counts (statistics only) | bytes
     const size_t off2 = smooth ? round_up_256(cap_samples * 8u) : (stat ? round_up_256(cap_samples * 4u) : 0u);
-    const size_t need = off2 + (smooth ? cap_samples * 4u : cap_samples);
+    const size_t off3 = off2 + round_up_256(cap_samples * 4u);   // (interior only)
+    const size_t need = interior ? off3 + cap_samples * 4u : off2 + (smooth ? cap_samples * 4u : cap_samples);
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
     if (rc != MBK_OK) return rc;
     uint8_t *base = (uint8_t *)sc->d_render;
     const Outputs samples = {smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr), smooth ? nullptr : base + off2,
-                             smooth ? (double *)base : nullptr, dist};
+                             smooth ? (double *)base : nullptr, dist, interior ? (int32_t *)(base + off3) : nullptr, interior != nullptr};
     const double *d_lut = eq ? sc->d_lut : nullptr;
     const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
 
@@ -3279,6 +3390,7 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         std::memset(&a, 0, sizeof(a));
         a.counts = samples.counts;
         a.smooth = samples.values;
+        a.period = samples.period;
         a.bytes = samples.bytes;
         a.out = d_out + (size_t)r * t.g.ncols + c;
         a.pitch = (uint64_t)nc * s;
@@ -3291,9 +3403,15 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         a.pal = render_palette(spec, d_palette);
         a.pal.lut = d_lut;
         a.pal.lut_mrd = eq ? lut_len - 2u : 0u;
+        if (interior) {
+            a.pal.unknown = interior->unknown;
+            a.pal.outside = interior->outside;
+        }
         const uint64_t pieces = (uint64_t)a.chunks_x * nr;
         const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
-        if (dist)
+        if (interior)
+            mbk::launch_resolve<true, mbk::kRuleInterior>(s, grid, use_lds ? lds : 0u, stream, a);
+        else if (dist)
             mbk::launch_resolve<true, mbk::kRuleDistance>(s, grid, use_lds ? lds : 0u, stream, a);
         else if (eq)
             mbk::launch_resolve<true, mbk::kRuleEqualized>(s, grid, use_lds ? lds : 0u, stream, a);
@@ -3319,14 +3437,12 @@ static int render_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
     return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, h_lut, lut_len);
 }
 
-static int render_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                          uint8_t *h_rgba, mbk_stats *stats, bool equalized = false, const double *h_lut = nullptr,
-                          uint32_t lut_len = 0u)
+// A checked render synchronously into a host image on slot 0: what follows the refusals of a *_render_compute call.
+static int render_compute_checked(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                  uint8_t *h_rgba, mbk_stats *stats, const double *h_lut, uint32_t lut_len,
+                                  const InteriorColours *interior = nullptr)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = render_check(ctx, t, mrd, flags, spec, h_rgba, equalized, h_lut, lut_len);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
+    int rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
     const size_t px = (size_t)t.g.ncols * t.g.nrows;
@@ -3336,7 +3452,7 @@ static int render_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t 
         // the bands add their statistics up in the slot's reduction scratch: cleared once, here
         MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len);
+        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len, interior);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
@@ -3344,6 +3460,16 @@ static int render_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t 
         return MBK_OK;
     };
     return sync_end(ctx, enqueue(), stats, false);
+}
+
+static int render_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                          uint8_t *h_rgba, mbk_stats *stats, bool equalized = false, const double *h_lut = nullptr,
+                          uint32_t lut_len = 0u)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = render_check(ctx, t, mrd, flags, spec, h_rgba, equalized, h_lut, lut_len);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, h_lut, lut_len);
 }
 
 int mbk_view_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
@@ -3523,6 +3649,99 @@ int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double 
                                       uint32_t height, const int32_t *counts, const double *smooth, uint8_t *rgba)
 {
     return resolve_host(spec, true, h_lut, lut_len, width, height, counts, nullptr, smooth, rgba);
+}
+
+// ---- interior renders (mbk.h "Interior views"): calls of their own on the render machinery above ------------------------
+
+static int validate_interior_spec(mbk_ctx *ctx, const mbk_interior_render_spec *spec)
+{
+    if (!spec) return fail(ctx, MBK_ERR_INVALID, "render spec is NULL");
+    if (!spec->palette) return fail(ctx, MBK_ERR_INVALID, "palette is NULL");
+    const uint32_t s = spec->supersample;
+    if (s != 1u && s != 2u && s != 3u && s != 4u && s != 8u) return fail(ctx, MBK_ERR_INVALID, "supersample must be 1, 2, 3, 4 or 8");
+    if (spec->palette_len < 1u || spec->palette_len > 65536u) return fail(ctx, MBK_ERR_INVALID, "interior renders take a palette of 1 .. 65536 entries");
+    if (!(spec->scale > 0.0) || !(spec->scale <= 0x1p80)) return fail(ctx, MBK_ERR_INVALID, "scale must lie in (0, 2^80]");
+    return MBK_OK;
+}
+
+// The spec as the render machinery reads it (scale, palette, supersampling, banding) and the two colours it has no field for.
+static mbk_render_spec interior_render_spec(const mbk_interior_render_spec *spec, InteriorColours *colours)
+{
+    mbk_render_spec r = {};
+    r.source = kRenderSourceInterior;
+    r.supersample = spec->supersample;
+    r.palette = spec->palette;
+    r.palette_len = spec->palette_len;
+    r.scale = spec->scale;
+    r.max_band_rows = spec->max_band_rows;
+    colours->unknown = pack_rgba(spec->unknown);
+    colours->outside = pack_rgba(spec->outside);
+    return r;
+}
+
+// Everything an interior render can refuse, before anything is allocated, enqueued or written.
+static int interior_render_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_interior_render_spec *spec,
+                                 const void *out, Target *t)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_interior_spec(ctx, spec);
+    if (rc != MBK_OK) return rc;
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    *t = view_target(view);
+    const uint32_t s = spec->supersample;
+    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
+    bool safe = false;
+    return interior_check(ctx, &samples.view, mrd, flags, &safe);
+}
+
+int mbk_view_interior_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                                    const mbk_interior_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    Target t;
+    int rc = interior_render_check(ctx, view, mrd, flags, spec, d_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    InteriorColours colours;
+    const mbk_render_spec r = interior_render_spec(spec, &colours);
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, &colours);
+}
+
+int mbk_view_interior_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                                     const mbk_interior_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    Target t;
+    int rc = interior_render_check(ctx, view, mrd, flags, spec, h_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    InteriorColours colours;
+    const mbk_render_spec r = interior_render_spec(spec, &colours);
+    return render_compute_checked(ctx, t, mrd, flags, &r, h_rgba, stats, nullptr, 0u, &colours);
+}
+
+int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                              const int32_t *period, const double *de, uint8_t *rgba)
+{
+    int rc = validate_interior_spec(nullptr, spec);
+    if (rc != MBK_OK) return rc;
+    if (!rgba) return fail(nullptr, MBK_ERR_INVALID, "output pointer is NULL");
+    const uint32_t s = spec->supersample;
+    if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
+        return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
+    if (!counts || !period || !de) return fail(nullptr, MBK_ERR_INVALID, "the sample arrays are NULL");
+    InteriorColours colours;
+    const mbk_render_spec r = interior_render_spec(spec, &colours);
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    mbk::RenderPalette pal = render_palette(&r, words.data());
+    pal.unknown = colours.unknown;
+    pal.outside = colours.outside;
+    mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, de, rgba, mbk::kRuleInterior, period);
+    return MBK_OK;
 }
 
 // ---- count histograms and the equalisation table (mbk_histogram.h; mbk.h "Count histograms") ------------------------------

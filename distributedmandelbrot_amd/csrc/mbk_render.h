@@ -1,6 +1,6 @@
 // mbk_render.h -- views to RGBA8 images (include/mbk.h, "Rendering"): the colour of one sample and the resolve of a pixel's
 // s x s samples, written once as __host__ __device__ functions that the resolve kernel and mbk_render_resolve_host share, and
-// the kernel itself (three rules for the binary64 samples: smooth, distance, equalised).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
+// the kernel itself (four rules for the binary64 samples: smooth, distance, equalised, interior).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
 //
 // Everything after the samples is integer arithmetic or exact binary64: t = fl(fl(nu * scale) + offset) are two rounded
 // operations (the translation unit is compiled with -ffp-contract=off), floor(t) and (t - floor(t)) * 256 are exact for
@@ -25,10 +25,12 @@ struct RenderPalette {
     double scale, offset;
     const double *lut;   // MBK_RENDER_EQUALIZED: the equalisation table, lut_mrd + 2 entries
     uint32_t lut_mrd;
+    uint32_t unknown, outside;   // interior renders: the colours of a sample with no period and of one that escapes
 };
 
 // How a binary64 sample becomes a colour: the three rules of the sources that share the (count, value) sample layout.
-enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2 };
+// kRuleInterior (mbk.h "Interior views") reads a third array, the periods, beside the same two.
+enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2, kRuleInterior = 3 };
 
 // Two colour channels at a time: a word holds channels 0 and 2 (or 1 and 3) in its 16-bit halves.
 __host__ __device__ inline uint32_t render_even(uint32_t c) { return c & 0x00ff00ffu; }
@@ -94,6 +96,22 @@ __host__ __device__ inline uint32_t render_colour_equalized(const RenderPalette 
     return render_colour_distance(p, entries, count, equalize_value(p.lut, p.lut_mrd, nu));
 }
 
+// The colour of one interior sample: `outside` if it escapes, `unknown` without a period; otherwise the palette entry of the
+// period (cyclic, 1 <= n <= 65536) with R, G, B scaled by f / 256, f = 256 from t = fl(de scale) >= 1 up (+inf included),
+// floor(256 t) below (exact: t < 1).  de is never NaN or negative.  Alpha is the entry's.
+__host__ __device__ inline uint32_t render_colour_interior(const RenderPalette &p, const uint32_t *entries, int32_t count, int32_t period,
+                                                           double de)
+{
+    if (count > 0) return p.outside;
+    if (period <= 0) return p.unknown;
+    const uint32_t base = entries[(uint32_t)(period - 1) % p.n];
+    const double t = de * p.scale;
+    const uint32_t f = t >= 1.0 ? 256u : (uint32_t)(t * 256.0);
+    const uint32_t even = ((render_even(base) * f + 0x00800080u) >> 8) & 0x00ff00ffu;   // R, B
+    const uint32_t green = ((((base >> 8) & 0xffu) * f + 128u) >> 8) & 0xffu;
+    return even | (green << 8) | (base & 0xff000000u);
+}
+
 template <int RULE>
 __host__ __device__ inline uint32_t render_colour(const RenderPalette &p, const uint32_t *entries, int32_t count, double value)
 {
@@ -128,6 +146,7 @@ struct RenderSum {
 struct RenderArgs {
     const int32_t *counts;   // MBK_RENDER_SMOOTH
     const double *smooth;
+    const int32_t *period;   // kRuleInterior
     const uint8_t *bytes;    // MBK_RENDER_BYTES
     uint32_t *out;
     uint64_t pitch, out_pitch;
@@ -195,10 +214,15 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
             for (int sy = 0; sy < S; ++sy) {
                 double nu[S];
                 int32_t cnt[S];
-                render_load_smooth<S>(a, ((uint64_t)row * S + sy) * a.pitch + (uint64_t)col * S, nu, cnt);
+                const uint64_t at = ((uint64_t)row * S + sy) * a.pitch + (uint64_t)col * S;
+                render_load_smooth<S>(a, at, nu, cnt);
 #pragma unroll
-                for (int sx = 0; sx < S; ++sx)
-                    sum.add(render_colour<RULE>(a.pal, entries, cnt[sx], nu[sx]));
+                for (int sx = 0; sx < S; ++sx) {
+                    if constexpr (RULE == kRuleInterior)
+                        sum.add(render_colour_interior(a.pal, entries, cnt[sx], a.period[at + sx], nu[sx]));
+                    else
+                        sum.add(render_colour<RULE>(a.pal, entries, cnt[sx], nu[sx]));
+                }
             }
             out_row[col] = sum.mean(S * S);
         } else {
@@ -253,7 +277,7 @@ inline void launch_resolve(uint32_t s, dim3 grid, size_t lds, hipStream_t stream
 // The same rule on the host, for caller-supplied samples of (width * s) x (height * s): mbk_render_resolve_host.
 inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, uint32_t s, uint32_t width, uint32_t height,
                                 const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba,
-                                int rule = kRuleSmooth)
+                                int rule = kRuleSmooth, const int32_t *period = nullptr)
 {
     const uint64_t pitch = (uint64_t)width * s;
     for (uint32_t y = 0; y < height; ++y)
@@ -263,6 +287,7 @@ inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, ui
                 for (uint32_t sx = 0; sx < s; ++sx) {
                     const uint64_t at = ((uint64_t)y * s + sy) * pitch + (uint64_t)x * s + sx;
                     sum.add(!smooth_source            ? pal.entries[bytes[at]]
+                            : rule == kRuleInterior  ? render_colour_interior(pal, pal.entries, counts[at], period[at], smooth[at])
                             : rule == kRuleDistance  ? render_colour_distance(pal, pal.entries, counts[at], smooth[at])
                             : rule == kRuleEqualized ? render_colour_equalized(pal, pal.entries, counts[at], smooth[at])
                                                      : render_colour_smooth(pal, pal.entries, counts[at], smooth[at]));

@@ -271,6 +271,42 @@ def julia_count_host(z, c, mrd: int) -> Tuple[int, float]:
     return int(n.value), float(mag.value)
 
 
+def interior_host(c, mrd: int) -> Tuple[int, int, int, float]:
+    """mbk_interior_host: (count, period, cycle_len, de) of the pixel c = (c_r, c_i) on the host, without a device: the
+    contract's four stages (include/mbk.h, "Interior views") compiled from the functions the kernel uses.  period 0 with
+    count 0 is an unknown pixel: no cycle showed within mrd."""
+    lib = L.load()
+    n, p, cl, de = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+    _check(lib, lib.mbk_interior_host(float(c[0]), float(c[1]), mrd, C.byref(n), C.byref(p), C.byref(cl), C.byref(de)))
+    return int(n.value), int(p.value), int(cl.value), float(de.value)
+
+
+def _interior_spec(palette, supersample, unknown, outside, scale, max_band_rows):
+    """(mbk_interior_render_spec, the palette array it points into) for a palette of uint8[n, 4] entries, entry k the colour
+    of period k + 1."""
+    pal = np.ascontiguousarray(getattr(palette, "entries", palette), dtype=np.uint8).reshape(-1, 4)
+    spec = L.mbk_interior_render_spec(int(supersample), pal.ctypes.data if pal.size else None, pal.shape[0],
+                                      (C.c_uint8 * 4)(*unknown), (C.c_uint8 * 4)(*outside), float(scale), int(max_band_rows))
+    return spec, pal
+
+
+def interior_resolve_host(counts, period, de, *, palette, supersample: int = 1, scale: float = 2.0 ** 80,
+                          unknown=(0, 0, 0, 255), outside=(255, 255, 255, 255)) -> np.ndarray:
+    """mbk_interior_resolve_host: the colour and resolve rules of an interior render on host samples of
+    (height * s, width * s); returns uint8[height, width, 4]."""
+    lib = L.load()
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    period = np.ascontiguousarray(period, dtype=np.int32)
+    de = np.ascontiguousarray(de, dtype=np.float64)
+    s = int(supersample)
+    height, width = (counts.shape[0] // s, counts.shape[1] // s) if s > 0 else counts.shape
+    spec, pal = _interior_spec(palette, s, unknown, outside, scale, 0)
+    out = np.zeros((height, width, 4), np.uint8)
+    _check(lib, lib.mbk_interior_resolve_host(C.byref(spec), width, height, counts.ctypes.data, period.ctypes.data, de.ctypes.data,
+                                              out.ctypes.data if out.size else None))
+    return out
+
+
 def density_cell_host(target: DensityTarget, z) -> Optional[Tuple[int, int]]:
     """mbk_density_cell_host: the cell (x, y) of the point z = (z_r, z_i) in `target`, or None when it falls outside."""
     lib = L.load()
@@ -520,6 +556,58 @@ class MandelbrotDevice:
         cv = self._cview(view, window)
         self._check(self._lib.mbk_view_launch_distance(self._h, C.byref(cv), mrd, L.KERNELS[kernel],
                                                        d_counts or None, d_distance, stream or None))
+
+    # -- interior views (include/mbk.h, "Interior views") -------------------------------------------
+    def compute_view_interior(self, view: View, mrd: int, *, window=None, kernel: str = "default", want_counts: bool = True,
+                              want_period: bool = True, want_distance: bool = True):
+        """Periods and interior distance estimates (not in the reference): for every pixel that never escapes, the period of
+        the attracting cycle its orbit settles on (0: none showed within mrd) and de = (1 - |A|^2) / |F + E B / (1 - A)| from the
+        cycle's derivatives, in complex-plane units: true distance to the boundary <= de <= 4 x true distance.  Escaping pixels
+        store 0 and 0.  The counts are those of compute_view.  kernel: "default", "scan" or "group", bit-identical.
+        Returns (period int32[nrows,ncols] | None, distance float64[nrows,ncols] | None, counts int32[nrows,ncols] | None,
+        TileStats)."""
+        cv = self._cview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        period = np.empty(shape, np.int32) if want_period else None
+        dist = np.empty(shape, np.float64) if want_distance else None
+        counts = np.empty(shape, np.int32) if want_counts else None
+        st = L.mbk_stats()
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        self._check(self._lib.mbk_view_interior_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], ptr(counts), ptr(period),
+                                                        ptr(dist), C.byref(st)))
+        return period, dist, counts, _stats(st)
+
+    def launch_view_interior(self, view: View, mrd: int, *, d_period: int = 0, d_distance: int = 0, d_counts: int = 0,
+                             stream: int = 0, window=None, kernel: str = "default") -> None:
+        """Asynchronous form on DEVICE pointers (int32 / float64 / int32 of the window's size; one of d_period, d_distance may
+        be 0) on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_view_interior_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], d_counts or None,
+                                                       d_period or None, d_distance or None, stream or None))
+
+    def render_view_interior(self, view: View, mrd: int, *, palette, scale: float = 2.0 ** 80, supersample: int = 1,
+                             unknown=(0, 0, 0, 255), outside=(255, 255, 255, 255), window=None, kernel: str = "default",
+                             max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+        """The period map as an RGBA8 image: a sample of period p takes palette entry (p - 1) mod n (uint8[n, 4] or an
+        image.Palette), its R, G, B scaled by min(de * scale, 1): scale = 2 ** 80 is the flat map, scale = 1 / (k * pitch)
+        darkens the inner k pixels towards the boundary.  `outside` colours escaping samples, `unknown` those without a period.
+        Supersampling, windows and bands as for render_view.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples)."""
+        cv = self._cview(view, window)
+        spec, pal = _interior_spec(palette, supersample, unknown, outside, scale, max_band_rows)
+        img = self._render_out(cv, out)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_interior_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                               img.ctypes.data, C.byref(st)))
+        return img, _stats(st)
+
+    def launch_render_view_interior(self, view: View, mrd: int, *, palette, d_rgba: int, scale: float = 2.0 ** 80,
+                                    supersample: int = 1, unknown=(0, 0, 0, 255), outside=(255, 255, 255, 255), stream: int = 0,
+                                    window=None, kernel: str = "default", max_band_rows: int = 0) -> None:
+        """Asynchronous interior render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream``."""
+        cv = self._cview(view, window)
+        spec, pal = _interior_spec(palette, supersample, unknown, outside, scale, max_band_rows)
+        self._check(self._lib.mbk_view_interior_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                              d_rgba or None, stream or None))
 
     def serialize_last(self) -> Tuple[bytes, int]:
         """The last tile's quantised bytes exactly as DataChunk.Serialize (DataChunk.cs:173-206) would

@@ -948,6 +948,88 @@ int mbk_density_resolve_host(const mbk_density_render_spec *spec, uint32_t width
                              uint8_t *rgba);
 int mbk_density_build_info(void);
 
+/*
+ * Interior views: periods and interior distance estimates.  NOT in the reference; additive (the ABI version stays 5): no
+ * existing call changes.  Every output above is about the outside of the set; a pixel that never escapes is "count 0" and
+ * nothing more.  An interior view says which component such a pixel lies in -- the period of the attracting cycle its orbit
+ * settles on -- and how far inside it is: the interior distance estimate, which Koebe's theorem holds to
+ * true distance <= de <= 4 x true distance.
+ *
+ * The cycle test of the count kernels cannot give the period: the bitwise period of a settled binary64 orbit is usually a
+ * proper multiple of the mathematical one (inside the main cardioid it reads 1, 2, 3, ... 98).  The contract therefore
+ * reduces the bitwise period with a tolerance.
+ *
+ * Contract (exact; tests/interior_model.py restates it in numpy, tests/test_interior.py and tests/test_gpu_interior.py hold the
+ * host twin and the GPU to it).  For the pixel with coordinate c of a plain mbk_view, in binary64, every operation rounded on
+ * its own.  step(z) is the recurrence of mbk_view_launch, unchanged; cmul(a, b) = (fl(fl(ar br) - fl(ai bi)),
+ * fl(fl(ar bi) + fl(ai br))); complex sums are componentwise; doublings are multiplications by 2.
+ *   count       n is exactly the count of mbk_view_launch.  A pixel with n > 0 stores period 0 and de 0.
+ *   cycle       for n = 0.  z_0 = c, reference r = z_0, window w = 1, since = 0.  For k = 1 .. mrd - 1: z_k = step(z_(k-1)),
+ *               since += 1; if both 64-bit patterns of z_k equal those of r (a bit compare: -0 != +0), L = since and the
+ *               search stops -- this is tested first; otherwise, if since == w: r = z_k, w = 2 w, since = 0.  No hit within
+ *               the mrd - 1 updates: the pixel is UNKNOWN, period 0 and de 0.  The schedule (w, since) is the same for every
+ *               pixel; L is Brent's minimal bitwise period and r lies on the cycle.
+ *   period      y_0 = r, y_d = step(y_(d-1)) for d = 1 .. L; p is the first d with
+ *               max(|fl(yr_d - rr)|, |fl(yi_d - ri)|) <= 2^-40.  d = L always qualifies.  The constant is part of the contract.
+ *   derivatives p steps from z = r with A = (1, 0) (dz), B = 0 (dc), E = 0 (dzz), F = 0 (dcz), every update from the old values:
+ *                 F' = 2 (cmul(z, F) + cmul(A, B)),  E' = 2 (cmul(A, A) + cmul(z, E)),
+ *                 B' = 2 cmul(z, B) + (1, 0) with the real part fl(2u + 1) as in "Distance estimates",
+ *                 A' = 2 cmul(z, A),  z' = step(z).
+ *   output      m2 = fl(fl(Ar^2) + fl(Ai^2)).  If not m2 < 1: de = 0, and the period stays p.  Otherwise g = (fl(1 - Ar), -Ai),
+ *               h = cmul(E, B), t = cmul(h, conj g), gm = fl(fl(gr^2) + fl(gi^2)), G = F + (fl(tr / gm), fl(ti / gm)),
+ *               den = fl(fl(Gr^2) + fl(Gi^2)) and de = fl(fl(1 - m2) / fl(sqrt(den))).  Division and square root are the
+ *               correctly rounded ones; there is no libm call, so host and device agree to the bit.  Never NaN and never
+ *               negative: 0 is stored where the expression is NaN; den = 0 gives +inf as IEEE does.  de is a length in the
+ *               complex plane, the unit of mbk_view_launch_distance.
+ *   mrd         0 and 1 run no step: everything is 0.  mrd >= 2^31 is refused.
+ * Windows of a view are bit-identical to the whole view.
+ * By hand: c = (0, 0) gives 0, 1, 0.5; c = (-1, 0) gives 0, 2, 0.25 from mrd 4 on and is unknown at mrd 3.
+ *
+ * Two passes (csrc/mbk_interior.h): the counts come from the count kernels mbk_view_launch would run for the selector, cycle test
+ * and all, into d_counts or scratch the ctx keeps per stream; then one lane per count-0 pixel runs the four stages.
+ * mbk_view_interior_launch: asynchronous, DEVICE pointers on the caller's stream (window-sized buffers; nothing is written
+ * outside them; no statistics).  d_counts may be NULL; one of d_period / d_distance may be NULL, not both.
+ * mbk_view_interior_compute: synchronous into HOST buffers on slot 0 (the slot-0 rule applies), the same pointer rules, stats as
+ * for mbk_view_compute_distance.
+ * `flags` carries kernel selection only: MBK_KERNEL_DEFAULT, _SCAN and _GROUP, bit-identical.  MBK_ERR_INVALID, with nothing
+ * written: MBK_KERNEL_ASM / _SIMPLE / _REFILL, MBK_PRECISION_F32, MBK_LAZY_UNIFORM, MBK_DEEP_BLA, any other flag bit, both value
+ * pointers NULL, mrd >= 2^31 and whatever mbk_view_launch refuses in a view.
+ * mbk_interior_host: one pixel on the HOST, compiled from the functions the kernel uses: no ctx, no device.  *cycle_len is L
+ * (0 for an escaping or an unknown pixel).  Every out pointer but count may be NULL.  MBK_ERR_INVALID for a NULL count and
+ * mrd >= 2^31.
+ *
+ * Interior renders are calls of their own, not an MBK_RENDER_* source.  Colour of a sample: `outside` if n > 0; `unknown` if it
+ * has no period; otherwise base = p[(period - 1) mod n], 1 <= n <= 65536, t = fl(de scale), f = 256 where t >= 1 (+inf
+ * included) and floor(256 t) below, each of R, G, B (base f + 128) >> 8, alpha the base's.  0 < scale <= 2^80, finite:
+ * scale = 2^80 is the flat period map, scale = 1 / (k pitch) darkens the inner k pixels towards the boundary.  Samples (16 bytes:
+ * count, period, de), supersampling set, resolve, output layout, banding under MBK_RENDER_BAND_BYTES, the palette's
+ * wait-on-change rule and the statistics of _compute are those of "Rendering"; flags as for mbk_view_interior_launch.
+ * mbk_interior_resolve_host: colour and resolve on the HOST for caller-supplied samples of (width s) x (height s).
+ *
+ * Out of scope: deep, extended-range and Julia views; sharding and slot forms; compacting the unknown pixels into full waves;
+ * a Newton search for the unknown pixels near the boundary.
+ */
+typedef struct mbk_interior_render_spec {
+    uint32_t supersample;   /* 1, 2, 3, 4, 8 */
+    const uint8_t *palette; /* HOST pointer, palette_len x RGBA8, entry k the colour of period k + 1; copied during the call */
+    uint32_t palette_len;   /* 1 .. 65536 */
+    uint8_t unknown[4];     /* a sample that never escapes and shows no cycle within mrd */
+    uint8_t outside[4];     /* a sample that escapes */
+    double scale;
+    uint32_t max_band_rows; /* 0 = the library's choice; any value gives the same image */
+} mbk_interior_render_spec;
+int mbk_view_interior_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *d_counts,
+                             int32_t *d_period, double *d_distance, void *hip_stream);
+int mbk_view_interior_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *h_counts,
+                              int32_t *h_period, double *h_distance, mbk_stats *stats);
+int mbk_interior_host(double c_r, double c_i, uint32_t mrd, int32_t *count, int32_t *period, int32_t *cycle_len, double *de);
+int mbk_view_interior_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                                    const mbk_interior_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_view_interior_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                                     const mbk_interior_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                              const int32_t *period, const double *de, uint8_t *rgba);
+
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
 #define MBK_CODEC_RLE 0x01u
