@@ -12,8 +12,12 @@ def axes(v):
     return np.linspace(sr, sr + rr, w), np.linspace(si, si + ri, h)
 
 
-def step(zr, zi, cr, ci):
-    """The recurrence of mbk_view_launch: zr' = fl(fl(fl(zr zr) - fl(zi zi)) + cr), zi' = fl(fl(fl(2 zr) zi) + ci)."""
+def step(zr, zi, cr, ci, fma=False):
+    """The recurrence of mbk_view_launch: zr' = fl(fl(fl(zr zr) - fl(zi zi)) + cr), zi' = fl(fl(fl(2 zr) zi) + ci).
+    fma=True is the kernels' rewrite zi' = fma(2, fl(zr zi), ci): 2 p is exact, so fl(fl(2 p) + ci) is the fused result.  The
+    two differ only where zr zi is a non-zero subnormal, and a launch takes the literal form on every view where that can show."""
+    if fma:
+        return (zr * zr - zi * zi) + cr, (2.0 * (zr * zi)) + ci
     return (zr * zr - zi * zi) + cr, ((2.0 * zr) * zi) + ci
 
 
@@ -21,7 +25,7 @@ def cmul(ar, ai, br, bi):
     return ar * br - ai * bi, ar * bi + ai * br
 
 
-def counts(cr, ci, mrd):
+def counts(cr, ci, mrd, fma=False):
     """n: the first k in 1 .. mrd - 1 with fl(fl(zr^2) + fl(zi^2)) >= 4, 0 if there is none."""
     cr, ci = np.asarray(cr, np.float64).ravel(), np.asarray(ci, np.float64).ravel()
     n = np.zeros(cr.size, np.int32)
@@ -31,7 +35,7 @@ def counts(cr, ci, mrd):
         for k in range(1, mrd):
             if idx.size == 0:
                 break
-            zr, zi = step(zr, zi, ar, ai)
+            zr, zi = step(zr, zi, ar, ai, fma)
             out = zr * zr + zi * zi >= 4.0
             if out.any():
                 n[idx[out]] = k
@@ -40,7 +44,7 @@ def counts(cr, ci, mrd):
     return n
 
 
-def cycle(cr, ci, mrd):
+def cycle(cr, ci, mrd, fma=False):
     """Stage 2 for pixels whose count is 0: (L, rr, ri, at_window) -- L = 0 where no repeat shows; at_window marks the hits
     that fell on a step with since == w."""
     m = cr.size
@@ -54,7 +58,7 @@ def cycle(cr, ci, mrd):
     for k in range(1, mrd):
         if idx.size == 0:
             break
-        zr, zi = step(zr, zi, ar, ai)
+        zr, zi = step(zr, zi, ar, ai, fma)
         since += 1
         hit = (zr.view(np.uint64) == rr.view(np.uint64)) & (zi.view(np.uint64) == ri.view(np.uint64))
         if hit.any():
@@ -69,7 +73,7 @@ def cycle(cr, ci, mrd):
     return L, rr_out, ri_out, at_window
 
 
-def period(rr, ri, cr, ci, L):
+def period(rr, ri, cr, ci, L, fma=False):
     """Stage 3: the first d in 1 .. L with max(|yr_d - rr|, |yi_d - ri|) <= 2^-40 (pixels with L > 0)."""
     p = np.zeros(rr.size, np.int32)
     idx = np.arange(rr.size)
@@ -77,7 +81,7 @@ def period(rr, ri, cr, ci, L):
     d = 0
     while idx.size:
         d += 1
-        yr, yi = step(yr, yi, cr[idx], ci[idx])
+        yr, yi = step(yr, yi, cr[idx], ci[idx], fma)
         ok = np.maximum(np.abs(yr - rr[idx]), np.abs(yi - ri[idx])) <= TOLERANCE
         assert ok[L[idx] == d].all()      # d = L always qualifies
         p[idx[ok]] = d
@@ -86,7 +90,7 @@ def period(rr, ri, cr, ci, L):
     return p
 
 
-def distance(rr, ri, cr, ci, p):
+def distance(rr, ri, cr, ci, p, fma=False):
     """Stages 4 and 5 (pixels with p > 0)."""
     m = rr.size
     zr, zi = rr.copy(), ri.copy()
@@ -101,7 +105,7 @@ def distance(rr, ri, cr, ci, p):
             zEr, zEi = cmul(zr, zi, Er, Ei)
             zBr, zBi = cmul(zr, zi, Br, Bi)
             zAr, zAi = cmul(zr, zi, Ar, Ai)
-            nzr, nzi = step(zr, zi, cr, ci)
+            nzr, nzi = step(zr, zi, cr, ci, fma)
             new = (2.0 * (zFr + ABr), 2.0 * (zFi + ABi), 2.0 * (AAr + zEr), 2.0 * (AAi + zEi), 2.0 * zBr + 1.0, 2.0 * zBi,
                    2.0 * zAr, 2.0 * zAi, nzr, nzi)     # (2u is exact, so fl(fl(2u) + 1) is the contract's fl(2u + 1))
             Fr, Fi, Er, Ei, Br, Bi, Ar, Ai, zr, zi = (np.where(on, a, b) for a, b in
@@ -119,31 +123,32 @@ def distance(rr, ri, cr, ci, p):
     return de
 
 
-def interior(cr, ci, mrd):
-    """The whole contract for the pixels (cr[k], ci[k]): dict of n, period, cycle (L), de, at_window -- flat arrays."""
+def interior(cr, ci, mrd, fma=False):
+    """The whole contract for the pixels (cr[k], ci[k]): dict of n, period, cycle (L), de, at_window -- flat arrays.
+    fma=True: every stage with the fused doubling (step), which is NOT the contract where the two differ."""
     cr, ci = np.asarray(cr, np.float64).ravel(), np.asarray(ci, np.float64).ravel()
-    n = counts(cr, ci, mrd)
+    n = counts(cr, ci, mrd, fma)
     out = {"n": n, "period": np.zeros(n.size, np.int32), "cycle": np.zeros(n.size, np.int32), "de": np.zeros(n.size),
            "at_window": np.zeros(n.size, bool)}
     inside = np.flatnonzero(n == 0)
     if mrd < 2 or inside.size == 0:
         return out
-    L, rr, ri, at_window = cycle(cr[inside], ci[inside], mrd)
+    L, rr, ri, at_window = cycle(cr[inside], ci[inside], mrd, fma)
     out["cycle"][inside] = L
     out["at_window"][inside] = at_window
     s = L > 0
-    p = period(rr[s], ri[s], cr[inside][s], ci[inside][s], L[s])
+    p = period(rr[s], ri[s], cr[inside][s], ci[inside][s], L[s], fma)
     out["period"][inside[s]] = p
-    out["de"][inside[s]] = distance(rr[s], ri[s], cr[inside][s], ci[inside][s], p)
+    out["de"][inside[s]] = distance(rr[s], ri[s], cr[inside][s], ci[inside][s], p, fma)
     return out
 
 
-def view(v, mrd, window=None):
+def view(v, mrd, window=None, fma=False):
     """interior() over a view tuple / window (col0, row0, ncols, nrows): dict of [nrows, ncols] arrays."""
     xr, xi = axes(v)
     c0, r0, nc, nr = window or (0, 0, v[4], v[5])
     cr, ci = np.meshgrid(xr[c0:c0 + nc], xi[r0:r0 + nr])
-    return {k: a.reshape(nr, nc) for k, a in interior(cr, ci, mrd).items()}
+    return {k: a.reshape(nr, nc) for k, a in interior(cr, ci, mrd, fma).items()}
 
 
 def colours(palette, unknown, outside, scale, n, period, de):

@@ -1,6 +1,8 @@
 """Interior views on the host (include/mbk.h, "Interior views"): mbk_interior_host and mbk_interior_resolve_host -- compiled from
 the functions the kernel and the resolve kernel use -- held to the numpy model of the contract (tests/interior_model.py), and the
-contract itself held to the two components whose boundaries are known in closed form.
+contract itself held to the two components whose boundaries are known in closed form (tests/test_interior_truth.py holds the
+value of de to the mathematics).  The hazard views -- rows with a subnormal c_i, where the fused doubling of the kernels would
+find other cycles -- are tabled here for the GPU tests, with the claims those rest on.
 
 Measured with the model on the 160 x 160 grid of [-2, 1] x [-1.5, 1.5] at mrd 4096: 4002 settled pixels, 3168 of them in the
 cardioid and 518 in the period-2 disc; period 1 on every cardioid pixel and 2 on every disc pixel, the period divides the cycle
@@ -12,11 +14,34 @@ import numpy as np
 import pytest
 
 import interior_model as M
+import interior_truth as T
 from distributedmandelbrot_amd import MbkError
 from distributedmandelbrot_amd import _lib as L
 from distributedmandelbrot_amd.device import interior_host, interior_resolve_host
 
 FULL = (-2.0, -1.5, 3.0, 3.0)
+
+# Hazard views: rows with 0 < |c_i| < 2^-900, where zi stays subnormal and the fused doubling fma(2, zr zi, c_i) rounds
+# differently from the contract's literal fl(fl(2 zr) zi) + c_i.  The counts are the same, but the cycle stage is a bit compare:
+# the two forms reach the bitwise repeat at different steps, and period and de follow.  A launch must take the literal kernel on
+# these views; the host twin always does.  (view, {mrd: pixels on which the fused model differs in period or de}) -- the mrd
+# lie just past a Brent window edge; from mrd 300 on the differences are gone on all but the first view, and the third has none
+# left at mrd 257, which is why that pair is not here.  test_hazard_claims asserts every figure.
+HAZARD_MIXED = (-2.0, 1e-310, 2.5, 0.7, 96, 8)      # row 0 alone is tiny: rows 1..7 are 0.1 .. 0.7
+HAZARD = [
+    ((-2.0, 1e-310, 2.5, 3e-310, 96, 8), {33: 12, 65: 23, 129: 14, 257: 13}),      # every row tiny
+    (HAZARD_MIXED, {33: 2, 65: 4, 129: 2, 257: 3}),                                # all in row 0
+    ((-1.5, -3e-323, 1.9, 6e-323, 29, 13), {33: 2, 65: 24, 129: 10}),              # rows of -6 .. 6 units of 2^-1074, row 6 is 0
+    ((-2.0, 1e-310, 2.5, 0.0, 96, 1), {33: 2, 65: 4, 129: 2, 257: 3}),             # one row, zero range
+    ((-2.0, -3e-310, 2.5, 6e-310, 96, 7), {33: 10, 65: 20, 129: 10, 257: 16}),     # rows on both sides of zero, row 3 is 0
+]
+HAZARD_CASES = [(v, mrd) for v, table in HAZARD for mrd in table]
+
+
+def differing_pixels(a, b):
+    """How many pixels of two results (dicts of arrays, or (period, de) pairs) differ in period or in the bits of de."""
+    (pa, da), (pb, db) = ((x["period"], x["de"]) if isinstance(x, dict) else x for x in (a, b))
+    return int(((pa != pb) | (np.ascontiguousarray(da).view(np.uint64) != np.ascontiguousarray(db).view(np.uint64))).sum())
 
 
 def _host(cr, ci, mrd):
@@ -76,12 +101,61 @@ def test_shallow_mrd(mrd):
         assert not m["n"].any() and not m["period"].any() and not m["de"].any()
 
 
-@pytest.fixture(scope="module")
-def grid160():
-    v = FULL + (160, 160)
+@pytest.mark.parametrize("v,table", HAZARD, ids=[str(i) for i in range(len(HAZARD))])
+def test_host_equals_the_literal_model_on_the_hazard_views(v, table):
     xr, xi = M.axes(v)
     cr, ci = np.meshgrid(xr, xi)
-    return cr.ravel(), ci.ravel(), M.interior(cr, ci, 4096)
+    assert ((xi != 0.0) & (np.abs(xi) < 2.0 ** -900)).any()
+    for mrd in table:
+        m = _assert_equals_model(cr, ci, mrd, (v, mrd))
+        assert (m["period"] > 0).any() and (m["n"] > 0).any()
+
+
+@pytest.mark.parametrize("v,table", HAZARD, ids=[str(i) for i in range(len(HAZARD))])
+def test_hazard_claims(v, table):
+    """What the GPU tests of the hazard views rest on: with the fused doubling the counts are the same and period or de are not,
+    on exactly the number of pixels the table records -- so a launch that took the fused kernel would show."""
+    assert table
+    for mrd, want in table.items():
+        lit, fused = M.view(v, mrd), M.view(v, mrd, fma=True)
+        assert np.array_equal(lit["n"], fused["n"]), (v, mrd)
+        diff = differing_pixels(lit, fused)
+        print(f"{v} mrd {mrd}: the fused model differs on {diff} pixels")
+        assert diff == want and diff >= 1, (v, mrd, diff)
+    if v == HAZARD_MIXED:      # rows 1..7 are ordinary: the two forms agree there, and all the differences lie in row 0
+        for mrd in table:
+            lit, fused = M.view(v, mrd, window=(0, 1, 96, 7)), M.view(v, mrd, window=(0, 1, 96, 7), fma=True)
+            assert differing_pixels(lit, fused) == 0 and np.array_equal(lit["cycle"], fused["cycle"])
+
+
+def test_fused_model_is_the_literal_one_on_ordinary_views():
+    """The fma option changes nothing where no row is tiny, cycle lengths included."""
+    v = FULL + (64, 64)
+    lit, fused = M.view(v, 300), M.view(v, 300, fma=True)
+    for k in lit:
+        assert np.array_equal(lit[k].view(np.uint64) if k == "de" else lit[k], fused[k].view(np.uint64) if k == "de" else fused[k]), k
+
+
+def test_guard_says_literal_for_every_hazard_view():
+    lib = L.load()
+
+    def guard(v, window=None):
+        c0, r0, nc, nr = window or (0, 0, v[4], v[5])
+        cv = L.mbk_view(v[0], v[1], v[2], v[3], v[4], v[5], c0, r0, nc, nr)
+        out = C.c_int(-1)
+        assert lib.mbk_view_needs_literal_doubling(C.byref(cv), 0, C.byref(out)) == L.MBK_OK
+        return out.value
+
+    for v, _ in HAZARD:
+        assert guard(v) == 1, v
+    assert guard(HAZARD_MIXED, (0, 0, 96, 1)) == 1 and guard(HAZARD_MIXED, (5, 0, 40, 3)) == 1
+    assert guard(HAZARD_MIXED, (0, 1, 96, 7)) == 0
+    assert guard(FULL + (64, 64)) == 0 and guard(FULL + (61, 45)) == 0
+
+
+@pytest.fixture(scope="module")
+def grid160():
+    return T.model_case(T.GRID160)      # (shared with tests/test_interior_truth.py: computed once)
 
 
 def _polyline_distance(px, py, bx, by):
