@@ -32,6 +32,7 @@ OPTIONS = {name: i for i, name in enumerate(
 MBK_PRECISION_F32 = 0x1000
 MBK_LAZY_UNIFORM = 0x2000
 MBK_DEEP_BLA = 0x8000   # deep count / render / histogram calls only
+MBK_DEEP_XBLA = 0x10000   # extended-range deep count / render / histogram calls only
 PRECISIONS = {"f64": 0, "f32": MBK_PRECISION_F32}
 MBK_SLOTS = 4
 MBK_WORKER_DEPTH = 3
@@ -237,6 +238,11 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "mbk_deep_xview_count_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "mbk_deep_xbla_info": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "mbk_deep_xbla_read": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mbk_deep_xbla_count_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "mbk_deep_xview_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
                                                C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
     "mbk_deep_xview_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,

@@ -28,6 +28,7 @@
 #include "mbk_deep.h"
 #include "mbk_deep_bla.h"
 #include "mbk_deep_wide.h"
+#include "mbk_deep_wide_bla.h"
 #include "mbk_histogram.h"
 #include "mbk_render.h"
 #include "mbk_chunks.h"
@@ -212,7 +213,8 @@ struct mbk_ctx {
     bool probe_valid = false;
     // deep-zoom views: this ctx's device copies of the orbits it has used, by orbit id (deep_copy)
     // beside each, the bilinear-approximation table of the last dcmax it was launched with (MBK_DEEP_BLA; bla_copy) and the
-    // wide table, once a wide view has been launched on the orbit (wide_copy)
+    // wide table, once a wide view has been launched on the orbit (wide_copy); beside that, the wide bilinear-approximation
+    // table of the last dcmax an MBK_DEEP_XBLA launch brought (xbla_copy)
     struct DeepCopy {
         uint64_t id;
         double4 *d;
@@ -223,6 +225,13 @@ struct mbk_ctx {
         double4 *d_ab;
         uint32_t levels;
         uint32_t off[mbk::kBlaMaxLevels];
+        bool has_xbla;
+        uint64_t xdcmax_bits;          // dcmax's mantissa
+        int32_t xdcmax_exp;            // ... and exponent
+        int32_t *d_xke;
+        mbk::WideBlaEntry *d_xab;
+        uint32_t xlevels;
+        uint32_t xoff[mbk::kBlaMaxLevels];
     };
     std::vector<DeepCopy> deep;
     hipDeviceProp_t prop;
@@ -390,6 +399,8 @@ static void free_deep_copy(mbk_ctx::DeepCopy &c)
     if (c.d_rc) (void)hipFree(c.d_rc);
     if (c.d_ab) (void)hipFree(c.d_ab);
     if (c.d_wide) (void)hipFree(c.d_wide);
+    if (c.d_xke) (void)hipFree(c.d_xke);
+    if (c.d_xab) (void)hipFree(c.d_xab);
     c = mbk_ctx::DeepCopy();
 }
 
@@ -1246,6 +1257,7 @@ static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t f
                        int32_t *d_counts, uint8_t *d_bytes, hipStream_t stream, double *d_smooth = nullptr, FuseStats *fuse = nullptr)
 {
     if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is a flag of the deep view calls");
+    if (flags & MBK_DEEP_XBLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is a flag of the extended-range deep view calls");
     if (fuse) fuse->fused = false;
     if (stream != ctx->last_tile_stream) {
         ctx->last_tile_stream = stream;
@@ -1985,6 +1997,7 @@ static int submit_view(mbk_ctx *ctx, Slot &sl, const mbk_view *view, uint32_t mr
     if (sl.busy) return fail(ctx, MBK_ERR_INVALID, "slot still has a tile in flight: call mbk_wait first");
     const bool wc = (flags & MBK_WANT_COUNTS) != 0, wb = (flags & MBK_WANT_BYTES) != 0;
     if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is a flag of the deep view calls");
+    if (flags & MBK_DEEP_XBLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is a flag of the extended-range deep view calls");
     int rc = check_wanted(ctx, flags, h_counts, h_bytes);
     if (rc != MBK_OK) return rc;
     bool dummy;
@@ -2172,7 +2185,7 @@ int mbk_view_launch_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uin
 {
     if (!ctx || !d_smooth) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t f = (flags & (MBK_KERNEL_MASK | MBK_PRECISION_F32)) | (d_counts ? MBK_WANT_COUNTS : 0u);
+    const uint32_t f = (flags & (MBK_KERNEL_MASK | MBK_PRECISION_F32 | MBK_DEEP_XBLA)) | (d_counts ? MBK_WANT_COUNTS : 0u);
     return launch_tile(ctx, view, mrd, f, d_counts, nullptr, (hipStream_t)hip_stream, d_smooth);
 }
 
@@ -2187,7 +2200,7 @@ int mbk_view_compute_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, ui
     if (rc != MBK_OK) return rc;
     return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_smooth, stats,
                           [&](int32_t *d_counts, double *d_smooth, hipStream_t stream) {
-                              return launch_tile(ctx, view, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, d_counts, nullptr, stream, d_smooth);
+                              return launch_tile(ctx, view, mrd, (flags & (MBK_KERNEL_MASK | MBK_DEEP_XBLA)) | MBK_WANT_COUNTS, d_counts, nullptr, stream, d_smooth);
                           });
 }
 
@@ -2199,6 +2212,7 @@ static int distance_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint
     int rc = validate_view(ctx, view, safe);
     if (rc != MBK_OK) return rc;
     if (mrd > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (flags & MBK_DEEP_XBLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is a flag of the extended-range deep view calls");
     if (flags & MBK_PRECISION_F32) return fail(ctx, MBK_ERR_INVALID, "distance estimates are implemented in binary64 only");
     const uint32_t kernel = flags & MBK_KERNEL_MASK;
     if (kernel > MBK_KERNEL_SCAN) return fail(ctx, MBK_ERR_INVALID, "unknown MBK_KERNEL_* selector");
@@ -2262,7 +2276,7 @@ int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, 
 {
     if (!ctx || !view || !h_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
     bool safe = false;
-    int rc = distance_check(ctx, view, mrd, flags & MBK_KERNEL_MASK, &safe);
+    int rc = distance_check(ctx, view, mrd, flags & (MBK_KERNEL_MASK | MBK_DEEP_XBLA), &safe);
     if (rc != MBK_OK) return rc;
     rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
@@ -2862,8 +2876,10 @@ static int validate_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const m
         ctx, orbit, v, mrd, flags,
         [&]() -> int {
             if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
-            if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES))
+            if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_DEEP_XBLA))
                 return fail(ctx, MBK_ERR_INVALID, "extended-range deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
+            if ((flags & MBK_DEEP_XBLA) && orbit->o.length > (1u << 31))
+                return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA: the orbit is longer than 2^31 (the table's indices are 32 bits wide)");
             return MBK_OK;
         },
         [&]() -> int {
@@ -2874,23 +2890,142 @@ static int validate_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const m
         });
 }
 
-// the wide kernel on device pointers (validated by the caller), on `stream`
-static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd,
-                            int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream)
+// dcmax of "Extended-range deep views with bilinear approximation": of the FULL view, normalised
+static mbk::WideReal wide_view_dcmax(const mbk_deep_xview *v)
+{
+    return mbk::wide_dcmax(deep_dc(0u, v->width, v->range_r), deep_dc(0u, v->height, v->range_i), v->exp2);
+}
+
+// This ctx's device copy of `orbit` with its wide table (wide_copy) and the wide bilinear-approximation table of `dcmax`
+// beside it: bla_copy's rule -- built on the host and uploaded when the copy has none or has another dcmax's, synchronously,
+// and after the device has drained, since a launch that reads the table it replaces may still be queued (mbk.h).  M >= 2.
+static int xbla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideReal &dcmax, const mbk_ctx::DeepCopy **out)
 {
     const mbk::WideEntry *d_orbit = nullptr;
     int rc = wide_copy(ctx, orbit, &d_orbit);
     if (rc != MBK_OK) return rc;
-    mbk::DeepWideArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.orbit = d_orbit;
+    mbk_ctx::DeepCopy *c = nullptr;
+    rc = deep_copy(ctx, orbit, &c);
+    if (rc != MBK_OK) return rc;
+    *out = c;
+    uint64_t bits;
+    std::memcpy(&bits, &dcmax.f, sizeof(bits));
+    if (c->has_xbla && c->xdcmax_bits == bits && c->xdcmax_exp == dcmax.e) return MBK_OK;
+    mbk::WideBlaTable t;
+    try {
+        mbk::build_wide_bla_table(orbit->o.wide, orbit->o.length, dcmax, &t);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, MBK_ERR_NOMEM, "out of host memory for the wide bilinear-approximation table");
+    }
+    if (c->has_xbla) MBK_HIP(ctx, hipDeviceSynchronize());
+    c->has_xbla = false;
+    if (!c->d_xke) {   // the sizes depend on M alone: allocated once per copy
+        MBK_HIP(ctx, hipMalloc((void **)&c->d_xke, t.ke.size() * sizeof(int32_t)));
+        MBK_HIP(ctx, hipMalloc((void **)&c->d_xab, t.ab.size() * sizeof(mbk::WideBlaEntry)));
+    }
+    MBK_HIP(ctx, hipMemcpy(c->d_xke, t.ke.data(), t.ke.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    MBK_HIP(ctx, hipMemcpy(c->d_xab, t.ab.data(), t.ab.size() * sizeof(mbk::WideBlaEntry), hipMemcpyHostToDevice));
+    c->xlevels = t.levels;
+    std::memcpy(c->xoff, t.off, sizeof(c->xoff));
+    c->xdcmax_bits = bits;
+    c->xdcmax_exp = dcmax.e;
+    c->has_xbla = true;
+    return MBK_OK;
+}
+
+// the wide kernel on device pointers (validated by the caller), on `stream`; xbla: MBK_DEEP_XBLA (an orbit of length 1 has no
+// table: the flag changes nothing)
+static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd,
+                            int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream, bool xbla = false)
+{
+    const mbk_ctx::DeepCopy *c = nullptr;
+    const mbk::WideEntry *d_orbit = nullptr;
+    const bool table = xbla && orbit->o.length >= 2u;
+    int rc = table ? xbla_copy(ctx, orbit, wide_view_dcmax(v), &c) : wide_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepWideBlaArgs b;
+    std::memset(&b, 0, sizeof(b));
+    mbk::DeepWideArgs &a = b.v;
+    a.orbit = table ? c->d_wide : d_orbit;
     a.z1 = orbit->o.wide[1];
     a.M = orbit->o.length;
     a.exp2 = v->exp2;
     fill_deep_window(a, v, mrd);
     fill_outputs(a, mrd, d_counts, d_bytes, d_smooth);
-    hipLaunchKernelGGL(mbk::deep_wide_kernel, block_grid(a), dim3(64), 0, stream, a);
+    if (table) {
+        b.ke = c->d_xke;
+        b.ab = c->d_xab;
+        b.levels = c->xlevels;
+        std::memcpy(b.off, c->xoff, sizeof(b.off));
+        hipLaunchKernelGGL(mbk::deep_wide_bla_kernel, block_grid(a), dim3(64), 0, stream, b);
+    } else {
+        hipLaunchKernelGGL(mbk::deep_wide_kernel, block_grid(a), dim3(64), 0, stream, a);
+    }
     MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// ---- host twins of the wide bilinear-approximation table and step (mbk_deep_wide_bla.h): no ctx, no device ---------------
+
+static int xbla_host_table(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, mbk::WideBlaTable *t)
+{
+    int rc = validate_deep_wide(nullptr, orbit, view, 0u, MBK_DEEP_XBLA);
+    if (rc != MBK_OK) return rc;
+    try {
+        mbk::build_wide_bla_table(orbit->o.wide, orbit->o.length, wide_view_dcmax(view), t);
+    } catch (const std::bad_alloc &) {
+        return fail(nullptr, MBK_ERR_NOMEM, "out of host memory for the wide bilinear-approximation table");
+    }
+    return MBK_OK;
+}
+
+int mbk_deep_xbla_info(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t *levels, uint64_t *entries)
+{
+    int rc = validate_deep_wide(nullptr, orbit, view, 0u, MBK_DEEP_XBLA);
+    if (rc != MBK_OK) return rc;
+    const uint32_t n = mbk::bla_levels(orbit->o.length);
+    uint64_t total = 0;
+    for (uint32_t l = 0; l < n; ++l) total += (orbit->o.length - 1u) >> l;
+    if (levels) *levels = n;
+    if (entries) *entries = total;
+    return MBK_OK;
+}
+
+int mbk_deep_xbla_read(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t level, double *A_r, double *A_i,
+                       int32_t *a_e, double *B_r, double *B_i, int32_t *b_e, int32_t *ke, uint64_t n)
+{
+    if (!A_r || !A_i || !a_e || !B_r || !B_i || !b_e || !ke) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::WideBlaTable t;
+    int rc = xbla_host_table(orbit, view, &t);
+    if (rc != MBK_OK) return rc;
+    if (level >= t.levels) return fail(nullptr, MBK_ERR_INVALID, "the table has no such level");
+    const uint32_t cnt = t.count(level);
+    if (n < cnt) return fail(nullptr, MBK_ERR_INVALID, "the outputs hold fewer than the level's entries");
+    for (uint32_t j = 0; j < cnt; ++j) {
+        const size_t at = (size_t)t.off[level] + j;
+        const mbk::WideBlaEntry &e = t.ab[at];
+        A_r[j] = e.ar;
+        A_i[j] = e.ai;
+        a_e[j] = e.ae;
+        B_r[j] = e.br;
+        B_i[j] = e.bi;
+        b_e[j] = e.be;
+        ke[j] = t.ke[at];
+    }
+    return MBK_OK;
+}
+
+int mbk_deep_xbla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                             int32_t *count, double *mag, uint64_t *steps_executed)
+{
+    if (!count || !mag || !steps_executed) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::WideBlaTable t;
+    int rc = xbla_host_table(orbit, view, &t);
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    mbk::wide_bla_count_host(orbit->o.wide, orbit->o.length, t, deep_dc(col, view->width, view->range_r),
+                             deep_dc(row, view->height, view->range_i), view->exp2, (int64_t)mrd, count, mag, steps_executed);
     return MBK_OK;
 }
 
@@ -3063,7 +3198,7 @@ struct Outputs {
 static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const Outputs &o, hipStream_t stream)
 {
     switch (t.kind) {
-        case Target::kWide: return launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream);
+        case Target::kWide: return launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
         case Target::kDeep:
             return o.distance ? launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
                               : launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
@@ -3304,7 +3439,7 @@ static const RenderRules kRenderRules[4] = {
      "MBK_RENDER_DISTANCE_REL is implemented for deep views only (plain views: MBK_RENDER_DISTANCE)"},
     {MBK_DEEP_BLA, "deep renders take MBK_DEEP_BLA only (no kernel selection, no fp32)",
      "MBK_RENDER_DISTANCE is implemented for plain views only (no deep renders)", nullptr},
-    {0u, "extended-range deep renders take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)",
+    {MBK_DEEP_XBLA, "extended-range deep renders take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)",
      "distance estimates are not implemented for extended-range deep views", "distance estimates are not implemented for extended-range deep views"},
 };
 
@@ -3802,7 +3937,7 @@ static const HistRules kHistRules[4] = {
     {MBK_KERNEL_MASK | MBK_PRECISION_F32, "histogram flags carry kernel selection and MBK_PRECISION_F32 only"},
     {MBK_KERNEL_MASK, "Julia histogram flags carry kernel selection only"},
     {MBK_DEEP_BLA, "deep histograms take MBK_DEEP_BLA only (no kernel selection, no fp32)"},
-    {0u, "extended-range deep histograms take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)"},
+    {MBK_DEEP_XBLA, "extended-range deep histograms take no flags (no MBK_DEEP_BLA, no kernel selection, no fp32)"},
 };
 
 // Everything a view histogram can refuse, before anything is allocated, enqueued or written: the sample launch's own rules.

@@ -271,6 +271,44 @@ def julia_count_host(z, c, mrd: int) -> Tuple[int, float]:
     return int(n.value), float(mag.value)
 
 
+def _cxview(view: "WideDeepView", window=None) -> L.mbk_deep_xview:
+    col0, row0, ncols, nrows = window if window is not None else (0, 0, view.width, view.height)
+    return L.mbk_deep_xview(view.range_r, view.range_i, view.exp2, view.width, view.height, col0, row0, ncols, nrows)
+
+
+def deep_xbla_table(orbit: "DeepOrbit", view: "WideDeepView", window=None) -> list:
+    """mbk_deep_xbla_info / _read: the table an xbla=True launch of `view` on `orbit` would use (include/mbk.h, "Extended-range
+    deep views with bilinear approximation"), built on the host, without a device.  A list of levels, each a dict of arrays:
+    Ar, Ai (float64), ae (int32), Br, Bi (float64), be, ke (int32); [] for an orbit of length 1.  The window plays no part."""
+    lib = L.load()
+    cv = _cxview(view, window)
+    levels, entries = C.c_uint32(), C.c_uint64()
+    _check(lib, lib.mbk_deep_xbla_info(orbit._h, C.byref(cv), C.byref(levels), C.byref(entries)))
+    out = []
+    for l in range(levels.value):
+        n = (orbit.length - 1) >> l
+        lv = {k: np.empty(n, np.float64 if k[0] in "AB" else np.int32) for k in ("Ar", "Ai", "ae", "Br", "Bi", "be", "ke")}
+        _check(lib, lib.mbk_deep_xbla_read(orbit._h, C.byref(cv), l, *[a.ctypes.data for a in lv.values()], n))
+        out.append(lv)
+    assert sum(lv["ke"].size for lv in out) == entries.value
+    return out
+
+
+def deep_xbla_count_host(orbit: "DeepOrbit", view: "WideDeepView", pixels, mrd: int, window=None):
+    """mbk_deep_xbla_count_host on the pixels (row-major indices of the FULL view): (count int32, mag float64, steps executed
+    int64 -- a skip is one) per pixel, on the host, from the functions the kernel uses."""
+    lib = L.load()
+    cv = _cxview(view, window)
+    pixels = np.asarray(pixels, np.int64).ravel()
+    count, mag, steps = np.empty(pixels.size, np.int32), np.empty(pixels.size, np.float64), np.empty(pixels.size, np.int64)
+    c, m, s = C.c_int32(), C.c_double(), C.c_uint64()
+    for j, k in enumerate(pixels):
+        _check(lib, lib.mbk_deep_xbla_count_host(orbit._h, C.byref(cv), int(k % view.width), int(k // view.width), int(mrd),
+                                                 C.byref(c), C.byref(m), C.byref(s)))
+        count[j], mag[j], steps[j] = c.value, m.value, s.value
+    return count, mag, steps
+
+
 def interior_host(c, mrd: int) -> Tuple[int, int, int, float]:
     """mbk_interior_host: (count, period, cycle_len, de) of the pixel c = (c_r, c_i) on the host, without a device: the
     contract's four stages (include/mbk.h, "Interior views") compiled from the functions the kernel uses.  period 0 with
@@ -662,7 +700,8 @@ class MandelbrotDevice:
 
     # -- deep-zoom views (include/mbk.h, "Deep-zoom views") ------------------------------------
     # Every method below takes a DeepView or a WideDeepView ("Extended-range deep views"): the wide view goes to the
-    # mbk_deep_xview_* call of the same name, which has no bilinear approximation and no distance estimate.
+    # mbk_deep_xview_* call of the same name, which has no distance estimate and a bilinear approximation of its own (xbla,
+    # MBK_DEEP_XBLA; bla stays refused there, and xbla is refused for a plain DeepView).
     @staticmethod
     def _cdeep(view: Union[DeepView, WideDeepView], window):
         col0, row0, ncols, nrows = window if window is not None else (0, 0, view.width, view.height)
@@ -670,14 +709,18 @@ class MandelbrotDevice:
             return L.mbk_deep_xview(view.range_r, view.range_i, view.exp2, view.width, view.height, col0, row0, ncols, nrows)
         return L.mbk_deep_view(view.span_r, view.span_i, view.width, view.height, col0, row0, ncols, nrows)
 
-    def _deep_fn(self, view, name: str, bla: bool = False, source: Optional[str] = None):
+    def _deep_fn(self, view, name: str, bla: bool = False, source: Optional[str] = None, xbla: bool = False):
         """(the C entry point `name` for this kind of deep view, its flags)"""
         if isinstance(view, WideDeepView):
             if bla:
                 raise ValueError("bla=True is not implemented for a WideDeepView")
             if source in ("distance", "distance_rel"):
                 raise ValueError("distance estimates are not implemented for a WideDeepView")
-            return getattr(self._lib, "mbk_deep_xview_" + name), 0
+            return getattr(self._lib, "mbk_deep_xview_" + name), (L.MBK_DEEP_XBLA if xbla else 0)
+        if xbla and bla:
+            raise ValueError("bla=True and xbla=True exclude each other")
+        if xbla:
+            raise ValueError("xbla=True is implemented for a WideDeepView only (a DeepView takes bla=True)")
         return getattr(self._lib, "mbk_deep_view_" + name), (L.MBK_DEEP_BLA if bla else 0)
 
     # One body per operation serves the four kinds of view.  A kind is named by keywords: orbit (a deep view, plain or wide,
@@ -686,10 +729,10 @@ class MandelbrotDevice:
         return self._cdeep(view, window) if orbit is not None else self._cview(view, window)
 
     def _kind_fn(self, name: str, view, cv, *, orbit=None, c=None, kernel: str = "default", precision: str = "f64", bla: bool = False,
-                 source: Optional[str] = None):
+                 source: Optional[str] = None, xbla: bool = False):
         """(the C entry point `name` for this kind of view, its arguments between the ctx and mrd, its flags)"""
         if orbit is not None:
-            fn, flags = self._deep_fn(view, name, bla, source)
+            fn, flags = self._deep_fn(view, name, bla, source, xbla)
             return fn, (orbit._h, C.byref(cv)), flags
         if c is not None:
             return getattr(self._lib, "mbk_julia_view_" + name), (C.byref(cv), float(c[0]), float(c[1])), L.KERNELS[kernel]
@@ -728,18 +771,20 @@ class MandelbrotDevice:
 
     def compute_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_counts: bool = True,
                           want_bytes: bool = True, want_smooth: bool = False, out_counts: Optional[np.ndarray] = None,
-                          out_bytes: Optional[np.ndarray] = None, bla: bool = False):
+                          out_bytes: Optional[np.ndarray] = None, bla: bool = False, xbla: bool = False):
         """Synchronous: (counts int32 | None, bytes uint8 | None, smooth float64 | None, TileStats), each [nrows, ncols].
         bla: step with bilinear approximation (MBK_DEEP_BLA; include/mbk.h, "Deep-zoom views with bilinear approximation"):
         runs of steps collapse into one linear map while the pixel's offset is tiny against the reference orbit -- several
-        times fewer steps on a deep view, counts that equal the exact rule's on all but a fraction of a percent of pixels."""
+        times fewer steps on a deep view, counts that equal the exact rule's on all but a fraction of a percent of pixels.
+        xbla: the same for a WideDeepView (MBK_DEEP_XBLA; "Extended-range deep views with bilinear approximation"): a table
+        of its own, mantissas with int32 exponents.  bla with a WideDeepView and xbla with a DeepView are refused."""
         cv = self._cdeep(view, window)
         shape = (cv.nrows, cv.ncols)
         counts = _out_array(out_counts, shape, np.int32) if want_counts else None
         byts = _out_array(out_bytes, shape, np.uint8) if want_bytes else None
         smooth = np.empty(shape, np.float64) if want_smooth else None
         flags, p_counts, p_bytes = _wanted(shape, counts, byts)
-        fn, extra = self._deep_fn(view, "compute", bla)
+        fn, extra = self._deep_fn(view, "compute", bla, xbla=xbla)
         st = L.mbk_stats()
         self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags | extra, p_counts, p_bytes,
                        smooth.ctypes.data if smooth is not None else None, C.byref(st)))
@@ -747,19 +792,19 @@ class MandelbrotDevice:
 
     def submit_deep_view(self, slot: int, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None,
                          out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None,
-                         bla: bool = False) -> None:
+                         bla: bool = False, xbla: bool = False) -> None:
         """Enqueue a deep view / window on `slot`; the host arrays are valid after wait(slot)."""
         cv = self._cdeep(view, window)
         flags, p_counts, p_bytes = _wanted((cv.nrows, cv.ncols), out_counts, out_bytes)
-        fn, extra = self._deep_fn(view, "submit", bla)
+        fn, extra = self._deep_fn(view, "submit", bla, xbla=xbla)
         self._check(fn(self._h, slot, orbit._h, C.byref(cv), mrd, flags | extra, p_counts, p_bytes))
 
     def launch_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_counts: int = 0, d_bytes: int = 0,
-                         d_smooth: int = 0, stream: int = 0, window=None, bla: bool = False) -> None:
-        """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream).  With bla the first launch of a
+                         d_smooth: int = 0, stream: int = 0, window=None, bla: bool = False, xbla: bool = False) -> None:
+        """Asynchronous launch on raw DEVICE pointers on ``stream`` (0 = HIP's null stream).  With bla or xbla the first launch of a
         view's spans on an orbit builds and uploads the table synchronously."""
         cv = self._cdeep(view, window)
-        fn, extra = self._deep_fn(view, "launch", bla)
+        fn, extra = self._deep_fn(view, "launch", bla, xbla=xbla)
         flags = (L.MBK_WANT_COUNTS if d_counts else 0) | (L.MBK_WANT_BYTES if d_bytes else 0) | extra
         self._check(fn(self._h, orbit._h, C.byref(cv), mrd, flags, d_counts or None, d_bytes or None, d_smooth or None,
                        stream or None))
@@ -815,14 +860,16 @@ class MandelbrotDevice:
 
     def render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, source: str = "smooth",
                          supersample: int = 1, window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None, lut=None,
-                         bla: bool = False):
+                         bla: bool = False, xbla: bool = False):
         """render_view for a deep view: the samples are those of the same orbit and spans at s times the width and height.
         Source "distance_rel" colours the deep distance estimate (compute_deep_view_distance; Palette.deep_distance); source
         "distance", the plain views' estimate in plane units, is refused (MbkError).  Source "equalized" and `lut` as for
         render_view (the table of deep_view_histogram of the whole view when lut is None).  bla: the samples (and that
-        histogram) are those of compute_deep_view(bla=True); refused with source "distance_rel"."""
+        histogram) are those of compute_deep_view(bla=True); refused with source "distance_rel".  xbla: likewise for a
+        WideDeepView (compute_deep_view(xbla=True))."""
         return self._render("compute", view, mrd, palette, source, supersample, window, max_band_rows, lut,
-                            lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla), out=out, orbit=orbit, bla=bla)
+                            lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla, xbla=xbla), out=out, orbit=orbit, bla=bla,
+                            xbla=xbla)
 
     def launch_render_view(self, view: View, mrd: int, *, palette, d_rgba: int, source: str = "smooth", supersample: int = 1,
                            stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0, lut=None) -> None:
@@ -834,9 +881,10 @@ class MandelbrotDevice:
 
     def launch_render_deep_view(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, d_rgba: int,
                                 source: str = "smooth", supersample: int = 1, stream: int = 0, window=None,
-                                max_band_rows: int = 0, lut=None, bla: bool = False) -> None:
+                                max_band_rows: int = 0, lut=None, bla: bool = False, xbla: bool = False) -> None:
         self._render("launch", view, mrd, palette, source, supersample, window, max_band_rows, lut,
-                     lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla), d_rgba=d_rgba, stream=stream, orbit=orbit, bla=bla)
+                     lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla, xbla=xbla), d_rgba=d_rgba, stream=stream, orbit=orbit,
+                     bla=bla, xbla=xbla)
 
     # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
     def view_histogram(self, view: View, mrd: int, *, window=None, kernel: str = "default", precision: str = "f64",
@@ -847,9 +895,9 @@ class MandelbrotDevice:
         return self._histogram(view, mrd, window, want_stats, kernel=kernel, precision=precision)
 
     def deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None, want_stats: bool = False,
-                            bla: bool = False):
-        """view_histogram for a deep view (bla: of the counts of compute_deep_view(bla=True))."""
-        return self._histogram(view, mrd, window, want_stats, orbit=orbit, bla=bla)
+                            bla: bool = False, xbla: bool = False):
+        """view_histogram for a deep view (bla / xbla: of the counts of compute_deep_view with the same keyword)."""
+        return self._histogram(view, mrd, window, want_stats, orbit=orbit, bla=bla, xbla=xbla)
 
     def launch_view_histogram(self, view: View, mrd: int, *, d_hist: int, stream: int = 0, window=None, kernel: str = "default",
                               precision: str = "f64") -> None:
@@ -858,8 +906,8 @@ class MandelbrotDevice:
         self._launch_histogram(view, mrd, d_hist, stream, window, kernel=kernel, precision=precision)
 
     def launch_deep_view_histogram(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_hist: int, stream: int = 0,
-                                   window=None, bla: bool = False) -> None:
-        self._launch_histogram(view, mrd, d_hist, stream, window, orbit=orbit, bla=bla)
+                                   window=None, bla: bool = False, xbla: bool = False) -> None:
+        self._launch_histogram(view, mrd, d_hist, stream, window, orbit=orbit, bla=bla, xbla=xbla)
 
     def counts_histogram(self, d_counts: int, n: int, mrd: int, d_hist: int, stream: int = 0) -> None:
         """Asynchronous: the histogram of n int32 counts in DEVICE memory is ADDED into the DEVICE table d_hist (uint64[mrd])

@@ -153,20 +153,24 @@ def render_view(devices: Sequence, view, mrd: int, *, band_rows: int = 128, want
 
 def render_deep_view(devices: Sequence, orbit, view, mrd: int, *, band_rows: int = 128, want_counts: bool = True,
                      want_bytes: bool = True, out_counts: Optional[np.ndarray] = None, out_bytes: Optional[np.ndarray] = None,
-                     bla: bool = False) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], List[dict]]:
+                     bla: bool = False, xbla: bool = False) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], List[dict]]:
     """render_view for a deep-zoom view (device.DeepView) over one DeepOrbit: row bands from a shared queue, two in flight
     per device (submit_deep_view / wait).  A band's offsets come from the whole view, so the image is bit-identical to
     compute_deep_view's -- with bla too: the table depends on the whole view, not on the band.  `view` may be a
-    device.WideDeepView (extended range; bla=True raises ValueError: it has no bilinear approximation)."""
+    device.WideDeepView (extended range; bla=True raises ValueError: its bilinear approximation is xbla=True, which a
+    DeepView refuses in turn)."""
     if bla and not hasattr(view, "span_r"):
         raise ValueError("bla=True is not implemented for a WideDeepView")
+    if xbla and hasattr(view, "span_r"):
+        raise ValueError("xbla=True is implemented for a WideDeepView only (a DeepView takes bla=True)")
+    more = {"xbla": True} if xbla else {}
 
     def submit(dev, s, window, oc, ob):
-        dev.submit_deep_view(s, orbit, view, mrd, window=window, out_counts=oc, out_bytes=ob, bla=bla)
+        dev.submit_deep_view(s, orbit, view, mrd, window=window, out_counts=oc, out_bytes=ob, bla=bla, **more)
 
     def compute(dev, window, oc, ob):
         return dev.compute_deep_view(orbit, view, mrd, window=window, want_counts=want_counts, want_bytes=want_bytes,
-                                     out_counts=oc, out_bytes=ob, bla=bla)[3]
+                                     out_counts=oc, out_bytes=ob, bla=bla, **more)[3]
 
     return _render_bands(devices, view.width, view.height, band_rows, want_counts, want_bytes, out_counts, out_bytes,
                          submit, compute, "submit_deep_view")

@@ -442,7 +442,8 @@ int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *vi
  * compares |Z_m + dz| with |dz|.  An extended-range view carries every number as a binary64 mantissa pair with one int32
  * exponent, on the host (the wide table) and on the device (csrc/mbk_deep_wide.h), so spans reach as far as the fixed-point
  * orbit does: P <= 4096 fraction bits, spans down to ~2^-4030.  It covers counts, bytes, smooth values, renders (sources
- * bytes, smooth, equalized) and histograms; distance estimates and MBK_DEEP_BLA are not implemented for it.
+ * bytes, smooth, equalized) and histograms; distance estimates and MBK_DEEP_BLA are not implemented for it (its bilinear
+ * approximation is a flag of its own: MBK_DEEP_XBLA, "Extended-range deep views with bilinear approximation", below).
  *
  * Contract (bit-exact; tests/deep_wide_model.py restates it in numpy; tests/test_deep_wide.py holds the host twins below to
  * it and it to the truth, tests/test_gpu_deep_wide.py holds the GPU to it).  Binary64 mantissas, int32 exponents, every
@@ -492,8 +493,8 @@ typedef struct mbk_deep_xview {
     uint32_t width, height, col0, row0, ncols, nrows;
 } mbk_deep_xview;
 
-/* The three forms, as mbk_deep_view_launch / _compute / _submit: the same outputs, flags (MBK_WANT_COUNTS | MBK_WANT_BYTES
- * only), statistics and refusals; in addition MBK_DEEP_BLA, ranges outside [2^-64, 4] and exp2 outside [-8192, 0] are
+/* The three forms, as mbk_deep_view_launch / _compute / _submit: the same outputs, flags (MBK_WANT_COUNTS | MBK_WANT_BYTES,
+ * and MBK_DEEP_XBLA, only), statistics and refusals; in addition MBK_DEEP_BLA, ranges outside [2^-64, 4] and exp2 outside [-8192, 0] are
  * MBK_ERR_INVALID. */
 int mbk_deep_xview_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
                           int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream);
@@ -505,6 +506,89 @@ int mbk_deep_xview_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, c
  * the full view: its count and the mag of the escaping step (0 for count 0).  MBK_ERR_INVALID for what the launch refuses. */
 int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
                               int32_t *count, double *mag);
+
+/*
+ * Extended-range deep views with bilinear approximation.  NOT in the reference; additive (the ABI version stays 5): without
+ * the flag every call stores what it stored before, and MBK_DEEP_BLA keeps being refused by every mbk_deep_xview_* call.
+ * Extended-range views are the ones with the largest iteration counts -- a pixel 2^-3000 from its centre runs ~2400 steps
+ * that are linear to working precision before anything else happens -- and their step is the most expensive in the library.
+ * The table of "Deep-zoom views with bilinear approximation" cannot serve them: its coefficients overflow binary64 (|A| grows
+ * like 4^(2^l)) and every useful radius is below 1e-308.  This table carries A, B and the radius as binary64 mantissas with
+ * int32 exponents, like the wide step; that also removes the overflow ceiling on the levels.
+ *
+ * MBK_DEEP_XBLA is a flag of mbk_deep_xview_launch / _compute / _submit, of mbk_deep_xview_render_launch / _compute and their
+ * _equalized_ forms (sources bytes, smooth, equalized) and of mbk_deep_xview_histogram_launch / _compute.  Every other call
+ * refuses it with MBK_ERR_INVALID and writes nothing: plain views, Julia views, mbk_deep_view_*, the distance, interior and
+ * density calls.  MBK_DEEP_XBLA | MBK_DEEP_BLA is refused as MBK_DEEP_BLA alone is.
+ *
+ * Contract (tests/deep_wide_bla_model.py restates it in numpy; tests/test_deep_wide_bla.py holds the host twins below to it
+ * and it to the truth, tests/test_gpu_deep_wide_bla.py holds the GPU to it, bit for bit).  Everything of "Extended-range deep
+ * views" stands: the wide table, the offsets dcm 2^exp2, sh, norm, EZ, the steps (a) .. (g), counts, bytes, smooth, statistics
+ * (pixel_iterations counts the reference's iterations -- count, or mrd - 1 for 0 -- not the steps executed).  Binary64
+ * mantissas, int32 exponents, every floating operation rounded on its own, no contraction.
+ *   numbers   a wide complex is (f_r, f_i, e) as norm produces it: the larger |component| in [0.5, 1), a zero is (0, 0, EZ).
+ *             A wide real >= 0 is (f, e) with f in [0.5, 1), or (0, EZ): real(v, e) = (ldexp(v, -s), e + s) with s the frexp
+ *             exponent of v > 0, (0, EZ) for v <= 0.  |(f_r, f_i, e)| = real(fl(sqrt(fl(fl(f_r^2) + fl(f_i^2)))), e).
+ *             Wide reals compare by exponent, then by mantissa.  Complex products are the four-product form of the plain
+ *             contract on the mantissas, (fl(fl(ac) - fl(bd)), fl(fl(ad) + fl(bc))) with (a, b) the left factor, at the sum of the
+ *             exponents, not renormalised before the next operation (nominal exponents, as in the wide step).
+ *   per view  dcmax = real(fl(|dcm_r(column 0)| + |dcm_i(row 0)|), exp2) of the FULL view, not the window (windows and bands
+ *             share one table and stay bit-identical to the whole view; a render's sample view at s times the width and height
+ *             is a full view of its own, as for MBK_DEEP_BLA).  eps = 2^-40.
+ *   table     Level l has n_l = floor((M - 1) / 2^l) entries, for l = 0 .. while n_l >= 1 (at most 32 levels); entry j covers
+ *             the 2^l steps that start at m = 1 + j 2^l.  With M <= 1 there is no table and the flag changes nothing.
+ *             Level 0: A = (X_r, X_i, xe + 1) of the wide table's entry m (2 Z_m, exact; not renormalised, so a mantissa of
+ *             exactly 1 stays), B = norm((1, 0), 0) = (0.5, 0, 1), r = (f, e - 40) with (f, e) = |A|.
+ *             Level l + 1, entry j, from x = entry 2j and y = entry 2j + 1 of level l:
+ *               A = norm(A_y A_x, e_Ay + e_Ax)
+ *               B: Q = A_y B_x at qe = e_Ay + e_Bx;  h = max(qe, e_By);  B = norm(fl(sh(Q, qe - h) + sh(B_y, e_By - h)), h)
+ *               t: (fa, ea) = |A_x|, (fb, eb) = |B_x|;  u = fl(fb f_dcmax) at ue = eb + e_dcmax;  g = max(e_ry, ue);
+ *                  d = fl(sh(f_ry, e_ry - g) - sh(u, ue - g));  t = real(fl(d / fa), g - ea)
+ *               r = min(r_x, t)
+ *   dead      An entry is dead -- r = (0, EZ), A = B = (0, 0, EZ) stored -- when any of these holds: it is a level-0 entry with
+ *             Z_m = 0; either child is dead; |A_x| = 0; d <= 0 (the radius max(t, 0) is 0); an exponent of the merged A or B
+ *             other than EZ exceeds 2^20 in magnitude; the exponent of r is below -2^20.  A radius that small admits no dz a
+ *             view with exp2 >= -8192 can hold; the bound keeps every sum of exponents inside int32 and EZ = -2^24 below every
+ *             live exponent.  A dead entry is never taken and death propagates upward: this replaces the plain contract's
+ *             "overflowed entries are never taken", and levels that overflow binary64 there are live here.
+ *   radius    Per entry one int32 ke: the largest integer with 2^ke <= fl(f_r 0.7071067811865476) 2^e_r, that is
+ *             e_r + (frexp exponent of that product) - 1; EZ for a dead entry.  A pixel state (w, q) passes iff EZ < q <= ke.
+ *             max(|w_r|, |w_i|) < 1, so q <= ke puts both components of dz below 2^ke <= r / sqrt 2: one integer compare and one
+ *             4-byte load per level probed, at the cost of at most a factor 2 in radius.  ke is non-increasing in l at a fixed
+ *             starting m.  A zero dz (q = EZ) passes no entry: it takes the plain step, which keeps it at dc.
+ *   step      state (w, q, m, i), i the index of the step about to run.  Take the highest level l with ALL of
+ *               m >= 1;  (m - 1) mod 2^l = 0;  (m - 1) >> l < n_l;  i + 2^l <= mrd;  EZ < q <= ke
+ *             (each is monotone in l: a search upward from level 0 that stops at the first failure finds the same level).
+ *             If there is one:
+ *               p1 = A w at e1 = e_A + q;  p2 = B dcm at e2 = e_B + exp2;  h = max(e1, e2)
+ *               (w, q) = norm(fl(sh(p1, e1 - h) + sh(p2, e2 - h)), h);  m += 2^l
+ *             and the step index becomes i + 2^l - 1.  If there is none, the steps (a) .. (d) run.  After either, (e), (f), (g)
+ *             run exactly as in "Extended-range deep views", m == M included.  The steps inside a skip are not tested.
+ *             m = 0, the state right after a rebase, always takes the plain step.  A zero dcm (the centre pixel of an odd-sized
+ *             view) keeps its nominal exponent e_B + exp2, as in step (c); a zero B has e_B = EZ and never sets h.
+ *   eps       2^-40, the plain contract's, held to the truth again here: against direct iteration at P + 128 bits the model
+ *             equals the truth on every sampled pixel of the five cases of tests/test_deep_wide.py (spans 2^-1100 and 2^-3000
+ *             on c = i and on a Misiurewicz point, and the centre 1e-400).  The cap is the wide contract's: >= 99 % of pixels.
+ *
+ * The ctx keeps the device copy of one such table beside each orbit copy's wide table, keyed by the orbit's id and dcmax
+ * (the bits of its mantissa and its exponent, which carries exp2): 4 + 48 bytes per entry, fewer than 2 (M - 1) entries.  It
+ * follows the rule of the MBK_DEEP_BLA table: built on the host and uploaded on the first MBK_DEEP_XBLA launch of the orbit
+ * on the ctx, and REBUILT whenever a launch brings another dcmax -- synchronously, and the rebuild first synchronises the
+ * device, since a queued launch may still read the table it replaces.  Launch once per (orbit, spans) before capturing, and
+ * expect alternating spans on one orbit to serialise.  The table is freed with the orbit copies.
+ */
+#define MBK_DEEP_XBLA 0x10000u
+/* Host twins for the CPU tests, compiled from the functions the builder and the kernel use: no ctx, no device.  `view` gives
+ * dcmax and exp2 (its window is not used); MBK_ERR_INVALID for what mbk_deep_xview_launch refuses in a view.
+ * _info: the number of levels (0 for M <= 1) and of entries over all levels.  _read: level `level` into seven arrays of
+ * capacity n (MBK_ERR_INVALID below n_level, or for a level the table does not have).  _count_host: the pixel (col, row) of
+ * the full view under the rule above -- its count, the mag of the escaping step (0 for count 0) and the number of steps
+ * executed, a skip counting as one. */
+int mbk_deep_xbla_info(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t *levels, uint64_t *entries);
+int mbk_deep_xbla_read(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t level, double *A_r, double *A_i,
+                       int32_t *a_e, double *B_r, double *B_i, int32_t *b_e, int32_t *ke, uint64_t n);
+int mbk_deep_xbla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                             int32_t *count, double *mag, uint64_t *steps_executed);
 
 /*
  * Distance estimates for deep views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes, and
@@ -648,7 +732,9 @@ int mbk_view_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, ui
 int mbk_deep_view_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                 uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
 /* Extended-range deep views ("Extended-range deep views"): sources MBK_RENDER_BYTES / _SMOOTH (and _EQUALIZED through the
- * _equalized_ calls below); MBK_RENDER_DISTANCE, MBK_RENDER_DISTANCE_REL and every flag are MBK_ERR_INVALID. */
+ * _equalized_ calls below); MBK_RENDER_DISTANCE, MBK_RENDER_DISTANCE_REL and every flag but MBK_DEEP_XBLA ("Extended-range
+ * deep views with bilinear approximation": the samples are then those of mbk_deep_xview_launch with the flag) are
+ * MBK_ERR_INVALID. */
 int mbk_deep_xview_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
 int mbk_deep_xview_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
@@ -701,7 +787,8 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
  * accumulate into one table.  n == 0 is a no-op.
  * mbk_view_histogram_launch / mbk_deep_view_histogram_launch: the window's counts are produced by mbk_view_launch /
  * mbk_deep_view_launch into scratch the ctx keeps per stream (the renders' sample scratch), with the same kernel selection and
- * refusal rules: `flags` carries kernel selection and MBK_PRECISION_F32 for a plain view, MBK_DEEP_BLA alone for a deep one.  4 bytes per
+ * refusal rules: `flags` carries kernel selection and MBK_PRECISION_F32 for a plain view, MBK_DEEP_BLA alone for a deep one, MBK_DEEP_XBLA alone for an
+ * extended-range one.  4 bytes per
  * sample, banded under MBK_RENDER_BAND_BYTES exactly as a render bands, so no view size needs more scratch.  Each band's
  * counts are ADDED into d_hist.
  * _compute: synchronous on slot 0 (the slot-0 rule applies); h_hist is OVERWRITTEN, not accumulated; stats as for
