@@ -35,6 +35,7 @@
 #include "mbk_distance.h"
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
+#include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
 #include "mbk_density.h"
 
@@ -3095,6 +3096,93 @@ double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double 
     return mbk::deep_distance_value(mag, dmagD, e, range_r, count);
 }
 
+// ---- distance estimates for extended-range deep views (mbk_deep_wide_distance.h; mbk.h, the section of that name) -------
+
+// the wide distance kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep_wide_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd,
+                                     int32_t *d_counts, double *d_rel, hipStream_t stream)
+{
+    const mbk::WideEntry *d_orbit = nullptr;
+    int rc = wide_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepWideDistanceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.v.orbit = d_orbit;
+    a.v.z1 = orbit->o.wide[1];
+    a.v.M = orbit->o.length;
+    a.v.exp2 = v->exp2;
+    fill_deep_window(a.v, v, mrd);
+    a.v.counts = d_counts;
+    a.range_r = v->range_r;
+    a.rel = d_rel;
+    hipLaunchKernelGGL(mbk::deep_wide_distance_kernel, block_grid(a.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// Everything a wide distance call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
+static int wide_distance_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags)
+{
+    if (flags & MBK_DEEP_XBLA)
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is not implemented for extended-range deep distance estimates");
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance estimates take no flags (no kernel selection, no fp32)");
+    return validate_deep_wide(ctx, orbit, view, mrd, 0u);
+}
+
+int mbk_deep_xview_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = wide_distance_check(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_deep_wide_distance(ctx, orbit, view, mrd, d_counts, d_rel, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_xview_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                    uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = wide_distance_check(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_rel, stats,
+                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
+                              return launch_deep_wide_distance(ctx, orbit, view, mrd, d_counts, d_rel, stream);
+                          });
+}
+
+// host twins (mbk_deep_wide_distance.h): no ctx, no device
+int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                                 int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel)
+{
+    if (!count || !extra || !mag || !D_r || !D_i || !e || !rel) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
+    if (rc != MBK_OK) return rc;
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    mbk::wide_distance_host(orbit->o.wide, orbit->o.length, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i),
+                            view->exp2, (int64_t)mrd, count, extra, mag, D_r, D_i, e);
+    const double r2 = *D_r * *D_r, i2 = *D_i * *D_i;
+    *rel = mbk::wide_distance_value(*mag, r2 + i2, *e, view->range_r, view->exp2, *count);
+    return MBK_OK;
+}
+
+int mbk_deep_xdistance_step_host(double z_r, double z_i, int32_t t, double *D_r, double *D_i, int32_t *e)
+{
+    if (!D_r || !D_i || !e) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::wide_dstep(z_r, z_i, t, *D_r, *D_i, *e);
+    return MBK_OK;
+}
+
+double mbk_deep_xdistance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t exp2, int32_t count)
+{
+    return mbk::wide_distance_value(mag, dmagD, e, range_r, exp2, count);
+}
+
 // ---- Julia views (mbk_julia.h; mbk.h "Julia views") ----------------------------------------------------------
 
 // Everything a Julia launch can refuse, before anything is allocated, enqueued or written.  flags: MBK_WANT_* (MBK_WANT_BYTES:
@@ -3198,7 +3286,9 @@ struct Outputs {
 static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const Outputs &o, hipStream_t stream)
 {
     switch (t.kind) {
-        case Target::kWide: return launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
+        case Target::kWide:
+            return o.distance ? launch_deep_wide_distance(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream)
+                              : launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
         case Target::kDeep:
             return o.distance ? launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
                               : launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
@@ -3877,6 +3967,50 @@ int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t wid
     pal.outside = colours.outside;
     mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, de, rgba, mbk::kRuleInterior, period);
     return MBK_OK;
+}
+
+// ---- distance renders of extended-range deep views (mbk.h "Distance estimates for extended-range deep views"): calls of
+// their own on the render machinery above; mbk_deep_xview_render_* keeps refusing the distance sources ---------------------
+
+// Everything such a render can refuse, before anything is allocated, enqueued or written.
+static int wide_distance_render_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                                      const mbk_render_spec *spec, const void *out, Target *t)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_render_spec(ctx, spec);
+    if (rc != MBK_OK) return rc;
+    if (spec->source != MBK_RENDER_DISTANCE_REL)
+        return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance renders take MBK_RENDER_DISTANCE_REL only");
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    *t = wide_target(orbit, view);
+    const uint32_t s = spec->supersample;
+    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
+    return wide_distance_check(ctx, orbit, &samples.wide, mrd, flags);
+}
+
+int mbk_deep_xview_distance_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    Target t;
+    int rc = wide_distance_render_check(ctx, orbit, view, mrd, flags, spec, d_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+}
+
+int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    Target t;
+    int rc = wide_distance_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, nullptr, 0u);
 }
 
 // ---- count histograms and the equalisation table (mbk_histogram.h; mbk.h "Count histograms") ------------------------------

@@ -309,6 +309,43 @@ def deep_xbla_count_host(orbit: "DeepOrbit", view: "WideDeepView", pixels, mrd: 
     return count, mag, steps
 
 
+def wide_distance_host(orbit: "DeepOrbit", view: "WideDeepView", pixels, mrd: int) -> dict:
+    """mbk_deep_xview_distance_host on the pixels (row-major indices of the FULL view), on the host, from the functions the
+    kernel uses (include/mbk.h, "Distance estimates for extended-range deep views"): a dict of arrays n (int32), extra (the
+    run-on steps taken, int32), mag, Dr, Di (float64), e (int64: d = D 2^e), dmagD and rel (float64, through the host's ln)."""
+    lib = L.load()
+    cv = _cxview(view)
+    pixels = np.asarray(pixels, np.int64).ravel()
+    out = {k: np.empty(pixels.size, t) for k, t in (("n", np.int32), ("extra", np.int32), ("mag", np.float64), ("Dr", np.float64),
+                                                   ("Di", np.float64), ("e", np.int64), ("rel", np.float64))}
+    n, x, e = C.c_int32(), C.c_int32(), C.c_int32()
+    mag, dr, di, rel = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    for j, k in enumerate(pixels):
+        _check(lib, lib.mbk_deep_xview_distance_host(orbit._h, C.byref(cv), int(k % view.width), int(k // view.width), int(mrd),
+                                                     C.byref(n), C.byref(x), C.byref(mag), C.byref(dr), C.byref(di), C.byref(e),
+                                                     C.byref(rel)))
+        for key, v in (("n", n), ("extra", x), ("mag", mag), ("Dr", dr), ("Di", di), ("e", e), ("rel", rel)):
+            out[key][j] = v.value
+    a = out["Dr"] * out["Dr"]
+    b = out["Di"] * out["Di"]
+    out["dmagD"] = a + b
+    return out
+
+
+def wide_distance_step_host(z_r: float, z_i: float, t: int, D_r: float, D_i: float, e: int) -> Tuple[float, float, int]:
+    """mbk_deep_xdistance_step_host: one derivative step d' = 2 zp d + 1 on zp = (z_r, z_i) 2^t and d = (D_r, D_i) 2^e;
+    returns the new (D_r, D_i, e)."""
+    lib = L.load()
+    dr, di, ce = C.c_double(float(D_r)), C.c_double(float(D_i)), C.c_int32(int(e))
+    _check(lib, lib.mbk_deep_xdistance_step_host(float(z_r), float(z_i), int(t), C.byref(dr), C.byref(di), C.byref(ce)))
+    return float(dr.value), float(di.value), int(ce.value)
+
+
+def wide_distance_value_host(mag: float, dmagD: float, e: int, range_r: float, exp2: int, count: int) -> float:
+    """mbk_deep_xdistance_value_host: the output rule rel = de / (range_r 2^exp2) on the host (with the host's ln)."""
+    return float(L.load().mbk_deep_xdistance_value_host(float(mag), float(dmagD), int(e), float(range_r), int(exp2), int(count)))
+
+
 def interior_host(c, mrd: int) -> Tuple[int, int, int, float]:
     """mbk_interior_host: (count, period, cycle_len, de) of the pixel c = (c_r, c_i) on the host, without a device: the
     contract's four stages (include/mbk.h, "Interior views") compiled from the functions the kernel uses.  period 0 with
@@ -700,8 +737,9 @@ class MandelbrotDevice:
 
     # -- deep-zoom views (include/mbk.h, "Deep-zoom views") ------------------------------------
     # Every method below takes a DeepView or a WideDeepView ("Extended-range deep views"): the wide view goes to the
-    # mbk_deep_xview_* call of the same name, which has no distance estimate and a bilinear approximation of its own (xbla,
-    # MBK_DEEP_XBLA; bla stays refused there, and xbla is refused for a plain DeepView).
+    # mbk_deep_xview_* call of the same name, which refuses the distance sources (the wide distance estimate has methods of
+    # its own: compute_wide_view_distance, below) and has a bilinear approximation of its own (xbla, MBK_DEEP_XBLA; bla stays
+    # refused there, and xbla is refused for a plain DeepView).
     @staticmethod
     def _cdeep(view: Union[DeepView, WideDeepView], window):
         col0, row0, ncols, nrows = window if window is not None else (0, 0, view.width, view.height)
@@ -814,7 +852,7 @@ class MandelbrotDevice:
         carried as D 2^e, so it cannot overflow however deep the view, and the value is rel = de / span_r, the distance as a
         fraction of the view's real span (rel * (width - 1) is the distance in pixels); 0 for never-escaped pixels.  The counts
         are those of compute_deep_view.  Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
-        self._deep_fn(view, "compute_distance", source="distance_rel")   # (a WideDeepView has no distance estimate)
+        self._deep_fn(view, "compute_distance", source="distance_rel")   # (a WideDeepView: compute_wide_view_distance)
         cv = self._cdeep(view, window)
         shape = (cv.nrows, cv.ncols)
         rel = np.empty(shape, np.float64)
@@ -831,6 +869,48 @@ class MandelbrotDevice:
         cv = self._cdeep(view, window)
         self._check(self._lib.mbk_deep_view_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
                                                             d_rel or None, stream or None))
+
+    # -- distance estimates for extended-range deep views (include/mbk.h, the section of that name): calls of their own --
+    def compute_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, window=None):
+        """compute_deep_view_distance for a WideDeepView: the derivative lives in the wide number system (binary64 mantissas,
+        an int32 exponent), so neither a span of 2^-3000 nor an orbit that returns to within 1e-400 of 0 loses it.  The value
+        is rel = de / (range_r 2^exp2), the distance as a fraction of the view's real span; the counts are those of
+        compute_deep_view.  Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
+        cv = _cxview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        rel = np.empty(shape, np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_compute_distance(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
+                                                              rel.ctypes.data, C.byref(st)))
+        return rel, counts, _stats(st)
+
+    def launch_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
+                                  stream: int = 0, window=None) -> None:
+        """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
+        cv = _cxview(view, window)
+        self._check(self._lib.mbk_deep_xview_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
+                                                             d_rel or None, stream or None))
+
+    def render_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, supersample: int = 1,
+                                  window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+        """The view as an RGBA8 image coloured by its distance estimate (source "distance_rel"; Palette.deep_distance), as
+        render_deep_view(source="distance_rel") does for a DeepView.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
+        cv = _cxview(view, window)
+        rgba = self._render_out(cv, out)
+        spec = palette.spec("distance_rel", supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_distance_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                                     rgba.ctypes.data, C.byref(st)))
+        return rgba, _stats(st)
+
+    def launch_render_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, d_rgba: int,
+                                         supersample: int = 1, stream: int = 0, window=None, max_band_rows: int = 0) -> None:
+        """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
+        cv = _cxview(view, window)
+        spec = palette.spec("distance_rel", supersample, max_band_rows)
+        self._check(self._lib.mbk_deep_xview_distance_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                                    d_rgba or None, stream or None))
 
     # -- rendering (include/mbk.h, "Rendering") ---------------------------------------------------
     def _render_out(self, cv, out):

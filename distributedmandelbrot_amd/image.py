@@ -96,13 +96,15 @@ class Palette:
         return Palette(Palette._ramp(near, far, n), inside=inside).for_distance(view, width_px, inner_px=inner_px)
 
     def for_deep_distance(self, view, width_px: float, *, inner_px: float = 0.0) -> "Palette":
-        """for_distance for a DeepView and source "distance_rel", whose samples are fractions of the view's real span: one
+        """for_distance for a DeepView or a WideDeepView and source "distance_rel", whose samples are fractions of the view's real span: one
         OUTPUT pixel is 1 / (width - 1) of it, so scale = (n - 1) (width - 1) / (width_px - inner_px) and
         offset = -inner_px (n - 1) / (width_px - inner_px), whatever the span and the supersampling factor."""
         if not width_px > inner_px >= 0.0:
             raise ValueError("0 <= inner_px < width_px")
         if view.width > 1:
             per_px = float(view.width - 1)
+        elif hasattr(view, "range_r"):   # a WideDeepView's single column: the common 2^exp2 cancels
+            per_px = max(view.height - 1, 1) * (view.range_r / view.range_i)
         else:   # a single column: the rows' pitch, in units of span_r
             per_px = max(view.height - 1, 1) * (view.span_r / view.span_i)
         span = float(width_px) - float(inner_px)

@@ -442,8 +442,9 @@ int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *vi
  * compares |Z_m + dz| with |dz|.  An extended-range view carries every number as a binary64 mantissa pair with one int32
  * exponent, on the host (the wide table) and on the device (csrc/mbk_deep_wide.h), so spans reach as far as the fixed-point
  * orbit does: P <= 4096 fraction bits, spans down to ~2^-4030.  It covers counts, bytes, smooth values, renders (sources
- * bytes, smooth, equalized) and histograms; distance estimates and MBK_DEEP_BLA are not implemented for it (its bilinear
- * approximation is a flag of its own: MBK_DEEP_XBLA, "Extended-range deep views with bilinear approximation", below).
+ * bytes, smooth, equalized) and histograms; its distance estimates are calls of their own ("Distance estimates for
+ * extended-range deep views", below) and MBK_DEEP_BLA is not implemented for it (its bilinear approximation is a flag of its
+ * own: MBK_DEEP_XBLA, "Extended-range deep views with bilinear approximation", below).
  *
  * Contract (bit-exact; tests/deep_wide_model.py restates it in numpy; tests/test_deep_wide.py holds the host twins below to
  * it and it to the truth, tests/test_gpu_deep_wide.py holds the GPU to it).  Binary64 mantissas, int32 exponents, every
@@ -641,6 +642,65 @@ int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, co
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count);
 
 /*
+ * Distance estimates for extended-range deep views.  NOT in the reference; additive (the ABI version stays 5): no existing
+ * call changes -- mbk_deep_xview_render_* keeps refusing the distance sources, the capability lives behind the names below.
+ * The views that need the estimate most are the deepest: at a span of 2^-1100 every visible structure is a filament thinner
+ * than a sample.  The contract above cannot be stretched to them: its zp and its orbit table are binary64 and its spans stop
+ * at 2^-960.  Here the derivative lives in the wide number system.
+ *
+ * Contract (tests/deep_wide_distance_model.py restates it in numpy; tests/test_deep_wide_distance.py holds the host twins
+ * below to it and it to the truth, tests/test_gpu_deep_wide_distance.py holds the GPU to it).  Everything of "Extended-range
+ * deep views" stands: the wide table, dcm 2^exp2, sh, norm, EZ, steps (a) .. (g), the counts.  Added per pixel, binary64
+ * mantissas, int32 exponents, every operation rounded on its own, no contraction:
+ *   state     zp = (zv_r, zv_i, t), the pixel's full z of the previous step: exactly the (zv, t) step (e) computes, kept wide
+ *             and NOT renormalised (nominal exponent, as the wide step does).  D = (D_r, D_i, e), a wide complex as norm makes
+ *             it, d = D 2^e.  Start: zp is step (e) applied to the entry 1 and the start state norm(dcm, exp2) (z_0 = c, taken
+ *             before the M == 1 rebase, which leaves the same value); D = norm((1, 0), 0) = (0.5, 0, 1).
+ *   step i    before the z step:
+ *               P = (fl(fl(zv_r D_r) - fl(zv_i D_i)), fl(fl(zv_r D_i) + fl(zv_i D_r)))
+ *               pe = t + e + 1 (the doubling is done in the exponent: exact);  h = max(pe, 0)
+ *               N = (fl(sh(P_r, pe - h) + sh(1, -h)), sh(P_i, pe - h));  (D, e) = norm(N, h), then e = min(e, 2^30)
+ *             Then steps (a) .. (g) unchanged; zp becomes the new (zv, t) (after a rebase dz = z: the same value either way).
+ *   why wide  near a deep minibrot the orbit returns to within 1e-400 of 0 while |d| is 1e+400: a binary64 zp is 0 there and
+ *             the product is lost.  For the same reason e may decrease.
+ *   corners   sh clamps at -1200: with pe > ~1074 the +1 is dropped (it is below half an ulp unless P cancels); with
+ *             pe < -1200 P is dropped and D = 1.  A zero D is (0, 0, EZ) and gives dmagD = 0, so rel = +inf, as in the plain
+ *             rule.
+ *   count     n is exactly the count of mbk_deep_xview_launch.
+ *   run-on    as in "Distance estimates for deep views": a pixel with n > 0 first applies (g) to the escaping step's state, then
+ *             runs the two recurrences uncounted (rebases and m == M included) until mag >= 2^32 or 64 further steps have run.
+ *   output    rel = de / (range_r 2^exp2), the distance as a fraction of the view's real span.  With range_r = f 2^k (frexp)
+ *             and dmagD = fl(fl(D_r^2) + fl(D_i^2)),
+ *               rel = ldexp(fl(fl(fl(sqrt(fl(mag / dmagD))) fl(ln mag)) / f), -(e + k + exp2)),
+ *             0 if n = 0; never NaN (0 instead).  The unit is the same for every window and every supersampling factor.
+ *   equals plain  wherever a plain view can name the spans and no value of the plain run is subnormal, D 2^e is the plain
+ *             contract's number (scaling by a power of two is exact) and rel is equal bit for bit.
+ *   mrd       0 and 1 run no step: every count and value is 0.
+ * Windows of a view are bit-identical to the whole view.
+ * Against d' = 2 z d + 1, z' = z^2 + c in mpmath at P + 128 bits from the exact c: the (count, run-on) of every escaped pick
+ * of the five truth cases of tests/test_deep_wide.py agree and rel is within WIDE_DERIVATIVE_REL of the model file.
+ *
+ * One pass (csrc/mbk_deep_wide_distance.h).  The two calls follow the rules of mbk_deep_view_launch_distance /
+ * _compute_distance: device pointers on the caller's stream / host buffers synchronously on slot 0 with the statistics of
+ * mbk_deep_xview_compute (the run-on steps are not counted); counts may be NULL.  MBK_ERR_INVALID, with nothing written: a
+ * NULL rel, any flag (MBK_DEEP_XBLA and MBK_DEEP_BLA each with a message of its own: the derivative of a skipped run needs
+ * coefficients of its own) and whatever mbk_deep_xview_launch refuses.
+ */
+int mbk_deep_xview_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
+int mbk_deep_xview_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                    uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats);
+/* Host twins for the CPU tests, compiled from the functions the kernel uses: no ctx, no device.  The pixel (col, row) of the
+ * full view: its count, the run-on steps taken, the final mag (0 for count 0), the final D 2^e and rel (with the host's ln).
+ * MBK_ERR_INVALID for what the launch refuses. */
+int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                                 int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel);
+/* "step i" above, once: zp = (z_r, z_i) 2^t, (D_r, D_i, e) in and out. */
+int mbk_deep_xdistance_step_host(double z_r, double z_i, int32_t t, double *D_r, double *D_i, int32_t *e);
+/* "output" above. */
+double mbk_deep_xdistance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t exp2, int32_t count);
+
+/*
  * Rendering: a view to an RGBA8 image on the device, with a palette and supersampling.  Replaces, for a view of any kind,
  * what the reference's Viewer does on the host for a chunk (DistributedMandelbrotViewer.py:110-135, data_to_img_array: the
  * bytes through matplotlib's jet, black where the byte is 0) -- mbk_palette_viewer is that colouring as a palette.  Additive
@@ -741,6 +801,14 @@ int mbk_deep_xview_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, con
                                   uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
 int mbk_deep_view_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                  uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+/* Distance renders of extended-range deep views ("Distance estimates for extended-range deep views"), calls of their own as
+ * the interior renders are: the source must be MBK_RENDER_DISTANCE_REL, the samples are what mbk_deep_xview_launch_distance
+ * writes for the sample view, and colour, banding, supersampling, statistics and refusals are those of a deep render with
+ * that source.  Every flag is MBK_ERR_INVALID. */
+int mbk_deep_xview_distance_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
 /* The reference Viewer's colouring as a 256-entry palette for MBK_RENDER_BYTES, host only: entry 0 black (0, 0, 0, 255),
  * entry b = jet(1 - b / 256) as data_to_img_array evaluates it, each channel floor(255 x + 0.5) (jet holds exact .5 ties, so
  * the rounding rule is part of the contract).  Computed from jet's public definition (its knots and matplotlib's 256-entry
