@@ -224,6 +224,20 @@ SIGNATURES = {
     "mbk_deep_view_compute_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                                  C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_deep_distance_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32]),
+    "mbk_deep_view_launch_distance_bla": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_compute_distance_bla": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_view_distance_bla_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                           C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_distance_bla_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                            C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_distance_bla_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "mbk_deep_distance_bla_skip_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "mbk_deep_bla_info": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "mbk_deep_bla_read": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_uint64]),

@@ -35,6 +35,7 @@
 #include "mbk_distance.h"
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
+#include "mbk_deep_distance_bla.h"
 #include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
 #include "mbk_density.h"
@@ -3096,6 +3097,33 @@ double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double 
     return mbk::deep_distance_value(mag, dmagD, e, range_r, count);
 }
 
+// ---- distance estimates for deep views with bilinear approximation (mbk_deep_distance_bla.h; mbk.h, the section of that
+// name): the launch; the entry points follow the renders, below -----------------------------------------------------------
+
+// the deep distance kernel that takes skips, on device pointers (validated by the caller), on `stream`: the table of the count
+// launches (bla_copy); an orbit of length 1 has none and takes deep_distance_kernel
+static int launch_deep_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
+                                    int32_t *d_counts, double *d_rel, hipStream_t stream)
+{
+    if (orbit->o.length < 2u) return launch_deep_distance(ctx, orbit, v, mrd, d_counts, d_rel, stream);
+    const mbk_ctx::DeepCopy *c = nullptr;
+    int rc = bla_copy(ctx, orbit, deep_dcmax(v), &c);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepDistanceBlaArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_deep_args(a.b.v, c->d, orbit, v, mrd);
+    a.b.v.counts = d_counts;
+    a.b.rc = c->d_rc;
+    a.b.ab = c->d_ab;
+    a.b.levels = c->levels;
+    std::memcpy(a.b.off, c->off, sizeof(a.b.off));
+    a.range_r = v->range_r;
+    a.rel = d_rel;
+    hipLaunchKernelGGL(mbk::deep_distance_bla_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // ---- distance estimates for extended-range deep views (mbk_deep_wide_distance.h; mbk.h, the section of that name) -------
 
 // the wide distance kernel on device pointers (validated by the caller), on `stream`
@@ -3290,8 +3318,10 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
             return o.distance ? launch_deep_wide_distance(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream)
                               : launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
         case Target::kDeep:
-            return o.distance ? launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
-                              : launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
+            if (o.distance)   // (MBK_DEEP_BLA reaches here from the _distance_bla calls alone: every public distance call refuses it)
+                return (flags & MBK_DEEP_BLA) ? launch_deep_distance_bla(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
+                                              : launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream);
+            return launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
         case Target::kJulia: return launch_julia(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.bytes, o.values, stream);
         case Target::kPlain: break;
     }
@@ -4011,6 +4041,111 @@ int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *o
     int rc = wide_distance_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
     if (rc != MBK_OK) return rc;
     return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, nullptr, 0u);
+}
+
+// ---- distance estimates for deep views with bilinear approximation (mbk.h, the section of that name): calls of their own on
+// the launch, the value scaffold and the render machinery above; the calls without _bla keep refusing MBK_DEEP_BLA -----------
+
+// Everything such a call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
+static int deep_distance_bla_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags)
+{
+    if (flags & MBK_DEEP_BLA)
+        return fail(ctx, MBK_ERR_INVALID, "the _distance_bla calls take no flags: the name selects the rule (MBK_DEEP_BLA is a flag of the count calls)");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
+    return validate_deep(ctx, orbit, view, mrd, MBK_DEEP_BLA);
+}
+
+int mbk_deep_view_launch_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                      uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = deep_distance_bla_check(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return target_launch(ctx, deep_target(orbit, view), mrd, MBK_DEEP_BLA, Outputs{d_counts, nullptr, d_rel, true}, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_view_compute_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                       uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = deep_distance_bla_check(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    const Target t = deep_target(orbit, view);
+    return compute_values(ctx, (size_t)t.g.ncols * t.g.nrows, mrd, h_counts, h_rel, stats,
+                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
+                              return target_launch(ctx, t, mrd, MBK_DEEP_BLA, Outputs{d_counts, nullptr, d_rel, true}, stream);
+                          });
+}
+
+// Everything such a render can refuse, before anything is allocated, enqueued or written.
+static int deep_distance_bla_render_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                                          const mbk_render_spec *spec, const void *out, Target *t)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_render_spec(ctx, spec);
+    if (rc != MBK_OK) return rc;
+    if (spec->source != MBK_RENDER_DISTANCE_REL)
+        return fail(ctx, MBK_ERR_INVALID, "deep distance renders with bilinear approximation take MBK_RENDER_DISTANCE_REL only");
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    *t = deep_target(orbit, view);
+    const uint32_t s = spec->supersample;
+    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
+    return deep_distance_bla_check(ctx, orbit, &samples.deep, mrd, flags);
+}
+
+int mbk_deep_view_distance_bla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                             uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    Target t;
+    int rc = deep_distance_bla_render_check(ctx, orbit, view, mrd, flags, spec, d_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, MBK_DEEP_BLA, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+}
+
+int mbk_deep_view_distance_bla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                              uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    Target t;
+    int rc = deep_distance_bla_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, MBK_DEEP_BLA, spec, h_rgba, stats, nullptr, 0u);
+}
+
+// host twins (mbk_deep_distance_bla.h): no ctx, no device
+int mbk_deep_distance_bla_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                               int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel,
+                               uint64_t *steps_executed)
+{
+    if (!count || !extra || !mag || !D_r || !D_i || !e || !rel || !steps_executed) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::BlaTable t;
+    int rc = bla_host_table(orbit, view, &t);
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    mbk::deep_distance_bla_host(orbit->o.table, orbit->o.length, t, deep_dc(col, view->width, view->range_r),
+                                deep_dc(row, view->height, view->range_i), (int64_t)mrd, count, extra, mag, D_r, D_i, e, steps_executed);
+    const double r2 = *D_r * *D_r, i2 = *D_i * *D_i;
+    *rel = mbk::deep_distance_value(*mag, r2 + i2, *e, view->range_r, *count);
+    return MBK_OK;
+}
+
+int mbk_deep_distance_bla_skip_host(double A_r, double A_i, double B_r, double B_i, double *D_r, double *D_i, int32_t *e)
+{
+    if (!D_r || !D_i || !e) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::deep_derivative_skip(A_r, A_i, B_r, B_i, *D_r, *D_i, *e);
+    return MBK_OK;
 }
 
 // ---- count histograms and the equalisation table (mbk_histogram.h; mbk.h "Count histograms") ------------------------------

@@ -58,8 +58,8 @@ struct DeepDistanceArgs {
     double *rel;
 };
 
-// d' = 2 zp d + 1 on the scaled pair, and the rescale
-__device__ __forceinline__ void deep_derivative_step(double zpr, double zpi, double &Dr, double &Di, int32_t &e, double &one)
+// d' = 2 zp d + 1 on the scaled pair, and the rescale (__host__ too: the host twin of mbk_deep_distance_bla.h calls it)
+__host__ __device__ __forceinline__ void deep_derivative_step(double zpr, double zpi, double &Dr, double &Di, int32_t &e, double &one)
 {
     const double p0 = zpr * Dr, p1 = zpi * Di, p2 = zpr * Di, p3 = zpi * Dr;
     const double u = p0 - p1;

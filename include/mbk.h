@@ -375,8 +375,8 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
  *
  * MBK_DEEP_BLA is a flag of mbk_deep_view_launch / _compute / _submit, of mbk_deep_view_render_launch / _compute and their
  * _equalized_ forms (every source but MBK_RENDER_DISTANCE_REL) and of mbk_deep_view_histogram_launch / _compute.  Every other
- * call refuses it with MBK_ERR_INVALID: the deep distance calls (their derivative would need coefficients of its own), every
- * plain view call and every Julia call.
+ * call refuses it with MBK_ERR_INVALID: the deep distance calls (the estimate that takes skips lives behind names of its own:
+ * "Distance estimates for deep views with bilinear approximation", below), every plain view call and every Julia call.
  *
  * Contract (tests/deep_bla_model.py restates it in numpy; tests/test_deep_bla.py holds the host twins below to it and it to
  * the truth, tests/test_gpu_deep_bla.py holds the GPU to it, bit for bit).  Everything of "Deep-zoom views" stands: orbit
@@ -642,6 +642,78 @@ int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, co
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count);
 
 /*
+ * Distance estimates for deep views with bilinear approximation.  NOT in the reference; additive (the ABI version stays 5): no
+ * existing call changes -- mbk_deep_view_launch_distance / _compute_distance and the MBK_RENDER_DISTANCE_REL source of
+ * mbk_deep_view_render_* keep refusing MBK_DEEP_BLA, the capability lives behind the names below.  Below spans of ~1e-15 a
+ * view is drawn by its distance estimate, and those are the views with the largest iteration counts: here the estimate takes
+ * the skips the count launches take (scripts/deep_distance_bla_rate.py, profiles/deep_distance_bla/).
+ *
+ * No second table.  d is the derivative of the pixel's full z = Z_m + dz with respect to c, and the reference orbit does not
+ * depend on dc: across a skip dz -> A dz + B dc the derivative follows d -> A d + B with the A and B the table already holds.
+ * The neglected terms are of the order of the |dz| / |Z| that the radius test bounds by eps = 2^-40 per step.
+ *
+ * Contract (tests/deep_distance_bla_model.py restates it in numpy; tests/test_deep_distance_bla.py holds the host twins below
+ * to it and it to the truth, tests/test_gpu_deep_distance_bla.py holds the GPU to it).  Everything of "Deep-zoom views with
+ * bilinear approximation" stands: the table and its bits, dcmax of the FULL view, eps, the level rule, the step index, and the
+ * count, which is exactly the count mbk_deep_view_compute stores with MBK_DEEP_BLA.  Everything of "Distance estimates for deep
+ * views" stands for a step that takes no level: zp, (D, e), one = ldexp(1, -e), u, v, Dr = fl(2u + one), Di = 2v, the 2^256
+ * rescale tested on that step; and so do the start state and the output expression (unit rel).  Binary64, every operation
+ * rounded on its own, no contraction.  Added:
+ *   skip      a step that takes level l applies, BEFORE the dz map (as the plain derivative step comes before the z step), to
+ *             d = D 2^e and the entry's (A, B):
+ *               ea = the frexp exponent of max(|A_r|, |A_i|) (0 for 0);  As = ldexp(A, -ea)     (exact: larger part in [0.5, 1))
+ *               eb = the frexp exponent of max(|B_r|, |B_i|) (0 for 0);  Bs = ldexp(B, -eb)
+ *               P  = (fl(fl(As_r D_r) - fl(As_i D_i)), fl(fl(As_r D_i) + fl(As_i D_r)))
+ *               pe = e + ea;  h = max(pe, eb, 0)
+ *               N  = fl(ldexp(P, max(pe - h, -1200)) + ldexp(Bs, max(eb - h, -1200)))            per component
+ *               then, if max(|N_r|, |N_i|) >= 2^256: N = fl(N 2^-256), h += 256 (once suffices: |N| < 2^258);
+ *               else, if max(|N_r|, |N_i|) < 2^-256 and h >= 256: N = N 2^256 (exact), h -= 256;
+ *               D = N, e = min(h, 2^30), one = ldexp(1, -e).
+ *             The second rescale is what a long orbit needs: |As| < 1, so each skip may move up to a binade from D into e, and
+ *             over the ~3000 skips of a pixel at mrd 30 000 D would decay (to 1e-207 on the seahorse view at 1e-20) until dmagD
+ *             underflows and rel is +inf.  With it max(|D_r|, |D_i|) stays in [2^-256, 2^256) wherever e >= 256.
+ *             It is finite for every entry that can be taken (A and B are finite binary64 up to 1e308, |D| < 2^256: the
+ *             product is formed on mantissas).  An addend more than 1200 binades below the other is dropped, never wrapped.
+ *             e stays a non-negative int32 at most 2^30, but it MAY DECREASE (|A| < 1 where the orbit passes near 0) and is no
+ *             longer a multiple of 256: the "e never decreases" of "Distance estimates for deep views" is not part of this
+ *             contract.  ea and eb are taken where the skip runs (frexp): nothing is stored beside the table, and what
+ *             mbk_deep_bla_read returns does not change.
+ *   rebase    after a skip zp becomes the z = fl(Z_m + dz) formed at the new m; D, e and zp do not change at a rebase.
+ *   run-on    a pixel with n > 0 first applies the rebase rule to the escaping step's state, then runs PLAIN steps only --
+ *             never a skip -- until mag >= 2^32 or 64 further steps have run.
+ *   no skip   where no level is ever taken (M <= 1: no table; or a view whose offsets never pass the radius test) every state
+ *             and rel equals "Distance estimates for deep views" bit for bit.
+ *   mrd       0 and 1 run no step: every count and value is 0.
+ * Windows of a view are bit-identical to the whole view.  Statistics: pixel_iterations counts the reference's iterations
+ * (count, or mrd - 1 for 0), not the steps executed and not the run-on.
+ * Against d' = 2 z d + 1, z' = z^2 + c in mpmath at P + 128 bits from the exact c, on the cases of tests/test_deep_distance.py:
+ * (count, run-on) agree on >= 99 % of the escaped picks and rel is within DEEP_BLA_DERIVATIVE_REL of the model file.  The
+ * error is NOT bounded by n 2^-39: it is a conditioning effect of the orbit-long product (measured figures in the model file).
+ *
+ * One pass (csrc/mbk_deep_distance_bla.h); with M <= 1 the launch is that of mbk_deep_view_launch_distance.  The argument rules
+ * are those of the calls without _bla: device pointers on the caller's stream / host buffers synchronously on slot 0 with the
+ * statistics above; counts may be NULL.  MBK_ERR_INVALID, with nothing written: a NULL rel, any flag -- MBK_DEEP_BLA too, with a
+ * message of its own: the name selects the rule --, an orbit longer than 2^31 and whatever mbk_deep_view_launch refuses (mrd
+ * above the orbit's, an empty window, ranges outside [2^-960, 4]).  The render calls take MBK_RENDER_DISTANCE_REL only: the
+ * banding, supersampling and colour code of "Rendering" on these samples, as mbk_deep_xview_distance_render_* are for
+ * extended-range views.  The ctx's table is the one of the MBK_DEEP_BLA count launches, keyed by the orbit's id and dcmax and
+ * shared with them: launch once per (orbit, spans) before capturing, and expect alternating spans on one orbit to serialise.
+ */
+int mbk_deep_view_launch_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                      uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
+int mbk_deep_view_compute_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                       uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats);
+/* (mbk_deep_view_distance_bla_render_launch / _compute are declared under "Rendering", below.) */
+/* Host twins for the CPU tests, compiled from the functions the kernel uses: no ctx, no device.  The pixel (col, row) of the
+ * full view: its count, the run-on steps taken, the final mag (0 for count 0), the final D 2^e, rel (with the host's ln) and
+ * the number of steps executed in the count loop, a skip counting as one.  MBK_ERR_INVALID for what the launch refuses. */
+int mbk_deep_distance_bla_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                               int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel,
+                               uint64_t *steps_executed);
+/* "skip" above, once: (D_r, D_i, e) in and out. */
+int mbk_deep_distance_bla_skip_host(double A_r, double A_i, double B_r, double B_i, double *D_r, double *D_i, int32_t *e);
+
+/*
  * Distance estimates for extended-range deep views.  NOT in the reference; additive (the ABI version stays 5): no existing
  * call changes -- mbk_deep_xview_render_* keeps refusing the distance sources, the capability lives behind the names below.
  * The views that need the estimate most are the deepest: at a span of 2^-1100 every visible structure is a filament thinner
@@ -809,6 +881,14 @@ int mbk_deep_xview_distance_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *or
                                           uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
 int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
                                            uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+/* Distance renders of deep views that take skips ("Distance estimates for deep views with bilinear approximation"), calls of
+ * their own in the same way: the source must be MBK_RENDER_DISTANCE_REL, the samples are what mbk_deep_view_launch_distance_bla
+ * writes for the sample view, and colour, banding, supersampling, statistics and refusals are those of a deep render with that
+ * source.  Every flag is MBK_ERR_INVALID. */
+int mbk_deep_view_distance_bla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                             uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_view_distance_bla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                              uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
 /* The reference Viewer's colouring as a 256-entry palette for MBK_RENDER_BYTES, host only: entry 0 black (0, 0, 0, 255),
  * entry b = jet(1 - b / 256) as data_to_img_array evaluates it, each channel floor(255 x + 0.5) (jet holds exact .5 ties, so
  * the rounding rule is part of the contract).  Computed from jet's public definition (its knots and matplotlib's 256-entry
