@@ -28,7 +28,8 @@ KERNELS = {"default": MBK_KERNEL_DEFAULT, "simple": MBK_KERNEL_SIMPLE, "asm": MB
 # enum mbk_option (include/mbk.h), in order
 OPTIONS = {name: i for i, name in enumerate(
     ["order", "waves_per_wg", "group_steps", "exact_steps", "probe_steps", "scan_waves", "scan_xcd_map", "scan_col_period", "heavy_share",
-     "rf_livemin", "rf_patience", "rf_batch", "rf_waves", "cycle_detect", "probe_mid", "prepass_overlap", "exact_long", "scan_inline", "wave_limit", "units_min_light", "xcd_balance", "m_late", "h_settled", "classify_wg", "scan_strip", "cycle_window", "spill_first", "spill_lanes", "spill_min_mrd", "spill_min_blocks", "spill_cyc_shift"])}
+     "rf_livemin", "rf_patience", "rf_batch", "rf_waves", "cycle_detect", "probe_mid", "prepass_overlap", "exact_long", "scan_inline", "wave_limit", "units_min_light", "xcd_balance", "m_late", "h_settled", "classify_wg", "scan_strip", "cycle_window", "spill_first", "spill_lanes", "spill_min_mrd", "spill_min_blocks", "spill_cyc_shift",
+     "sure_interior"])}
 MBK_PRECISION_F32 = 0x1000
 MBK_LAZY_UNIFORM = 0x2000
 MBK_DEEP_BLA = 0x8000   # deep count / render / histogram calls only
@@ -200,6 +201,10 @@ SIGNATURES = {
     "mbk_quantise_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mbk_units_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_units_lookup": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mbk_sure_interior_point": (C.c_int, [C.c_double, C.c_double]),
+    "mbk_sure_interior_blocks": (C.c_int, [C.POINTER(mbk_view), C.POINTER(C.c_uint64)]),
+    "mbk_sure_interior_flag": (C.c_int, [C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.c_uint32)]),
     "mbk_reduce_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                     C.POINTER(mbk_stats)]),
     "mbk_worker_run": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint16, C.c_uint64, C.c_uint32,

@@ -456,8 +456,11 @@ static int get_scratch(mbk_ctx *ctx, hipStream_t stream, StreamScratch **out)
 // edge strips of launch_refill and the bands of a view are windows of their own):
 //   fast_bx_end / fast_by_end   leading whole 8x8 blocks that hold no pinned last sample (TileArgs comment);
 //   ring_possible               conservative rectangle test against | |c|^2 - 4 | < margin (kernel margins are
-//                               1e-9 fp64 / 1e-3 fp32 per pixel; the host test allows 1e-6 / 2e-3).
-static void set_window_facts(TileArgs &a, bool f32);
+//                               1e-9 fp64 / 1e-3 fp32 per pixel; the host test allows 1e-6 / 2e-3);
+//   sure_interior               MBK_OPT_SURE_INTERIOR as this launch takes it (sure_interior_word): from the option's value, the
+//                               kind of launch (a.mrd, f32, cyc) and the window.  The scan path passes no option: its kernels
+//                               do not have the test-free loop.
+static void set_window_facts(TileArgs &a, bool f32, bool cyc = true, uint32_t sure_option = 0u);
 static void shares_from_fractions(const double *f, uint32_t *cum);
 static double window_heavy_share(const TileArgs &a);
 static double window_heavy_share(mbk_ctx *ctx, const TileArgs &a);
@@ -550,8 +553,8 @@ static BlockLaunchPlan block_launch_plan(mbk_ctx *ctx, TileArgs &a, uint32_t ker
     p.wpw = ctx->opt[MBK_OPT_WAVES_PER_WG];
     a.blocks_x = (a.ncols + 8u * p.wpw - 1u) / (8u * p.wpw);
     p.by = (a.nrows + 7u) / 8u;
-    set_window_facts(a, f32);
     p.cyc = ctx->opt[MBK_OPT_CYCLE_DETECT] != 0u;
+    set_window_facts(a, f32, p.cyc, ctx->opt[MBK_OPT_SURE_INTERIOR]);
     p.grid = dim3(a.blocks_x * p.by);
     p.block = dim3(64u * p.wpw);
     p.order_mode = ctx->opt[MBK_OPT_ORDER];
@@ -958,8 +961,34 @@ static bool window_may_touch_ring(const TileArgs &a, double margin = 1e-6)
     return !(rmax2 < 4.0 - margin || rmin2 > 4.0 + margin);
 }
 
-static void set_window_facts(TileArgs &a, bool f32)
+// MBK_OPT_SURE_INTERIOR as one launch takes it (TileArgs::sure_interior): non-zero only for a strict fp64 launch of at least 64
+// steps whose window can hold certified blocks at all -- its rectangle meets the box [-1.3, 0.4] x [-0.7, 0.7] around the main
+// cardioid and the period-2 disk, and one of the 16 x 16 probe pixels of window_heavy_share's grid passes the certificate.  A deep
+// zoom beside the set lies inside that box and holds no such pixel; it, like an all-exterior tile, must not pay 14 instructions
+// per heavy block for a certificate that never holds.  A window whose certified area falls between the probe pixels (under
+// 1/256 of it) merely keeps today's path.  Force mode (2) ignores the window.  A deterministic function of its arguments.
+static uint32_t sure_interior_word(const TileArgs &a, bool f32, bool cyc, uint32_t option)
 {
+    if (option == 0u || f32 || cyc || a.mrd < 65) return 0u;
+    if (option == 2u) return 2u;
+    if (a.ncols == 0u || a.nrows == 0u) return 0u;
+    const double x0 = axis_value_host(a.re, a.col0), x1 = axis_value_host(a.re, a.col0 + a.ncols - 1u);
+    const double y0 = axis_value_host(a.im, a.row0), y1 = axis_value_host(a.im, a.row0 + a.nrows - 1u);
+    const double xlo = std::fmin(x0, x1), xhi = std::fmax(x0, x1), ylo = std::fmin(y0, y1), yhi = std::fmax(y0, y1);
+    if (!(xlo <= 0.4 && xhi >= -1.3 && ylo <= 0.7 && yhi >= -0.7)) return 0u;
+    const uint32_t k = 16;
+    for (uint32_t j = 0; j < k; ++j) {
+        const double ci = axis_value_host(a.im, a.row0 + (uint32_t)(((uint64_t)(2u * j + 1u) * a.nrows) / (2u * k)));
+        for (uint32_t i = 0; i < k; ++i)
+            if (mbk::sure_interior_point(axis_value_host(a.re, a.col0 + (uint32_t)(((uint64_t)(2u * i + 1u) * a.ncols) / (2u * k))), ci))
+                return 1u;
+    }
+    return 0u;
+}
+
+static void set_window_facts(TileArgs &a, bool f32, bool cyc, uint32_t sure_option)
+{
+    a.sure_interior = sure_interior_word(a, f32, cyc, sure_option);
     a.ring_possible = window_may_touch_ring(a, f32 ? 2e-3 : 1e-6) ? 1u : 0u;
     a.fast_bx_end = a.fast_by_end = 0u;
     if (a.re.step_is_zero || a.im.step_is_zero) return;
@@ -1791,7 +1820,8 @@ int mbk_create(int device, mbk_ctx **out)
         /* RF_LIVEMIN */ 48u, /* RF_PATIENCE */ 256u, /* RF_BATCH */ 1u, /* RF_WAVES */ 8u, /* CYCLE_DETECT */ 1u,
         /* PROBE_MID */ 65537u, /* PREPASS_OVERLAP */ 1u, /* EXACT_LONG */ 0u, /* SCAN_INLINE */ 1u, /* WAVE_LIMIT */ 0u,
         /* UNITS_MIN_LIGHT */ 32768u, /* XCD_BALANCE */ 0u, /* M_LATE */ 8u, /* H_SETTLED */ 6u, /* CLASSIFY_WG */ 1024u,
-        /* SCAN_STRIP */ 1u, /* CYCLE_WINDOW */ 32u, /* SPILL_FIRST */ 256u, /* SPILL_LANES */ 16u, /* SPILL_MIN_MRD */ 2048u, /* SPILL_MIN_BLOCKS */ 19u, /* SPILL_CYC_SHIFT */ 5u};
+        /* SCAN_STRIP */ 1u, /* CYCLE_WINDOW */ 32u, /* SPILL_FIRST */ 256u, /* SPILL_LANES */ 16u, /* SPILL_MIN_MRD */ 2048u, /* SPILL_MIN_BLOCKS */ 19u, /* SPILL_CYC_SHIFT */ 5u,
+        /* SURE_INTERIOR */ 1u};
     std::memcpy(ctx->opt, kDefaults, sizeof(kDefaults));
 #define MBK_CREATE_HIP(call)                                                        \
     do {                                                                            \
@@ -2467,6 +2497,7 @@ int mbk_set_option(mbk_ctx *ctx, int option, uint32_t value)
         case MBK_OPT_SPILL_MIN_MRD: ok = true; break;
         case MBK_OPT_SPILL_MIN_BLOCKS: ok = value <= 31u; break;
         case MBK_OPT_SPILL_CYC_SHIFT: ok = value <= 31u; break;
+        case MBK_OPT_SURE_INTERIOR: ok = value <= 2u; break;
         default: return fail(ctx, MBK_ERR_INVALID, "unknown MBK_OPT_* selector");
     }
     if (!ok) return fail(ctx, MBK_ERR_INVALID, "option value out of range");
@@ -2544,6 +2575,49 @@ int mbk_units_lookup(const uint32_t *plan, uint32_t id, uint32_t *list, uint32_t
         return MBK_OK;
     *list = is_h ? 1u : (i < plan[1] ? 2u : 3u);
     *index = is_h ? i : (i < plan[1] ? i : i - plan[1]);
+    return MBK_OK;
+}
+
+// MBK_OPT_SURE_INTERIOR on the host (no device, no context): the certificate block_pixel evaluates, the blocks of a window that
+// pass it whole, and the word a launch would carry.
+int mbk_sure_interior_point(double cr, double ci) { return mbk::sure_interior_point(cr, ci) ? 1 : 0; }
+
+int mbk_sure_interior_blocks(const mbk_view *view, uint64_t *certified)
+{
+    if (!view || !certified) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    const int rc = validate_view(nullptr, view, &safe);
+    if (rc != MBK_OK) return rc;
+    TileArgs a = view_window_args(view);
+    set_window_facts(a, false);
+    // the blocks block_pixel calls `interior`: their coordinates are the regular formula's, as evaluated there
+    uint64_t n = 0;
+    for (uint32_t by = 0; by < a.fast_by_end; ++by)
+        for (uint32_t bx = 0; bx < a.fast_bx_end; ++bx) {
+            bool all = true;
+            for (uint32_t ly = 0; ly < 8u && all; ++ly) {
+                const double ci = (double)(a.row0 + by * 8u + ly) * a.im.step + a.im.start;
+                for (uint32_t lx = 0; lx < 8u && all; ++lx)
+                    all = mbk::sure_interior_point((double)(a.col0 + bx * 8u + lx) * a.re.step + a.re.start, ci);
+            }
+            n += all ? 1u : 0u;
+        }
+    *certified = n;
+    return MBK_OK;
+}
+
+int mbk_sure_interior_flag(const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t cycle_detect, uint32_t option, uint32_t *flag)
+{
+    if (!view || !flag) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    if (option > 2u || mrd > 0x7fffffffu) return fail(nullptr, MBK_ERR_INVALID, "option value out of range");
+    const bool f32 = (flags & MBK_PRECISION_F32) != 0;
+    bool safe = false;
+    const int rc = validate_view(nullptr, view, &safe, f32);
+    if (rc != MBK_OK) return rc;
+    TileArgs a = view_window_args(view);
+    a.mrd = (int32_t)mrd;
+    set_window_facts(a, f32, cycle_detect != 0u, option);
+    *flag = a.sure_interior;
     return MBK_OK;
 }
 

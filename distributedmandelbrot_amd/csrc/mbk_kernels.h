@@ -81,7 +81,26 @@ struct TileArgs {
     void *spill_z;        // [block * spill_lanes + rank]: (zr, zi) of a spilled lane, as two T
     uint32_t *spill_meta; // [block * spill_lanes + rank]: lane in the block (bits 0..5) | steps done (bits 6..31)
     uint32_t *spill_cnt;  // [block]: lanes the block spilled | the number of its checkpoint << 8 (zeroed by the host before the launch)
+    uint32_t sure_interior;  // MBK_OPT_SURE_INTERIOR as this launch takes it (set_window_facts): 0 = no block of it runs the test-free
+                          // loop; 1 = the 16-step-group blocks whose 64 pixels pass sure_interior_point do; 2 = all of them (tests)
 };
+
+// MBK_OPT_SURE_INTERIOR, the certificate: is c = (cr, ci) inside the main cardioid or the period-2 disk, kSureMargin away from
+// their boundaries as measured by the two closed forms (q (q + x) < ci^2 / 4 with x = cr - 1/4, q = x^2 + ci^2; and
+// (cr + 1)^2 + ci^2 < 1/16)?  Such a pixel never escapes.  Plain binary64, every operation rounded on its own, in the order
+// written: the host twin (mbk_sure_interior_point) gives the same answer for the same c.  Nothing rests on the certificate being
+// right: it only PREDICTS that the test-free loop will end with no lane tripped (block_pixel); a wrong prediction costs a replay.
+constexpr double kSureMargin = 1e-4;
+__host__ __device__ inline bool sure_interior_point(double cr, double ci)
+{
+    const double ci2 = ci * ci;
+    const double x = cr - 0.25;
+    const double q = x * x + ci2;
+    const bool cardioid = q * (q + x) < 0.25 * ci2 - kSureMargin;
+    const double xd = cr + 1.0;
+    const bool disk = xd * xd + ci2 < 0.0625 - kSureMargin;
+    return cardioid || disk;
+}
 
 // np.linspace sample k (numpy/_core/function_base.py): two roundings, endpoint pinned.
 __device__ __forceinline__ double axis_value(const Axis &a, uint32_t k)
@@ -217,6 +236,38 @@ __global__ __launch_bounds__(256) void tile_simple_kernel(TileArgs p)
 #undef MBK_CYC_MOV
 
 
+// Does any pixel of the wave lie within 1e-9 of the ring |c| = 2 (block_pixel's test, for the one caller that needs it apart)?
+__device__ __forceinline__ bool wave_touches_ring(double cr, double ci)
+{
+    const double c2 = cr * cr + ci * ci;
+    return __ballot(__builtin_fabs(c2 - 4.0) < 1e-9) != 0ull;
+}
+
+// A word / a pointer of the kernel argument segment, fetched where it is needed and kept nowhere else (as leave_stamp does in
+// mbk_units.h): the compiler loads every argument it sees at the kernel's entry and holds it from there on.
+template <uint32_t kOffset>
+__device__ __forceinline__ uint32_t kernarg_u32()
+{
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, %2\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(kOffset)
+                 : "memory");
+    return v;
+}
+template <uint32_t kOffset>
+__device__ __forceinline__ unsigned long long kernarg_u64()
+{
+    unsigned long long v;
+    asm volatile("s_load_dwordx2 %0, %1, %2\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : "=&s"(v)
+                 : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(kOffset)
+                 : "memory");
+    return v;
+}
+
 // One pixel of an 8x8 block, start to finish (one lane each; the whole wave calls it): coordinates, the
 // escape loop of the chosen kind, the stores.  T = double: the reference's arithmetic.  T = float: the fp32
 // variant (coordinates are generated in fp64 exactly as for the fp64 path and then rounded once to fp32; the
@@ -228,7 +279,8 @@ __global__ __launch_bounds__(256) void tile_simple_kernel(TileArgs p)
 // kCycle: the grouped loops retire exactly periodic orbits early (mbk_loops.inc, MBK_G_CYC).
 // (ucol, urow): the block's first column / row inside the window, wave-uniform; (lx, ly): this lane's pixel in the block.
 // Returns the lane's count (-1: the lane has no pixel -- outside the window).
-template <typename T, bool kFmaDouble, int kGroup, bool kCycle = false>
+// kSure (tile_units_kernel and tile_asm_kernel; strict fp64 with 16-step groups only): MBK_OPT_SURE_INTERIOR, below.
+template <typename T, bool kFmaDouble, int kGroup, bool kCycle = false, bool kSure = false>
 __device__ __forceinline__ int32_t block_pixel(const TileArgs &p, uint32_t ucol, uint32_t urow, uint32_t lx, uint32_t ly,
                                                bool long_groups, bool interior = false)
 {
@@ -243,6 +295,36 @@ __device__ __forceinline__ int32_t block_pixel(const TileArgs &p, uint32_t ucol,
         if (lc >= p.ncols || lr >= p.nrows) return -1;
         cr = (T)axis_value(p.re, p.col0 + lc);
         ci = (T)axis_value(p.im, p.row0 + lr);
+    }
+    // MBK_OPT_SURE_INTERIOR (strict fp64 launches; TileArgs::sure_interior is the host's word for this launch).  An interior-class
+    // block runs mrd - 1 steps in 16-step groups and pays one v_add and one v_cmp per group for a test that never trips: 6.125
+    // issue slots per step where 6 are arithmetic.  When all 64 pixels of the block pass the certificate (sure_interior_point: the
+    // ballot covers the wave) the block runs the test-free loop instead (mbk_loops.inc, escape_steps_sure) and is tested ONCE,
+    // behind its last step.  No lane tripped: every count is 0, and the stores are constants (the quantiser's byte for 0 is 0, the
+    // smooth value of a pixel that never escapes 0).  Some lane tripped -- the certificate was wrong, or the option is in force
+    // mode (2: every such block comes here whatever the certificate says, so that tests reach this branch) --: the state is
+    // dropped and the block takes today's path from z = c, the grouped loop with everything it records.  So the certificate
+    // decides how long a block takes and never what it stores.  All branches here are wave-uniform.
+    // Registers: the units kernel has no scalar register to spare (its comment), and every word of p read here would be one more
+    // kept -- or spilled -- across the whole kernel.  kSure therefore means "p is the launch's TileArgs at the head of the kernel
+    // argument segment" (true of both kernels that set it): the option's word and what the constant stores need are fetched from
+    // there on the spot, once per block of ~6 (mrd - 1) instructions.  Where p.counts / p.bytes / p.smooth differ from the
+    // launch's they are null (the units kernel pins the outputs its instantiation does not write), and that is asked of p.
+    if constexpr (kSure && kFmaDouble && kGroup == 16 && !kCycle && sizeof(T) == 8) {
+        const uint32_t sure = (long_groups && interior) ? kernarg_u32<offsetof(TileArgs, sure_interior)>() : 0u;
+        if (sure != 0u) {
+            bool take = __ballot(sure_interior_point((double)cr, (double)ci)) == ~0ull;   // (implies |c|^2 < 1.6: no ring test)
+            if (!take && sure == 2u) take = !(ring_test && wave_touches_ring(cr, ci));
+            if (take && escape_steps_sure(cr, ci, kernarg_u32<offsetof(TileArgs, mrd)>() - 1u) == 0ull) {
+                const uint32_t pitch = kernarg_u32<offsetof(TileArgs, out_pitch)>();
+                const size_t ubase = (size_t)(urow + kernarg_u32<offsetof(TileArgs, out_row0)>()) * pitch + ucol + kernarg_u32<offsetof(TileArgs, out_col0)>();
+                const uint32_t loff = ly * pitch + lx;
+                if (p.counts) (reinterpret_cast<int32_t *>(kernarg_u64<offsetof(TileArgs, counts)>()) + ubase)[loff] = 0;
+                if (p.bytes) (reinterpret_cast<uint8_t *>(kernarg_u64<offsetof(TileArgs, bytes)>()) + ubase)[loff] = (uint8_t)0;
+                if (p.smooth) (reinterpret_cast<double *>(kernarg_u64<offsetof(TileArgs, smooth)>()) + ubase)[loff] = 0.0;
+                return 0;
+            }
+        }
     }
     int32_t count;
     T m = 0;  // |z|^2 at the escaping step (only meaningful when count > 0)
@@ -441,7 +523,7 @@ __global__ __launch_bounds__(256) void tile_asm_kernel(TileArgs p)
     if (kSpill && kFmaDouble && kGroup >= 8 && interior)
         block_pixel_spill<T, kGroup, kCycle>(p, wcol * 8u, by * 8u, lane & 7u, lane >> 3, long_groups, by * p.blocks_x + wcol);
     else
-    block_pixel<T, kFmaDouble, kGroup, kCycle>(p, wcol * 8u, by * 8u, lane & 7u, lane >> 3, long_groups, interior);
+    block_pixel<T, kFmaDouble, kGroup, kCycle, true>(p, wcol * 8u, by * 8u, lane & 7u, lane >> 3, long_groups, interior);
 }
 
 // ---------------------------------------------------------------------------------------------

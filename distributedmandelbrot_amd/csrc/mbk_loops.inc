@@ -623,6 +623,53 @@ __device__ __forceinline__ int32_t escape_count_group(MBK_T cr, MBK_T ci, int32_
     return kCycle && cnt < 0 ? 0 : cnt;   // -1: retired by the cycle test = never escapes
 }
 
+// ---- the test-free loop (MBK_OPT_SURE_INTERIOR; block_pixel's certified blocks) ---------------------------------
+// Steps 1 .. total from z = c, every one the in-place step MBK_G_A2A: 6 arithmetic instructions and nothing else -- no m, no
+// compare, no trip label, no cnt -- in trips of 32 on a scalar counter, the remainder (total mod 32) as single steps, untested
+// too.  ONE NaN-inclusive test behind the last step stands for all the tests the grouped loop would have made on the way:
+// "once |z|^2 >= 4 it stays >= 4 and ends in inf, then NaN" (the grouped test's invariant above; it needs |c| <= 2 - 1e-9, which
+// the caller guarantees), so a lane that would have tripped any of them trips this one.  Returns the wave's trip mask.  Zero:
+// no lane of the wave ever escaped, every count is 0.  Non-zero: the state is worthless (nobody knows WHEN a lane left) and the
+// caller runs the block again with the grouped loop.  Operand order as in the grouped steps, so every (zr, zi) on the way is
+// the one the grouped loop computes.  total >= 1: z = c itself is never tested.
+#define MBK_G_A2A4 MBK_G_A2A MBK_G_A2A MBK_G_A2A MBK_G_A2A
+#define MBK_G_A2A32 MBK_G_A2A4 MBK_G_A2A4 MBK_G_A2A4 MBK_G_A2A4 MBK_G_A2A4 MBK_G_A2A4 MBK_G_A2A4 MBK_G_A2A4
+#define MBK_SURE_LOOP                                      \
+    "s_lshr_b32 %[n], %[total], 5\n"                       \
+    "s_cmp_eq_u32 %[n], 0\n"                               \
+    "s_cbranch_scc1 .Lsrem_%=\n"                           \
+    ".Lsmain_%=:\n"                                        \
+    MBK_G_A2A32                                            \
+    "s_sub_u32 %[n], %[n], 1\n"                            \
+    "s_cmp_lg_u32 %[n], 0\n"                               \
+    "s_cbranch_scc1 .Lsmain_%=\n"                          \
+    ".Lsrem_%=:\n"                                         \
+    "s_and_b32 %[n], %[total], 31\n"                       \
+    "s_cmp_eq_u32 %[n], 0\n"                               \
+    "s_cbranch_scc1 .Lsend_%=\n"                           \
+    ".Lsone_%=:\n"                                         \
+    MBK_G_A2A                                              \
+    "s_sub_u32 %[n], %[n], 1\n"                            \
+    "s_cmp_lg_u32 %[n], 0\n"                               \
+    "s_cbranch_scc1 .Lsone_%=\n"                           \
+    ".Lsend_%=:\n"                                         \
+    "v_add_" MBK_F " %[m], %[a], %[b]\n"                   \
+    "v_cmp_ngt_" MBK_F " vcc, 4.0, %[m]\n"                 \
+    "s_mov_b64 %[mask], vcc\n"
+__device__ __forceinline__ unsigned long long escape_steps_sure(MBK_T cr, MBK_T ci, uint32_t total)
+{
+    MBK_T zr = cr, zi = ci;
+    MBK_T a = zr * zr, b = zi * zi, m, t, p;
+    uint32_t n;
+    unsigned long long mask;
+    asm volatile(MBK_SURE_LOOP
+                 : [zr] "+&v"(zr), [zi] "+&v"(zi), [a] "+&v"(a), [b] "+&v"(b), [m] "=&v"(m), [t] "=&v"(t), [p] "=&v"(p),
+                   [n] "=&s"(n), [mask] "=&s"(mask)
+                 : [cr] "v"(cr), [ci] "v"(ci), [total] "s"(total)
+                 : "vcc", "scc");
+    return mask;
+}
+
 // The same two routines for an orbit that starts at z0 = (z0r, z0i) instead of c: the Julia set of the parameter c (mbk_julia.h).
 // The step loops above keep state and parameter apart; only the seed differs.  z0 is never tested, as c is not above.  What the
 // grouped test and the cycle test rest on carries over: ">= 4 stays >= 4" needs |c| <= 2 - 1e-9 and nothing of z (the caller

@@ -338,7 +338,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             const uint32_t e = scalar_load_u32(p.order, is_h ? (late ? 2u * n + 2u - i : (i < hs0 ? i - n_ml : (uint32_t)units_settled_base(n) + (i - hs0)))
                                                               : n + 3u + i);
             const uint32_t by = e >> 16, bx = e & 0xffffu;
-            const int32_t c = block_pixel<T, true, kGroup, kCycle>(p, bx * 8u, by * 8u, lx, ly, kGroup >= 16 && is_h && !late,
+            const int32_t c = block_pixel<T, true, kGroup, kCycle, true>(p, bx * 8u, by * 8u, lx, ly, kGroup >= 16 && is_h && !late,
                                                                    bx < p.fast_bx_end && by < p.fast_by_end);
             if (kStats && c >= 0) heavy += c > 0 ? (unsigned long long)(uint32_t)c : (1ull << 47) + never_cap;
         } else {

@@ -1482,6 +1482,16 @@ enum mbk_option {
     MBK_OPT_SPILL_CYC_SHIFT, /* SPILL with the cycle test: the second pass resumes orbits that have n steps behind them; the window of its
                               first reference state is n >> this checks (of 8 steps) instead of 1 -- [5]: where the schedule of an
                               unbroken run would stand (windows of ~ n / 4 steps); 31 = start at 1.  Any schedule is exact.  0 .. 31 */
+    MBK_OPT_SURE_INTERIOR, /* group, strict fp64 launches (no cycle test, 16-step groups, mrd >= 65; csrc/mbk_kernels.h block_pixel,
+                              csrc/mbk_loops.inc escape_steps_sure).  A block of the interior class whose 64 pixels all lie inside the
+                              main cardioid or the period-2 disk by a margin of 1e-4 (two closed forms, mbk_sure_interior_point below)
+                              runs its mrd - 1 steps with NO bailout test -- 6 issue slots per step instead of 6.125 -- and is tested
+                              once behind the last step; "|z|^2 >= 4 stays >= 4" makes that one NaN-inclusive test stand for all the
+                              others.  A wave whose test trips computes its block again the usual way, so the certificate only
+                              predicts and never decides a result: identical counts, bytes and smooth values.  A launch whose window
+                              holds no certified pixel (deep zooms, exterior tiles: a host probe) does not evaluate it.
+                              [0] off, 1 on, 2 force: every block of the interior class takes the test-free loop whatever the
+                              certificate says (for tests of the fallback; slower) */
     MBK_OPT_COUNT_
 };
 /* Read-only diagnostics through mbk_get_option: what hipOccupancyMaxActiveBlocksPerMultiprocessor reports for the
@@ -1503,6 +1513,18 @@ int mbk_get_option(mbk_ctx *ctx, int option, uint32_t *value);
  * entry *index, 2 middle entry *index, 3 row unit *index.  Every entry of every list is taken by exactly one id. */
 int mbk_units_plan(uint32_t n_h, uint32_t n_v, uint32_t n_m, const double *fractions, uint32_t *plan);
 int mbk_units_lookup(const uint32_t *plan, uint32_t id, uint32_t *list, uint32_t *index);
+
+/* MBK_OPT_SURE_INTERIOR on the host, without a device or a context: the function the kernels call and what the host makes of it.
+ * mbk_sure_interior_point: 1 when c = (cr, ci) passes the certificate -- q (q + x) < ci^2 / 4 - 1e-4 with x = cr - 1/4,
+ * q = x^2 + ci^2 (main cardioid), or (cr + 1)^2 + ci^2 < 1/16 - 1e-4 (period-2 disk); binary64, every operation rounded on
+ * its own -- else 0.  mbk_sure_interior_blocks: how many 8x8 blocks of the view's window a launch would certify (blocks wholly
+ * inside the window that hold no pinned last sample of an axis, all 64 pixels passing).  mbk_sure_interior_flag: the word a
+ * launch of that window carries to its kernel under MBK_OPT_SURE_INTERIOR = option and MBK_OPT_CYCLE_DETECT = cycle_detect
+ * (flags: MBK_PRECISION_F32 or 0): 0 = no block evaluates the certificate, else the option's value. */
+int mbk_sure_interior_point(double cr, double ci);
+int mbk_sure_interior_blocks(const mbk_view *view, uint64_t *certified);
+int mbk_sure_interior_flag(const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t cycle_detect, uint32_t option,
+                           uint32_t *flag);
 
 /* The quantiser alone, on the device: h_bytes[i] = uint8(ceil(h_counts[i] * 256 / mrd)) for n host counts
  * (WorkerCUDA.py:96-98; each count must lie in [0, mrd-1], which is what calc_mb_value returns).
