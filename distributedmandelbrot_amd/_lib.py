@@ -272,6 +272,21 @@ SIGNATURES = {
                                                         C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
     "mbk_deep_xview_distance_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
                                                          C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_launch_distance_xbla": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_compute_distance_xbla": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_distance_xbla_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32,
+                                                             C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_distance_xbla_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32,
+                                                              C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p,
+                                                              C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_distance_xbla_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "mbk_deep_xdistance_skip_host": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "mbk_deep_xbla_info": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "mbk_deep_xbla_read": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),

@@ -36,6 +36,7 @@
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
 #include "mbk_deep_distance_bla.h"
+#include "mbk_deep_wide_distance_bla.h"
 #include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
 #include "mbk_density.h"
@@ -3222,6 +3223,34 @@ static int launch_deep_wide_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, 
     return MBK_OK;
 }
 
+// the wide distance kernel that takes skips, on device pointers (validated by the caller), on `stream`: the table of the
+// MBK_DEEP_XBLA count launches (xbla_copy); an orbit of length 1 has none and takes deep_wide_distance_kernel
+static int launch_deep_wide_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd,
+                                          int32_t *d_counts, double *d_rel, hipStream_t stream)
+{
+    if (orbit->o.length < 2u) return launch_deep_wide_distance(ctx, orbit, v, mrd, d_counts, d_rel, stream);
+    const mbk_ctx::DeepCopy *c = nullptr;
+    int rc = xbla_copy(ctx, orbit, wide_view_dcmax(v), &c);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepWideDistanceBlaArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.b.v.orbit = c->d_wide;
+    a.b.v.z1 = orbit->o.wide[1];
+    a.b.v.M = orbit->o.length;
+    a.b.v.exp2 = v->exp2;
+    fill_deep_window(a.b.v, v, mrd);
+    a.b.v.counts = d_counts;
+    a.b.ke = c->d_xke;
+    a.b.ab = c->d_xab;
+    a.b.levels = c->xlevels;
+    std::memcpy(a.b.off, c->xoff, sizeof(a.b.off));
+    a.range_r = v->range_r;
+    a.rel = d_rel;
+    hipLaunchKernelGGL(mbk::deep_wide_distance_bla_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // Everything a wide distance call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
 static int wide_distance_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags)
 {
@@ -3389,8 +3418,10 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
 {
     switch (t.kind) {
         case Target::kWide:
-            return o.distance ? launch_deep_wide_distance(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream)
-                              : launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
+            if (o.distance)   // (MBK_DEEP_XBLA reaches here from the _distance_xbla calls alone: every other distance call refuses it)
+                return (flags & MBK_DEEP_XBLA) ? launch_deep_wide_distance_xbla(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream)
+                                               : launch_deep_wide_distance(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream);
+            return launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
         case Target::kDeep:
             if (o.distance)   // (MBK_DEEP_BLA reaches here from the _distance_bla calls alone: every public distance call refuses it)
                 return (flags & MBK_DEEP_BLA) ? launch_deep_distance_bla(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
@@ -4219,6 +4250,115 @@ int mbk_deep_distance_bla_skip_host(double A_r, double A_i, double B_r, double B
 {
     if (!D_r || !D_i || !e) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
     mbk::deep_derivative_skip(A_r, A_i, B_r, B_i, *D_r, *D_i, *e);
+    return MBK_OK;
+}
+
+// ---- distance estimates for extended-range deep views with bilinear approximation (mbk.h, the section of that name): calls
+// of their own on the launch, the value scaffold and the render machinery above; the calls without _xbla keep refusing
+// MBK_DEEP_XBLA ------------------------------------------------------------------------------------------------------------
+
+// Everything such a call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
+static int wide_distance_xbla_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags)
+{
+    if (flags & MBK_DEEP_XBLA)
+        return fail(ctx, MBK_ERR_INVALID, "the _distance_xbla calls take no flags: the name selects the rule (MBK_DEEP_XBLA is a flag of the count calls)");
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance estimates take no flags (no kernel selection, no fp32)");
+    return validate_deep_wide(ctx, orbit, view, mrd, MBK_DEEP_XBLA);
+}
+
+int mbk_deep_xview_launch_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                        uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = wide_distance_xbla_check(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return target_launch(ctx, wide_target(orbit, view), mrd, MBK_DEEP_XBLA, Outputs{d_counts, nullptr, d_rel, true}, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_xview_compute_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                         uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = wide_distance_xbla_check(ctx, orbit, view, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    const Target t = wide_target(orbit, view);
+    return compute_values(ctx, (size_t)t.g.ncols * t.g.nrows, mrd, h_counts, h_rel, stats,
+                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
+                              return target_launch(ctx, t, mrd, MBK_DEEP_XBLA, Outputs{d_counts, nullptr, d_rel, true}, stream);
+                          });
+}
+
+// Everything such a render can refuse, before anything is allocated, enqueued or written.
+static int wide_distance_xbla_render_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, const void *out, Target *t)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_render_spec(ctx, spec);
+    if (rc != MBK_OK) return rc;
+    if (spec->source != MBK_RENDER_DISTANCE_REL)
+        return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance renders with bilinear approximation take MBK_RENDER_DISTANCE_REL only");
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    *t = wide_target(orbit, view);
+    const uint32_t s = spec->supersample;
+    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
+    return wide_distance_xbla_check(ctx, orbit, &samples.wide, mrd, flags);
+}
+
+int mbk_deep_xview_distance_xbla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                               uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    Target t;
+    int rc = wide_distance_xbla_render_check(ctx, orbit, view, mrd, flags, spec, d_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, MBK_DEEP_XBLA, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+}
+
+int mbk_deep_xview_distance_xbla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                                uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    Target t;
+    int rc = wide_distance_xbla_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, MBK_DEEP_XBLA, spec, h_rgba, stats, nullptr, 0u);
+}
+
+// host twins (mbk_deep_wide_distance_bla.h): no ctx, no device
+int mbk_deep_xview_distance_xbla_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                                      int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel,
+                                      uint64_t *steps_executed)
+{
+    if (!count || !extra || !mag || !D_r || !D_i || !e || !rel || !steps_executed) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::WideBlaTable t;
+    int rc = xbla_host_table(orbit, view, &t);
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    mbk::wide_distance_bla_host(orbit->o.wide, orbit->o.length, t, deep_dc(col, view->width, view->range_r),
+                                deep_dc(row, view->height, view->range_i), view->exp2, (int64_t)mrd, count, extra, mag, D_r, D_i, e,
+                                steps_executed);
+    const double r2 = *D_r * *D_r, i2 = *D_i * *D_i;
+    *rel = mbk::wide_distance_value(*mag, r2 + i2, *e, view->range_r, view->exp2, *count);
+    return MBK_OK;
+}
+
+int mbk_deep_xdistance_skip_host(double A_r, double A_i, int32_t a_e, double B_r, double B_i, int32_t b_e, double *D_r, double *D_i,
+                                 int32_t *e)
+{
+    if (!D_r || !D_i || !e) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    mbk::wide_dskip(A_r, A_i, a_e, B_r, B_i, b_e, *D_r, *D_i, *e);
     return MBK_OK;
 }
 

@@ -346,6 +346,42 @@ def wide_distance_value_host(mag: float, dmagD: float, e: int, range_r: float, e
     return float(L.load().mbk_deep_xdistance_value_host(float(mag), float(dmagD), int(e), float(range_r), int(exp2), int(count)))
 
 
+def wide_distance_xbla_host(orbit: "DeepOrbit", view: "WideDeepView", pixels, mrd: int, window=None) -> dict:
+    """mbk_deep_xview_distance_xbla_host on the pixels (row-major indices of the FULL view), on the host, from the functions the
+    kernel uses (include/mbk.h, "Distance estimates for extended-range deep views with bilinear approximation"): a dict of
+    arrays n (int32), extra (the run-on steps taken, int32), mag, Dr, Di (float64), e (int64: d = D 2^e), dmagD and rel
+    (float64, through the host's ln) and steps (int64: the steps executed in the count loop, a skip counting as one).  A
+    window changes nothing: the table is the full view's."""
+    lib = L.load()
+    cv = _cxview(view, window)
+    pixels = np.asarray(pixels, np.int64).ravel()
+    out = {k: np.empty(pixels.size, t) for k, t in (("n", np.int32), ("extra", np.int32), ("mag", np.float64), ("Dr", np.float64),
+                                                   ("Di", np.float64), ("e", np.int64), ("rel", np.float64), ("steps", np.int64))}
+    n, x, e, s = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+    mag, dr, di, rel = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    for j, k in enumerate(pixels):
+        _check(lib, lib.mbk_deep_xview_distance_xbla_host(orbit._h, C.byref(cv), int(k % view.width), int(k // view.width), int(mrd),
+                                                          C.byref(n), C.byref(x), C.byref(mag), C.byref(dr), C.byref(di),
+                                                          C.byref(e), C.byref(rel), C.byref(s)))
+        for key, v in (("n", n), ("extra", x), ("mag", mag), ("Dr", dr), ("Di", di), ("e", e), ("rel", rel), ("steps", s)):
+            out[key][j] = v.value
+    a = out["Dr"] * out["Dr"]
+    b = out["Di"] * out["Di"]
+    out["dmagD"] = a + b
+    return out
+
+
+def wide_distance_xbla_skip_host(A_r: float, A_i: float, a_e: int, B_r: float, B_i: float, b_e: int, D_r: float, D_i: float,
+                                 e: int) -> Tuple[float, float, int]:
+    """mbk_deep_xdistance_skip_host: the derivative across one skip, d' = A d + B on A = (A_r, A_i) 2^a_e, B = (B_r, B_i) 2^b_e
+    and d = (D_r, D_i) 2^e; returns the new (D_r, D_i, e)."""
+    lib = L.load()
+    dr, di, ce = C.c_double(float(D_r)), C.c_double(float(D_i)), C.c_int32(int(e))
+    _check(lib, lib.mbk_deep_xdistance_skip_host(float(A_r), float(A_i), int(a_e), float(B_r), float(B_i), int(b_e), C.byref(dr),
+                                                 C.byref(di), C.byref(ce)))
+    return float(dr.value), float(di.value), int(ce.value)
+
+
 def deep_distance_bla_host(orbit: "DeepOrbit", view: "DeepView", pixels, mrd: int) -> dict:
     """mbk_deep_distance_bla_host on the pixels (row-major indices of the FULL view), on the host, from the functions the kernel
     uses (include/mbk.h, "Distance estimates for deep views with bilinear approximation"): a dict of arrays n (int32), extra
@@ -997,6 +1033,50 @@ class MandelbrotDevice:
         spec = palette.spec("distance_rel", supersample, max_band_rows)
         self._check(self._lib.mbk_deep_xview_distance_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
                                                                     d_rgba or None, stream or None))
+
+    # -- distance estimates for extended-range deep views with bilinear approximation (include/mbk.h, the section of that
+    # name): calls of their own; compute_wide_view_distance keeps its rule and the flag stays refused there --
+    def compute_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, window=None):
+        """compute_wide_view_distance with the skips of compute_deep_view(xbla=True): across a skip dz -> A dz + B dc the
+        derivative follows d -> A d + B, from the table the count launches use.  The counts are those of
+        compute_deep_view(xbla=True); tests/deep_wide_distance_bla_model.py has the measured error of rel.
+        Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
+        cv = _cxview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        rel = np.empty(shape, np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_compute_distance_xbla(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
+                                                                   rel.ctypes.data, C.byref(st)))
+        return rel, counts, _stats(st)
+
+    def launch_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
+                                       stream: int = 0, window=None) -> None:
+        """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream).  The
+        first launch of a view's spans on an orbit builds and uploads the table synchronously."""
+        cv = _cxview(view, window)
+        self._check(self._lib.mbk_deep_xview_launch_distance_xbla(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
+                                                                  d_rel or None, stream or None))
+
+    def render_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, supersample: int = 1,
+                                       window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+        """The view as an RGBA8 image coloured by that estimate (source "distance_rel"; Palette.deep_distance), as
+        render_wide_view_distance does without skips.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
+        cv = _cxview(view, window)
+        rgba = self._render_out(cv, out)
+        spec = palette.spec("distance_rel", supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_distance_xbla_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                                          rgba.ctypes.data, C.byref(st)))
+        return rgba, _stats(st)
+
+    def launch_render_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, d_rgba: int,
+                                              supersample: int = 1, stream: int = 0, window=None, max_band_rows: int = 0) -> None:
+        """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
+        cv = _cxview(view, window)
+        spec = palette.spec("distance_rel", supersample, max_band_rows)
+        self._check(self._lib.mbk_deep_xview_distance_xbla_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
+                                                                         d_rgba or None, stream or None))
 
     # -- rendering (include/mbk.h, "Rendering") ---------------------------------------------------
     def _render_out(self, cv, out):

@@ -756,7 +756,8 @@ int mbk_deep_distance_bla_skip_host(double A_r, double A_i, double B_r, double B
  * _compute_distance: device pointers on the caller's stream / host buffers synchronously on slot 0 with the statistics of
  * mbk_deep_xview_compute (the run-on steps are not counted); counts may be NULL.  MBK_ERR_INVALID, with nothing written: a
  * NULL rel, any flag (MBK_DEEP_XBLA and MBK_DEEP_BLA each with a message of its own: the derivative of a skipped run needs
- * coefficients of its own) and whatever mbk_deep_xview_launch refuses.
+ * coefficients of its own -- since built, behind names of its own: the next section) and whatever mbk_deep_xview_launch
+ * refuses.
  */
 int mbk_deep_xview_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
                                    uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
@@ -771,6 +772,71 @@ int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xvi
 int mbk_deep_xdistance_step_host(double z_r, double z_i, int32_t t, double *D_r, double *D_i, int32_t *e);
 /* "output" above. */
 double mbk_deep_xdistance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t exp2, int32_t count);
+
+/*
+ * Distance estimates for extended-range deep views with bilinear approximation.  NOT in the reference; additive (the ABI
+ * version stays 5): no existing call changes -- mbk_deep_xview_launch_distance / _compute_distance and the renders on them keep
+ * refusing MBK_DEEP_XBLA, the capability lives behind the names below, as *_distance_bla does for plain deep views.  Below
+ * spans of 2^-960 the distance picture is the one a user wants and the step is the most expensive of the library; this was
+ * the last deep output that ran every step.  No second table: d is the derivative of the pixel's full z = Z_m + dz and the
+ * reference orbit does not depend on dc, so across a skip dz -> A dz + B dc the derivative follows d -> A d + B with the A and
+ * B the table of "Extended-range deep views with bilinear approximation" already holds.
+ *
+ * Contract (tests/deep_wide_distance_bla_model.py restates it in numpy; tests/test_deep_wide_distance_bla.py holds the host
+ * twins below to it and it to the truth, tests/test_gpu_deep_wide_distance_bla.py holds the GPU to it).  Everything of
+ * "Extended-range deep views with bilinear approximation" stands: the table and its bits, dcmax of the FULL view, eps = 2^-40,
+ * ke and the level rule, the step index, the apply rule (p1, p2, h, norm), the tail (e), (f), (g), and the count, which is
+ * exactly the count mbk_deep_xview_compute stores with MBK_DEEP_XBLA.  Everything of "Distance estimates for extended-range
+ * deep views" stands for a step that takes no level: zp = (zv, t), D = (D_r, D_i, e) as norm makes it, step i, the start state
+ * (0.5, 0, 1), the output expression and its unit rel.  Binary64 mantissas, int32 exponents, every operation rounded on its
+ * own, no contraction.  Added:
+ *   skip      a step that takes level l applies, BEFORE the dz map (as the plain derivative step comes before the z step), to
+ *             d = D 2^e and the entry's (A, e_A), (B, e_B):
+ *               P  = (fl(fl(A_r D_r) - fl(A_i D_i)), fl(fl(A_r D_i) + fl(A_i D_r))),  pe = e_A + e
+ *               h  = max(pe, e_B)
+ *               N  = fl(sh(P, pe - h) + sh(B, e_B - h))                                       per component
+ *               (D, e) = norm(N, h), then e = min(e, 2^30)
+ *             No 2^256 rescale and no floor at 0: norm does both jobs.  A zero D has exponent EZ and never sets h (a live A
+ *             is non-zero, |e_A| <= 2^20).  An addend more than 1200 binades below the other is dropped by sh, never wrapped.
+ *             e may decrease (|A| < 1 where the orbit passes near 0).  Nothing is stored beside the table, and what
+ *             mbk_deep_xbla_read returns does not change.
+ *   zp        after a skip zp becomes the (zv, t) that step (e) forms at the new m; D, e and zp do not change at a rebase.
+ *   run-on    a pixel with n > 0 first applies (g) to the escaping step's state, then runs PLAIN steps only -- never a skip --
+ *             until mag >= 2^32 or 64 further steps have run.
+ *   no skip   where no level is ever taken (M <= 1: no table; or a view such as the centre 1e-400 at span 4, whose level 0 is
+ *             never within its radius) every state and rel equals mbk_deep_xview_launch_distance bit for bit.
+ *   mrd       0 and 1 run no step: every count and value is 0.
+ * Windows of a view are bit-identical to the whole view.  Statistics: pixel_iterations counts the reference's iterations
+ * (count, or mrd - 1 for 0), not the steps executed and not the run-on.
+ * Against d' = 2 z d + 1, z' = z^2 + c in mpmath at P + 128 bits from the exact c, on the five truth cases of
+ * tests/test_deep_wide.py: (count, run-on) agree on >= 99 % of the escaped picks and rel is within XBLA_DERIVATIVE_REL of the
+ * model file, which holds the measured figures.  What a skip neglects is of the order of the |dz| / |Z| that the radius test
+ * bounds by 2^-40 per step; the error of rel is that times the conditioning of the orbit-long product.
+ *
+ * One pass (csrc/mbk_deep_wide_distance_bla.h); with M <= 1 the launch is that of mbk_deep_xview_launch_distance.  The argument
+ * rules are those of the calls without _xbla: device pointers on the caller's stream / host buffers synchronously on slot 0
+ * with the statistics above; counts may be NULL.  MBK_ERR_INVALID, with nothing written: a NULL rel, any flag -- MBK_DEEP_XBLA
+ * and MBK_DEEP_BLA each with a message of its own: the name selects the rule --, an orbit longer than 2^31 and whatever
+ * mbk_deep_xview_launch refuses.  The render calls take MBK_RENDER_DISTANCE_REL only: banding, supersampling, colour,
+ * statistics and refusals are those of mbk_deep_xview_distance_render_*; the sample view at s x is a full view of its own and
+ * has a table of its own, as for MBK_DEEP_XBLA.  The ctx's table is the one of the MBK_DEEP_XBLA count launches, keyed by the
+ * orbit's id and dcmax and shared with them: launch once per (orbit, spans) before capturing, and expect alternating spans on
+ * one orbit to serialise.
+ */
+int mbk_deep_xview_launch_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                        uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
+int mbk_deep_xview_compute_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                         uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats);
+/* (mbk_deep_xview_distance_xbla_render_launch / _compute are declared under "Rendering", below.) */
+/* Host twins for the CPU tests, compiled from the functions the kernel uses: no ctx, no device.  The pixel (col, row) of the
+ * full view: its count, the run-on steps taken, the final mag (0 for count 0), the final D 2^e, rel (with the host's ln) and
+ * the number of steps executed in the count loop, a skip counting as one.  MBK_ERR_INVALID for what the launch refuses. */
+int mbk_deep_xview_distance_xbla_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                                      int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel,
+                                      uint64_t *steps_executed);
+/* "skip" above, once: A = (A_r, A_i) 2^a_e, B = (B_r, B_i) 2^b_e, (D_r, D_i, e) in and out. */
+int mbk_deep_xdistance_skip_host(double A_r, double A_i, int32_t a_e, double B_r, double B_i, int32_t b_e, double *D_r, double *D_i,
+                                 int32_t *e);
 
 /*
  * Rendering: a view to an RGBA8 image on the device, with a palette and supersampling.  Replaces, for a view of any kind,
@@ -889,6 +955,14 @@ int mbk_deep_view_distance_bla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit 
                                              uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
 int mbk_deep_view_distance_bla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                               uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+/* Distance renders of extended-range deep views that take skips ("Distance estimates for extended-range deep views with
+ * bilinear approximation"), calls of their own in the same way: the source must be MBK_RENDER_DISTANCE_REL, the samples are
+ * what mbk_deep_xview_launch_distance_xbla writes for the sample view, and colour, banding, supersampling, statistics and
+ * refusals are those of mbk_deep_xview_distance_render_*.  Every flag is MBK_ERR_INVALID. */
+int mbk_deep_xview_distance_xbla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                               uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_xview_distance_xbla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                                uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
 /* The reference Viewer's colouring as a 256-entry palette for MBK_RENDER_BYTES, host only: entry 0 black (0, 0, 0, 255),
  * entry b = jet(1 - b / 256) as data_to_img_array evaluates it, each channel floor(255 x + 0.5) (jet holds exact .5 ties, so
  * the rounding rule is part of the contract).  Computed from jet's public definition (its knots and matplotlib's 256-entry
