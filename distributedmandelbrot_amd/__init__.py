@@ -18,7 +18,9 @@ There is no CPU fallback anywhere in this package.
 """
 from .device import DeepOrbit, DeepView, DensityStats, DensityTarget, MandelbrotDevice, MbkError, TileStats, View, WideDeepView, device_count  # noqa: F401
 from .device import deep_distance_bla_host, deep_distance_bla_skip_host  # noqa: F401
+from .device import Nucleus, NucleusError, deep_nucleus_host, locate_nucleus, pick_nucleus_seed, refine_nucleus  # noqa: F401
 from .image import Palette, write_png  # noqa: F401
 
-__all__ = ["DeepOrbit", "DeepView", "DensityStats", "DensityTarget", "MandelbrotDevice", "MbkError", "Palette", "TileStats", "View", "WideDeepView",
-           "deep_distance_bla_host", "deep_distance_bla_skip_host", "device_count", "write_png"]
+__all__ = ["DeepOrbit", "DeepView", "DensityStats", "DensityTarget", "MandelbrotDevice", "MbkError", "Nucleus", "NucleusError", "Palette",
+           "TileStats", "View", "WideDeepView", "deep_distance_bla_host", "deep_distance_bla_skip_host", "deep_nucleus_host",
+           "device_count", "locate_nucleus", "pick_nucleus_seed", "refine_nucleus", "write_png"]

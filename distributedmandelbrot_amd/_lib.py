@@ -229,6 +229,18 @@ SIGNATURES = {
     "mbk_deep_view_compute_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                                  C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_deep_distance_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32]),
+    "mbk_deep_view_launch_nucleus": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_view_compute_nucleus": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_nucleus_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_double)]),
+    "mbk_deep_orbit_newton_host": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int32)]),
+    "mbk_deep_orbit_size_host": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_int32)]),
     "mbk_deep_view_launch_distance_bla": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "mbk_deep_view_compute_distance_bla": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,

@@ -36,6 +36,7 @@
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
 #include "mbk_deep_distance_bla.h"
+#include "mbk_deep_nucleus.h"
 #include "mbk_deep_wide_distance_bla.h"
 #include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
@@ -1498,16 +1499,17 @@ static int sync_end(mbk_ctx *ctx, int rc, mbk_stats *stats, bool have_bytes, boo
 // The calls that return one binary64 value per pixel (smooth, distance, deep distance, interior) between sync_begin and the return:
 // launch(d_counts, d_values, stream) enqueues the kernels that write both.  with_tail (interior views): the device values are
 // followed by px int32 (the periods, at d_values + px), which the launch writes too; they go to h_tail, and h_values and h_tail
-// may each be NULL.
+// may each be NULL.  per_px (atom periods and Newton seeds): that many binary64 values per pixel, the tail after all of them.
 template <typename Launch>
 static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch,
-                          bool with_tail = false, int32_t *h_tail = nullptr)
+                          bool with_tail = false, int32_t *h_tail = nullptr, size_t per_px = 1u)
 {
     Slot &sl = ctx->s[0];
     auto enqueue = [&]() -> int {
         int rc = ensure_buffers(ctx, sl, px);
         if (rc != MBK_OK) return rc;
-        const size_t cap = with_tail ? px + (px + 1u) / 2u : px;   // (in binary64 values)
+        const size_t vals = per_px * px;
+        const size_t cap = with_tail ? vals + (px + 1u) / 2u : vals;   // (in binary64 values)
         rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, cap, cap * sizeof(double));
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
@@ -1517,8 +1519,8 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
         rc = launch_reduce(ctx, sl, sl.d_counts, nullptr, px, mrd, sl.stream);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
-        if (h_values) MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
-        if (h_tail) MBK_HIP(ctx, hipMemcpyAsync(h_tail, ctx->d_smooth + px, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+        if (h_values) MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, vals * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        if (h_tail) MBK_HIP(ctx, hipMemcpyAsync(h_tail, ctx->d_smooth + vals, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
         ctx->last_px = 0;   // (no bytes on the device: mbk_serialize_last has nothing to read)
@@ -3170,6 +3172,117 @@ int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, co
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count)
 {
     return mbk::deep_distance_value(mag, dmagD, e, range_r, count);
+}
+
+// ---- atom periods and Newton seeds of deep views (mbk_deep_nucleus.h; mbk.h "Locating minibrots in deep views") ----------
+
+// the nucleus kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd,
+                               int32_t *d_counts, int32_t *d_period, double *d_delta, hipStream_t stream)
+{
+    mbk_ctx::DeepCopy *c = nullptr;
+    int rc = deep_copy(ctx, orbit, &c);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepNucleusArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_deep_args(a.v, c->d, orbit, v, mrd);
+    a.v.counts = d_counts;
+    a.range_r = v->range_r;
+    a.period = d_period;
+    a.delta = d_delta;
+    hipLaunchKernelGGL(mbk::deep_nucleus_kernel, block_grid(a.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// Everything a nucleus call can refuse, before anything is allocated, enqueued or written.
+static int deep_nucleus_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                              const void *period, const void *delta)
+{
+    if (!period || !delta) return fail(ctx, MBK_ERR_INVALID, "NULL period or delta pointer");
+    if (flags & MBK_DEEP_BLA)
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for atom periods (a skipped run has no |z_n| to compare)");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "atom periods take no flags (no kernel selection, no fp32)");
+    return validate_deep(ctx, orbit, view, mrd, 0u);
+}
+
+int mbk_deep_view_launch_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                 uint32_t flags, int32_t *d_counts, int32_t *d_period, double *d_delta, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = deep_nucleus_check(ctx, orbit, view, mrd, flags, d_period, d_delta);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_deep_nucleus(ctx, orbit, view, mrd, d_counts, d_period, d_delta, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_view_compute_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *h_counts, int32_t *h_period, double *h_delta, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = deep_nucleus_check(ctx, orbit, view, mrd, flags, h_period, h_delta);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    // the device values: 2 px binary64 (delta), then px int32 (the periods)
+    const size_t px = (size_t)view->ncols * view->nrows;
+    return compute_values(
+        ctx, px, mrd, h_counts, h_delta, stats,
+        [&](int32_t *d_counts, double *d_delta, hipStream_t stream) {
+            return launch_deep_nucleus(ctx, orbit, view, mrd, d_counts, reinterpret_cast<int32_t *>(d_delta + 2u * px), d_delta, stream);
+        },
+        true, h_period, 2u);
+}
+
+// host twins (mbk_deep_nucleus.h): no ctx, no device
+int mbk_deep_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                          int32_t *count, int32_t *period, double *best, double *z_b, double *D_b, int32_t *e_b, double *delta)
+{
+    if (!count || !period || !best || !z_b || !D_b || !e_b || !delta) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = validate_deep(nullptr, orbit, view, mrd, 0u);
+    if (rc != MBK_OK) return rc;
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    mbk::NucleusBest b;
+    mbk::deep_nucleus_host(orbit->o.table, orbit->o.length, deep_dc(col, view->width, view->range_r),
+                           deep_dc(row, view->height, view->range_i), view->range_r, (int64_t)mrd, count, &b, delta);
+    *period = b.arg + 1;
+    *best = b.best;
+    z_b[0] = b.zr;
+    z_b[1] = b.zi;
+    D_b[0] = b.Dr;
+    D_b[1] = b.Di;
+    *e_b = b.e;
+    return MBK_OK;
+}
+
+static int orbit_period_check(const mbk_deep_orbit *orbit, uint32_t period, const void *a, const void *b, const void *c)
+{
+    if (!orbit || !a || !b || !c) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    if (period == 0u) return fail(nullptr, MBK_ERR_INVALID, "period must be >= 1");
+    if (orbit->o.length < period) return fail(nullptr, MBK_ERR_INVALID, "the orbit is shorter than the period");
+    return MBK_OK;
+}
+
+int mbk_deep_orbit_newton_host(const mbk_deep_orbit *orbit, uint32_t period, double *d_r, double *d_i, int32_t *d_e)
+{
+    int rc = orbit_period_check(orbit, period, d_r, d_i, d_e);
+    if (rc != MBK_OK) return rc;
+    const mbk::WideComplex w = mbk::wide_newton_step(orbit->o.wide, period);
+    *d_r = w.r;
+    *d_i = w.i;
+    *d_e = w.e;
+    return MBK_OK;
+}
+
+int mbk_deep_orbit_size_host(const mbk_deep_orbit *orbit, uint32_t period, double *s_r, double *s_i, int32_t *s_e)
+{
+    int rc = orbit_period_check(orbit, period, s_r, s_i, s_e);
+    if (rc != MBK_OK) return rc;
+    const mbk::WideComplex w = mbk::wide_size_estimate(orbit->o.wide, period);
+    *s_r = w.r;
+    *s_i = w.i;
+    *s_e = w.e;
+    return MBK_OK;
 }
 
 // ---- distance estimates for deep views with bilinear approximation (mbk_deep_distance_bla.h; mbk.h, the section of that

@@ -8,10 +8,10 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from decimal import Decimal
 from fractions import Fraction
-from typing import Optional, Tuple, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 
@@ -413,6 +413,325 @@ def deep_distance_bla_skip_host(A_r: float, A_i: float, B_r: float, B_i: float, 
     dr, di, ce = C.c_double(float(D_r)), C.c_double(float(D_i)), C.c_int32(int(e))
     _check(lib, lib.mbk_deep_distance_bla_skip_host(float(A_r), float(A_i), float(B_r), float(B_i), C.byref(dr), C.byref(di), C.byref(ce)))
     return float(dr.value), float(di.value), int(ce.value)
+
+
+# -- locating minibrots (include/mbk.h, "Locating minibrots in deep views") ---------------------------------------------------
+
+class NucleusError(RuntimeError):
+    """refine_nucleus / locate_nucleus could not deliver a nucleus; `reason` is "no seed", "not converged" or "precision"."""
+
+    def __init__(self, reason: str, message: str):
+        super().__init__(f"{reason}: {message}")
+        self.reason = reason
+
+
+def _big_int(digits: str) -> int:
+    """int(digits) for a string of decimal digits of any length (int() refuses more than a few thousand at once)."""
+    v = 0
+    for k in range(0, len(digits), 1000):
+        part = digits[k:k + 1000]
+        v = v * 10 ** len(part) + int(part)
+    return v
+
+
+def _big_str(v: int) -> str:
+    """str(v) for a non-negative int of any size."""
+    parts = []
+    while True:
+        v, low = divmod(v, 10 ** 1000)
+        if v == 0:
+            parts.append(str(low))
+            break
+        parts.append(str(low).rjust(1000, "0"))
+    return "".join(reversed(parts))
+
+
+def _exact_fraction(x) -> Fraction:
+    """The exact value of a centre coordinate (str in the library's decimal syntax, Decimal, Fraction, int or float)."""
+    if isinstance(x, Fraction):
+        return x
+    if isinstance(x, (int, float)) and not isinstance(x, bool):
+        return Fraction(x)
+    s = str(x).strip().lower()
+    neg = s.startswith("-")
+    if s[:1] in "+-":
+        s = s[1:]
+    mant, _, ex = s.partition("e")
+    whole, _, frac = mant.partition(".")
+    if not (whole + frac).isdigit():
+        raise ValueError(f"not a decimal number: {x!r}")
+    e10 = (int(ex) if ex else 0) - len(frac)
+    v = Fraction(_big_int(whole + frac)) * (Fraction(10) ** e10)
+    return -v if neg else v
+
+
+def _dyadic_decimal(x: Fraction) -> str:
+    """The exact decimal string of a Fraction whose denominator is a power of two."""
+    k = x.denominator.bit_length() - 1
+    if x.denominator != 1 << k:
+        raise ValueError("not a dyadic fraction")
+    q = _big_str(abs(x.numerator) * 5 ** k).rjust(k + 1, "0")
+    body = q[:-k] + "." + q[-k:] if k else q
+    return ("-" if x < 0 else "") + body
+
+
+def _wide_fraction(m: float, e: int) -> Fraction:
+    """m 2^e exactly (a wide zero, exponent -2^24, is 0)."""
+    if m == 0.0:
+        return Fraction(0)
+    if not math.isfinite(m):
+        raise NucleusError("not converged", "a non-finite value")
+    return Fraction(m) * (Fraction(2) ** int(e))
+
+
+def deep_nucleus_host(orbit: "DeepOrbit", view: "DeepView", pixels, mrd: int) -> dict:
+    """mbk_deep_nucleus_host on the pixels (row-major indices of the FULL view), on the host, from the functions the kernel uses
+    (include/mbk.h, "Locating minibrots in deep views"): a dict of arrays n, period (int32), best (float64), z (float64[N, 2]),
+    D (float64[N, 2]), e (int64: d_b = D 2^e) and delta (float64[N, 2])."""
+    lib = L.load()
+    if not isinstance(view, DeepView):
+        raise ValueError("atom periods are implemented for a DeepView only")
+    cv = L.mbk_deep_view(view.span_r, view.span_i, view.width, view.height, 0, 0, view.width, view.height)
+    pixels = np.asarray(pixels, np.int64).ravel()
+    N = pixels.size
+    out = {"n": np.empty(N, np.int32), "period": np.empty(N, np.int32), "best": np.empty(N, np.float64),
+           "z": np.empty((N, 2), np.float64), "D": np.empty((N, 2), np.float64), "e": np.empty(N, np.int64),
+           "delta": np.empty((N, 2), np.float64)}
+    n, p, e, best = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+    z, d, delta = (C.c_double * 2)(), (C.c_double * 2)(), (C.c_double * 2)()
+    for j, k in enumerate(pixels):
+        _check(lib, lib.mbk_deep_nucleus_host(orbit._h, C.byref(cv), int(k % view.width), int(k // view.width), int(mrd),
+                                              C.byref(n), C.byref(p), C.byref(best), z, d, C.byref(e), delta))
+        out["n"][j], out["period"][j], out["best"][j], out["e"][j] = n.value, p.value, best.value, e.value
+        out["z"][j], out["D"][j], out["delta"][j] = tuple(z), tuple(d), tuple(delta)
+    return out
+
+
+def _orbit_wide_call(name: str, orbit: "DeepOrbit", period: int) -> Tuple[float, float, int]:
+    lib = L.load()
+    r, i, e = C.c_double(), C.c_double(), C.c_int32()
+    _check(lib, getattr(lib, name)(orbit._h, int(period), C.byref(r), C.byref(i), C.byref(e)))
+    return float(r.value), float(i.value), int(e.value)
+
+
+def orbit_newton_host(orbit: "DeepOrbit", period: int) -> Tuple[float, float, int]:
+    """mbk_deep_orbit_newton_host: the Newton step -Z_p / D_p at the orbit's own centre as (d_r, d_i, d_e), value d 2^d_e."""
+    return _orbit_wide_call("mbk_deep_orbit_newton_host", orbit, period)
+
+
+def orbit_size_host(orbit: "DeepOrbit", period: int) -> Tuple[float, float, int]:
+    """mbk_deep_orbit_size_host: the size estimate 1 / (b l^2) of the component whose nucleus the orbit's centre is, as
+    (s_r, s_i, s_e), value s 2^s_e."""
+    return _orbit_wide_call("mbk_deep_orbit_size_host", orbit, period)
+
+
+def _pixel_offsets(view: "DeepView"):
+    """(dc_r[width], dc_i[height]): the offsets of the view's columns and rows as the kernels form them."""
+    def axis(n, span):
+        if n <= 1:
+            return np.zeros(n, np.float64)
+        return (np.arange(n, dtype=np.float64) - np.float64((n - 1) / 2)) * (np.float64(span) / np.float64(n - 1))
+    return axis(view.width, view.span_r), axis(view.height, view.span_i)
+
+
+class NucleusSeed(NamedTuple):
+    pixel: Tuple[int, int]   # (row, col)
+    period: int
+    offset_r: Fraction       # the target, from the view's centre, in the plane's units
+    offset_i: Fraction
+
+
+def pick_nucleus_seed(view: "DeepView", period, delta) -> Optional[NucleusSeed]:
+    """The Newton seed of a view from the outputs of compute_deep_view_nucleus (period int32[height, width], delta
+    float64[height, width, 2]).  The target of a pixel is its offset plus delta * span_r, exactly (Fractions); it is in view
+    when it lies within the view's rectangle.  Among the in-view pixels with a finite delta the lowest period wins, among those
+    the smallest |delta|, among those the first in image order.  None when no target is in view."""
+    period = np.asarray(period)
+    delta = np.asarray(delta, np.float64).reshape(view.height, view.width, 2)
+    assert period.shape == (view.height, view.width)
+    dcr, dci = _pixel_offsets(view)
+    span_r, span_i = Fraction(view.span_r), Fraction(view.span_i)
+    finite = np.isfinite(delta).all(axis=2)
+    with np.errstate(all="ignore"):
+        tr = dcr[None, :] + delta[..., 0] * view.span_r
+        ti = dci[:, None] + delta[..., 1] * view.span_r
+        # the float test decides all but the targets within 1e-12 (relative) of an edge; those are decided exactly
+        near = 1e-12
+        surely_in = finite & (np.abs(tr) <= view.span_r / 2 * (1 - near)) & (np.abs(ti) <= view.span_i / 2 * (1 - near))
+        maybe_in = finite & (np.abs(tr) <= view.span_r / 2 * (1 + near)) & (np.abs(ti) <= view.span_i / 2 * (1 + near))
+        mag2 = delta[..., 0] * delta[..., 0] + delta[..., 1] * delta[..., 1]
+
+    def target(r, c):
+        return (Fraction(float(dcr[c])) + Fraction(float(delta[r, c, 0])) * span_r,
+                Fraction(float(dci[r])) + Fraction(float(delta[r, c, 1])) * span_r)
+
+    def in_view(r, c):
+        if surely_in[r, c]:
+            return True
+        t = target(r, c)
+        return abs(t[0]) * 2 <= span_r and abs(t[1]) * 2 <= span_i
+
+    for p in np.unique(period[maybe_in]):
+        cand = [(r, c) for r, c in zip(*np.nonzero(maybe_in & (period == p))) if in_view(r, c)]
+        if not cand:
+            continue
+        low = min(mag2[r, c] for r, c in cand)
+        close = [(r, c) for r, c in cand if mag2[r, c] <= low * (1 + near)]
+        exact = lambda rc: Fraction(float(delta[rc[0], rc[1], 0])) ** 2 + Fraction(float(delta[rc[0], rc[1], 1])) ** 2
+        r, c = min(close, key=exact)   # (min keeps the first of equals: image order)
+        t = target(r, c)
+        return NucleusSeed((int(r), int(c)), int(p), t[0], t[1])
+    return None
+
+
+@dataclass(frozen=True)
+class Nucleus:
+    """A located minibrot: its nucleus as decimal strings (found at precision_bits fraction bits, then polished at more: see
+    refine_nucleus), its minimal period and the
+    size estimate (size_r, size_i) 2^size_e of its component (complex: its argument is the minibrot's orientation)."""
+    center_r: str
+    center_i: str
+    period: int
+    size_r: float
+    size_i: float
+    size_e: int
+    precision_bits: int
+    rounds: int
+    polish_rounds: int = 0   # further rounds at a higher precision: the centre strings carry more than precision_bits
+    seed_pixel: Optional[Tuple[int, int]] = None
+    inside: Optional[bool] = None
+
+    @property
+    def size_log2(self) -> float:
+        """log2 |size|"""
+        return self.size_e + math.log2(math.hypot(self.size_r, self.size_i))
+
+    def orbit(self, mrd: int) -> "DeepOrbit":
+        """The reference orbit of the nucleus at precision_bits."""
+        return DeepOrbit(self.center_r, self.center_i, mrd, precision_bits=self.precision_bits)
+
+    def view(self, width: int, height: Optional[int] = None, frame: float = 4.0):
+        """The view centred on the nucleus whose real span is frame * |size|: a DeepView, or a WideDeepView when that span is
+        below 2^-960."""
+        f, k = math.frexp(float(frame) * math.hypot(self.size_r, self.size_i))
+        if self.size_e + k - 1 < -960:
+            return WideDeepView(f, self.size_e + k, width, height)
+        return DeepView(min(4.0, math.ldexp(f, self.size_e + k)), width, height)
+
+
+def refine_nucleus(center_r, center_i, period: int, precision_bits: int, max_rounds: int = 32) -> Nucleus:
+    """Newton's method on Z_p(C) = 0 from the seed (center_r, center_i), on the host.  Each round builds the reference orbit of
+    C at precision_bits fraction bits, takes the step -Z_p / D_p (mbk_deep_orbit_newton_host) and adds it to C exactly; it has
+    converged when |step| <= 2^(32 - precision_bits) (the fixed-point orbit's truncation noise in Z_p / D_p is of the order of
+    p 2^-precision_bits).  The period is then reduced to the smallest divisor of `period` whose own Newton step at the result
+    meets the same bound, and the size estimate is taken.  Last, the centre is polished: Z_p(C) = D_p (C - root) with |D_p| about
+    1 / sqrt(size), so a centre good to its last place at precision_bits still leaves Z_p far above 2^-precision_bits; the same
+    rounds at precision_bits + log2(1 / sqrt(size)) + 64 bits (at most 4096) go on until |Z_p| <= 2^(38 - precision_bits), and the
+    centre strings returned carry those bits (Nucleus.orbit reads precision_bits of them; a later, deeper orbit may read more).
+    Raises NucleusError: "not converged" (max_rounds used up in either phase, or the
+    iterate left the set's neighbourhood), or "precision" (-log2 |size| + 64 > precision_bits: the component is too small for
+    this precision to place a view in it)."""
+    period, P = int(period), int(precision_bits)
+    if period < 1:
+        raise ValueError("period must be >= 1")
+    bound2 = Fraction(4) ** (32 - P)
+
+    def truncated(v):
+        """what the library reads of v: truncated towards zero at P fraction bits"""
+        v = _exact_fraction(v)
+        t = Fraction((abs(v.numerator) << P) // v.denominator, 1 << P)
+        return -t if v < 0 else t
+
+    Cr, Ci = truncated(center_r), truncated(center_i)   # (dyadic from here on: every sum below is exact and has a finite decimal)
+
+    def step_at(cr, ci, q):
+        """(orbit, the Newton step of period q at (cr, ci) as two Fractions)"""
+        try:
+            o = DeepOrbit(_dyadic_decimal(cr), _dyadic_decimal(ci), period + 1, precision_bits=P)
+            d = orbit_newton_host(o, q)
+        except MbkError as err:
+            raise NucleusError("not converged", f"no Newton step of period {q} at the iterate ({err})") from None
+        return o, _wide_fraction(d[0], d[2]), _wide_fraction(d[1], d[2])
+
+    rounds = 0
+    while True:
+        if rounds == max_rounds:
+            raise NucleusError("not converged", f"|step| is still above 2^{32 - P} after {max_rounds} rounds")
+        _, dr, di = step_at(Cr, Ci, period)
+        Cr, Ci = Cr + dr, Ci + di
+        rounds += 1
+        if dr * dr + di * di <= bound2:
+            break
+    Cr, Ci = truncated(Cr), truncated(Ci)
+    o, _, _ = step_at(Cr, Ci, period)
+    minimal = period
+    for q in range(1, period):
+        if period % q == 0:
+            d = orbit_newton_host(o, q)
+            qr, qi = _wide_fraction(d[0], d[2]), _wide_fraction(d[1], d[2])
+            if qr * qr + qi * qi <= bound2:
+                minimal = q
+                break
+    s = orbit_size_host(o, minimal)
+    mag = math.hypot(s[0], s[1])
+    if not (math.isfinite(mag) and mag > 0.0):
+        raise NucleusError("not converged", "the size estimate is not finite")
+    need = -(s[2] + math.log2(mag)) + 64
+    if need > P:
+        raise NucleusError("precision", f"the component has size 2^{s[2] + math.log2(mag):.1f}: {math.ceil(need)} fraction bits "
+                                        f"are needed, precision_bits is {P}")
+    # Polish.  C is now within 2^(32 - P) of the root, but Z_p(C) = D_p (C - root) and |D_p| = |b l| ~ 1 / sqrt(size) of a deep
+    # minibrot is huge: a last-place error of C leaves Z_p far above 2^-P.  The same Newton rounds at Q = P + log2(1 / sqrt(size))
+    # + 64 bits (a multiple of 64, at most 4096) go on until Z_p itself is below 2^(38 - P); the centre strings carry Q bits.
+    Q = min(4096, -(-(P + math.ceil(need - 64) // 2 + 64) // 64) * 64)
+    polish = 0
+    while Q > P:
+        try:
+            o = DeepOrbit(_dyadic_decimal(Cr), _dyadic_decimal(Ci), minimal + 1, precision_bits=Q)
+            d = orbit_newton_host(o, minimal)
+        except MbkError as err:
+            raise NucleusError("not converged", f"no Newton step at the polished iterate ({err})") from None
+        xr, xi, xe = (a[minimal] for a in o.wide_table())
+        z = (_wide_fraction(float(xr), int(xe)), _wide_fraction(float(xi), int(xe)))
+        dr, di = _wide_fraction(d[0], d[2]), _wide_fraction(d[1], d[2])
+        if z[0] * z[0] + z[1] * z[1] <= Fraction(4) ** (38 - P) or dr * dr + di * di <= Fraction(4) ** (32 - Q):
+            break
+        if polish == max_rounds:
+            raise NucleusError("not converged", f"|Z_p| is still above 2^{38 - P} after {max_rounds} polishing rounds at {Q} bits")
+        Cr, Ci = Cr + dr, Ci + di
+        t = [Fraction((abs(v.numerator) << Q) // v.denominator, 1 << Q) * (-1 if v < 0 else 1) for v in (Cr, Ci)]
+        Cr, Ci = t
+        polish += 1
+    return Nucleus(_dyadic_decimal(Cr), _dyadic_decimal(Ci), minimal, s[0], s[1], s[2], P, rounds, polish)
+
+
+def nucleus_precision_bits(view: "DeepView") -> int:
+    """locate_nucleus' default precision: the next multiple of 64 at or above 2 log2(1 / span) + 128, at most 4096 -- the sizes
+    found in a view are about its span squared."""
+    span = min(view.span_r, view.span_i)
+    bits = math.ceil(2 * max(0.0, -math.log2(span)) + 128)
+    return min(4096, -(-bits // 64) * 64)
+
+
+def locate_nucleus(orbit: "DeepOrbit", view: "DeepView", mrd: int, *, seeds, precision_bits: Optional[int] = None,
+                   max_rounds: int = 32) -> Nucleus:
+    """The minibrot a view points at, from the view's atom periods and Newton seeds: seeds = (period, delta) as
+    compute_deep_view_nucleus (or deep_nucleus_host over every pixel) gives them.  pick_nucleus_seed chooses the seed,
+    refine_nucleus refines it at precision_bits (default nucleus_precision_bits(view)).  Host only;
+    MandelbrotDevice.locate_nucleus computes the seeds on the device and calls this.  Raises NucleusError ("no seed": no
+    target lies in the view)."""
+    if not isinstance(view, DeepView):
+        raise ValueError("locating a nucleus is implemented for a DeepView only")
+    period, delta = seeds
+    seed = pick_nucleus_seed(view, period, delta)
+    if seed is None:
+        raise NucleusError("no seed", f"no pixel's Newton target lies in the view at mrd {mrd}")
+    P = int(precision_bits) if precision_bits is not None else nucleus_precision_bits(view)
+    C0 = (_exact_fraction(orbit.center[0]), _exact_fraction(orbit.center[1]))
+    n = refine_nucleus(C0[0] + seed.offset_r, C0[1] + seed.offset_i, seed.period, P, max_rounds)
+    off = (_exact_fraction(n.center_r) - C0[0], _exact_fraction(n.center_i) - C0[1])
+    inside = abs(off[0]) * 2 <= Fraction(view.span_r) and abs(off[1]) * 2 <= Fraction(view.span_i)
+    return replace(n, seed_pixel=seed.pixel, inside=bool(inside))
 
 
 def interior_host(c, mrd: int) -> Tuple[int, int, int, float]:
@@ -938,6 +1257,47 @@ class MandelbrotDevice:
         cv = self._cdeep(view, window)
         self._check(self._lib.mbk_deep_view_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
                                                             d_rel or None, stream or None))
+
+    # -- locating minibrots (include/mbk.h, "Locating minibrots in deep views") --
+    @staticmethod
+    def _nucleus_view(view) -> None:
+        if not isinstance(view, DeepView):
+            raise ValueError("atom periods and Newton seeds are implemented for a DeepView only (not from below 2^-960)")
+
+    def compute_deep_view_nucleus(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None):
+        """Atom periods and Newton seeds of a deep view: per pixel the period p = 1 + the step at which |z| was smallest, and
+        delta, one Newton step from the pixel towards the root of z_p(c) = 0 as a fraction of span_r (+inf in both components:
+        no seed); the pixel's own offset is not included.  The counts are those of compute_deep_view.
+        Returns (period int32[nrows,ncols], delta float64[nrows,ncols,2], counts int32[nrows,ncols], TileStats)."""
+        self._nucleus_view(view)
+        cv = self._cdeep(view, window)
+        shape = (cv.nrows, cv.ncols)
+        period = np.empty(shape, np.int32)
+        delta = np.empty(shape + (2,), np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_view_compute_nucleus(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
+                                                            period.ctypes.data, delta.ctypes.data, C.byref(st)))
+        return period, delta, counts, _stats(st)
+
+    def launch_deep_view_nucleus(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_period: int, d_delta: int,
+                                 d_counts: int = 0, stream: int = 0, window=None) -> None:
+        """Asynchronous form on DEVICE pointers (int32, 2 x float64 and int32 per pixel of the window) on ``stream`` (0 = HIP's
+        null stream)."""
+        self._nucleus_view(view)
+        cv = self._cdeep(view, window)
+        self._check(self._lib.mbk_deep_view_launch_nucleus(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
+                                                           d_period or None, d_delta or None, stream or None))
+
+    def locate_nucleus(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, precision_bits: Optional[int] = None, seeds=None,
+                       max_rounds: int = 32) -> Nucleus:
+        """Find the minibrot in this view: atom periods and Newton seeds on the device (or `seeds` = (period, delta)), the seed
+        pick_nucleus_seed chooses, refine_nucleus on the host.  Nucleus.orbit(mrd) and Nucleus.view(width, height) then show it."""
+        self._nucleus_view(view)
+        if seeds is None:
+            period, delta, _, _ = self.compute_deep_view_nucleus(orbit, view, mrd)
+            seeds = (period, delta)
+        return locate_nucleus(orbit, view, mrd, seeds=seeds, precision_bits=precision_bits, max_rounds=max_rounds)
 
     # -- distance estimates for deep views with bilinear approximation (include/mbk.h, the section of that name): calls of
     # their own; compute_deep_view_distance and render_deep_view(source="distance_rel") keep refusing bla --

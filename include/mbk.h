@@ -642,6 +642,68 @@ int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, co
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count);
 
 /*
+ * Locating minibrots in deep views: atom periods, Newton seeds, refinement.  NOT in the reference; additive (the ABI version
+ * stays 5): no existing call changes.  A deep view needs its centre as a decimal string of hundreds of digits; these calls
+ * find such centres.  Per pixel the atom period -- the n at which |z_n| is smallest -- and one Newton step from the pixel
+ * towards the root of z_p(c) = 0 come out of the loop that already carries the derivative; the refinement at full precision
+ * and the size of the component found are host functions over a reference orbit and its wide table.
+ *
+ * Index convention.  The pixel's orbit is z_0 = c, z_{i+1} = z_i^2 + c with d_0 = 1, d_{i+1} = 2 z_i d_i + 1 (d_i = dz_i/dc),
+ * as everywhere in the deep contracts; the reference table is Z_0 = 0, Z_1 = C, Z_{k+1} = Z_k^2 + C, so z_i corresponds to
+ * Z_{i+1}.  A nucleus of period p has Z_p = 0, i.e. z_{p-1} = 0: the step arg at which |z_i| is smallest gives the
+ * CONVENTIONAL period p = arg + 1, and that is what is stored.  On the table D_1 = 1, D_{k+1} = 2 Z_k D_k + 1 (D_k = dZ_k/dC).
+ *
+ * Contract of the device calls (tests/deep_nucleus_model.py restates it in numpy; tests/test_deep_nucleus.py holds the host
+ * twin to it and it to the truth, tests/test_gpu_deep_nucleus.py holds the GPU to the host twin).  Everything of "Deep-zoom
+ * views" stands (orbit table, offsets dc, the step, rebasing, the count) and so does the state and "step i" of "Distance
+ * estimates for deep views" (zp, D, e, one, the 2^256 rescale on every step).  There is no run-on.  Added per pixel, binary64,
+ * every operation rounded on its own:
+ *   start     best = fl(fl(z_0.r^2) + fl(z_0.i^2)) (as mag is formed), arg = 0, kept state (z_b, D_b, e_b) = (z_0, (1, 0), 0).
+ *   step i    (i = 1 .. mrd - 1) the derivative step, the z step, mag = |z_i|^2.  mag >= 4: n = i and the pixel ends; the
+ *             escaping z is never a candidate.  Otherwise, if mag < best (strict: the first minimum wins): best = mag, arg = i,
+ *             z_b = zp (the z of this step), (D_b, e_b) = (D, e).  Then the rebase rule, unchanged.
+ *   period    arg + 1 (int32).
+ *   count     n is exactly the count of mbk_deep_view_launch.
+ *   delta     the Newton step -z_b / (D_b 2^e_b) as a FRACTION OF range_r, two binary64 per pixel (re, im).  With
+ *             range_r = f 2^k, 0.5 <= f < 1 (frexp):
+ *               den = fl(fl(D_b.r^2) + fl(D_b.i^2))
+ *               N   = (fl(fl(z_b.r D_b.r) + fl(z_b.i D_b.i)), fl(fl(z_b.i D_b.r) - fl(z_b.r D_b.i)))           z_b conj(D_b)
+ *               delta = ldexp(-fl(fl(N / den) / f), -(e_b + k)) per component (division correctly rounded, ldexp rounding once
+ *             where the result is subnormal).  If either component is not finite both are stored as +inf: "no seed".
+ *             delta does NOT include the pixel's own offset: the target is pixel offset + delta range_r, and the caller adds
+ *             the offset exactly.
+ *   mrd       0 and 1 run no step: count 0, period 1, delta from the start state (-z_0 as a fraction of range_r).
+ * Windows of a view are bit-identical to the whole view.  Plain deep views only (spans 4 down to 2^-960; a shallow view is a
+ * deep view too): locating from an extended-range view is not implemented.
+ *
+ * One pass (csrc/mbk_deep_nucleus.h).  _launch_nucleus: DEVICE pointers on the caller's stream (d_period: int32 per pixel of the
+ * window, d_delta: 2 binary64 per pixel; nothing is written outside them; no statistics).  _compute_nucleus: synchronous into
+ * HOST buffers on slot 0 (the slot-0 rule applies), stats as for mbk_deep_view_compute.  d_counts / h_counts may be NULL.
+ * MBK_ERR_INVALID, with nothing written: a NULL period or delta, any flag -- MBK_DEEP_BLA with a message of its own: a skipped
+ * run has no |z_n| to compare -- and whatever mbk_deep_view_launch refuses.
+ */
+int mbk_deep_view_launch_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                 uint32_t flags, int32_t *d_counts, int32_t *d_period, double *d_delta, void *hip_stream);
+int mbk_deep_view_compute_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *h_counts, int32_t *h_period, double *h_delta, mbk_stats *stats);
+/* Host twin for the CPU tests, compiled from the functions the kernel uses: no ctx, no device.  The pixel (col, row) of the
+ * full view: its count, period, best, z_b[2], D_b[2], e_b and delta[2].  MBK_ERR_INVALID for what the launch refuses. */
+int mbk_deep_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                          int32_t *count, int32_t *period, double *best, double *z_b, double *D_b, int32_t *e_b, double *delta);
+/* Host only (no ctx, no device), in the wide number system of "Extended-range deep views" -- binary64 mantissa pairs, the
+ * larger |component| in [0.5, 1), with one int32 exponent; a zero is (0, 0, -2^24):
+ *   _newton_host   the Newton step at the orbit's own centre C, -Z_p / D_p = (d_r, d_i) 2^d_e.  Z_p is the wide table's entry,
+ *                  correctly rounded from the fixed-point value, so a tiny Z_p keeps 53 bits: Newton reaches the orbit's
+ *                  precision.  D_k is carried by "step i" of "Distance estimates for extended-range deep views" (what
+ *                  mbk_deep_xdistance_step_host runs) from D_1 = 1.
+ *   _size_host     the size estimate 1 / (b l^2) = (s_r, s_i) 2^s_e of the component whose nucleus C is:
+ *                  l = prod_{k=1}^{p-1} 2 Z_k, b = 1 + sum_{k=1}^{p-1} 1 / l_k over the partial products l_k.  Period 1 gives
+ *                  exactly 1.  A Z_k = 0 below p (p is not the minimal period) gives non-finite mantissas.
+ * MBK_ERR_INVALID: a NULL argument, period 0, an orbit shorter than `period` (it escaped, or its mrd is below the period). */
+int mbk_deep_orbit_newton_host(const mbk_deep_orbit *orbit, uint32_t period, double *d_r, double *d_i, int32_t *d_e);
+int mbk_deep_orbit_size_host(const mbk_deep_orbit *orbit, uint32_t period, double *s_r, double *s_i, int32_t *s_e);
+
+/*
  * Distance estimates for deep views with bilinear approximation.  NOT in the reference; additive (the ABI version stays 5): no
  * existing call changes -- mbk_deep_view_launch_distance / _compute_distance and the MBK_RENDER_DISTANCE_REL source of
  * mbk_deep_view_render_* keep refusing MBK_DEEP_BLA, the capability lives behind the names below.  Below spans of ~1e-15 a
