@@ -280,6 +280,14 @@ SIGNATURES = {
     "mbk_deep_xdistance_step_host": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                C.POINTER(C.c_int32)]),
     "mbk_deep_xdistance_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32]),
+    "mbk_deep_xview_launch_nucleus": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_compute_nucleus": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_nucleus_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "mbk_deep_xview_distance_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
                                                         C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
     "mbk_deep_xview_distance_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,

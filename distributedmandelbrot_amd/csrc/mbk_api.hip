@@ -37,6 +37,7 @@
 #include "mbk_deep_distance.h"
 #include "mbk_deep_distance_bla.h"
 #include "mbk_deep_nucleus.h"
+#include "mbk_deep_wide_nucleus.h"
 #include "mbk_deep_wide_distance_bla.h"
 #include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
@@ -3282,6 +3283,98 @@ int mbk_deep_orbit_size_host(const mbk_deep_orbit *orbit, uint32_t period, doubl
     *s_r = w.r;
     *s_i = w.i;
     *s_e = w.e;
+    return MBK_OK;
+}
+
+// ---- the same from extended-range deep views (mbk_deep_wide_nucleus.h; mbk.h "Locating minibrots in extended-range deep
+// views") ------------------------------------------------------------------------------------------------------------------
+
+// the wide nucleus kernel on device pointers (validated by the caller), on `stream`
+static int launch_deep_wide_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd,
+                                    int32_t *d_counts, int32_t *d_period, double *d_delta, hipStream_t stream)
+{
+    const mbk::WideEntry *d_orbit = nullptr;
+    int rc = wide_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepWideNucleusArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.v.orbit = d_orbit;
+    a.v.z1 = orbit->o.wide[1];
+    a.v.M = orbit->o.length;
+    a.v.exp2 = v->exp2;
+    fill_deep_window(a.v, v, mrd);
+    a.v.counts = d_counts;
+    a.range_r = v->range_r;
+    a.period = d_period;
+    a.delta = d_delta;
+    hipLaunchKernelGGL(mbk::deep_wide_nucleus_kernel, block_grid(a.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// Everything a wide nucleus call can refuse, before anything is allocated, enqueued or written.
+static int wide_nucleus_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                              const void *period, const void *delta)
+{
+    if (!period || !delta) return fail(ctx, MBK_ERR_INVALID, "NULL period or delta pointer");
+    if (flags & MBK_DEEP_XBLA)
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is not implemented for atom periods (a skipped run has no |z_n| to compare)");
+    if (flags & MBK_DEEP_BLA)
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views (and a skipped run has no |z_n| to compare)");
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range atom periods take no flags (no kernel selection, no fp32)");
+    return validate_deep_wide(ctx, orbit, view, mrd, 0u);
+}
+
+int mbk_deep_xview_launch_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *d_counts, int32_t *d_period, double *d_delta, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = wide_nucleus_check(ctx, orbit, view, mrd, flags, d_period, d_delta);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_deep_wide_nucleus(ctx, orbit, view, mrd, d_counts, d_period, d_delta, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_xview_compute_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *h_counts, int32_t *h_period, double *h_delta, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = wide_nucleus_check(ctx, orbit, view, mrd, flags, h_period, h_delta);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    // the device values: 2 px binary64 (delta), then px int32 (the periods)
+    const size_t px = (size_t)view->ncols * view->nrows;
+    return compute_values(
+        ctx, px, mrd, h_counts, h_delta, stats,
+        [&](int32_t *d_counts, double *d_delta, hipStream_t stream) {
+            return launch_deep_wide_nucleus(ctx, orbit, view, mrd, d_counts, reinterpret_cast<int32_t *>(d_delta + 2u * px), d_delta, stream);
+        },
+        true, h_period, 2u);
+}
+
+// host twin (mbk_deep_wide_nucleus.h): no ctx, no device
+int mbk_deep_xview_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                                int32_t *count, int32_t *period, double *best_m, int32_t *best_e, double *z_b, int32_t *t_b, double *D_b,
+                                int32_t *e_b, double *delta)
+{
+    if (!count || !period || !best_m || !best_e || !z_b || !t_b || !D_b || !e_b || !delta)
+        return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
+    if (rc != MBK_OK) return rc;
+    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    mbk::WideNucleusBest b;
+    mbk::wide_nucleus_host(orbit->o.wide, orbit->o.length, deep_dc(col, view->width, view->range_r),
+                           deep_dc(row, view->height, view->range_i), view->range_r, view->exp2, (int64_t)mrd, count, &b, delta);
+    *period = b.arg + 1;
+    *best_m = b.bm;
+    *best_e = b.be;
+    z_b[0] = b.zr;
+    z_b[1] = b.zi;
+    *t_b = b.t;
+    D_b[0] = b.Dr;
+    D_b[1] = b.Di;
+    *e_b = b.e;
     return MBK_OK;
 }
 

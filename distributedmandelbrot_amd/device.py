@@ -546,19 +546,26 @@ def pick_nucleus_seed(view: "DeepView", period, delta) -> Optional[NucleusSeed]:
     float64[height, width, 2]).  The target of a pixel is its offset plus delta * span_r, exactly (Fractions); it is in view
     when it lies within the view's rectangle.  Among the in-view pixels with a finite delta the lowest period wins, among those
     the smallest |delta|, among those the first in image order.  None when no target is in view."""
+    return _pick_seed(view.width, view.height, view.span_r, view.span_i, Fraction(1), period, delta)
+
+
+def _pick_seed(width: int, height: int, range_r: float, range_i: float, unit: Fraction, period, delta) -> Optional[NucleusSeed]:
+    """pick_nucleus_seed's rule on a view of spans range_r unit x range_i unit (unit 1: a DeepView; 2^exp2: a WideDeepView).
+    Every decision is taken in units of `unit` -- the float pre-test on the offsets and delta * range_r as binary64, the exact
+    one on Fractions -- so nothing is ever multiplied by the unit in binary64; only the offsets returned carry it."""
     period = np.asarray(period)
-    delta = np.asarray(delta, np.float64).reshape(view.height, view.width, 2)
-    assert period.shape == (view.height, view.width)
-    dcr, dci = _pixel_offsets(view)
-    span_r, span_i = Fraction(view.span_r), Fraction(view.span_i)
+    delta = np.asarray(delta, np.float64).reshape(height, width, 2)
+    assert period.shape == (height, width)
+    dcr, dci = _pixel_offsets(DeepView(range_r, width, height, range_i))
+    span_r, span_i = Fraction(range_r), Fraction(range_i)
     finite = np.isfinite(delta).all(axis=2)
     with np.errstate(all="ignore"):
-        tr = dcr[None, :] + delta[..., 0] * view.span_r
-        ti = dci[:, None] + delta[..., 1] * view.span_r
+        tr = dcr[None, :] + delta[..., 0] * range_r
+        ti = dci[:, None] + delta[..., 1] * range_r
         # the float test decides all but the targets within 1e-12 (relative) of an edge; those are decided exactly
         near = 1e-12
-        surely_in = finite & (np.abs(tr) <= view.span_r / 2 * (1 - near)) & (np.abs(ti) <= view.span_i / 2 * (1 - near))
-        maybe_in = finite & (np.abs(tr) <= view.span_r / 2 * (1 + near)) & (np.abs(ti) <= view.span_i / 2 * (1 + near))
+        surely_in = finite & (np.abs(tr) <= range_r / 2 * (1 - near)) & (np.abs(ti) <= range_i / 2 * (1 - near))
+        maybe_in = finite & (np.abs(tr) <= range_r / 2 * (1 + near)) & (np.abs(ti) <= range_i / 2 * (1 + near))
         mag2 = delta[..., 0] * delta[..., 0] + delta[..., 1] * delta[..., 1]
 
     def target(r, c):
@@ -580,7 +587,7 @@ def pick_nucleus_seed(view: "DeepView", period, delta) -> Optional[NucleusSeed]:
         exact = lambda rc: Fraction(float(delta[rc[0], rc[1], 0])) ** 2 + Fraction(float(delta[rc[0], rc[1], 1])) ** 2
         r, c = min(close, key=exact)   # (min keeps the first of equals: image order)
         t = target(r, c)
-        return NucleusSeed((int(r), int(c)), int(p), t[0], t[1])
+        return NucleusSeed((int(r), int(c)), int(p), t[0] * unit, t[1] * unit)
     return None
 
 
@@ -731,6 +738,74 @@ def locate_nucleus(orbit: "DeepOrbit", view: "DeepView", mrd: int, *, seeds, pre
     n = refine_nucleus(C0[0] + seed.offset_r, C0[1] + seed.offset_i, seed.period, P, max_rounds)
     off = (_exact_fraction(n.center_r) - C0[0], _exact_fraction(n.center_i) - C0[1])
     inside = abs(off[0]) * 2 <= Fraction(view.span_r) and abs(off[1]) * 2 <= Fraction(view.span_i)
+    return replace(n, seed_pixel=seed.pixel, inside=bool(inside))
+
+
+# -- the same from extended-range views (include/mbk.h, "Locating minibrots in extended-range deep views") ---------------------
+
+def wide_nucleus_host(orbit: "DeepOrbit", view: "WideDeepView", pixels, mrd: int) -> dict:
+    """mbk_deep_xview_nucleus_host on the pixels (row-major indices of the FULL view), on the host, from the functions the kernel
+    uses: a dict of arrays n, period (int32), best_m (float64) and best_e (int64: the normalised |z_b|^2 = best_m 2^best_e),
+    z (float64[N, 2]) and t (int64: z_b = z 2^t), D (float64[N, 2]) and e (int64: d_b = D 2^e), and delta (float64[N, 2])."""
+    lib = L.load()
+    if not isinstance(view, WideDeepView):
+        raise ValueError("wide_nucleus_host takes a WideDeepView (a DeepView: deep_nucleus_host)")
+    cv = _cxview(view)
+    pixels = np.asarray(pixels, np.int64).ravel()
+    N = pixels.size
+    out = {"n": np.empty(N, np.int32), "period": np.empty(N, np.int32), "best_m": np.empty(N, np.float64),
+           "best_e": np.empty(N, np.int64), "z": np.empty((N, 2), np.float64), "t": np.empty(N, np.int64),
+           "D": np.empty((N, 2), np.float64), "e": np.empty(N, np.int64), "delta": np.empty((N, 2), np.float64)}
+    n, p, be, t, e, bm = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+    z, d, delta = (C.c_double * 2)(), (C.c_double * 2)(), (C.c_double * 2)()
+    for j, k in enumerate(pixels):
+        _check(lib, lib.mbk_deep_xview_nucleus_host(orbit._h, C.byref(cv), int(k % view.width), int(k // view.width), int(mrd),
+                                                    C.byref(n), C.byref(p), C.byref(bm), C.byref(be), z, C.byref(t), d, C.byref(e),
+                                                    delta))
+        out["n"][j], out["period"][j], out["best_m"][j], out["best_e"][j] = n.value, p.value, bm.value, be.value
+        out["t"][j], out["e"][j] = t.value, e.value
+        out["z"][j], out["D"][j], out["delta"][j] = tuple(z), tuple(d), tuple(delta)
+    return out
+
+
+def pick_wide_nucleus_seed(view: "WideDeepView", period, delta) -> Optional[NucleusSeed]:
+    """pick_nucleus_seed for a WideDeepView, from the outputs of compute_wide_view_nucleus: the lowest period whose target is in
+    view, then the smallest |delta|, then image order.  The target of a pixel is its offset plus delta * range_r in units of
+    2^exp2; the float pre-test and the exact decision both work in those units, and only the offsets returned -- Fractions in
+    the plane's units -- carry the 2^exp2, which binary64 cannot hold."""
+    if not isinstance(view, WideDeepView):
+        raise ValueError("pick_wide_nucleus_seed takes a WideDeepView (a DeepView: pick_nucleus_seed)")
+    return _pick_seed(view.width, view.height, view.range_r, view.range_i, Fraction(2) ** view.exp2, period, delta)
+
+
+def wide_nucleus_precision_bits(view: "WideDeepView") -> int:
+    """locate_wide_nucleus' default precision: the next multiple of 64 at or above 2 * (-view.min_span_exp2) + 128, at most
+    4096 -- the sizes found in a view are about its span squared."""
+    bits = 2 * max(0, -view.min_span_exp2) + 128
+    return min(4096, -(-bits // 64) * 64)
+
+
+def locate_wide_nucleus(orbit: "DeepOrbit", view: "WideDeepView", mrd: int, *, seeds, precision_bits: Optional[int] = None,
+                        max_rounds: Optional[int] = None) -> Nucleus:
+    """locate_nucleus for a WideDeepView: seeds = (period, delta) as compute_wide_view_nucleus (or wide_nucleus_host over every
+    pixel) gives them, pick_wide_nucleus_seed chooses the seed, refine_nucleus refines it at precision_bits (default
+    wide_nucleus_precision_bits(view)).  max_rounds None: max(32, ceil(precision_bits / 40)) -- a binary64 Newton step gains
+    about 51 bits a round, so a seed good to the view's span needs about precision_bits / 51 rounds.  Host only;
+    MandelbrotDevice.locate_wide_nucleus computes the seeds on the device and calls this.  Raises NucleusError as locate_nucleus
+    does."""
+    if not isinstance(view, WideDeepView):
+        raise ValueError("locate_wide_nucleus takes a WideDeepView (a DeepView: locate_nucleus)")
+    period, delta = seeds
+    seed = pick_wide_nucleus_seed(view, period, delta)
+    if seed is None:
+        raise NucleusError("no seed", f"no pixel's Newton target lies in the view at mrd {mrd}")
+    P = int(precision_bits) if precision_bits is not None else wide_nucleus_precision_bits(view)
+    rounds = int(max_rounds) if max_rounds is not None else max(32, -(-P // 40))
+    C0 = (_exact_fraction(orbit.center[0]), _exact_fraction(orbit.center[1]))
+    n = refine_nucleus(C0[0] + seed.offset_r, C0[1] + seed.offset_i, seed.period, P, rounds)
+    off = (_exact_fraction(n.center_r) - C0[0], _exact_fraction(n.center_i) - C0[1])
+    unit = Fraction(2) ** view.exp2
+    inside = abs(off[0]) * 2 <= Fraction(view.range_r) * unit and abs(off[1]) * 2 <= Fraction(view.range_i) * unit
     return replace(n, seed_pixel=seed.pixel, inside=bool(inside))
 
 
@@ -1262,7 +1337,7 @@ class MandelbrotDevice:
     @staticmethod
     def _nucleus_view(view) -> None:
         if not isinstance(view, DeepView):
-            raise ValueError("atom periods and Newton seeds are implemented for a DeepView only (not from below 2^-960)")
+            raise ValueError("the deep_view_nucleus calls take a DeepView (a WideDeepView: the wide_view_nucleus calls)")
 
     def compute_deep_view_nucleus(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, window=None):
         """Atom periods and Newton seeds of a deep view: per pixel the period p = 1 + the step at which |z| was smallest, and
@@ -1298,6 +1373,50 @@ class MandelbrotDevice:
             period, delta, _, _ = self.compute_deep_view_nucleus(orbit, view, mrd)
             seeds = (period, delta)
         return locate_nucleus(orbit, view, mrd, seeds=seeds, precision_bits=precision_bits, max_rounds=max_rounds)
+
+    # -- the same from extended-range views (include/mbk.h, "Locating minibrots in extended-range deep views"): calls of their
+    # own; the plain calls above keep refusing a WideDeepView --
+    @staticmethod
+    def _wide_nucleus_view(view) -> None:
+        if not isinstance(view, WideDeepView):
+            raise ValueError("the wide_view_nucleus calls take a WideDeepView (a DeepView: the deep_view_nucleus calls)")
+
+    def compute_wide_view_nucleus(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, window=None):
+        """compute_deep_view_nucleus for a WideDeepView: the candidates are ordered by a wide |z|^2 (near a deep minibrot |z| is
+        1e-400: its square is 0 in binary64), the kept state is wide, and delta is the Newton step as a fraction of the view's
+        real span range_r 2^exp2 (+inf in both components: no seed); the pixel's own offset is not included.  The counts are
+        those of compute_deep_view.
+        Returns (period int32[nrows,ncols], delta float64[nrows,ncols,2], counts int32[nrows,ncols], TileStats)."""
+        self._wide_nucleus_view(view)
+        cv = _cxview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        period = np.empty(shape, np.int32)
+        delta = np.empty(shape + (2,), np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_compute_nucleus(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
+                                                             period.ctypes.data, delta.ctypes.data, C.byref(st)))
+        return period, delta, counts, _stats(st)
+
+    def launch_wide_view_nucleus(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, d_period: int, d_delta: int,
+                                 d_counts: int = 0, stream: int = 0, window=None) -> None:
+        """Asynchronous form on DEVICE pointers (int32, 2 x float64 and int32 per pixel of the window) on ``stream`` (0 = HIP's
+        null stream)."""
+        self._wide_nucleus_view(view)
+        cv = _cxview(view, window)
+        self._check(self._lib.mbk_deep_xview_launch_nucleus(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
+                                                            d_period or None, d_delta or None, stream or None))
+
+    def locate_wide_nucleus(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, precision_bits: Optional[int] = None,
+                            seeds=None, max_rounds: Optional[int] = None) -> Nucleus:
+        """locate_nucleus from a WideDeepView: atom periods and Newton seeds on the device (or `seeds` = (period, delta)), the
+        seed pick_wide_nucleus_seed chooses, refine_nucleus on the host.  With Nucleus.view and Nucleus.orbit the chain view ->
+        nucleus -> view goes on below 2^-960."""
+        self._wide_nucleus_view(view)
+        if seeds is None:
+            period, delta, _, _ = self.compute_wide_view_nucleus(orbit, view, mrd)
+            seeds = (period, delta)
+        return locate_wide_nucleus(orbit, view, mrd, seeds=seeds, precision_bits=precision_bits, max_rounds=max_rounds)
 
     # -- distance estimates for deep views with bilinear approximation (include/mbk.h, the section of that name): calls of
     # their own; compute_deep_view_distance and render_deep_view(source="distance_rel") keep refusing bla --

@@ -674,7 +674,7 @@ double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double 
  *             the offset exactly.
  *   mrd       0 and 1 run no step: count 0, period 1, delta from the start state (-z_0 as a fraction of range_r).
  * Windows of a view are bit-identical to the whole view.  Plain deep views only (spans 4 down to 2^-960; a shallow view is a
- * deep view too): locating from an extended-range view is not implemented.
+ * deep view too): an extended-range view has calls of its own ("Locating minibrots in extended-range deep views", below).
  *
  * One pass (csrc/mbk_deep_nucleus.h).  _launch_nucleus: DEVICE pointers on the caller's stream (d_period: int32 per pixel of the
  * window, d_delta: 2 binary64 per pixel; nothing is written outside them; no statistics).  _compute_nucleus: synchronous into
@@ -834,6 +834,64 @@ int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xvi
 int mbk_deep_xdistance_step_host(double z_r, double z_i, int32_t t, double *D_r, double *D_i, int32_t *e);
 /* "output" above. */
 double mbk_deep_xdistance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t exp2, int32_t count);
+
+/*
+ * Locating minibrots in extended-range deep views.  NOT in the reference; additive (the ABI version stays 5): no existing call
+ * changes -- mbk_deep_view_launch_nucleus / _compute_nucleus and mbk_deep_nucleus_host keep taking plain deep views only, the
+ * capability lives behind the names below.  The minibrot found in a view of span s has a size of about s^2, so the view that
+ * frames a nucleus located from a span of 1e-200 is 1e-401 wide: without these calls the chain view -> nucleus -> view stops
+ * after one link, at the views whose centres have 400 to 1200 digits.  The index convention, the host refinement
+ * (mbk_deep_orbit_newton_host / _size_host) and the meaning of period and delta are those of "Locating minibrots in deep
+ * views".
+ *
+ * Contract (tests/deep_wide_nucleus_model.py restates it in numpy; tests/test_deep_wide_nucleus.py holds the host twin to it
+ * and it to the truth, tests/test_gpu_deep_wide_nucleus.py holds the GPU to the host twin).  Everything of "Extended-range deep
+ * views" stands: the wide table, dcm 2^exp2, sh, norm, EZ, steps (a) .. (g), rebasing with m == M included, the count.  So do
+ * the state (zp, D, e), its start and "step i" of "Distance estimates for extended-range deep views": D = norm((1, 0), 0) =
+ * (0.5, 0, 1), the derivative step before the z step.  There is no run-on.  Added per pixel, binary64 mantissas, int32
+ * exponents, every operation rounded on its own, no contraction:
+ *   nmag      the magnitude that orders the candidates is WIDE: near a deep minibrot |z| is 1e-400, |z|^2 as a binary64 (step
+ *             (e)'s mag) is 0 and cannot order anything.  From the mg and t step (e) leaves, |z|^2 = mg 2^(2t), mg not
+ *             normalised:  nmag(mg, t) = (bm, be) with s = the frexp exponent of mg, bm = ldexp(mg, -s) in [0.5, 1) (exact) and
+ *             be = 2t + s;  mg == 0 gives (0, -2^30).  (bm', be') < (bm, be) iff be' < be, or be' == be and bm' < bm.
+ *   start     best = nmag of z_0's (mg, t), arg = 0, kept state z_b = (zv_r, zv_i, t) exactly as step (e) left it (nominal
+ *             exponent, NOT renormalised), (D_b, e_b) = (0.5, 0, 1).
+ *   step i    (i = 1 .. mrd - 1) the derivative step, steps (a) .. (e), mag.  mag >= 4: n = i and the pixel ends; the escaping
+ *             z is never a candidate.  Otherwise, if nmag(mg, t) < best (strict: the first minimum wins): best, arg = i,
+ *             z_b = (zv, t) of this step and (D_b, e_b) = (D, e) are replaced.  Then (g), unchanged.
+ *   period    arg + 1 (int32).
+ *   count     n is exactly the count of mbk_deep_xview_launch.
+ *   delta     the Newton step -z_b / (D_b 2^e_b) as a FRACTION OF THE VIEW'S REAL SPAN range_r 2^exp2, two binary64 per pixel
+ *             (re, im).  With range_r = f 2^k, 0.5 <= f < 1 (frexp), on the mantissas:
+ *               den = fl(fl(D_b.r^2) + fl(D_b.i^2))
+ *               N   = (fl(fl(z_b.r D_b.r) + fl(z_b.i D_b.i)), fl(fl(z_b.i D_b.r) - fl(z_b.r D_b.i)))           z_b conj(D_b)
+ *               delta = ldexp(-fl(fl(N / den) / f), t_b - e_b - k - exp2) per component (division correctly rounded, ldexp
+ *             rounding once where the result is subnormal; underflow to 0 is a valid value).  If either component is not finite
+ *             both are stored as +inf: "no seed".  delta does NOT include the pixel's own offset: the target is pixel offset +
+ *             delta range_r, in units of 2^exp2, and the caller adds the offset exactly.
+ *   equals plain  the kept states of this contract and of the plain one differ by exact powers of two only, so wherever a plain
+ *             view can name the spans and no value of the plain run is subnormal, period, count and delta are the plain
+ *             contract's, bit for bit.
+ *   mrd       0 and 1 run no step: count 0, period 1, delta from the start state.
+ * Windows of a view are bit-identical to the whole view.
+ *
+ * One pass (csrc/mbk_deep_wide_nucleus.h).  The two calls follow the rules of mbk_deep_view_launch_nucleus / _compute_nucleus:
+ * device pointers on the caller's stream (d_period: int32 per pixel of the window, d_delta: 2 binary64 per pixel; nothing is
+ * written outside them; no statistics) / host buffers synchronously on slot 0 with the statistics of mbk_deep_xview_compute;
+ * counts may be NULL.  MBK_ERR_INVALID, with nothing written: a NULL period or delta, any flag -- MBK_DEEP_XBLA and
+ * MBK_DEEP_BLA each with a message of its own: a skipped run has no |z_n| to compare -- and whatever mbk_deep_xview_launch
+ * refuses.
+ */
+int mbk_deep_xview_launch_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *d_counts, int32_t *d_period, double *d_delta, void *hip_stream);
+int mbk_deep_xview_compute_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *h_counts, int32_t *h_period, double *h_delta, mbk_stats *stats);
+/* Host twin for the CPU tests, compiled from the functions the kernel uses: no ctx, no device.  The pixel (col, row) of the
+ * full view: its count, period, best = (best_m, best_e), z_b[2] with t_b, D_b[2] with e_b and delta[2].  MBK_ERR_INVALID for
+ * what the launch refuses. */
+int mbk_deep_xview_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                                int32_t *count, int32_t *period, double *best_m, int32_t *best_e, double *z_b, int32_t *t_b, double *D_b,
+                                int32_t *e_b, double *delta);
 
 /*
  * Distance estimates for extended-range deep views with bilinear approximation.  NOT in the reference; additive (the ABI
