@@ -1724,6 +1724,19 @@ static double deep_dc(uint32_t k, uint32_t n, double range)
     return dc;
 }
 
+// The common front of the one-pixel host twins, after the view's own checks: the pixel must lie in the view; its dc.
+struct PixelDc {
+    int rc;
+    double r, i;
+};
+
+template <typename V>
+static PixelDc pixel_dc(const V *view, uint32_t col, uint32_t row)
+{
+    if (col >= view->width || row >= view->height) return PixelDc{fail(nullptr, MBK_ERR_INVALID, "pixel outside the view"), 0.0, 0.0};
+    return PixelDc{MBK_OK, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i)};
+}
+
 template <typename V>
 static bool deep_ranges_within(const V *v, double lo)
 {
@@ -2883,11 +2896,8 @@ int mbk_deep_bla_info(const mbk_deep_orbit *orbit, const mbk_deep_view *view, ui
 {
     int rc = validate_deep(nullptr, orbit, view, 0u, MBK_DEEP_BLA);
     if (rc != MBK_OK) return rc;
-    const uint32_t n = mbk::bla_levels(orbit->o.length);
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < n; ++l) total += (orbit->o.length - 1u) >> l;
-    if (levels) *levels = n;
-    if (entries) *entries = total;
+    if (levels) *levels = mbk::bla_levels(orbit->o.length);
+    if (entries) *entries = mbk::bla_entries(orbit->o.length);
     return MBK_OK;
 }
 
@@ -2920,8 +2930,9 @@ int mbk_deep_bla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_view *vi
     int rc = bla_host_table(orbit, view, &t);
     if (rc != MBK_OK) return rc;
     if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    mbk::bla_count_host(orbit->o.table, orbit->o.length, t, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i),
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    mbk::bla_count_host(orbit->o.table, orbit->o.length, t, dc.r, dc.i,
                         (int64_t)mrd, count, mag, steps_executed);
     return MBK_OK;
 }
@@ -2968,6 +2979,18 @@ static int validate_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const m
             if (v->exp2 > 0 || v->exp2 < -8192) return fail(ctx, MBK_ERR_INVALID, "extended-range deep view exp2 must lie in [-8192, 0]");
             return MBK_OK;
         });
+}
+
+// what the wide kernels share: the wide orbit, exp2, the view's geometry and window, mrd (every other field zero)
+static void fill_deep_wide_args(mbk::DeepWideArgs &a, const mbk::WideEntry *d_orbit, const mbk_deep_orbit *orbit, const mbk_deep_xview *v,
+                                uint32_t mrd)
+{
+    std::memset(&a, 0, sizeof(a));
+    a.orbit = d_orbit;
+    a.z1 = orbit->o.wide[1];
+    a.M = orbit->o.length;
+    a.exp2 = v->exp2;
+    fill_deep_window(a, v, mrd);
 }
 
 // dcmax of "Extended-range deep views with bilinear approximation": of the FULL view, normalised
@@ -3026,11 +3049,7 @@ static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk
     mbk::DeepWideBlaArgs b;
     std::memset(&b, 0, sizeof(b));
     mbk::DeepWideArgs &a = b.v;
-    a.orbit = table ? c->d_wide : d_orbit;
-    a.z1 = orbit->o.wide[1];
-    a.M = orbit->o.length;
-    a.exp2 = v->exp2;
-    fill_deep_window(a, v, mrd);
+    fill_deep_wide_args(a, table ? c->d_wide : d_orbit, orbit, v, mrd);
     fill_outputs(a, mrd, d_counts, d_bytes, d_smooth);
     if (table) {
         b.ke = c->d_xke;
@@ -3063,11 +3082,8 @@ int mbk_deep_xbla_info(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, 
 {
     int rc = validate_deep_wide(nullptr, orbit, view, 0u, MBK_DEEP_XBLA);
     if (rc != MBK_OK) return rc;
-    const uint32_t n = mbk::bla_levels(orbit->o.length);
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < n; ++l) total += (orbit->o.length - 1u) >> l;
-    if (levels) *levels = n;
-    if (entries) *entries = total;
+    if (levels) *levels = mbk::bla_levels(orbit->o.length);
+    if (entries) *entries = mbk::bla_entries(orbit->o.length);
     return MBK_OK;
 }
 
@@ -3103,9 +3119,9 @@ int mbk_deep_xbla_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *
     int rc = xbla_host_table(orbit, view, &t);
     if (rc != MBK_OK) return rc;
     if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    mbk::wide_bla_count_host(orbit->o.wide, orbit->o.length, t, deep_dc(col, view->width, view->range_r),
-                             deep_dc(row, view->height, view->range_i), view->exp2, (int64_t)mrd, count, mag, steps_executed);
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    mbk::wide_bla_count_host(orbit->o.wide, orbit->o.length, t, dc.r, dc.i, view->exp2, (int64_t)mrd, count, mag, steps_executed);
     return MBK_OK;
 }
 
@@ -3116,8 +3132,9 @@ int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview 
     if (!count || !mag) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
     int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
     if (rc != MBK_OK) return rc;
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    mbk::wide_count_host(orbit->o.wide, orbit->o.length, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i),
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    mbk::wide_count_host(orbit->o.wide, orbit->o.length, dc.r, dc.i,
                          view->exp2, (int64_t)mrd, count, mag);
     return MBK_OK;
 }
@@ -3242,10 +3259,10 @@ int mbk_deep_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view
     if (!count || !period || !best || !z_b || !D_b || !e_b || !delta) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
     int rc = validate_deep(nullptr, orbit, view, mrd, 0u);
     if (rc != MBK_OK) return rc;
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
     mbk::NucleusBest b;
-    mbk::deep_nucleus_host(orbit->o.table, orbit->o.length, deep_dc(col, view->width, view->range_r),
-                           deep_dc(row, view->height, view->range_i), view->range_r, (int64_t)mrd, count, &b, delta);
+    mbk::deep_nucleus_host(orbit->o.table, orbit->o.length, dc.r, dc.i, view->range_r, (int64_t)mrd, count, &b, delta);
     *period = b.arg + 1;
     *best = b.best;
     z_b[0] = b.zr;
@@ -3298,11 +3315,7 @@ static int launch_deep_wide_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, c
     if (rc != MBK_OK) return rc;
     mbk::DeepWideNucleusArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.v.orbit = d_orbit;
-    a.v.z1 = orbit->o.wide[1];
-    a.v.M = orbit->o.length;
-    a.v.exp2 = v->exp2;
-    fill_deep_window(a.v, v, mrd);
+    fill_deep_wide_args(a.v, d_orbit, orbit, v, mrd);
     a.v.counts = d_counts;
     a.range_r = v->range_r;
     a.period = d_period;
@@ -3362,10 +3375,10 @@ int mbk_deep_xview_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_xvie
         return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
     int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
     if (rc != MBK_OK) return rc;
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
     mbk::WideNucleusBest b;
-    mbk::wide_nucleus_host(orbit->o.wide, orbit->o.length, deep_dc(col, view->width, view->range_r),
-                           deep_dc(row, view->height, view->range_i), view->range_r, view->exp2, (int64_t)mrd, count, &b, delta);
+    mbk::wide_nucleus_host(orbit->o.wide, orbit->o.length, dc.r, dc.i, view->range_r, view->exp2, (int64_t)mrd, count, &b, delta);
     *period = b.arg + 1;
     *best_m = b.bm;
     *best_e = b.be;
@@ -3416,11 +3429,7 @@ static int launch_deep_wide_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, 
     if (rc != MBK_OK) return rc;
     mbk::DeepWideDistanceArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.v.orbit = d_orbit;
-    a.v.z1 = orbit->o.wide[1];
-    a.v.M = orbit->o.length;
-    a.v.exp2 = v->exp2;
-    fill_deep_window(a.v, v, mrd);
+    fill_deep_wide_args(a.v, d_orbit, orbit, v, mrd);
     a.v.counts = d_counts;
     a.range_r = v->range_r;
     a.rel = d_rel;
@@ -3440,11 +3449,7 @@ static int launch_deep_wide_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *or
     if (rc != MBK_OK) return rc;
     mbk::DeepWideDistanceBlaArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.b.v.orbit = c->d_wide;
-    a.b.v.z1 = orbit->o.wide[1];
-    a.b.v.M = orbit->o.length;
-    a.b.v.exp2 = v->exp2;
-    fill_deep_window(a.b.v, v, mrd);
+    fill_deep_wide_args(a.b.v, c->d_wide, orbit, v, mrd);
     a.b.v.counts = d_counts;
     a.b.ke = c->d_xke;
     a.b.ab = c->d_xab;
@@ -3500,8 +3505,9 @@ int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xvi
     if (!count || !extra || !mag || !D_r || !D_i || !e || !rel) return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
     int rc = validate_deep_wide(nullptr, orbit, view, mrd, 0u);
     if (rc != MBK_OK) return rc;
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    mbk::wide_distance_host(orbit->o.wide, orbit->o.length, deep_dc(col, view->width, view->range_r), deep_dc(row, view->height, view->range_i),
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    mbk::wide_distance_host(orbit->o.wide, orbit->o.length, dc.r, dc.i,
                             view->exp2, (int64_t)mrd, count, extra, mag, D_r, D_i, e);
     const double r2 = *D_r * *D_r, i2 = *D_i * *D_i;
     *rel = mbk::wide_distance_value(*mag, r2 + i2, *e, view->range_r, view->exp2, *count);
@@ -4444,9 +4450,9 @@ int mbk_deep_distance_bla_host(const mbk_deep_orbit *orbit, const mbk_deep_view 
     int rc = bla_host_table(orbit, view, &t);
     if (rc != MBK_OK) return rc;
     if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    mbk::deep_distance_bla_host(orbit->o.table, orbit->o.length, t, deep_dc(col, view->width, view->range_r),
-                                deep_dc(row, view->height, view->range_i), (int64_t)mrd, count, extra, mag, D_r, D_i, e, steps_executed);
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    mbk::deep_distance_bla_host(orbit->o.table, orbit->o.length, t, dc.r, dc.i, (int64_t)mrd, count, extra, mag, D_r, D_i, e, steps_executed);
     const double r2 = *D_r * *D_r, i2 = *D_i * *D_i;
     *rel = mbk::deep_distance_value(*mag, r2 + i2, *e, view->range_r, *count);
     return MBK_OK;
@@ -4551,9 +4557,9 @@ int mbk_deep_xview_distance_xbla_host(const mbk_deep_orbit *orbit, const mbk_dee
     int rc = xbla_host_table(orbit, view, &t);
     if (rc != MBK_OK) return rc;
     if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
-    if (col >= view->width || row >= view->height) return fail(nullptr, MBK_ERR_INVALID, "pixel outside the view");
-    mbk::wide_distance_bla_host(orbit->o.wide, orbit->o.length, t, deep_dc(col, view->width, view->range_r),
-                                deep_dc(row, view->height, view->range_i), view->exp2, (int64_t)mrd, count, extra, mag, D_r, D_i, e,
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    mbk::wide_distance_bla_host(orbit->o.wide, orbit->o.length, t, dc.r, dc.i, view->exp2, (int64_t)mrd, count, extra, mag, D_r, D_i, e,
                                 steps_executed);
     const double r2 = *D_r * *D_r, i2 = *D_i * *D_i;
     *rel = mbk::wide_distance_value(*mag, r2 + i2, *e, view->range_r, view->exp2, *count);

@@ -12,11 +12,15 @@
 // is empty).  No wave-uniform value is taken from a lane.  Before the first rebase every lane reads the same entry (one
 // broadcast line); after that each lane has its own m.  The entry the NEXT step needs, Z_{m+1}, is loaded one step ahead
 // (`pre`), so its L1/L2 latency hides behind a step's ~20 dependent fp64 operations; entry 1 (the state right after a
-// rebase) comes with the arguments.
+// rebase) comes with the arguments.  The pixel set-up and the cursor that holds m and the entries are mbk_deep_cursor.h's, which
+// the deep kernels use; the start state, the plain step and the rebase test below are shared with the other binary64 kernels
+// and their host twins.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "mbk_deep_cursor.h"
 
 namespace mbk {
 
@@ -36,64 +40,71 @@ struct DeepArgs {
     double *smooth;           // may be null
 };
 
+// the plain step with c2 = 2 Z_m
+__host__ __device__ __forceinline__ void deep_plain_step(double c2r, double c2i, double dcr, double dci, double &dzr, double &dzi)
+{
+    const double ar = c2r + dzr, ai = c2i + dzi;
+    const double xr = ar * dzr, yr = ai * dzi;
+    const double xi = ar * dzi, yi = ai * dzr;
+    dzr = (xr - yr) + dcr;
+    dzi = (xi + yi) + dci;
+}
+
+// The start state, shared by the kernels and the host twins: z_0 = c = fl(Z_1 + dc) and dz = dc at m = 1 -- or, for an orbit of
+// length 1 (no Z_2), rebased at once: dz = z_0 at m = 0.  Returns m.
+__host__ __device__ __forceinline__ uint32_t deep_start(double z1r, double z1i, uint32_t M, double dcr, double dci, double &dzr, double &dzi,
+                                                        double &zr, double &zi)
+{
+    zr = z1r + dcr;
+    zi = z1i + dci;
+    if (M == 1u) {
+        dzr = zr;
+        dzi = zi;
+        return 0u;
+    }
+    dzr = dcr;
+    dzi = dci;
+    return 1u;
+}
+
+// The rebase comparison, |z|^2 < |dz|^2 with mg = |z|^2 (wide_rebase of mbk_deep_wide.h is its wide form).  A pixel also rebases
+// where the table ends: m == M, the cursor's last().
+__host__ __device__ __forceinline__ bool deep_rebase(double mg, double dzr, double dzi)
+{
+    const double dm = dzr * dzr + dzi * dzi;
+    return mg < dm;
+}
+
 __global__ __launch_bounds__(64) void deep_view_kernel(DeepArgs p)
 {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    // dc = fl(fl(k - (W-1)/2) * s): the subtraction is exact (|k| < 2^32, a half-integer at most)
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M;
-    double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double c2r = p.z1.z, c2i = p.z1.w;   // 2 Z_m
-    double4 nz;                          // entry m + 1
-    if (M == 1u) {
-        // no Z_2: the start state is rebased at once (z = Z_1 + dc, m = 0)
-        dzr = p.z1.x + dcr;
-        dzi = p.z1.y + dci;
-        m = 0u;
-        c2r = 0.0;
-        c2i = 0.0;
-        nz = p.z1;
-    } else {
-        nz = p.orbit[2];
-    }
-    double4 pre = p.orbit[m + 2u < M ? m + 2u : M];   // entry m + 2 (clamped: unused once m + 1 == M)
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
+    double dzr, dzi, zr, zi;
+    OrbitCursor<double4> c(p.orbit, p.z1, p.M, deep_start(p.z1.x, p.z1.y, p.M, dcr, dci, dzr, dzi, zr, zi));
     int32_t count = 0;
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
-        const double ar = c2r + dzr, ai = c2i + dzi;
-        const double xr = ar * dzr, yr = ai * dzi;
-        const double xi = ar * dzi, yi = ai * dzr;
-        dzr = (xr - yr) + dcr;
-        dzi = (xi + yi) + dci;
-        ++m;
-        const double zr = nz.x + dzr, zi = nz.y + dzi;
+        deep_plain_step(c.cur.z, c.cur.w, dcr, dci, dzr, dzi);
+        c.step();
+        zr = c.nz.x + dzr;
+        zi = c.nz.y + dzi;
         const double mg = zr * zr + zi * zi;
         if (mg >= 4.0) {
             count = i;
             mag = mg;
             break;
         }
-        const double dm = dzr * dzr + dzi * dzi;
-        if (mg < dm || m == M) {   // rebase: the pixel's own z becomes its offset from Z_0 = 0
+        if (deep_rebase(mg, dzr, dzi) || c.last()) {
             dzr = zr;
             dzi = zi;
-            m = 0u;
-            c2r = 0.0;
-            c2i = 0.0;
-            nz = p.z1;
+            c.rebased();
         } else {
-            c2r = nz.z;
-            c2i = nz.w;
-            nz = pre;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
+        c.prefetch();
     }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
     if (p.smooth) p.smooth[o] = smooth_value(count, mag);

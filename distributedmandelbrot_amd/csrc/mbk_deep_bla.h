@@ -4,14 +4,15 @@
 // While a pixel's offset dz is tiny against the reference orbit, dz -> 2 Z_m dz + dz^2 + dc is linear in (dz, dc) to working
 // precision, and 2^l such steps collapse into dz -> A dz + B dc.  (A, B) and the radius r below which the map may be used
 // are merged pairwise over the orbit into levels l = 0 .. ; entry j of level l covers the 2^l steps that start at
-// m = 1 + j 2^l.  The kernel is deep_view_kernel (mbk_deep.h) with one more branch per step: the lane takes the highest
-// level its (dz, m, i) allows, or the plain step, and the z / bailout / rebase tail is common to both.
+// m = 1 + j 2^l.  The kernel has deep_view_kernel's shape (mbk_deep.h) with one more branch per step: the lane takes the highest
+// level its (dz, m, i) allows, or the plain step, and the z / bailout / rebase tail is common to both.  The orbit entries and
+// level 0's rc come from a BlaCursor (mbk_deep_cursor.h).
 //
 // Memory: the rc values (r / sqrt 2, compared with max(|dz.r|, |dz.i|)) live in their own array, so probing the levels
 // costs 8-byte loads only; (A, B) is one 32-byte entry, loaded once the level is chosen.  Level 0's rc rides one step ahead
-// of its use, as the orbit entries do (`qn`, `pre`), so a step that cannot skip pays no load latency for having asked.
-// After the first rebase the lanes of a wave hold different m: skip and plain step are the two sides of a divergent branch,
-// and no wave-uniform value is taken from a lane.
+// of its use, as the orbit entries do (the cursor's `rn`, `pre`), so a step that cannot skip pays no load latency for having
+// asked.  After the first rebase the lanes of a wave hold different m: skip and plain step are the two sides of a divergent
+// branch, and no wave-uniform value is taken from a lane.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,6 +44,14 @@ inline uint32_t bla_levels(uint32_t M)
     if (M >= 2u)
         while (levels < kBlaMaxLevels && ((M - 1u) >> levels) >= 1u) ++levels;
     return levels;
+}
+
+// the entries of all levels together: level l holds (M - 1) >> l
+inline uint64_t bla_entries(uint32_t M)
+{
+    uint64_t total = 0;
+    for (uint32_t l = 0, n = bla_levels(M); l < n; ++l) total += (M - 1u) >> l;
+    return total;
 }
 
 inline double bla_norm(double r, double i)
@@ -136,16 +145,6 @@ __host__ __device__ inline void bla_apply(double Ar, double Ai, double Br, doubl
     dzi = (xi + yi) + (ui + vi);
 }
 
-// the plain step of "Deep-zoom views" with c2 = 2 Z_m
-__host__ __device__ inline void deep_plain_step(double c2r, double c2i, double dcr, double dci, double &dzr, double &dzi)
-{
-    const double ar = c2r + dzr, ai = c2i + dzi;
-    const double xr = ar * dzr, yr = ai * dzi;
-    const double xi = ar * dzi, yi = ai * dzr;
-    dzr = (xr - yr) + dcr;
-    dzi = (xi + yi) + dci;
-}
-
 // max(|dz.r|, |dz.i|) < rc, false if either is a NaN
 __host__ __device__ inline bool bla_within(double dzr, double dzi, double rc, double *ad)
 {
@@ -165,63 +164,42 @@ struct DeepBlaArgs {
 __global__ __launch_bounds__(64) void deep_bla_kernel(DeepBlaArgs q)
 {
     const DeepArgs &p = q.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M, n0 = M - 1u;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
     double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double c2r = p.z1.z, c2i = p.z1.w;                 // 2 Z_m
-    double4 nz = p.orbit[2];                           // entry m + 1 (M >= 2)
-    double4 pre = p.orbit[3u < M ? 3u : M];            // entry m + 2 (clamped: unused once m + 1 == M)
-    double q0 = q.rc[0];                               // level 0's rc at m (0 at m == 0: the plain step)
-    double qn = q.rc[1u < n0 ? 1u : n0 - 1u];          // ... at m + 1 (clamped: unused once m + 1 == M)
+    BlaCursor<double4, double> c(p.orbit, p.z1, p.M, q.rc, 0.0);   // the radius is level 0's rc; 0 at m == 0
     int32_t count = 0;
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
         double ad;
-        if (bla_within(dzr, dzi, q0, &ad)) {
-            const uint32_t l = bla_climb(q.rc, q.off, q.levels, M, m, i, p.mrd, ad);
-            const double4 e = q.ab[q.off[l] + ((m - 1u) >> l)];
+        if (bla_within(dzr, dzi, c.r0, &ad)) {
+            const uint32_t l = bla_climb(q.rc, q.off, q.levels, c.M, c.m, i, p.mrd, ad);
+            const double4 e = q.ab[q.off[l] + ((c.m - 1u) >> l)];
             bla_apply(e.x, e.y, e.z, e.w, dcr, dci, dzr, dzi);
-            m += 1u << l;                              // <= M: entry j of level l ends at 1 + (j + 1) 2^l <= 1 + (M - 1)
+            c.skip(l);
             i += (int32_t)((1u << l) - 1u);            // < mrd: the level was taken with i + 2^l <= mrd
-            nz = p.orbit[m];
-            pre = p.orbit[m + 1u < M ? m + 1u : M];
-            qn = q.rc[(m < M ? m : n0) - 1u];          // level 0 at the new m (unused at m == M: the rebase)
         } else {
-            deep_plain_step(c2r, c2i, dcr, dci, dzr, dzi);
-            ++m;
+            deep_plain_step(c.cur.z, c.cur.w, dcr, dci, dzr, dzi);
+            c.step();
         }
-        const double zr = nz.x + dzr, zi = nz.y + dzi;
+        const double zr = c.nz.x + dzr, zi = c.nz.y + dzi;
         const double mg = zr * zr + zi * zi;
         if (mg >= 4.0) {
             count = i;
             mag = mg;
             break;
         }
-        const double dm = dzr * dzr + dzi * dzi;
-        if (mg < dm || m == M) {   // rebase: the pixel's own z becomes its offset from Z_0 = 0
+        if (deep_rebase(mg, dzr, dzi) || c.last()) {
             dzr = zr;
             dzi = zi;
-            m = 0u;
-            c2r = 0.0;
-            c2i = 0.0;
-            nz = p.z1;
-            q0 = 0.0;
+            c.rebased();
         } else {
-            c2r = nz.z;
-            c2i = nz.w;
-            nz = pre;
-            q0 = qn;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
-        qn = q.rc[m < n0 ? m : n0 - 1u];
+        c.prefetch();
     }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
     if (p.smooth) p.smooth[o] = smooth_value(count, mag);
@@ -233,13 +211,8 @@ inline void bla_count_host(const std::vector<double> &orbit, uint32_t M, const B
                            int32_t *count, double *mag, uint64_t *steps)
 {
     const double *Z = orbit.data();
-    double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    if (M == 1u) {
-        dzr = Z[4] + dcr;
-        dzi = Z[5] + dci;
-        m = 0u;
-    }
+    double dzr, dzi, zr, zi;
+    uint32_t m = deep_start(Z[4], Z[5], M, dcr, dci, dzr, dzi, zr, zi);
     *count = 0;
     *mag = 0.0;
     *steps = 0;
@@ -256,15 +229,15 @@ inline void bla_count_host(const std::vector<double> &orbit, uint32_t M, const B
             deep_plain_step(Z[4 * (size_t)m + 2], Z[4 * (size_t)m + 3], dcr, dci, dzr, dzi);
             ++m;
         }
-        const double zr = Z[4 * (size_t)m] + dzr, zi = Z[4 * (size_t)m + 1] + dzi;
+        zr = Z[4 * (size_t)m] + dzr;
+        zi = Z[4 * (size_t)m + 1] + dzi;
         const double mg = zr * zr + zi * zi;
         if (mg >= 4.0) {
             *count = (int32_t)i;
             *mag = mg;
             return;
         }
-        const double dm = dzr * dzr + dzi * dzi;
-        if (mg < dm || m == M) {
+        if (deep_rebase(mg, dzr, dzi) || m == M) {
             dzr = zr;
             dzi = zi;
             m = 0u;

@@ -16,9 +16,10 @@
 // D, e, one and zp do not change at a rebase, so they stay out of the rebase branch: the phi copies of the parent loop
 // (profiles/deep/README.md) are not added to.  e is a VGPR (lanes differ).
 //
-// The main loop is deep_view_kernel's (one lane per pixel, 8x8 block per single-wave workgroup, image order, the orbit entry
-// prefetched a step ahead).  A lane that escapes leaves it; when the wave is through, the escaped lanes run on together in a
-// second, short loop that reads its entries by index.
+// The main loop has deep_view_kernel's shape (one lane per pixel, 8x8 block per single-wave workgroup, image order, the orbit
+// entries from the cursor of mbk_deep_cursor.h).  A lane that escapes leaves it; when the wave is through, the escaped lanes run
+// on together in a second, short loop that reads its entries by index (deep_run_on, which mbk_deep_distance_bla.h and the host
+// twins call too).
 #pragma once
 
 #include <cmath>
@@ -74,99 +75,79 @@ __host__ __device__ __forceinline__ void deep_derivative_step(double zpr, double
     }
 }
 
-__global__ __launch_bounds__(64) void deep_distance_kernel(DeepDistanceArgs q)
+// the table's entry m as the kernels hold it, from the device's table or from the host's flat one
+__host__ __device__ __forceinline__ double4 deep_entry(const double4 *Z, uint32_t m) { return Z[m]; }
+__host__ __device__ __forceinline__ double4 deep_entry(const double *Z, uint32_t m)
 {
-    const DeepArgs &p = q.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M;
-    double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double c2r = p.z1.z, c2i = p.z1.w;   // 2 Z_m
-    double4 nz;                          // entry m + 1
-    double zpr = p.z1.x + dcr, zpi = p.z1.y + dci;   // z_0 = c = fl(Z_1 + dc)
-    if (M == 1u) {
+    return make_double4(Z[4 * (size_t)m], Z[4 * (size_t)m + 1], Z[4 * (size_t)m + 2], Z[4 * (size_t)m + 3]);
+}
+
+// The run-on of a pixel that escaped with |z|^2 = mag at orbit index m, shared by the kernels and the host twins: the escaping
+// step's rebase test (the count loop stopped before it), then plain steps that read their entries by index until mag reaches
+// the large radius.  m < M at the top of every step, so entries m and m + 1 exist (entry 0 is (0, 0, 0, 0)).  Returns the
+// number of steps taken.
+template <typename Table>
+__host__ __device__ __forceinline__ int32_t deep_run_on(const Table *Z, uint32_t M, uint32_t m, double dcr, double dci, double &dzr, double &dzi,
+                                                        double &zpr, double &zpi, double &mag, double &Dr, double &Di, int32_t &e, double &one)
+{
+    if (deep_rebase(mag, dzr, dzi) || m == M) {
         dzr = zpr;
         dzi = zpi;
         m = 0u;
-        c2r = 0.0;
-        c2i = 0.0;
-        nz = p.z1;
-    } else {
-        nz = p.orbit[2];
     }
-    double4 pre = p.orbit[m + 2u < M ? m + 2u : M];
+    int32_t extra = 0;
+    for (; extra < kDistanceRunOn && !(mag >= kDistanceRadius2); ++extra) {
+        deep_derivative_step(zpr, zpi, Dr, Di, e, one);
+        const double4 zm = deep_entry(Z, m), zn = deep_entry(Z, m + 1u);
+        deep_plain_step(zm.z, zm.w, dcr, dci, dzr, dzi);
+        ++m;
+        zpr = zn.x + dzr;
+        zpi = zn.y + dzi;
+        mag = zpr * zpr + zpi * zpi;
+        if (deep_rebase(mag, dzr, dzi) || m == M) {
+            dzr = zpr;
+            dzi = zpi;
+            m = 0u;
+        }
+    }
+    return extra;
+}
+
+__global__ __launch_bounds__(64) void deep_distance_kernel(DeepDistanceArgs q)
+{
+    const DeepArgs &p = q.v;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
+    double dzr, dzi, zpr, zpi;           // zp starts as z_0 = c
+    OrbitCursor<double4> c(p.orbit, p.z1, p.M, deep_start(p.z1.x, p.z1.y, p.M, dcr, dci, dzr, dzi, zpr, zpi));
     double Dr = 1.0, Di = 0.0, one = 1.0;
     int32_t e = 0;
     int32_t count = 0;
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
         deep_derivative_step(zpr, zpi, Dr, Di, e, one);
-        const double ar = c2r + dzr, ai = c2i + dzi;
-        const double xr = ar * dzr, yr = ai * dzi;
-        const double xi = ar * dzi, yi = ai * dzr;
-        dzr = (xr - yr) + dcr;
-        dzi = (xi + yi) + dci;
-        ++m;
-        zpr = nz.x + dzr;
-        zpi = nz.y + dzi;
+        deep_plain_step(c.cur.z, c.cur.w, dcr, dci, dzr, dzi);
+        c.step();
+        zpr = c.nz.x + dzr;
+        zpi = c.nz.y + dzi;
         const double mg = zpr * zpr + zpi * zpi;
         if (mg >= 4.0) {
             count = i;
             mag = mg;
             break;
         }
-        const double dm = dzr * dzr + dzi * dzi;
-        if (mg < dm || m == M) {
+        if (deep_rebase(mg, dzr, dzi) || c.last()) {
             dzr = zpr;
             dzi = zpi;
-            m = 0u;
-            c2r = 0.0;
-            c2i = 0.0;
-            nz = p.z1;
+            c.rebased();
         } else {
-            c2r = nz.z;
-            c2i = nz.w;
-            nz = pre;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
+        c.prefetch();
     }
-    if (count > 0) {
-        // the escaping step's rebase test (the count loop stopped before it), then the run-on: m < M at the top of every step,
-        // so entries m and m + 1 exist (entry 0 is (0, 0, 0, 0))
-        {
-            const double dm = dzr * dzr + dzi * dzi;
-            if (mag < dm || m == M) {
-                dzr = zpr;
-                dzi = zpi;
-                m = 0u;
-            }
-        }
-        for (int extra = 0; extra < kDistanceRunOn && !(mag >= kDistanceRadius2); ++extra) {
-            deep_derivative_step(zpr, zpi, Dr, Di, e, one);
-            const double4 zm = p.orbit[m], zn = p.orbit[m + 1u];
-            const double ar = zm.z + dzr, ai = zm.w + dzi;
-            const double xr = ar * dzr, yr = ai * dzi;
-            const double xi = ar * dzi, yi = ai * dzr;
-            dzr = (xr - yr) + dcr;
-            dzi = (xi + yi) + dci;
-            ++m;
-            zpr = zn.x + dzr;
-            zpi = zn.y + dzi;
-            mag = zpr * zpr + zpi * zpi;
-            const double dm = dzr * dzr + dzi * dzi;
-            if (mag < dm || m == M) {
-                dzr = zpr;
-                dzi = zpi;
-                m = 0u;
-            }
-        }
-    }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    if (count > 0) deep_run_on(p.orbit, c.M, c.m, dcr, dci, dzr, dzi, zpr, zpi, mag, Dr, Di, e, one);
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     const double r2 = Dr * Dr, i2 = Di * Di;
     q.rel[o] = deep_distance_value(mag, r2 + i2, e, q.range_r, count);

@@ -1,7 +1,7 @@
 // mbk_deep_distance_bla.h -- distance estimates for deep views that take bilinear-approximation skips (include/mbk.h,
-// "Distance estimates for deep views with bilinear approximation"): the loop of deep_bla_kernel (mbk_deep_bla.h) with the
-// derivative of deep_distance_kernel (mbk_deep_distance.h) riding in it, the derivative across a skip, and the one-pixel host
-// twin the CPU tests read.
+// "Distance estimates for deep views with bilinear approximation"): deep_bla_kernel's steps (mbk_deep_bla.h) on the same cursor
+// (mbk_deep_cursor.h) with the derivative of mbk_deep_distance.h riding in them, the derivative across a skip, and the one-pixel
+// host twin the CPU tests read.
 //
 // No second table: d is the derivative of the pixel's full z = Z_m + dz with respect to c, and the reference orbit does not
 // depend on dc, so across a skip dz -> A dz + B dc the derivative follows d -> A d + B with the coefficients the count table
@@ -17,7 +17,7 @@
 //
 // The kernel: the skip side does the level search, loads (A, B) once, runs the derivative skip, then the dz map; the plain side
 // is deep_derivative_step and deep_plain_step; the z / bailout / rebase tail is common, and zp is the z it forms (at the new m
-// after a skip).  D, e, one and zp stay out of the rebase branch.  The run-on is deep_distance_kernel's second loop: plain
+// after a skip).  D, e, one and zp stay out of the rebase branch.  The run-on is deep_run_on (mbk_deep_distance.h): plain
 // steps only.  After the first rebase the lanes of a wave hold different m: no wave-uniform value is taken from a lane.
 #pragma once
 
@@ -77,20 +77,11 @@ __global__ __launch_bounds__(64) void deep_distance_bla_kernel(DeepDistanceBlaAr
 {
     const DeepBlaArgs &t = q.b;
     const DeepArgs &p = t.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M, n0 = M - 1u;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
     double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double c2r = p.z1.z, c2i = p.z1.w;                 // 2 Z_m
-    double4 nz = p.orbit[2];                           // entry m + 1 (M >= 2)
-    double4 pre = p.orbit[3u < M ? 3u : M];            // entry m + 2 (clamped: unused once m + 1 == M)
-    double q0 = t.rc[0];                               // level 0's rc at m (0 at m == 0: the plain step)
-    double qn = t.rc[1u < n0 ? 1u : n0 - 1u];          // ... at m + 1 (clamped: unused once m + 1 == M)
+    BlaCursor<double4, double> c(p.orbit, p.z1, p.M, t.rc, 0.0);   // the radius is level 0's rc; 0 at m == 0
     double zpr = p.z1.x + dcr, zpi = p.z1.y + dci;     // z_0 = c = fl(Z_1 + dc)
     double Dr = 1.0, Di = 0.0, one = 1.0;
     int32_t e = 0;
@@ -98,76 +89,38 @@ __global__ __launch_bounds__(64) void deep_distance_bla_kernel(DeepDistanceBlaAr
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
         double ad;
-        if (bla_within(dzr, dzi, q0, &ad)) {
-            const uint32_t l = bla_climb(t.rc, t.off, t.levels, M, m, i, p.mrd, ad);
-            const double4 c = t.ab[t.off[l] + ((m - 1u) >> l)];
-            deep_derivative_skip(c.x, c.y, c.z, c.w, Dr, Di, e);
+        if (bla_within(dzr, dzi, c.r0, &ad)) {
+            const uint32_t l = bla_climb(t.rc, t.off, t.levels, c.M, c.m, i, p.mrd, ad);
+            const double4 ab = t.ab[t.off[l] + ((c.m - 1u) >> l)];
+            deep_derivative_skip(ab.x, ab.y, ab.z, ab.w, Dr, Di, e);
             one = ldexp(1.0, -e);
-            bla_apply(c.x, c.y, c.z, c.w, dcr, dci, dzr, dzi);
-            m += 1u << l;                              // <= M: entry j of level l ends at 1 + (j + 1) 2^l <= 1 + (M - 1)
+            bla_apply(ab.x, ab.y, ab.z, ab.w, dcr, dci, dzr, dzi);
+            c.skip(l);
             i += (int32_t)((1u << l) - 1u);            // < mrd: the level was taken with i + 2^l <= mrd
-            nz = p.orbit[m];
-            pre = p.orbit[m + 1u < M ? m + 1u : M];
-            qn = t.rc[(m < M ? m : n0) - 1u];          // level 0 at the new m (unused at m == M: the rebase)
         } else {
             deep_derivative_step(zpr, zpi, Dr, Di, e, one);
-            deep_plain_step(c2r, c2i, dcr, dci, dzr, dzi);
-            ++m;
+            deep_plain_step(c.cur.z, c.cur.w, dcr, dci, dzr, dzi);
+            c.step();
         }
-        zpr = nz.x + dzr;
-        zpi = nz.y + dzi;
+        zpr = c.nz.x + dzr;
+        zpi = c.nz.y + dzi;
         const double mg = zpr * zpr + zpi * zpi;
         if (mg >= 4.0) {
             count = i;
             mag = mg;
             break;
         }
-        const double dm = dzr * dzr + dzi * dzi;
-        if (mg < dm || m == M) {   // rebase: the pixel's own z becomes its offset from Z_0 = 0
+        if (deep_rebase(mg, dzr, dzi) || c.last()) {
             dzr = zpr;
             dzi = zpi;
-            m = 0u;
-            c2r = 0.0;
-            c2i = 0.0;
-            nz = p.z1;
-            q0 = 0.0;
+            c.rebased();
         } else {
-            c2r = nz.z;
-            c2i = nz.w;
-            nz = pre;
-            q0 = qn;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
-        qn = t.rc[m < n0 ? m : n0 - 1u];
+        c.prefetch();
     }
-    if (count > 0) {
-        // the escaping step's rebase test (the count loop stopped before it), then the run-on, plain steps only: m < M at the top
-        // of every step, so entries m and m + 1 exist (entry 0 is (0, 0, 0, 0))
-        {
-            const double dm = dzr * dzr + dzi * dzi;
-            if (mag < dm || m == M) {
-                dzr = zpr;
-                dzi = zpi;
-                m = 0u;
-            }
-        }
-        for (int extra = 0; extra < kDistanceRunOn && !(mag >= kDistanceRadius2); ++extra) {
-            deep_derivative_step(zpr, zpi, Dr, Di, e, one);
-            const double4 zm = p.orbit[m], zn = p.orbit[m + 1u];
-            deep_plain_step(zm.z, zm.w, dcr, dci, dzr, dzi);
-            ++m;
-            zpr = zn.x + dzr;
-            zpi = zn.y + dzi;
-            mag = zpr * zpr + zpi * zpi;
-            const double dm = dzr * dzr + dzi * dzi;
-            if (mag < dm || m == M) {
-                dzr = zpr;
-                dzi = zpi;
-                m = 0u;
-            }
-        }
-    }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    if (count > 0) deep_run_on(p.orbit, c.M, c.m, dcr, dci, dzr, dzi, zpr, zpi, mag, Dr, Di, e, one);
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     const double r2 = Dr * Dr, i2 = Di * Di;
     q.rel[o] = deep_distance_value(mag, r2 + i2, e, q.range_r, count);
@@ -180,14 +133,8 @@ inline void deep_distance_bla_host(const std::vector<double> &orbit, uint32_t M,
                                    int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e_out, uint64_t *steps)
 {
     const double *Z = orbit.data();
-    double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double zpr = Z[4] + dcr, zpi = Z[5] + dci;
-    if (M == 1u) {
-        dzr = zpr;
-        dzi = zpi;
-        m = 0u;
-    }
+    double dzr, dzi, zpr, zpi;
+    uint32_t m = deep_start(Z[4], Z[5], M, dcr, dci, dzr, dzi, zpr, zpi);
     double Dr = 1.0, Di = 0.0, one = 1.0;
     int32_t e = 0;
     *count = 0;
@@ -213,34 +160,18 @@ inline void deep_distance_bla_host(const std::vector<double> &orbit, uint32_t M,
         zpr = Z[4 * (size_t)m] + dzr;
         zpi = Z[4 * (size_t)m + 1] + dzi;
         const double mg = zpr * zpr + zpi * zpi;
-        const double dm = dzr * dzr + dzi * dzi;
-        const bool rebase = mg < dm || m == M;
-        if (rebase) {   // (for an escaping step this is the rebase the run-on starts with)
-            dzr = zpr;
-            dzi = zpi;
-            m = 0u;
-        }
         if (mg >= 4.0) {
             *count = (int32_t)i;
             *mag = mg;
             break;
         }
-    }
-    if (*count > 0)
-        for (; *extra < kDistanceRunOn && !(*mag >= kDistanceRadius2); ++*extra) {
-            deep_derivative_step(zpr, zpi, Dr, Di, e, one);
-            deep_plain_step(Z[4 * (size_t)m + 2], Z[4 * (size_t)m + 3], dcr, dci, dzr, dzi);
-            ++m;
-            zpr = Z[4 * (size_t)m] + dzr;
-            zpi = Z[4 * (size_t)m + 1] + dzi;
-            *mag = zpr * zpr + zpi * zpi;
-            const double dm = dzr * dzr + dzi * dzi;
-            if (*mag < dm || m == M) {
-                dzr = zpr;
-                dzi = zpi;
-                m = 0u;
-            }
+        if (deep_rebase(mg, dzr, dzi) || m == M) {
+            dzr = zpr;
+            dzi = zpi;
+            m = 0u;
         }
+    }
+    if (*count > 0) *extra = deep_run_on(Z, M, m, dcr, dci, dzr, dzi, zpr, zpi, *mag, Dr, Di, e, one);
     *D_r = Dr;
     *D_i = Di;
     *e_out = e;

@@ -1,8 +1,8 @@
 // mbk_deep_nucleus.h -- atom periods and Newton seeds of deep views (include/mbk.h, "Locating minibrots in deep views"): the
-// main loop of deep_distance_kernel (mbk_deep_distance.h) without the run-on.  Beside the count each pixel keeps the step at
-// which its |z| was smallest and the state there, and stores that step as its atom period and one Newton step from the pixel
-// towards the root of z_p(c) = 0.  The host side -- the Newton step and the size estimate at an orbit's own centre, in the wide
-// arithmetic of mbk_deep_wide_distance.h -- is below the kernel.
+// steps of deep_distance_kernel (mbk_deep_distance.h) on the cursor of mbk_deep_cursor.h, with no run-on.  Beside the count each
+// pixel keeps the step at which its |z| was smallest and the state there, and stores that step as its atom period and one Newton
+// step from the pixel towards the root of z_p(c) = 0.  The host side -- the Newton step and the size estimate at an orbit's own
+// centre, in the wide arithmetic of mbk_deep_wide_distance.h -- is below the kernel.
 //
 // Per step, in deep_distance_kernel's order: deep_derivative_step (d' = 2 zp d + 1 on D 2^e with its 2^256 rescale), the z step,
 // mg = |z|^2, the bailout test, then
@@ -14,8 +14,8 @@
 // deep_distance_value does: the quotient is formed on the mantissas and one ldexp applies -(e_b + k).  The translation unit is
 // compiled -ffp-contract=off: every operation of deep_nucleus_delta rounds on its own.
 //
-// One lane per pixel, one 8x8 block per single-wave workgroup, image order, the orbit entry prefetched a step ahead; no
-// wave-uniform value is taken from a lane.  deep_nucleus_host runs the same functions on the host.
+// One lane per pixel, one 8x8 block per single-wave workgroup, image order (deep_pixel), the orbit entry prefetched a step ahead
+// (OrbitCursor); no wave-uniform value is taken from a lane.  deep_nucleus_host runs the same functions on the host.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -87,61 +87,40 @@ struct DeepNucleusArgs {
 __global__ __launch_bounds__(64) void deep_nucleus_kernel(DeepNucleusArgs q)
 {
     const DeepArgs &p = q.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M;
-    double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double c2r = p.z1.z, c2i = p.z1.w;   // 2 Z_m
-    double4 nz;                          // entry m + 1
-    double zpr = p.z1.x + dcr, zpi = p.z1.y + dci;   // z_0 = c = fl(Z_1 + dc)
-    if (M == 1u) {
-        dzr = zpr;
-        dzi = zpi;
-        m = 0u;
-        c2r = 0.0;
-        c2i = 0.0;
-        nz = p.z1;
-    } else {
-        nz = p.orbit[2];
-    }
-    double4 pre = p.orbit[m + 2u < M ? m + 2u : M];
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
+    double dzr, dzi, zpr, zpi;           // zp starts as z_0 = c
+    OrbitCursor<double4> c(p.orbit, p.z1, p.M, deep_start(p.z1.x, p.z1.y, p.M, dcr, dci, dzr, dzi, zpr, zpi));
     double Dr = 1.0, Di = 0.0, one = 1.0;
     int32_t e = 0;
     int32_t count = 0;
     NucleusBest b = {zpr * zpr + zpi * zpi, 0, zpr, zpi, 1.0, 0.0, 0};
     for (int32_t i = 1; i < p.mrd; ++i) {
         deep_derivative_step(zpr, zpi, Dr, Di, e, one);
-        deep_plain_step(c2r, c2i, dcr, dci, dzr, dzi);
-        ++m;
-        zpr = nz.x + dzr;
-        zpi = nz.y + dzi;
+        deep_plain_step(c.cur.z, c.cur.w, dcr, dci, dzr, dzi);
+        c.step();
+        zpr = c.nz.x + dzr;
+        zpi = c.nz.y + dzi;
         const double mg = zpr * zpr + zpi * zpi;
         if (mg >= 4.0) {
             count = i;
             break;
         }
         deep_nucleus_keep(b, mg, i, zpr, zpi, Dr, Di, e);
-        const double dm = dzr * dzr + dzi * dzi;
-        if (mg < dm || m == M) {
+        // one value, not two short-circuited tests: the compiler then selects over the rebase instead of branching around it,
+        // which is 7 % faster with the kept state live (profiles/deep_shared/README.md)
+        const bool last = c.last();
+        if (deep_rebase(mg, dzr, dzi) | last) {
             dzr = zpr;
             dzi = zpi;
-            m = 0u;
-            c2r = 0.0;
-            c2i = 0.0;
-            nz = p.z1;
+            c.rebased();
         } else {
-            c2r = nz.z;
-            c2i = nz.w;
-            nz = pre;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
+        c.prefetch();
     }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     q.period[o] = b.arg + 1;
     double xr, xi;
@@ -155,14 +134,8 @@ inline void deep_nucleus_host(const std::vector<double> &orbit, uint32_t M, doub
                               int32_t *count, NucleusBest *best, double *delta)
 {
     const double *Z = orbit.data();
-    double dzr = dcr, dzi = dci;
-    uint32_t m = 1u;
-    double zpr = Z[4] + dcr, zpi = Z[5] + dci;
-    if (M == 1u) {
-        dzr = zpr;
-        dzi = zpi;
-        m = 0u;
-    }
+    double dzr, dzi, zpr, zpi;
+    uint32_t m = deep_start(Z[4], Z[5], M, dcr, dci, dzr, dzi, zpr, zpi);
     double Dr = 1.0, Di = 0.0, one = 1.0;
     int32_t e = 0;
     *count = 0;
@@ -181,8 +154,7 @@ inline void deep_nucleus_host(const std::vector<double> &orbit, uint32_t M, doub
             break;
         }
         deep_nucleus_keep(b, mg, (int32_t)i, zpr, zpi, Dr, Di, e);
-        const double da = dzr * dzr, dbb = dzi * dzi;
-        if (mg < da + dbb || m == M) {
+        if (deep_rebase(mg, dzr, dzi) || m == M) {
             dzr = zpr;
             dzi = zpi;
             m = 0u;

@@ -11,7 +11,8 @@
 //
 // The kernel has the shape of deep_view_kernel: one lane per pixel, one 8x8 block per single-wave workgroup in image order,
 // an ordinary divergent loop bounded by mrd (a lane that escapes leaves EXEC), no wave-uniform value taken from a lane, the
-// entry the next step needs loaded one step ahead.  wide_count_host runs the same step functions on the host.
+// entry the next step needs loaded one step ahead -- the pixel and the cursor of mbk_deep_cursor.h.  wide_count_host runs the
+// same start and step functions on the host.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 
 #include <cmath>
 
+#include "mbk_deep_cursor.h"
 #include "mbk_deep_orbit.h"
 
 namespace mbk {
@@ -112,62 +114,48 @@ struct DeepWideArgs {
     double *smooth;           // may be null
 };
 
+// The start state, shared by the kernels and the host twins: dz = norm(dc) and z_0 = c = Z_1 + dc (with its mg) at m = 1 -- or,
+// for an orbit of length 1 (no Z_2), rebased at once: dz = norm(z_0) at m = 0.  Returns m.
+__host__ __device__ __forceinline__ uint32_t wide_start(const WideEntry &z1, uint32_t M, double dcr, double dci, int32_t exp2, double &wr,
+                                                        double &wi, int32_t &q, double &zr, double &zi, int32_t &t, double &mg)
+{
+    wide_norm(dcr, dci, exp2, wr, wi, q);
+    wide_z(z1.xr, z1.xi, z1.xe, wr, wi, q, zr, zi, t, mg);
+    if (M != 1u) return 1u;
+    wide_norm(zr, zi, t, wr, wi, q);
+    return 0u;
+}
+
 __global__ __launch_bounds__(64) void deep_wide_kernel(DeepWideArgs p)
 {
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
     const int32_t exp2 = p.exp2;
-    const WideEntry zero = {0.0, 0.0, kWideZeroExp, {0, 0, 0}};
-    double wr, wi;
-    int32_t q;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    WideEntry cur = p.z1;                // entry m
-    WideEntry nz;                        // entry m + 1
-    if (M == 1u) {
-        // no Z_2: the start state is rebased at once (z = Z_1 + dc, m = 0)
-        double zr, zi, mg;
-        int32_t t;
-        wide_z(cur.xr, cur.xi, cur.xe, wr, wi, q, zr, zi, t, mg);
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-        cur = zero;
-        nz = p.z1;
-    } else {
-        nz = p.orbit[2];
-    }
-    WideEntry pre = p.orbit[m + 2u < M ? m + 2u : M];   // entry m + 2 (clamped: unused once m + 1 == M)
+    double wr, wi, zr, zi, mg;
+    int32_t q, t;
+    OrbitCursor<WideEntry> c(p.orbit, p.z1, p.M, wide_start(p.z1, p.M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg));
     int32_t count = 0;
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
-        wide_step(cur.xr, cur.xi, cur.xe, dcr, dci, exp2, wr, wi, q);
-        ++m;
-        double zr, zi, mg;
-        int32_t t;
-        wide_z(nz.xr, nz.xi, nz.xe, wr, wi, q, zr, zi, t, mg);
+        wide_step(c.cur.xr, c.cur.xi, c.cur.xe, dcr, dci, exp2, wr, wi, q);
+        c.step();
+        wide_z(c.nz.xr, c.nz.xi, c.nz.xe, wr, wi, q, zr, zi, t, mg);
         const double mgs = wide_mag(mg, t);
         if (mgs >= 4.0) {
             count = i;
             mag = mgs;
             break;
         }
-        if (wide_rebase(mg, wr, wi, q, t) || m == M) {   // rebase: the pixel's own z becomes its offset from Z_0 = 0
+        if (wide_rebase(mg, wr, wi, q, t) || c.last()) {
             wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-            cur = zero;
-            nz = p.z1;
+            c.rebased();
         } else {
-            cur = nz;
-            nz = pre;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
+        c.prefetch();
     }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
     if (p.smooth) p.smooth[o] = smooth_value(count, mag);
@@ -180,13 +168,7 @@ inline void wide_count_host(const std::vector<WideEntry> &orbit, uint32_t M, dou
     const WideEntry *Z = orbit.data();
     double wr, wi, zr, zi, mg;
     int32_t q, t;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    if (M == 1u) {
-        wide_z(Z[1].xr, Z[1].xi, Z[1].xe, wr, wi, q, zr, zi, t, mg);
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-    }
+    uint32_t m = wide_start(Z[1], M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg);
     *count = 0;
     *mag = 0.0;
     for (int64_t i = 1; i < mrd; ++i) {

@@ -9,9 +9,10 @@
 // components below r / sqrt 2).
 //
 // Memory: the ke values live in their own array, so probing the levels costs 4-byte loads only; (A, B) is one 48-byte
-// entry, loaded once the level is chosen.  Level 0's ke rides one step ahead of its use, as the orbit entries do (`kn`,
-// `pre`).  The kernel is deep_wide_kernel with one more branch per step: skip and plain step are the two sides of a divergent
-// branch, the z / bailout / rebase tail is common to both, and no wave-uniform value is taken from a lane.
+// entry, loaded once the level is chosen.  Level 0's ke rides one step ahead of its use, as the orbit entries do (`rn`,
+// `pre` of the BlaCursor, mbk_deep_cursor.h).  The kernel has deep_wide_kernel's shape with one more branch per step: skip and
+// plain step are the two sides of a divergent branch, the z / bailout / rebase tail is common to both, and no wave-uniform value
+// is taken from a lane.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -203,65 +204,46 @@ struct DeepWideBlaArgs {
 __global__ __launch_bounds__(64) void deep_wide_bla_kernel(DeepWideBlaArgs a)
 {
     const DeepWideArgs &p = a.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M, n0 = M - 1u;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
     const int32_t exp2 = p.exp2;
-    const WideEntry zero = {0.0, 0.0, kWideZeroExp, {0, 0, 0}};
     double wr, wi;
     int32_t q;
     wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    WideEntry cur = p.z1;                                // entry m
-    WideEntry nz = p.orbit[2];                           // entry m + 1 (M >= 2)
-    WideEntry pre = p.orbit[3u < M ? 3u : M];            // entry m + 2 (clamped: unused once m + 1 == M)
-    int32_t k0 = a.ke[0];                                // level 0's ke at m (kWideZeroExp at m == 0: the plain step)
-    int32_t kn = a.ke[1u < n0 ? 1u : n0 - 1u];           // ... at m + 1 (clamped: unused once m + 1 == M)
+    BlaCursor<WideEntry, int32_t> c(p.orbit, p.z1, p.M, a.ke, kWideZeroExp);   // the radius is level 0's ke; kWideZeroExp at m == 0
     int32_t count = 0;
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
-        if (wide_bla_within(q, k0)) {
+        if (wide_bla_within(q, c.r0)) {
             uint32_t l;
-            const uint32_t at = wide_bla_climb(a.ke, a.off, a.levels, M, m, i, p.mrd, q, &l);
+            const uint32_t at = wide_bla_climb(a.ke, a.off, a.levels, c.M, c.m, i, p.mrd, q, &l);
             const WideBlaEntry e = a.ab[at];
             wide_bla_apply(e.ar, e.ai, e.ae, e.br, e.bi, e.be, dcr, dci, exp2, wr, wi, q);
-            m += 1u << l;                              // <= M: entry j of level l ends at 1 + (j + 1) 2^l <= 1 + (M - 1)
+            c.skip(l);
             i += (int32_t)((1u << l) - 1u);            // < mrd: the level was taken with i + 2^l <= mrd
-            nz = p.orbit[m];
-            pre = p.orbit[m + 1u < M ? m + 1u : M];
-            kn = a.ke[(m < M ? m : n0) - 1u];          // level 0 at the new m (unused at m == M: the rebase)
         } else {
-            wide_step(cur.xr, cur.xi, cur.xe, dcr, dci, exp2, wr, wi, q);
-            ++m;
+            wide_step(c.cur.xr, c.cur.xi, c.cur.xe, dcr, dci, exp2, wr, wi, q);
+            c.step();
         }
         double zr, zi, mg;
         int32_t t;
-        wide_z(nz.xr, nz.xi, nz.xe, wr, wi, q, zr, zi, t, mg);
+        wide_z(c.nz.xr, c.nz.xi, c.nz.xe, wr, wi, q, zr, zi, t, mg);
         const double mgs = wide_mag(mg, t);
         if (mgs >= 4.0) {
             count = i;
             mag = mgs;
             break;
         }
-        if (wide_rebase(mg, wr, wi, q, t) || m == M) {   // rebase: the pixel's own z becomes its offset from Z_0 = 0
+        if (wide_rebase(mg, wr, wi, q, t) || c.last()) {
             wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-            cur = zero;
-            nz = p.z1;
-            k0 = kWideZeroExp;
+            c.rebased();
         } else {
-            cur = nz;
-            nz = pre;
-            k0 = kn;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
-        kn = a.ke[m < n0 ? m : n0 - 1u];
+        c.prefetch();
     }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
     if (p.smooth) p.smooth[o] = smooth_value(count, mag);
@@ -275,13 +257,7 @@ inline void wide_bla_count_host(const std::vector<WideEntry> &orbit, uint32_t M,
     const WideEntry *Z = orbit.data();
     double wr, wi, zr, zi, mg;
     int32_t q, t;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    if (M == 1u) {
-        wide_z(Z[1].xr, Z[1].xi, Z[1].xe, wr, wi, q, zr, zi, t, mg);
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-    }
+    uint32_t m = wide_start(Z[1], M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg);
     *count = 0;
     *mag = 0.0;
     *steps = 0;

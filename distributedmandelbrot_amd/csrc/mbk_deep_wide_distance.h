@@ -11,11 +11,12 @@
 // there and the product is lost -- and for the same reason e may decrease.  Wherever the plain contract of
 // mbk_deep_distance.h meets no subnormal, D 2^e is its number (scaling by a power of two is exact) and rel its bits.
 //
-// D, e and zp do not change at a rebase, so they stay out of the rebase branch, as in mbk_deep_distance.h.  The main loop is
-// deep_wide_kernel's (one lane per pixel, one 8x8 block per single-wave workgroup in image order, an ordinary divergent loop
-// bounded by mrd, the entry the next step needs loaded a step ahead, no wave-uniform value taken from a lane).  A lane that
+// D, e and zp do not change at a rebase, so they stay out of the rebase branch, as in mbk_deep_distance.h.  The main loop has
+// deep_wide_kernel's shape (one lane per pixel, one 8x8 block per single-wave workgroup in image order, an ordinary divergent
+// loop bounded by mrd, the entries from the cursor of mbk_deep_cursor.h, no wave-uniform value taken from a lane).  A lane that
 // escapes leaves it; when the wave is through, the escaped lanes run on together in a second, short loop that reads its
-// entries by index.  wide_distance_host runs the same step and value functions on the host.
+// entries by index (wide_run_on, which mbk_deep_wide_distance_bla.h calls too).  wide_distance_host runs the same start, step,
+// run-on and value functions on the host.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,84 +66,69 @@ struct DeepWideDistanceArgs {
     double *rel;
 };
 
+// The run-on of a pixel that escaped with |z|^2 = mag at orbit index m, shared by the kernels and the host twins: the escaping
+// step's rebase test (the count loop stopped before it), then plain steps that read their entries by index until mag reaches
+// the large radius.  m < M at the top of every step, so entries m and m + 1 exist (entry 0 is (0, 0, EZ)).  Returns the number
+// of steps taken.
+__host__ __device__ __forceinline__ int32_t wide_run_on(const WideEntry *Z, uint32_t M, uint32_t m, double dcr, double dci, int32_t exp2, double &wr,
+                                                        double &wi, int32_t &q, double &zr, double &zi, int32_t &t, double &mg, double &mag,
+                                                        double &Dr, double &Di, int32_t &e)
+{
+    if (wide_rebase(mg, wr, wi, q, t) || m == M) {
+        wide_norm(zr, zi, t, wr, wi, q);
+        m = 0u;
+    }
+    int32_t extra = 0;
+    for (; extra < kDistanceRunOn && !(mag >= kDistanceRadius2); ++extra) {
+        wide_dstep(zr, zi, t, Dr, Di, e);
+        const WideEntry zm = Z[m], zn = Z[m + 1u];
+        wide_step(zm.xr, zm.xi, zm.xe, dcr, dci, exp2, wr, wi, q);
+        ++m;
+        wide_z(zn.xr, zn.xi, zn.xe, wr, wi, q, zr, zi, t, mg);
+        mag = wide_mag(mg, t);
+        if (wide_rebase(mg, wr, wi, q, t) || m == M) {
+            wide_norm(zr, zi, t, wr, wi, q);
+            m = 0u;
+        }
+    }
+    return extra;
+}
+
 __global__ __launch_bounds__(64) void deep_wide_distance_kernel(DeepWideDistanceArgs a)
 {
     const DeepWideArgs &p = a.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
     const int32_t exp2 = p.exp2;
-    const WideEntry zero = {0.0, 0.0, kWideZeroExp, {0, 0, 0}};
-    double wr, wi;
-    int32_t q;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    WideEntry cur = p.z1;                // entry m
-    WideEntry nz;                        // entry m + 1
-    double zr, zi, mg;                   // zp = (zr, zi) 2^t and its |.|^2 on that exponent
-    int32_t t;
-    wide_z(cur.xr, cur.xi, cur.xe, wr, wi, q, zr, zi, t, mg);   // z_0 = c = Z_1 + dc
-    if (M == 1u) {
-        // no Z_2: the start state is rebased at once (m = 0); z_0 is the same value
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-        cur = zero;
-        nz = p.z1;
-    } else {
-        nz = p.orbit[2];
-    }
-    WideEntry pre = p.orbit[m + 2u < M ? m + 2u : M];   // entry m + 2 (clamped: unused once m + 1 == M)
+    double wr, wi, zr, zi, mg;           // zp = (zr, zi) 2^t and its |.|^2 on that exponent; it starts as z_0 = c
+    int32_t q, t;
+    OrbitCursor<WideEntry> c(p.orbit, p.z1, p.M, wide_start(p.z1, p.M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg));
     double Dr = 0.5, Di = 0.0;           // norm((1, 0), 0)
     int32_t e = 1;
     int32_t count = 0;
     double mag = 0.0;
     for (int32_t i = 1; i < p.mrd; ++i) {
         wide_dstep(zr, zi, t, Dr, Di, e);
-        wide_step(cur.xr, cur.xi, cur.xe, dcr, dci, exp2, wr, wi, q);
-        ++m;
-        wide_z(nz.xr, nz.xi, nz.xe, wr, wi, q, zr, zi, t, mg);
+        wide_step(c.cur.xr, c.cur.xi, c.cur.xe, dcr, dci, exp2, wr, wi, q);
+        c.step();
+        wide_z(c.nz.xr, c.nz.xi, c.nz.xe, wr, wi, q, zr, zi, t, mg);
         const double mgs = wide_mag(mg, t);
         if (mgs >= 4.0) {
             count = i;
             mag = mgs;
             break;
         }
-        if (wide_rebase(mg, wr, wi, q, t) || m == M) {
+        if (wide_rebase(mg, wr, wi, q, t) || c.last()) {
             wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-            cur = zero;
-            nz = p.z1;
+            c.rebased();
         } else {
-            cur = nz;
-            nz = pre;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
+        c.prefetch();
     }
-    if (count > 0) {
-        // the escaping step's rebase test (the count loop stopped before it), then the run-on: m < M at the top of every step,
-        // so entries m and m + 1 exist (entry 0 is (0, 0, EZ))
-        if (wide_rebase(mg, wr, wi, q, t) || m == M) {
-            wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-        }
-        for (int extra = 0; extra < kDistanceRunOn && !(mag >= kDistanceRadius2); ++extra) {
-            wide_dstep(zr, zi, t, Dr, Di, e);
-            const WideEntry zm = p.orbit[m], zn = p.orbit[m + 1u];
-            wide_step(zm.xr, zm.xi, zm.xe, dcr, dci, exp2, wr, wi, q);
-            ++m;
-            wide_z(zn.xr, zn.xi, zn.xe, wr, wi, q, zr, zi, t, mg);
-            mag = wide_mag(mg, t);
-            if (wide_rebase(mg, wr, wi, q, t) || m == M) {
-                wide_norm(zr, zi, t, wr, wi, q);
-                m = 0u;
-            }
-        }
-    }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    if (count > 0) wide_run_on(p.orbit, c.M, c.m, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg, mag, Dr, Di, e);
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     const double r2 = Dr * Dr, i2 = Di * Di;
     a.rel[o] = wide_distance_value(mag, r2 + i2, e, a.range_r, exp2, count);
@@ -156,13 +142,7 @@ inline void wide_distance_host(const std::vector<WideEntry> &orbit, uint32_t M, 
     const WideEntry *Z = orbit.data();
     double wr, wi, zr, zi, mg;
     int32_t q, t;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    wide_z(Z[1].xr, Z[1].xi, Z[1].xe, wr, wi, q, zr, zi, t, mg);
-    if (M == 1u) {
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-    }
+    uint32_t m = wide_start(Z[1], M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg);
     double Dr = 0.5, Di = 0.0;
     int32_t e = 1;
     *count = 0;
@@ -174,31 +154,17 @@ inline void wide_distance_host(const std::vector<WideEntry> &orbit, uint32_t M, 
         ++m;
         wide_z(Z[m].xr, Z[m].xi, Z[m].xe, wr, wi, q, zr, zi, t, mg);
         const double mgs = wide_mag(mg, t);
-        const bool rebase = wide_rebase(mg, wr, wi, q, t) || m == M;   // (the escaping step's included: the run-on starts from it)
-        if (rebase) {
-            wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-        }
         if (mgs >= 4.0) {
             *count = (int32_t)i;
             *mag = mgs;
             break;
         }
-    }
-    if (*count > 0) {
-        while (*extra < kDistanceRunOn && !(*mag >= kDistanceRadius2)) {
-            wide_dstep(zr, zi, t, Dr, Di, e);
-            wide_step(Z[m].xr, Z[m].xi, Z[m].xe, dcr, dci, exp2, wr, wi, q);
-            ++m;
-            wide_z(Z[m].xr, Z[m].xi, Z[m].xe, wr, wi, q, zr, zi, t, mg);
-            *mag = wide_mag(mg, t);
-            if (wide_rebase(mg, wr, wi, q, t) || m == M) {
-                wide_norm(zr, zi, t, wr, wi, q);
-                m = 0u;
-            }
-            ++*extra;
+        if (wide_rebase(mg, wr, wi, q, t) || m == M) {
+            wide_norm(zr, zi, t, wr, wi, q);
+            m = 0u;
         }
     }
+    if (*count > 0) *extra = wide_run_on(Z, M, m, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg, *mag, Dr, Di, e);
     *Dr_out = Dr;
     *Di_out = Di;
     *e_out = e;

@@ -13,7 +13,7 @@
 //
 // The kernel: the skip side does the level search, loads (A, B) once, runs the derivative skip, then the dz map; the plain side
 // is wide_dstep and wide_step; the z / bailout / rebase tail is common, and zp is the (zv, t) it forms (at the new m after a
-// skip).  D, e and zp stay out of the rebase branch.  The run-on is deep_wide_distance_kernel's second loop: plain steps only,
+// skip).  D, e and zp stay out of the rebase branch.  The run-on is wide_run_on's loop (mbk_deep_wide_distance.h): plain steps,
 // entries read by index.  After the first rebase the lanes of a wave hold different m: no wave-uniform value is taken from a
 // lane.  The launch bound asks for 8 waves per SIMD: left to itself the allocator takes 66 VGPRs (7 waves), with the bound 54,
 // with no scratch either way.
@@ -49,6 +49,10 @@ struct DeepWideDistanceBlaArgs {
     double *rel;
 };
 
+// This kernel keeps its loop written out -- its own pixel set-up, cursor and run-on, the text deep_wide_bla_kernel and
+// deep_wide_distance_kernel had before they moved onto mbk_deep_cursor.h and wide_run_on.  On the shared pieces it compiled to a
+// loop that was a steady 0.3 to 0.5 % slower on the seahorse view (profiles/deep_shared/README.md); written out, its ISA is the
+// earlier one, instruction for instruction.  A fix to a clamp or to the M == 1 rule has to be made here as well.
 __global__ __launch_bounds__(64, 8) void deep_wide_distance_bla_kernel(DeepWideDistanceBlaArgs a)
 {
     const DeepWideBlaArgs &b = a.b;
@@ -152,13 +156,7 @@ inline void wide_distance_bla_host(const std::vector<WideEntry> &orbit, uint32_t
     const WideEntry *Z = orbit.data();
     double wr, wi, zr, zi, mg;
     int32_t q, t;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    wide_z(Z[1].xr, Z[1].xi, Z[1].xe, wr, wi, q, zr, zi, t, mg);
-    if (M == 1u) {
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-    }
+    uint32_t m = wide_start(Z[1], M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg);
     double Dr = 0.5, Di = 0.0;
     int32_t e = 1;
     *count = 0;
@@ -182,31 +180,17 @@ inline void wide_distance_bla_host(const std::vector<WideEntry> &orbit, uint32_t
         }
         wide_z(Z[m].xr, Z[m].xi, Z[m].xe, wr, wi, q, zr, zi, t, mg);
         const double mgs = wide_mag(mg, t);
-        const bool rebase = wide_rebase(mg, wr, wi, q, t) || m == M;   // (the escaping step's included: the run-on starts from it)
-        if (rebase) {
-            wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-        }
         if (mgs >= 4.0) {
             *count = (int32_t)i;
             *mag = mgs;
             break;
         }
-    }
-    if (*count > 0) {
-        while (*extra < kDistanceRunOn && !(*mag >= kDistanceRadius2)) {
-            wide_dstep(zr, zi, t, Dr, Di, e);
-            wide_step(Z[m].xr, Z[m].xi, Z[m].xe, dcr, dci, exp2, wr, wi, q);
-            ++m;
-            wide_z(Z[m].xr, Z[m].xi, Z[m].xe, wr, wi, q, zr, zi, t, mg);
-            *mag = wide_mag(mg, t);
-            if (wide_rebase(mg, wr, wi, q, t) || m == M) {
-                wide_norm(zr, zi, t, wr, wi, q);
-                m = 0u;
-            }
-            ++*extra;
+        if (wide_rebase(mg, wr, wi, q, t) || m == M) {
+            wide_norm(zr, zi, t, wr, wi, q);
+            m = 0u;
         }
     }
+    if (*count > 0) *extra = wide_run_on(Z, M, m, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg, *mag, Dr, Di, e);
     *Dr_out = Dr;
     *Di_out = Di;
     *e_out = e;

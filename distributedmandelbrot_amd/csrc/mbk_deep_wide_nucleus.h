@@ -1,8 +1,8 @@
 // mbk_deep_wide_nucleus.h -- atom periods and Newton seeds of extended-range deep views (include/mbk.h, "Locating minibrots in
-// extended-range deep views"): the main loop of deep_wide_distance_kernel (mbk_deep_wide_distance.h) without the run-on, keeping
-// the minimum as deep_nucleus_kernel (mbk_deep_nucleus.h) does.  Beside the count each pixel keeps the step at which its |z| was
-// smallest and the state there, and stores that step as its atom period and one Newton step from the pixel towards the root of
-// z_p(c) = 0.
+// extended-range deep views"): the steps of deep_wide_distance_kernel (mbk_deep_wide_distance.h) on the cursor of
+// mbk_deep_cursor.h, with no run-on, keeping the minimum as deep_nucleus_kernel (mbk_deep_nucleus.h) does.  Beside the count
+// each pixel keeps the step at which its |z| was smallest and the state there, and stores that step as its atom period and one
+// Newton step from the pixel towards the root of z_p(c) = 0.
 //
 // The magnitude that orders the candidates has to be wide: near a deep minibrot |z| is 1e-400 and |z|^2 as a binary64
 // (wide_mag) is 0.  From the mg and t that wide_z leaves, |z|^2 = mg 2^(2t) with mg not normalised,
@@ -113,27 +113,9 @@ struct DeepWideNucleusArgs {
     double *delta;      // two per pixel: (re, im)
 };
 
-__global__ __launch_bounds__(64) void deep_wide_nucleus_kernel(DeepWideNucleusArgs a)
+// the kept state of step 0: z_0 = c = (zr, zi) 2^t with its mg, d_0 = 1
+__host__ __device__ __forceinline__ WideNucleusBest wide_nucleus_first(double zr, double zi, int32_t t, double mg)
 {
-    const DeepWideArgs &p = a.v;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t by = blockIdx.x / p.blocks_x, bx = blockIdx.x - by * p.blocks_x;
-    const uint32_t lc = bx * 8u + (lane & 7u), lr = by * 8u + (lane >> 3);
-    if (lc >= p.ncols || lr >= p.nrows) return;
-    const double dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
-    const double dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
-    const uint32_t M = p.M;
-    const int32_t exp2 = p.exp2;
-    const WideEntry zero = {0.0, 0.0, kWideZeroExp, {0, 0, 0}};
-    double wr, wi;
-    int32_t q;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    WideEntry cur = p.z1;                // entry m
-    WideEntry nz;                        // entry m + 1
-    double zr, zi, mg;                   // zp = (zr, zi) 2^t and its |.|^2 on that exponent
-    int32_t t;
-    wide_z(cur.xr, cur.xi, cur.xe, wr, wi, q, zr, zi, t, mg);   // z_0 = c = Z_1 + dc
     WideNucleusBest b;
     wide_nmag(mg, t, b.bm, b.be);
     b.arg = 0;
@@ -143,42 +125,43 @@ __global__ __launch_bounds__(64) void deep_wide_nucleus_kernel(DeepWideNucleusAr
     b.Dr = 0.5;
     b.Di = 0.0;
     b.e = 1;
-    if (M == 1u) {
-        // no Z_2: the start state is rebased at once (m = 0); z_0 is the same value
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-        cur = zero;
-        nz = p.z1;
-    } else {
-        nz = p.orbit[2];
-    }
-    WideEntry pre = p.orbit[m + 2u < M ? m + 2u : M];   // entry m + 2 (clamped: unused once m + 1 == M)
+    return b;
+}
+
+__global__ __launch_bounds__(64) void deep_wide_nucleus_kernel(DeepWideNucleusArgs a)
+{
+    const DeepWideArgs &p = a.v;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const double dcr = px.dcr, dci = px.dci;
+    const int32_t exp2 = p.exp2;
+    double wr, wi, zr, zi, mg;           // zp = (zr, zi) 2^t and its |.|^2 on that exponent; it starts as z_0 = c
+    int32_t q, t;
+    OrbitCursor<WideEntry> c(p.orbit, p.z1, p.M, wide_start(p.z1, p.M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg));
+    WideNucleusBest b = wide_nucleus_first(zr, zi, t, mg);
     double Dr = 0.5, Di = 0.0;           // norm((1, 0), 0)
     int32_t e = 1;
     int32_t count = 0;
     for (int32_t i = 1; i < p.mrd; ++i) {
         wide_dstep(zr, zi, t, Dr, Di, e);
-        wide_step(cur.xr, cur.xi, cur.xe, dcr, dci, exp2, wr, wi, q);
-        ++m;
-        wide_z(nz.xr, nz.xi, nz.xe, wr, wi, q, zr, zi, t, mg);
+        wide_step(c.cur.xr, c.cur.xi, c.cur.xe, dcr, dci, exp2, wr, wi, q);
+        c.step();
+        wide_z(c.nz.xr, c.nz.xi, c.nz.xe, wr, wi, q, zr, zi, t, mg);
         const double mgs = wide_mag(mg, t);
         if (mgs >= 4.0) {
             count = i;
             break;
         }
         wide_nucleus_keep(b, mg, i, zr, zi, t, Dr, Di, e);
-        if (wide_rebase(mg, wr, wi, q, t) || m == M) {
+        if (wide_rebase(mg, wr, wi, q, t) || c.last()) {
             wide_norm(zr, zi, t, wr, wi, q);
-            m = 0u;
-            cur = zero;
-            nz = p.z1;
+            c.rebased();
         } else {
-            cur = nz;
-            nz = pre;
+            c.advanced();
         }
-        pre = p.orbit[m + 2u < M ? m + 2u : M];
+        c.prefetch();
     }
-    const size_t o = (size_t)lr * p.ncols + lc;
+    const size_t o = (size_t)px.lr * p.ncols + px.lc;
     if (p.counts) p.counts[o] = count;
     a.period[o] = b.arg + 1;
     double xr, xi;
@@ -194,22 +177,8 @@ inline void wide_nucleus_host(const std::vector<WideEntry> &orbit, uint32_t M, d
     const WideEntry *Z = orbit.data();
     double wr, wi, zr, zi, mg;
     int32_t q, t;
-    wide_norm(dcr, dci, exp2, wr, wi, q);
-    uint32_t m = 1u;
-    wide_z(Z[1].xr, Z[1].xi, Z[1].xe, wr, wi, q, zr, zi, t, mg);
-    WideNucleusBest b;
-    wide_nmag(mg, t, b.bm, b.be);
-    b.arg = 0;
-    b.zr = zr;
-    b.zi = zi;
-    b.t = t;
-    b.Dr = 0.5;
-    b.Di = 0.0;
-    b.e = 1;
-    if (M == 1u) {
-        wide_norm(zr, zi, t, wr, wi, q);
-        m = 0u;
-    }
+    uint32_t m = wide_start(Z[1], M, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg);
+    WideNucleusBest b = wide_nucleus_first(zr, zi, t, mg);
     double Dr = 0.5, Di = 0.0;
     int32_t e = 1;
     *count = 0;
