@@ -383,6 +383,16 @@ SIGNATURES = {
                                                    C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_julia_count_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_double)]),
+    "mbk_julia_view_launch_distance": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_compute_distance": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_julia_view_distance_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32,
+                                                        C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p, C.c_void_p]),
+    "mbk_julia_view_distance_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_double, C.c_double, C.c_uint32,
+                                                         C.c_uint32, C.POINTER(mbk_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_julia_distance_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32)] + [C.POINTER(C.c_double)] * 7),
     "mbk_view_interior_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
     "mbk_view_interior_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

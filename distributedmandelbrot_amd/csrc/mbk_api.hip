@@ -41,6 +41,7 @@
 #include "mbk_deep_wide_distance_bla.h"
 #include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
+#include "mbk_julia_distance.h"
 #include "mbk_density.h"
 
 using mbk::Axis;
@@ -3591,6 +3592,58 @@ static int launch_julia(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i,
     return MBK_OK;
 }
 
+// Everything a Julia distance call can refuse, before anything is allocated, enqueued or written: its own flag rule (kernel
+// selection only), then the rules of the count launch.
+static int julia_distance_check(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags)
+{
+    if (flags & ~(uint32_t)MBK_KERNEL_MASK)
+        return fail(ctx, MBK_ERR_INVALID, "Julia distance estimates take kernel selection only (binary64; no MBK_LAZY_UNIFORM, no MBK_DEEP_BLA / MBK_DEEP_XBLA)");
+    return julia_check(ctx, v, c_r, c_i, mrd, flags);
+}
+
+// A checked launch (mbk_julia_distance.h).  Kernel "asm": one pass, the derivative rides in a per-step escape loop.  Every
+// other selector: launch_julia with that selector writes the counts, then the derivative pass runs each escaped pixel for
+// exactly its count.  The doubling is the count launch's (julia_needs_literal), so both passes walk the same z.
+static int launch_julia_distance(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                 int32_t *d_counts, double *d_distance, hipStream_t stream)
+{
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    const bool one_pass = kernel == MBK_KERNEL_ASM;
+    const size_t px = (size_t)v->ncols * v->nrows;
+    if (!one_pass) {
+        if (!d_counts) {
+            StreamScratch *sc = nullptr;
+            int rc = get_scratch(ctx, stream, &sc);
+            if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
+            if (rc != MBK_OK) return rc;
+            d_counts = sc->d_dist_counts;
+        }
+        int rc = launch_julia(ctx, v, c_r, c_i, mrd, kernel, d_counts, nullptr, nullptr, stream);
+        if (rc != MBK_OK) return rc;
+    }
+    mbk::JuliaDistanceArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_window(a, v);
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.cr = c_r;
+    a.ci = c_i;
+    a.mrd = (int32_t)mrd;
+    a.counts_in = one_pass ? nullptr : d_counts;
+    a.counts_out = one_pass ? d_counts : nullptr;
+    a.distance = d_distance;
+    const bool literal = mbk::julia_needs_literal(c_i);
+    const dim3 grid(a.blocks_x * ((v->nrows + 7u) / 8u)), block(64);   // (at most 2^31 / 64 blocks: validate_view)
+    if (one_pass) {
+        if (literal) hipLaunchKernelGGL((mbk::julia_distance_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mbk::julia_distance_kernel<true, true>), grid, block, 0, stream, a);
+    } else {
+        if (literal) hipLaunchKernelGGL((mbk::julia_distance_kernel<false, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mbk::julia_distance_kernel<true, false>), grid, block, 0, stream, a);
+    }
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // ---- the count calls of the deep, extended-range and Julia views, and what renders and histograms share with them --------
 
 // Everything a sample launch on `t` can refuse, before anything is allocated, enqueued or written: the rules of the kind's own
@@ -3639,7 +3692,10 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
                 return (flags & MBK_DEEP_BLA) ? launch_deep_distance_bla(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
                                               : launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream);
             return launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
-        case Target::kJulia: return launch_julia(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.bytes, o.values, stream);
+        case Target::kJulia:
+            if (o.distance)   // (reached from mbk_julia_view_distance_render_* alone: mbk_julia_view_render_* refuses the source)
+                return launch_julia_distance(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.values, stream);
+            return launch_julia(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.bytes, o.values, stream);
         case Target::kPlain: break;
     }
     if (o.interior) {
@@ -3764,6 +3820,60 @@ int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_
     *count = literal ? mbk::julia_count<false>(z_r, z_i, c_r, c_i, (int32_t)mrd, &m)
                      : mbk::julia_count<true>(z_r, z_i, c_r, c_i, (int32_t)mrd, &m);
     if (mag) *mag = m;
+    return MBK_OK;
+}
+
+// ---- distance estimates for Julia views (mbk_julia_distance.h; mbk.h, the section of that name) ------------------------
+
+int mbk_julia_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                   int32_t *d_counts, double *d_distance, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!d_distance) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = julia_distance_check(ctx, view, c_r, c_i, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_julia_distance(ctx, view, c_r, c_i, mrd, flags, d_counts, d_distance, (hipStream_t)hip_stream);
+}
+
+int mbk_julia_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                    int32_t *h_counts, double *h_distance, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!h_distance) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    int rc = julia_distance_check(ctx, view, c_r, c_i, mrd, flags);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_distance, stats,
+                          [&](int32_t *d_counts, double *d_distance, hipStream_t stream) {
+                              return launch_julia_distance(ctx, view, c_r, c_i, mrd, flags, d_counts, d_distance, stream);
+                          });
+}
+
+int mbk_julia_distance_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, int32_t *extra,
+                            double *zr, double *zi, double *dr, double *di, double *mag, double *dmag, double *de)
+{
+    if (!count) return fail(nullptr, MBK_ERR_INVALID, "count is NULL");
+    if (!std::isfinite(c_r) || !std::isfinite(c_i)) return fail(nullptr, MBK_ERR_INVALID, "the Julia parameter must be finite");
+    if (mrd > 0x7fffffffu) return fail(nullptr, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    // the doubling a launch with this parameter would use, and the literal one for a z_r no view can hold (mbk_julia_count_host)
+    const bool literal = mbk::julia_needs_literal(c_i) || !(std::fabs(z_r) <= kMaxCoord);
+    double d_r = 1.0, d_i = 0.0, m = 0.0;
+    int32_t n = 0, x = 0;
+    if (literal) mbk::julia_distance_orbit<false>(z_r, z_i, d_r, d_i, c_r, c_i, (int32_t)mrd, n, x, m);
+    else mbk::julia_distance_orbit<true>(z_r, z_i, d_r, d_i, c_r, c_i, (int32_t)mrd, n, x, m);
+    const double r2 = d_r * d_r, i2 = d_i * d_i;
+    const double dm = r2 + i2;
+    *count = n;
+    if (extra) *extra = x;
+    if (zr) *zr = z_r;
+    if (zi) *zi = z_i;
+    if (dr) *dr = d_r;
+    if (di) *di = d_i;
+    if (mag) *mag = m;
+    if (dmag) *dmag = dm;
+    if (de) *de = mbk::distance_value(m, dm, n);
     return MBK_OK;
 }
 
@@ -4356,6 +4466,49 @@ int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *o
 {
     Target t;
     int rc = wide_distance_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, nullptr, 0u);
+}
+
+// ---- distance renders of Julia views (mbk.h "Distance estimates for Julia views"): calls of their own in the same way;
+// mbk_julia_view_render_* keeps refusing the distance sources ------------------------------------------------------------
+
+// Everything such a render can refuse, before anything is allocated, enqueued or written.
+static int julia_distance_render_check(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                       const mbk_render_spec *spec, const void *out, Target *t)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = validate_render_spec(ctx, spec);
+    if (rc != MBK_OK) return rc;
+    if (spec->source != MBK_RENDER_DISTANCE) return fail(ctx, MBK_ERR_INVALID, "Julia distance renders take MBK_RENDER_DISTANCE only");
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    *t = julia_target(view, c_r, c_i);
+    const uint32_t s = spec->supersample;
+    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
+    return julia_distance_check(ctx, &samples.view, c_r, c_i, mrd, flags);
+}
+
+int mbk_julia_view_distance_render_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                          const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    Target t;
+    int rc = julia_distance_render_check(ctx, view, c_r, c_i, mrd, flags, spec, d_rgba, &t);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+}
+
+int mbk_julia_view_distance_render_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                           const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    Target t;
+    int rc = julia_distance_render_check(ctx, view, c_r, c_i, mrd, flags, spec, h_rgba, &t);
     if (rc != MBK_OK) return rc;
     return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, nullptr, 0u);
 }

@@ -271,6 +271,20 @@ def julia_count_host(z, c, mrd: int) -> Tuple[int, float]:
     return int(n.value), float(mag.value)
 
 
+def julia_distance_host(z, c, mrd: int) -> dict:
+    """mbk_julia_distance_host: one Julia orbit with its derivative dz_k/dz_0 on the host, without a device, compiled from the
+    step function the kernels use (include/mbk.h, "Distance estimates for Julia views"): a dict of the final state -- n, extra
+    (the run-on steps taken), zr, zi, dr, di, mag, dmag and de (through the host's ln)."""
+    lib = L.load()
+    n, x = C.c_int32(0), C.c_int32(0)
+    vals = [C.c_double(0.0) for _ in range(7)]
+    _check(lib, lib.mbk_julia_distance_host(float(z[0]), float(z[1]), float(c[0]), float(c[1]), mrd, C.byref(n), C.byref(x),
+                                            *[C.byref(v) for v in vals]))
+    out = {"n": int(n.value), "extra": int(x.value)}
+    out.update((k, float(v.value)) for k, v in zip(("zr", "zi", "dr", "di", "mag", "dmag", "de"), vals))
+    return out
+
+
 def _cxview(view: "WideDeepView", window=None) -> L.mbk_deep_xview:
     col0, row0, ncols, nrows = window if window is not None else (0, 0, view.width, view.height)
     return L.mbk_deep_xview(view.range_r, view.range_i, view.exp2, view.width, view.height, col0, row0, ncols, nrows)
@@ -1752,6 +1766,50 @@ class MandelbrotDevice:
                                     kernel: str = "default") -> None:
         """Asynchronous form: the window's histogram is ADDED into the DEVICE table d_hist (uint64[mrd]) on ``stream``."""
         self._launch_histogram(view, mrd, d_hist, stream, window, c=c, kernel=kernel)
+
+    # -- distance estimates for Julia views (include/mbk.h, the section of that name): calls of their own; render_julia_view
+    # keeps refusing the distance sources --
+    def compute_julia_view_distance(self, view: View, c, mrd: int, *, window=None, kernel: str = "default"):
+        """Exterior distance estimates of the Julia set of c: de = 2 |z| ln |z| / |dz/dz_0| in complex-plane units, evaluated
+        after the orbit has run on to |z|^2 >= 2^32, 0 for never-escaped pixels.  The counts are those of compute_julia_view.
+        kernel "asm" takes the one-pass form; "default" and "group" compute the counts with that kernel first and the
+        derivative in a second pass; all store the same values.  A pixel at exactly 0 (the critical point) that escapes has
+        derivative 0 and stores +inf.  Returns (distance float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
+        cv = self._cview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        dist = np.empty(shape, np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_julia_view_compute_distance(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
+                                                              counts.ctypes.data, dist.ctypes.data, C.byref(st)))
+        return dist, counts, _stats(st)
+
+    def launch_julia_view_distance(self, view: View, c, mrd: int, *, d_distance: int, d_counts: int = 0, stream: int = 0,
+                                   window=None, kernel: str = "default") -> None:
+        """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_julia_view_launch_distance(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
+                                                             d_counts or None, d_distance or None, stream or None))
+
+    def render_julia_view_distance(self, view: View, c, mrd: int, *, palette, supersample: int = 1, window=None,
+                                   kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None):
+        """The Julia set of c as an RGBA8 image coloured by its distance estimate (source "distance"; Palette.distance), as
+        render_view(source="distance") does for a plain view.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
+        cv = self._cview(view, window)
+        rgba = self._render_out(cv, out)
+        spec = palette.spec("distance", supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_julia_view_distance_render_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
+                                                                     L.KERNELS[kernel], C.byref(spec), rgba.ctypes.data, C.byref(st)))
+        return rgba, _stats(st)
+
+    def launch_render_julia_view_distance(self, view: View, c, mrd: int, *, palette, d_rgba: int, supersample: int = 1,
+                                          stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0) -> None:
+        """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        spec = palette.spec("distance", supersample, max_band_rows)
+        self._check(self._lib.mbk_julia_view_distance_render_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
+                                                                    L.KERNELS[kernel], C.byref(spec), d_rgba or None, stream or None))
 
     # -- stored chunks (include/mbk.h, "Stored chunks") ---------------------------------------------
     def decode_chunk(self, stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None):

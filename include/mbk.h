@@ -1008,7 +1008,8 @@ int mbk_deep_xdistance_skip_host(double A_r, double A_i, int32_t a_e, double B_r
  * except that the palette does NOT wrap: t >= n - 1 (+inf included) gives p[n - 1], otherwise k = floor(t),
  * f = floor((t - k) * 256) and p[k], p[k + 1] are blended as above.  2 <= n <= 65536, |offset| <= 2^20 and, for this source
  * only, 0 < scale <= 2^80 (de of a view 1e-13 wide is ~1e-16: scale is in units of 1 / pitch).  mbk_render_resolve_host takes
- * the source too, reading de through its `smooth` argument. */
+ * the source too, reading de through its `smooth` argument.  mbk_julia_view_distance_render_* ("Distance estimates for Julia
+ * views") takes this source and no other, on the samples of mbk_julia_view_launch_distance; mbk_julia_view_render_* refuses it. */
 #define MBK_RENDER_DISTANCE 3u
 /* MBK_RENDER_DISTANCE_REL (deep renders only; a plain render refuses it): the samples are what mbk_deep_view_launch_distance
  * writes for the sample view (12 bytes per sample, banded like MBK_RENDER_SMOOTH): rel, the distance as a fraction of the
@@ -1248,8 +1249,9 @@ int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double 
  * doubling a launch with this c would use.  *mag (may be NULL) is the mag of the last step run (mag_n if n > 0; 0 if no step
  * ran).  MBK_ERR_INVALID for a NULL count, a non-finite c, mrd >= 2^31; z may be anything.
  *
- * Out of scope: distance estimates and deep (perturbation) Julia views, an fp32 form, the scan / refill / units machinery,
- * the z -> -z symmetry.
+ * Distance estimates are calls of their own: "Distance estimates for Julia views", below.
+ *
+ * Out of scope: deep (perturbation) Julia views, an fp32 form, the scan / refill / units machinery, the z -> -z symmetry.
  */
 int mbk_julia_view_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
                           int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, void *hip_stream);
@@ -1272,6 +1274,78 @@ int mbk_julia_view_histogram_launch(mbk_ctx *ctx, const mbk_view *view, double c
 int mbk_julia_view_histogram_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
                                      uint64_t *h_hist, mbk_stats *stats);
 int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, double *mag);
+
+/*
+ * Distance estimates for Julia views.  NOT in the reference; additive (the ABI version stays 5): no existing call changes what
+ * it stores or refuses.  The exterior distance estimate began with Julia sets: for a fixed c the derivative of the orbit with
+ * respect to its STARTING POINT is carried along, and the pixel reports
+ *     de = 2 |z| ln |z| / |d|,   d = dz_k / dz_0,
+ * a length in the complex plane within a known factor of the true distance from p to the Julia set of c (Koebe: between
+ * about de / 4 and de for a connected set).  Dendrites and Cantor dusts (c = i, c = -0.8 + 0.156i) are thinner than any pixel
+ * and every sample of them escapes; this is the output that shows them.
+ *
+ * Contract (tests/julia_distance_model.py restates it in numpy; tests/test_julia_distance.py and
+ * tests/test_gpu_julia_distance.py hold the host twin and the GPU to it).  For a pixel with coordinate p of an mbk_view and a
+ * parameter c = (c_r, c_i), binary64, every operation rounded on its own, no contraction:
+ *   state     z_0 = p, d_0 = (1, 0).  Step k -> k + 1:
+ *               u = fl(fl(zr dr) - fl(zi di)), v = fl(fl(zr di) + fl(zi dr))   both from z_k and d_k
+ *               d' = (2u, 2v)     both doublings are exact, subnormals included; an overflow is the infinity IEEE gives.  There
+ *                                 is no "+ 1": that term of "Distance estimates" is dc/dc, and here c does not move.
+ *               z_(k+1) by the recurrence of "Julia views", unchanged, with the doubling a count launch with this c takes
+ *               (|c_i| < 2^-900: the literal form; otherwise fma(2, fl(zr zi), c_i), the same bits there).
+ *   count     n is exactly the count of mbk_julia_view_launch: the first k >= 1 with mag_k >= 4, 0 if none, at most mrd - 1
+ *             updates.
+ *   run-on    a pixel with n > 0 runs on, uncounted, with both recurrences until mag >= 2^32 or 64 further steps have run: the
+ *             constant pair of "Distance estimates".  For |c| > 2 mag may fall below 4 again during the run-on; that changes
+ *             nothing: n stays, and the steps go on.
+ *   output    de = the output expression of "Distance estimates" (the same function, shared) at the final state, with
+ *             dmag = fl(fl(dr^2) + fl(di^2)): 0 for n = 0, 0 instead of NaN, infinities as IEEE gives them.  The allowance
+ *             against the correctly rounded value is measured on Julia pairs (tests/julia_distance_model.py: J0 for the host,
+ *             J0 + 1 for the device).
+ *   critical  the one case plain views do not have: a z_0 that is exactly 0 -- the critical point -- has d_1 = 2 z_0 d_0 = 0 and
+ *   point     so d_k = 0 for every k >= 1.  With n > 0 its dmag is 0 and it stores +inf.  (The centre pixel of the 65 x 65 view
+ *             of [-2, 2]^2 with c = (0.285, 0.01), mrd = 500: n = 19, dmag = 0, de = +inf, the only infinity in that view.)  A
+ *             view with an odd number of samples on both axes, centred on 0, holds that pixel; colour rules that clamp
+ *             (MBK_RENDER_DISTANCE: the last palette entry) take it in their stride.
+ *   mrd       0 and 1 run no step: every count and de is 0.
+ *   windows   a window is bit-identical to the same pixels of the whole view.
+ *
+ * Two designs, selected by the kernel bits of `flags`, bit-identical in what they store:
+ *   MBK_KERNEL_DEFAULT / _GROUP   two passes: mbk_julia_view_launch with that selector writes the counts (grouped test and
+ *             cycle test as its own two rules decide), then a derivative pass runs each pixel with n > 0 for exactly n steps
+ *             without a bailout test, plus the run-on.  A block whose counts are all 0 -- the whole interior of a connected
+ *             set -- stores zeros after one load.  With d_counts == NULL the counts live in the per-stream scratch of
+ *             mbk_view_launch_distance.
+ *   MBK_KERNEL_ASM                one pass: the derivative rides in a per-step escape loop; no counts are read.
+ * mbk_julia_view_launch_distance: asynchronous, DEVICE pointers (window-sized, nothing is written outside them), the caller's
+ * stream.  _compute_distance: synchronous into HOST buffers on slot 0; stats as for mbk_view_compute_distance (the run-on
+ * steps are not in pixel_iterations).  The counts pointer may be NULL in both.
+ * mbk_julia_view_distance_render_launch / _compute: the render calls on these samples, calls of their own as the other
+ * distance renders are.  The source must be MBK_RENDER_DISTANCE; colour rule, supersampling, banding, statistics and every
+ * other refusal are those of mbk_view_render_* with that source.  mbk_julia_view_render_* keeps refusing the distance sources.
+ * mbk_julia_distance_host: one orbit on the host, no ctx, no device, compiled from the step function the kernels use, with
+ * the doubling a launch with this c would use (and the literal one for |z_r| > 2^500, as mbk_julia_count_host).  It returns the
+ * final state: *count = n, *extra = the run-on steps taken, z, d, mag, dmag and de (the host's ln).  Every output pointer but
+ * count may be NULL; z may be anything.
+ *
+ * MBK_ERR_INVALID, with nothing written: MBK_KERNEL_SIMPLE / _REFILL / _SCAN; MBK_PRECISION_F32, MBK_LAZY_UNIFORM, MBK_DEEP_BLA,
+ * MBK_DEEP_XBLA and any other flag bit; a non-finite c; mrd >= 2^31; a NULL distance or rgba pointer; whatever
+ * mbk_julia_view_launch refuses in a view; in the render calls every source but MBK_RENDER_DISTANCE; in the host twin a NULL
+ * count.
+ *
+ * Out of scope: deep (perturbation) Julia views, Julia interior views, a sharding form, slot / submit forms, the z -> -z
+ * symmetry.
+ */
+int mbk_julia_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                   int32_t *d_counts, double *d_distance, void *hip_stream);
+int mbk_julia_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                    int32_t *h_counts, double *h_distance, mbk_stats *stats);
+int mbk_julia_view_distance_render_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                          const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_julia_view_distance_render_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                           const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+int mbk_julia_distance_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, int32_t *extra,
+                            double *zr, double *zi, double *dr, double *di, double *mag, double *dmag, double *de);
 
 /*
  * Density views (Buddhabrot / Nebulabrot).  NOT in the reference; additive (the ABI version stays 5): no existing call changes.
