@@ -43,6 +43,7 @@
 #include "mbk_julia.h"
 #include "mbk_julia_distance.h"
 #include "mbk_density.h"
+#include "mbk_adaptive.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -4331,6 +4332,206 @@ int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double 
                                       uint32_t height, const int32_t *counts, const double *smooth, uint8_t *rgba)
 {
     return resolve_host(spec, true, h_lut, lut_len, width, height, counts, nullptr, smooth, rgba);
+}
+
+// ---- adaptive supersampling (mbk.h "Adaptive supersampling", mbk_adaptive.h): plain views, MBK_RENDER_SMOOTH ----------------
+
+// Everything an adaptive render can refuse, before anything is allocated, enqueued or written: its own rules, then the smooth
+// render's for the sample view at s (render_check) and the sample launch's for the base view.
+static int adaptive_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                          uint32_t threshold, const void *out)
+{
+    if (spec && spec->source != MBK_RENDER_SMOOTH)
+        return fail(ctx, MBK_ERR_INVALID, "adaptive supersampling is implemented for MBK_RENDER_SMOOTH only");
+    if (threshold > 256u) return fail(ctx, MBK_ERR_INVALID, "threshold must lie in [0, 256]");
+    int rc = render_check(ctx, t, mrd, flags, spec, out);
+    if (rc != MBK_OK) return rc;
+    return target_check(ctx, target_samples(t, 1u, 0u, 0u, t.g.width, t.g.height), mrd, flags);
+}
+
+// The bands of an adaptive render: per band the base samples of its halo (12 bytes each, the band grown by one pixel on each
+// side) and the list (4 bytes per pixel of the band) fit MBK_RENDER_BAND_BYTES beside the two counters.
+static BandPlan adaptive_band_plan(uint32_t ncols, uint32_t nrows, uint32_t max_rows)
+{
+    const uint64_t budget = MBK_RENDER_BAND_BYTES - 2048u;   // (the parts of the scratch start on 256-byte lines)
+    const uint64_t halo_row = ((uint64_t)ncols + 2u) * 12u, row = halo_row + (uint64_t)ncols * 4u;
+    BandPlan p = {ncols, nrows, ncols, 1u};
+    if (2u * halo_row + row <= budget) {
+        // (bands of equal height: 4096 rows that miss the budget by the halo become 2 x 2048, not 4094 + 2)
+        const uint32_t fit = (uint32_t)std::min<uint64_t>(nrows, (budget - 2u * halo_row) / row), bands = (nrows + fit - 1u) / fit;
+        p.band_rows = (nrows + bands - 1u) / bands;
+    } else
+        p.tile_cols = (uint32_t)((budget - 72u) / 40u);   // 3 (tile_cols + 2) 12 + 4 tile_cols <= budget
+    if (max_rows) p.band_rows = std::min(p.band_rows, max_rows);
+    return p;
+}
+
+// A checked adaptive render (adaptive_check) onto the device image d_out (ncols x nrows words) and, if not NULL, the device
+// mask d_mask (ncols x nrows bytes), on `stream`.  stat: the slot whose reduction scratch the classify and refine kernels add
+// their samples' statistics to and whose ev_k1 marks the last kernel (_compute), or NULL.
+static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                        uint32_t threshold, uint32_t *d_out, uint8_t *d_mask, hipStream_t stream, Slot *stat)
+{
+    const uint32_t s = spec->supersample;
+    StreamScratch *sc = nullptr;
+    int rc = get_scratch(ctx, stream, &sc);
+    if (rc != MBK_OK) return rc;
+    rc = stream_palette(ctx, sc, stream, spec->palette, spec->palette_len);
+    if (rc != MBK_OK) return rc;
+
+    const BandPlan plan = adaptive_band_plan(t.g.ncols, t.g.nrows, spec->max_band_rows);
+    const size_t cap_halo = ((size_t)plan.tile_cols + 2u) * ((size_t)plan.band_rows + 2u);
+    // layout: nu | counts (the halo's base samples, as a smooth render's) | list | length, cursor
+    const size_t off_counts = round_up_256(cap_halo * 8u);
+    const size_t off_list = off_counts + round_up_256(cap_halo * 4u);
+    const size_t off_words = off_list + round_up_256(plan.cap_px() * 4u);
+    const size_t need = off_words + 256u;
+    rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
+    if (rc != MBK_OK) return rc;
+    uint8_t *base = (uint8_t *)sc->d_render;
+    const Outputs samples = {(int32_t *)(base + off_counts), nullptr, (double *)base, false, nullptr, false};
+    uint32_t *d_list = (uint32_t *)(base + off_list), *d_words = (uint32_t *)(base + off_words);
+    const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
+
+    const size_t lds = (size_t)spec->palette_len * sizeof(uint32_t);
+    const size_t tile_lds = mbk::kAdaptiveCells * sizeof(uint32_t);   // (the classify kernel's own, beside the palette)
+    const bool use_lds = spec->palette_len <= mbk::kRenderLdsEntries && lds + tile_lds <= ctx->prop.sharedMemPerBlock;
+    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
+    const uint32_t wg_per_cu = use_lds ? (uint32_t)std::min<size_t>(8u, std::max<size_t>(1u, (160u << 10) / (lds + tile_lds))) : 8u;
+    const bool per_step = (flags & MBK_KERNEL_MASK) == MBK_KERNEL_ASM;
+    ReduceSlot *d_red = stat ? stat->d_red : nullptr;
+
+    rc = for_each_band(ctx, plan, nullptr, 1u, mrd, stream, nullptr, [&](uint32_t r, uint32_t c, uint32_t nr, uint32_t nc, bool is_last) -> int {
+        // 1. the base samples of the band's halo: grown by one pixel, clamped to the VIEW
+        const uint32_t x0 = t.g.col0 + c, y0 = t.g.row0 + r;
+        const uint32_t ox = x0 > 0u ? 1u : 0u, oy = y0 > 0u ? 1u : 0u;
+        const uint32_t hc = ox + nc + (x0 + nc < t.g.width ? 1u : 0u), hr = oy + nr + (y0 + nr < t.g.height ? 1u : 0u);
+        int rc = target_launch(ctx, target_samples(t, 1u, x0 - ox, y0 - oy, hc, hr), mrd, flags, samples, stream);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipMemsetAsync(d_words, 0, 2u * sizeof(uint32_t), stream));
+        // 2. classify: base image, mask, list
+        mbk::AdaptiveClassifyArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.counts = samples.counts;
+        a.smooth = samples.values;
+        a.hc = hc;
+        a.hr = hr;
+        a.ox = ox;
+        a.oy = oy;
+        a.nc = nc;
+        a.nr = nr;
+        a.tiles_x = (nc + mbk::kAdaptiveTileX - 1u) / mbk::kAdaptiveTileX;
+        a.threshold = threshold;
+        a.mrd = mrd;
+        a.lds_palette = use_lds ? 1u : 0u;
+        a.out = d_out + (size_t)r * t.g.ncols + c;
+        a.mask = d_mask ? d_mask + (size_t)r * t.g.ncols + c : nullptr;
+        a.out_pitch = t.g.ncols;
+        a.list = d_list;
+        a.len = d_words;
+        a.stats = d_red;
+        a.pal = render_palette(spec, d_palette);
+        const uint64_t tiles = (uint64_t)a.tiles_x * ((nr + mbk::kAdaptiveTileY - 1u) / mbk::kAdaptiveTileY);
+        hipLaunchKernelGGL(mbk::adaptive_classify_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, (uint64_t)cus * wg_per_cu)), dim3(256),
+                           use_lds ? lds : 0u, stream, a);
+        MBK_HIP(ctx, hipGetLastError());
+        // 3. refine: the fine samples of the listed pixels (at s = 1 a refined pixel is its base pixel: nothing to do)
+        if (s > 1u && threshold < 256u) {
+            mbk::AdaptiveRefineArgs f;
+            std::memset(&f, 0, sizeof(f));
+            f.re = make_axis(t.view.start_r, t.view.range_r, t.g.width * s);
+            f.im = make_axis(t.view.start_i, t.view.range_i, t.g.height * s);
+            f.px0 = x0;
+            f.py0 = y0;
+            f.nc = nc;
+            f.mrd = (int32_t)mrd;
+            f.exact_steps = ctx->opt[MBK_OPT_EXACT_STEPS];
+            f.cyc_window = ctx->opt[MBK_OPT_CYCLE_WINDOW];
+            f.list = d_list;
+            f.len = d_words;
+            f.cursor = d_words + 1;
+            f.out = a.out;
+            f.out_pitch = t.g.ncols;
+            f.stats = d_red;
+            f.pal = a.pal;
+            // 6 waves per SIMD, which every instantiation's registers allow at once; no more workgroups than groups the
+            // fullest list can hold
+            const uint32_t per_group = 64u / (s * s);
+            const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
+            const dim3 grid((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * 6u));
+            if (per_step) mbk::launch_adaptive_refine<0>(s, grid, stream, f);
+            else mbk::launch_adaptive_refine<8>(s, grid, stream, f);
+            MBK_HIP(ctx, hipGetLastError());
+        }
+        if (stat && is_last) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
+        return MBK_OK;
+    });
+    if (rc != MBK_OK || !stat) return rc;
+    // the kernels have added everything up: only the copy of the partial results is left
+    return launch_reduce(ctx, stat->d_red, stat->h_red, nullptr, nullptr, 0u, mrd, stream, false);
+}
+
+int mbk_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                    uint32_t threshold, uint8_t *d_rgba, uint8_t *d_mask, void *hip_stream)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    const Target t = view_target(view);
+    int rc = adaptive_check(ctx, t, mrd, flags, spec, threshold, d_rgba);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return adaptive_run(ctx, t, mrd, flags, spec, threshold, (uint32_t *)d_rgba, d_mask, (hipStream_t)hip_stream, nullptr);
+}
+
+int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                     uint32_t threshold, uint8_t *h_rgba, uint8_t *h_mask, mbk_stats *stats)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    const Target t = view_target(view);
+    int rc = adaptive_check(ctx, t, mrd, flags, spec, threshold, h_rgba);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    Slot &sl = ctx->s[0];
+    const size_t px = (size_t)t.g.ncols * t.g.nrows;
+    auto enqueue = [&]() -> int {
+        // the ctx' device image, with the mask behind it: px words and px bytes
+        const size_t words = px + (px + 3u) / 4u;
+        int rc = grow(ctx, ctx->d_rgba, ctx->rgba_cap_px, words, words * sizeof(uint32_t));
+        if (rc != MBK_OK) return rc;
+        uint8_t *d_mask = h_mask ? (uint8_t *)(ctx->d_rgba + px) : nullptr;
+        MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
+        rc = adaptive_run(ctx, t, mrd, flags, spec, threshold, ctx->d_rgba, d_mask, sl.stream, &sl);
+        if (rc != MBK_OK) return rc;
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
+        MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
+        if (h_mask) MBK_HIP(ctx, hipMemcpyAsync(h_mask, d_mask, px, hipMemcpyDeviceToHost, sl.stream));
+        MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
+        return MBK_OK;
+    };
+    return sync_end(ctx, enqueue(), stats, false);
+}
+
+int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, uint32_t width, uint32_t height,
+                             const int32_t *base_counts, const double *base_smooth, const int32_t *fine_counts,
+                             const double *fine_smooth, uint8_t *rgba, uint8_t *mask)
+{
+    int rc = validate_render_spec(nullptr, spec, false);
+    if (rc != MBK_OK) return rc;
+    if (spec->source != MBK_RENDER_SMOOTH)
+        return fail(nullptr, MBK_ERR_INVALID, "adaptive supersampling is implemented for MBK_RENDER_SMOOTH only");
+    if (threshold > 256u) return fail(nullptr, MBK_ERR_INVALID, "threshold must lie in [0, 256]");
+    if (!rgba) return fail(nullptr, MBK_ERR_INVALID, "output pointer is NULL");
+    const uint32_t s = spec->supersample;
+    if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
+        return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
+    if (!base_counts || !base_smooth || !fine_counts || !fine_smooth) return fail(nullptr, MBK_ERR_INVALID, "the sample arrays are NULL");
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    mbk::render_adaptive_host(render_palette(spec, words.data()), s, threshold, width, height, base_counts, base_smooth, fine_counts,
+                              fine_smooth, rgba, mask);
+    return MBK_OK;
 }
 
 // ---- interior renders (mbk.h "Interior views"): calls of their own on the render machinery above ------------------------

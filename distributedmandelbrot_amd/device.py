@@ -1625,6 +1625,35 @@ class MandelbrotDevice:
                      lambda: self.deep_view_histogram(orbit, view, mrd, bla=bla, xbla=xbla), d_rgba=d_rgba, stream=stream, orbit=orbit,
                      bla=bla, xbla=xbla)
 
+    # -- adaptive supersampling (include/mbk.h, "Adaptive supersampling"): plain views, source "smooth" --
+    def render_view_adaptive(self, view: View, mrd: int, *, palette, supersample: int, threshold: int, window=None,
+                             kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None,
+                             want_mask: bool = False):
+        """render_view(source="smooth") that computes the s x s samples only where they change the picture: a pixel is refined
+        when its s = 1 colour differs from one of its up to eight neighbours' in the whole view by `threshold` (0 .. 256) or
+        more in some channel, and is its s = 1 colour otherwise.  threshold 0 is render_view at `supersample` bit for bit,
+        256 is render_view at 1.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples computed for the window's
+        pixels), or with want_mask (rgba, mask uint8[nrows, ncols] -- 1 where refined --, TileStats)."""
+        cv = self._cview(view, window)
+        rgba = self._render_out(cv, out)
+        mask = np.empty((cv.nrows, cv.ncols), np.uint8) if want_mask else None
+        spec = palette.spec("smooth", supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_render_adaptive_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                               int(threshold), rgba.ctypes.data,
+                                                               mask.ctypes.data if want_mask else None, C.byref(st)))
+        return (rgba, mask, _stats(st)) if want_mask else (rgba, _stats(st))
+
+    def launch_render_view_adaptive(self, view: View, mrd: int, *, palette, supersample: int, threshold: int, d_rgba: int,
+                                    d_mask: int = 0, stream: int = 0, window=None, kernel: str = "default",
+                                    max_band_rows: int = 0) -> None:
+        """Asynchronous form into a DEVICE buffer of nrows * ncols * 4 bytes and, with d_mask, a DEVICE mask of nrows * ncols
+        bytes, on ``stream`` (0 = HIP's null stream).  Nothing of the list of refined pixels reaches the host."""
+        cv = self._cview(view, window)
+        spec = palette.spec("smooth", supersample, max_band_rows)
+        self._check(self._lib.mbk_view_render_adaptive_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                              int(threshold), d_rgba or None, d_mask or None, stream or None))
+
     # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
     def view_histogram(self, view: View, mrd: int, *, window=None, kernel: str = "default", precision: str = "f64",
                        want_stats: bool = False):
@@ -1882,3 +1911,23 @@ class MandelbrotDevice:
 def _stats(st: L.mbk_stats) -> TileStats:
     return TileStats(float(st.kernel_ms), float(st.d2h_ms), int(st.pixel_iterations),
                      int(st.never_pixels), bool(st.all_bytes_zero), bool(st.all_bytes_one), int(st.rle_runs))
+
+
+def render_adaptive_host(palette, supersample: int, threshold: int, width: int, height: int, *, base_counts, base_smooth,
+                         fine_counts, fine_smooth, want_mask: bool = False):
+    """mbk_render_adaptive_host: the adaptive-supersampling contract on the host, no device -- the same functions the kernels are
+    compiled from.  base_*: the samples of the FULL (height, width) view; fine_*: those of the FULL (height s, width s) view.
+    Returns rgba uint8[height, width, 4], or with want_mask (rgba, mask uint8[height, width])."""
+    lib = L.load()
+    s = int(supersample)
+    arrs = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((base_counts, np.int32), (base_smooth, np.float64),
+                                                            (fine_counts, np.int32), (fine_smooth, np.float64))]
+    for a, n in zip(arrs, (width * height, width * height, width * height * s * s, width * height * s * s)):
+        if a.size != n:
+            raise ValueError("base arrays hold height x width samples, fine arrays (height * s) x (width * s)")
+    rgba = np.empty((height, width, 4), np.uint8)
+    mask = np.empty((height, width), np.uint8) if want_mask else None
+    spec = palette.spec("smooth", s)
+    _check(lib, lib.mbk_render_adaptive_host(C.byref(spec), int(threshold), width, height, *[a.ctypes.data for a in arrs],
+                                             rgba.ctypes.data, mask.ctypes.data if want_mask else None))
+    return (rgba, mask) if want_mask else rgba

@@ -1098,6 +1098,62 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
                             const uint8_t *bytes, const double *smooth, uint8_t *rgba);
 
 /*
+ * Adaptive supersampling: the s x s samples of a render are computed only for the output pixels that straddle a colour edge.
+ * NOT in the reference; additive (the ABI version stays 5): no existing call, flag or default changes.  Plain Mandelbrot views
+ * (mbk_view) and MBK_RENDER_SMOOTH only.  A render at s = 8 computes 64 samples for every pixel; away from the boundary of the
+ * set neighbouring pixels take nearly the same colour and the mean of 64 samples is what one sample gives.
+ *
+ * Contract (all integer arithmetic past the samples' colours; tests/adaptive_model.py restates it in numpy,
+ * tests/test_adaptive.py holds the host twin and tests/test_gpu_adaptive.py the GPU to it).  Given a view of W x H output
+ * pixels, a window of it, a factor s in {1, 2, 3, 4, 8}, an mbk_render_spec and a threshold in [0, 256]:
+ *   base      B[y][x] is the colour mbk_view_render_launch gives pixel (x, y) at supersample = 1: the MBK_RENDER_SMOOTH colour
+ *             of sample (x, y) of the W x H view, count and nu exactly as mbk_view_launch_smooth stores them.  It is defined
+ *             over the whole view, not the window.
+ *   N(x, y)   the up to eight pixels (x + dx, y + dy), dx, dy in {-1, 0, 1} and not both 0, that lie inside the FULL view:
+ *             clamped at the view's edges, never at the window's or a band's.
+ *   diff      diff(p, q) = the largest |p.ch - q.ch| over the four channels, alpha included.
+ *   refined   pixel (x, y) is refined iff threshold == 0, or some q in N(x, y) has diff(B[y][x], B[q]) >= threshold.  So
+ *             threshold 0 refines every pixel (a 1 x 1 view's too) and 256 none.
+ *   output    a refined pixel is exactly the pixel of mbk_view_render_launch at factor s (the rounded mean of the colours of
+ *             its s x s samples of the W s x H s view, "resolve" above); any other pixel is B[y][x].  Threshold 0 therefore
+ *             gives the existing render at s bit for bit, threshold 256 the existing render at 1, and s = 1 the existing
+ *             render at every threshold.  A window or a band is bit-identical to the same rectangle of the whole image.
+ *   mask      optional, uint8[nrows][ncols]: 1 where refined, 0 elsewhere; of the window, decided on the full view.
+ *   stats     (_compute) pixel_iterations and never_pixels count the base samples of the window's own pixels plus the s^2
+ *             samples of each refined pixel of the window (at s = 1 that one sample is the base sample: counted once); the
+ *             halo below is not counted and nothing is counted twice across bands.  The other fields are
+ *             mbk_view_render_compute's.
+ *
+ * How it runs (csrc/mbk_adaptive.h).  Per band: the base samples of the band grown by one pixel on each side and clamped to the
+ * view, by the sample kernels the flags select; a classify kernel that colours them, writes B, the mask and a list of the
+ * refined pixels; a refine kernel that computes the s^2 samples of each listed pixel, one lane per sample.  The length of the
+ * list stays on the device: the launch form is asynchronous on the caller's stream, waits for nothing but the palette's
+ * change (as every render) and can be captured into a graph after a first call.  Scratch: 12 bytes per base sample of the
+ * haloed band plus 4 per pixel of the band for the list, within MBK_RENDER_BAND_BYTES; max_band_rows keeps its meaning.
+ * _compute keeps one byte per pixel for the mask behind the ctx' device image.
+ *
+ * `flags` are those mbk_view_render_* accepts for MBK_RENDER_SMOOTH: kernel selection, which applies to the base pass;
+ * MBK_KERNEL_ASM also runs the refine kernel on the per-step loop instead of the grouped loop with the cycle test (same
+ * image).  MBK_ERR_INVALID, with nothing written: whatever mbk_view_render_* refuses for MBK_RENDER_SMOOTH, any other source,
+ * threshold > 256, MBK_PRECISION_F32.  d_mask / h_mask may be NULL.
+ *
+ * Out of scope: Julia, deep and extended-range deep views (each is one more kind of sample launch on the same three steps); the
+ * bytes, distance and equalised sources; a distance-guided criterion, which would also catch filaments thinner than a pixel
+ * inside a region of one colour (this criterion sees only what the s = 1 samples hit); sharding and slot forms.
+ */
+int mbk_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                    uint32_t threshold, uint8_t *d_rgba, uint8_t *d_mask, void *hip_stream);
+int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                     uint32_t threshold, uint8_t *h_rgba, uint8_t *h_mask, mbk_stats *stats);
+/* The contract on the HOST for caller-supplied samples, no ctx, no device; compiled from the functions the kernels use.
+ * base_*: the samples of the FULL width x height view; fine_*: those of the FULL (width s) x (height s) view, row-major.
+ * rgba: width * height * 4 bytes; mask: width * height bytes or NULL.  MBK_ERR_INVALID as above, for a NULL sample array or
+ * rgba, and for a width or height of 0 or width s, height s >= 2^31. */
+int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, uint32_t width, uint32_t height,
+                             const int32_t *base_counts, const double *base_smooth, const int32_t *fine_counts,
+                             const double *fine_smooth, uint8_t *rgba, uint8_t *mask);
+
+/*
  * Count histograms and histogram-equalised colouring.  NOT in the reference; additive (the ABI version stays 5): no existing
  * call changes.  Every colouring above maps a sample to a palette position through a scale and an offset the caller must
  * already know; a deep view's escaped counts lie in a narrow, unknown interval far from 0.  A histogram of the view's counts,
