@@ -44,6 +44,7 @@
 #include "mbk_julia_distance.h"
 #include "mbk_density.h"
 #include "mbk_adaptive.h"
+#include "mbk_deep_adaptive.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -219,18 +220,24 @@ struct mbk_ctx {
     double probe_share = 0.0;
     bool probe_valid = false;
     // deep-zoom views: this ctx's device copies of the orbits it has used, by orbit id (deep_copy)
-    // beside each, the bilinear-approximation table of the last dcmax it was launched with (MBK_DEEP_BLA; bla_copy) and the
-    // wide table, once a wide view has been launched on the orbit (wide_copy); beside that, the wide bilinear-approximation
-    // table of the last dcmax an MBK_DEEP_XBLA launch brought (xbla_copy)
+    // beside each, the bilinear-approximation tables of the two dcmax it was last launched with (MBK_DEEP_BLA; bla_copy: an
+    // adaptive render needs the base view's and the fine view's at once) and the wide table, once a wide view has been
+    // launched on the orbit (wide_copy); beside that, the wide bilinear-approximation table of the last dcmax an MBK_DEEP_XBLA
+    // launch brought (xbla_copy)
+    struct BlaSlot {
+        bool has;
+        uint64_t dcmax_bits;
+        uint64_t used;                 // bla_clock at the last launch that asked for it: the smaller one is replaced
+        double *d_rc;
+        double4 *d_ab;
+    };
     struct DeepCopy {
         uint64_t id;
         double4 *d;
         mbk::WideEntry *d_wide;
-        bool has_bla;
-        uint64_t dcmax_bits;
-        double *d_rc;
-        double4 *d_ab;
-        uint32_t levels;
+        BlaSlot bla[2];
+        uint64_t bla_clock;
+        uint32_t levels;               // (the levels and their offsets depend on M alone: the same for every dcmax)
         uint32_t off[mbk::kBlaMaxLevels];
         bool has_xbla;
         uint64_t xdcmax_bits;          // dcmax's mantissa
@@ -403,8 +410,10 @@ static int validate_view(mbk_ctx *ctx, const mbk_view *v, bool *safe_doubling, b
 static void free_deep_copy(mbk_ctx::DeepCopy &c)
 {
     if (c.d) (void)hipFree(c.d);
-    if (c.d_rc) (void)hipFree(c.d_rc);
-    if (c.d_ab) (void)hipFree(c.d_ab);
+    for (mbk_ctx::BlaSlot &b : c.bla) {
+        if (b.d_rc) (void)hipFree(b.d_rc);
+        if (b.d_ab) (void)hipFree(b.d_ab);
+    }
     if (c.d_wide) (void)hipFree(c.d_wide);
     if (c.d_xke) (void)hipFree(c.d_xke);
     if (c.d_xab) (void)hipFree(c.d_xab);
@@ -2814,38 +2823,72 @@ static double deep_dcmax(const mbk_deep_view *v)
     return s;
 }
 
-// This ctx's device copy of `orbit` (deep_copy) with the table of `dcmax` beside it.  The table is built on the host and
-// uploaded when the copy has none or has another dcmax's: synchronously, and after the device has drained, since a launch that
-// reads the table it replaces may still be queued (mbk.h).  M >= 2.
-static int bla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, double dcmax, const mbk_ctx::DeepCopy **out)
+static uint64_t dcmax_key(double dcmax)
+{
+    uint64_t bits;
+    std::memcpy(&bits, &dcmax, sizeof(bits));
+    return bits;
+}
+
+// the resident table of `dcmax` beside the copy, or NULL
+static mbk_ctx::BlaSlot *bla_find(mbk_ctx::DeepCopy *c, double dcmax)
+{
+    for (mbk_ctx::BlaSlot &b : c->bla)
+        if (b.has && b.dcmax_bits == dcmax_key(dcmax)) return &b;
+    return nullptr;
+}
+
+// This ctx's device copy of `orbit` (deep_copy) with the table of `dcmax` beside it.  A copy holds two tables (DESIGN.md "Two
+// tables per orbit").  A table that is not resident is built on the host and uploaded, synchronously, into a free place or
+// over the table asked for least recently -- never over `keep` --, and that only after the device has drained, since a launch
+// that reads the table it replaces may still be queued (mbk.h).  *out and *table point into ctx->deep: good until the next
+// call.  M >= 2.
+static int bla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, double dcmax, const mbk_ctx::DeepCopy **out,
+                    const mbk_ctx::BlaSlot **table, const mbk_ctx::BlaSlot *keep = nullptr)
 {
     mbk_ctx::DeepCopy *c = nullptr;
     int rc = deep_copy(ctx, orbit, &c);
     if (rc != MBK_OK) return rc;
     *out = c;
-    uint64_t bits;
-    std::memcpy(&bits, &dcmax, sizeof(bits));
-    if (c->has_bla && c->dcmax_bits == bits) return MBK_OK;
+    mbk_ctx::BlaSlot *b = bla_find(c, dcmax);
+    if (b) {
+        b->used = ++c->bla_clock;
+        *table = b;
+        return MBK_OK;
+    }
+    for (mbk_ctx::BlaSlot &x : c->bla) {
+        if (&x == keep) continue;
+        if (!b || (b->has && (!x.has || x.used < b->used))) b = &x;
+    }
     mbk::BlaTable t;
     try {
         mbk::build_bla_table(orbit->o.table, orbit->o.length, dcmax, &t);
     } catch (const std::bad_alloc &) {
         return fail(ctx, MBK_ERR_NOMEM, "out of host memory for the bilinear-approximation table");
     }
-    if (c->has_bla) MBK_HIP(ctx, hipDeviceSynchronize());
-    c->has_bla = false;
-    if (!c->d_rc) {   // the sizes depend on M alone: allocated once per copy
-        const size_t n = t.rc.size();
-        MBK_HIP(ctx, hipMalloc((void **)&c->d_rc, n * sizeof(double)));
-        MBK_HIP(ctx, hipMalloc((void **)&c->d_ab, n * sizeof(double4)));
-    }
-    MBK_HIP(ctx, hipMemcpy(c->d_rc, t.rc.data(), t.rc.size() * sizeof(double), hipMemcpyHostToDevice));
-    MBK_HIP(ctx, hipMemcpy(c->d_ab, t.ab.data(), t.ab.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (b->has) MBK_HIP(ctx, hipDeviceSynchronize());
+    b->has = false;
+    // the sizes depend on M alone: allocated once per place
+    if (!b->d_rc) MBK_HIP(ctx, hipMalloc((void **)&b->d_rc, t.rc.size() * sizeof(double)));
+    if (!b->d_ab) MBK_HIP(ctx, hipMalloc((void **)&b->d_ab, t.rc.size() * sizeof(double4)));
+    MBK_HIP(ctx, hipMemcpy(b->d_rc, t.rc.data(), t.rc.size() * sizeof(double), hipMemcpyHostToDevice));
+    MBK_HIP(ctx, hipMemcpy(b->d_ab, t.ab.data(), t.ab.size() * sizeof(double), hipMemcpyHostToDevice));
     c->levels = t.levels;
     std::memcpy(c->off, t.off, sizeof(c->off));
-    c->dcmax_bits = bits;
-    c->has_bla = true;
+    b->dcmax_bits = dcmax_key(dcmax);
+    b->used = ++c->bla_clock;
+    b->has = true;
+    *table = b;
     return MBK_OK;
+}
+
+// the table of a launch in a kernel's arguments
+static void fill_bla_table(mbk::DeepBlaArgs &a, const mbk_ctx::DeepCopy *c, const mbk_ctx::BlaSlot *table)
+{
+    a.rc = table->d_rc;
+    a.ab = table->d_ab;
+    a.levels = c->levels;
+    std::memcpy(a.off, c->off, sizeof(a.off));
 }
 
 // the deep kernel on device pointers (validated by the caller), on `stream`; bla: MBK_DEEP_BLA (an orbit of length 1 has no
@@ -2855,16 +2898,14 @@ static int launch_deep(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep
 {
     if (bla && orbit->o.length >= 2u) {
         const mbk_ctx::DeepCopy *c = nullptr;
-        int rc = bla_copy(ctx, orbit, deep_dcmax(v), &c);
+        const mbk_ctx::BlaSlot *table = nullptr;
+        int rc = bla_copy(ctx, orbit, deep_dcmax(v), &c, &table);
         if (rc != MBK_OK) return rc;
         mbk::DeepBlaArgs a;
         std::memset(&a, 0, sizeof(a));
         fill_deep_args(a.v, c->d, orbit, v, mrd);
         fill_outputs(a.v, mrd, d_counts, d_bytes, d_smooth);
-        a.rc = c->d_rc;
-        a.ab = c->d_ab;
-        a.levels = c->levels;
-        std::memcpy(a.off, c->off, sizeof(a.off));
+        fill_bla_table(a, c, table);
         hipLaunchKernelGGL(mbk::deep_bla_kernel, block_grid(a.v), dim3(64), 0, stream, a);
         MBK_HIP(ctx, hipGetLastError());
         return MBK_OK;
@@ -3403,16 +3444,14 @@ static int launch_deep_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, c
 {
     if (orbit->o.length < 2u) return launch_deep_distance(ctx, orbit, v, mrd, d_counts, d_rel, stream);
     const mbk_ctx::DeepCopy *c = nullptr;
-    int rc = bla_copy(ctx, orbit, deep_dcmax(v), &c);
+    const mbk_ctx::BlaSlot *table = nullptr;
+    int rc = bla_copy(ctx, orbit, deep_dcmax(v), &c, &table);
     if (rc != MBK_OK) return rc;
     mbk::DeepDistanceBlaArgs a;
     std::memset(&a, 0, sizeof(a));
     fill_deep_args(a.b.v, c->d, orbit, v, mrd);
     a.b.v.counts = d_counts;
-    a.b.rc = c->d_rc;
-    a.b.ab = c->d_ab;
-    a.b.levels = c->levels;
-    std::memcpy(a.b.off, c->off, sizeof(a.b.off));
+    fill_bla_table(a.b, c, table);
     a.range_r = v->range_r;
     a.rel = d_rel;
     hipLaunchKernelGGL(mbk::deep_distance_bla_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
@@ -4334,7 +4373,8 @@ int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double 
     return resolve_host(spec, true, h_lut, lut_len, width, height, counts, nullptr, smooth, rgba);
 }
 
-// ---- adaptive supersampling (mbk.h "Adaptive supersampling", mbk_adaptive.h): plain views, MBK_RENDER_SMOOTH ----------------
+// ---- adaptive supersampling (mbk.h "Adaptive supersampling" and "Adaptive supersampling of deep views"; mbk_adaptive.h,
+// mbk_deep_adaptive.h): plain and deep views, MBK_RENDER_SMOOTH ----------------------------------------------------------
 
 // Everything an adaptive render can refuse, before anything is allocated, enqueued or written: its own rules, then the smooth
 // render's for the sample view at s (render_check) and the sample launch's for the base view.
@@ -4344,6 +4384,8 @@ static int adaptive_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t 
     if (spec && spec->source != MBK_RENDER_SMOOTH)
         return fail(ctx, MBK_ERR_INVALID, "adaptive supersampling is implemented for MBK_RENDER_SMOOTH only");
     if (threshold > 256u) return fail(ctx, MBK_ERR_INVALID, "threshold must lie in [0, 256]");
+    if (t.kind == Target::kDeep && (flags & MBK_DEEP_XBLA))
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA belongs to extended-range deep views, which adaptive supersampling does not cover (a deep view takes MBK_DEEP_BLA)");
     int rc = render_check(ctx, t, mrd, flags, spec, out);
     if (rc != MBK_OK) return rc;
     return target_check(ctx, target_samples(t, 1u, 0u, 0u, t.g.width, t.g.height), mrd, flags);
@@ -4366,11 +4408,70 @@ static BandPlan adaptive_band_plan(uint32_t ncols, uint32_t nrows, uint32_t max_
     return p;
 }
 
+// The tables of a checked adaptive render of a deep view with MBK_DEEP_BLA, acquired TOGETHER before the render enqueues
+// anything: the base pass steps with the table of the W x H view's dcmax, the refine kernel with that of the (W s) x (H s)
+// view's, and neither may take the other's place (bla_copy's `keep`); equal dcmax are one table.  Once both are resident this
+// finds them and waits for nothing.  fine: the refine kernel's table, copied out of the ctx; rc stays NULL where the refine
+// kernel takes the plain step (no flag, an orbit of length 1) or does not run (s = 1, threshold 256: the base pass looks its
+// own table up, as every deep launch does).
+static int adaptive_tables(mbk_ctx *ctx, const Target &t, uint32_t flags, uint32_t s, uint32_t threshold, mbk::DeepBlaArgs *fine)
+{
+    std::memset(fine, 0, sizeof(*fine));
+    if (t.kind != Target::kDeep || !(flags & MBK_DEEP_BLA) || t.orbit->o.length < 2u || s == 1u || threshold == 256u) return MBK_OK;
+    const Target b = target_samples(t, 1u, 0u, 0u, t.g.width, t.g.height), f = target_samples(t, s, 0u, 0u, t.g.width, t.g.height);
+    const double dc_base = deep_dcmax(&b.deep), dc_fine = deep_dcmax(&f.deep);
+    mbk_ctx::DeepCopy *c = nullptr;
+    int rc = deep_copy(ctx, t.orbit, &c);
+    if (rc != MBK_OK) return rc;
+    const mbk_ctx::DeepCopy *cc = nullptr;
+    const mbk_ctx::BlaSlot *tb = nullptr, *tf = nullptr;
+    rc = bla_copy(ctx, t.orbit, dc_base, &cc, &tb, bla_find(c, dc_fine));
+    if (rc != MBK_OK) return rc;
+    rc = bla_copy(ctx, t.orbit, dc_fine, &cc, &tf, tb);
+    if (rc != MBK_OK) return rc;
+    fill_bla_table(*fine, cc, tf);
+    return MBK_OK;
+}
+
+// The refine step of a deep view's band: the fine samples of the listed pixels by perturbation (mbk_deep_adaptive.h), with the
+// skips of `fine` where it holds a table.  (x0, y0, nc, nr): the band in the W x H view.
+static int launch_deep_refine(mbk_ctx *ctx, const Target &t, uint32_t s, uint32_t x0, uint32_t y0, uint32_t nc, uint32_t nr, uint32_t mrd,
+                              const mbk::DeepBlaArgs &fine, const mbk::AdaptiveClassifyArgs &a, uint32_t *d_words, hipStream_t stream)
+{
+    mbk_ctx::DeepCopy *c = nullptr;
+    int rc = deep_copy(ctx, t.orbit, &c);
+    if (rc != MBK_OK) return rc;
+    const Target samples = target_samples(t, s, x0, y0, nc, nr);
+    mbk::DeepAdaptiveRefineArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.b = fine;
+    fill_deep_args(f.b.v, c->d, t.orbit, &samples.deep, mrd);
+    f.nc = nc;
+    f.list = a.list;
+    f.len = d_words;
+    f.cursor = d_words + 1;
+    f.out = a.out;
+    f.out_pitch = a.out_pitch;
+    f.stats = a.stats;
+    f.pal = a.pal;
+    // 5 waves per SIMD, which every instantiation's registers allow at once (74 .. 85 VGPRs: 5 or 6); no more workgroups than
+    // groups the fullest list can hold
+    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
+    const uint32_t per_group = 64u / (s * s);
+    const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
+    const dim3 grid((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * 5u));
+    if (fine.rc) mbk::launch_deep_adaptive_refine<true>(s, grid, stream, f);
+    else mbk::launch_deep_adaptive_refine<false>(s, grid, stream, f);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // A checked adaptive render (adaptive_check) onto the device image d_out (ncols x nrows words) and, if not NULL, the device
 // mask d_mask (ncols x nrows bytes), on `stream`.  stat: the slot whose reduction scratch the classify and refine kernels add
-// their samples' statistics to and whose ev_k1 marks the last kernel (_compute), or NULL.
+// their samples' statistics to and whose ev_k1 marks the last kernel (_compute), or NULL.  fine: adaptive_tables' (deep views).
 static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                        uint32_t threshold, uint32_t *d_out, uint8_t *d_mask, hipStream_t stream, Slot *stat)
+                        uint32_t threshold, uint32_t *d_out, uint8_t *d_mask, hipStream_t stream, Slot *stat,
+                        const mbk::DeepBlaArgs *fine = nullptr)
 {
     const uint32_t s = spec->supersample;
     StreamScratch *sc = nullptr;
@@ -4435,8 +4536,12 @@ static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t fl
         hipLaunchKernelGGL(mbk::adaptive_classify_kernel, dim3((uint32_t)std::min<uint64_t>(tiles, (uint64_t)cus * wg_per_cu)), dim3(256),
                            use_lds ? lds : 0u, stream, a);
         MBK_HIP(ctx, hipGetLastError());
-        // 3. refine: the fine samples of the listed pixels (at s = 1 a refined pixel is its base pixel: nothing to do)
-        if (s > 1u && threshold < 256u) {
+        // 3. refine: the fine samples of the listed pixels (at s = 1 a refined pixel is its base pixel: nothing to do), by the
+        // kernel of the kind
+        if (s > 1u && threshold < 256u && t.kind == Target::kDeep) {
+            rc = launch_deep_refine(ctx, t, s, x0, y0, nc, nr, mrd, *fine, a, d_words, stream);
+            if (rc != MBK_OK) return rc;
+        } else if (s > 1u && threshold < 256u) {
             mbk::AdaptiveRefineArgs f;
             std::memset(&f, 0, sizeof(f));
             f.re = make_axis(t.view.start_r, t.view.range_r, t.g.width * s);
@@ -4471,26 +4576,31 @@ static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t fl
     return launch_reduce(ctx, stat->d_red, stat->h_red, nullptr, nullptr, 0u, mrd, stream, false);
 }
 
-int mbk_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                                    uint32_t threshold, uint8_t *d_rgba, uint8_t *d_mask, void *hip_stream)
+// The two forms of an adaptive render on a target: device pointers on a stream, host pointers synchronously on slot 0.
+static int adaptive_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                           uint32_t threshold, uint8_t *d_rgba, uint8_t *d_mask, void *hip_stream)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    const Target t = view_target(view);
     int rc = adaptive_check(ctx, t, mrd, flags, spec, threshold, d_rgba);
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return adaptive_run(ctx, t, mrd, flags, spec, threshold, (uint32_t *)d_rgba, d_mask, (hipStream_t)hip_stream, nullptr);
+    mbk::DeepBlaArgs fine;
+    rc = adaptive_tables(ctx, t, flags, spec->supersample, threshold, &fine);
+    if (rc != MBK_OK) return rc;
+    return adaptive_run(ctx, t, mrd, flags, spec, threshold, (uint32_t *)d_rgba, d_mask, (hipStream_t)hip_stream, nullptr, &fine);
 }
 
-int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
-                                     uint32_t threshold, uint8_t *h_rgba, uint8_t *h_mask, mbk_stats *stats)
+static int adaptive_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                            uint32_t threshold, uint8_t *h_rgba, uint8_t *h_mask, mbk_stats *stats)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    const Target t = view_target(view);
     int rc = adaptive_check(ctx, t, mrd, flags, spec, threshold, h_rgba);
     if (rc != MBK_OK) return rc;
     rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepBlaArgs fine;
+    rc = adaptive_tables(ctx, t, flags, spec->supersample, threshold, &fine);
     if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
     const size_t px = (size_t)t.g.ncols * t.g.nrows;
@@ -4502,7 +4612,7 @@ int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_
         uint8_t *d_mask = h_mask ? (uint8_t *)(ctx->d_rgba + px) : nullptr;
         MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-        rc = adaptive_run(ctx, t, mrd, flags, spec, threshold, ctx->d_rgba, d_mask, sl.stream, &sl);
+        rc = adaptive_run(ctx, t, mrd, flags, spec, threshold, ctx->d_rgba, d_mask, sl.stream, &sl, &fine);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
@@ -4511,6 +4621,32 @@ int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_
         return MBK_OK;
     };
     return sync_end(ctx, enqueue(), stats, false);
+}
+
+int mbk_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                    uint32_t threshold, uint8_t *d_rgba, uint8_t *d_mask, void *hip_stream)
+{
+    return adaptive_launch(ctx, view_target(view), mrd, flags, spec, threshold, d_rgba, d_mask, hip_stream);
+}
+
+int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
+                                     uint32_t threshold, uint8_t *h_rgba, uint8_t *h_mask, mbk_stats *stats)
+{
+    return adaptive_compute(ctx, view_target(view), mrd, flags, spec, threshold, h_rgba, h_mask, stats);
+}
+
+int mbk_deep_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                         uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *d_rgba,
+                                         uint8_t *d_mask, void *hip_stream)
+{
+    return adaptive_launch(ctx, deep_target(orbit, view), mrd, flags, spec, threshold, d_rgba, d_mask, hip_stream);
+}
+
+int mbk_deep_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *h_rgba,
+                                          uint8_t *h_mask, mbk_stats *stats)
+{
+    return adaptive_compute(ctx, deep_target(orbit, view), mrd, flags, spec, threshold, h_rgba, h_mask, stats);
 }
 
 int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, uint32_t width, uint32_t height,

@@ -414,12 +414,12 @@ int mbk_deep_view_submit(mbk_ctx *ctx, int slot, const mbk_deep_orbit *orbit, co
  *             seahorse view at span 1e-20, mrd 30000; the 2^-24 the literature suggests for binary64 reaches 88.75 % there, off
  *             by up to 140 (tests/test_deep_bla.py keeps that test).  The same cap as the plain contract: >= 99 % of pixels.
  *
- * The ctx keeps the device copy of one table beside each orbit copy, keyed by the orbit's id and the bits of dcmax: 40 bytes
- * per entry, fewer than 2 (M - 1) entries.  It is built on the host and uploaded on the first MBK_DEEP_BLA launch of the orbit
- * on the ctx, and REBUILT whenever a launch brings another dcmax (another span or aspect of the full view) -- synchronously, and
- * the rebuild first synchronises the device, since a queued launch may still read the table it replaces.  So the orbit's
- * "first launch" rule covers it: launch once per (orbit, spans) before capturing, and expect alternating spans on one orbit to
- * serialise.  The table is freed with the orbit copies.
+ * The ctx keeps the device copies of up to two tables beside each orbit copy, keyed by the orbit's id and the bits of dcmax:
+ * 40 bytes per entry, fewer than 2 (M - 1) entries each.  A table is built on the host and uploaded, synchronously, by the
+ * first MBK_DEEP_BLA launch on the ctx that brings its dcmax (another span, aspect or size of the full view); once both places
+ * are taken it goes over the table asked for least recently, and that first synchronises the device, since a queued launch may
+ * still read the table it replaces.  So the orbit's "first launch" rule covers it: launch once per (orbit, spans) before
+ * capturing, and expect three or more dcmax in turn on one orbit to serialise.  The tables are freed with the orbit copies.
  */
 #define MBK_DEEP_BLA 0x8000u
 /* Host twins for the CPU tests, compiled from the functions the builder and the kernel use: no ctx, no device.  `view` gives
@@ -758,8 +758,9 @@ int mbk_deep_orbit_size_host(const mbk_deep_orbit *orbit, uint32_t period, doubl
  * message of its own: the name selects the rule --, an orbit longer than 2^31 and whatever mbk_deep_view_launch refuses (mrd
  * above the orbit's, an empty window, ranges outside [2^-960, 4]).  The render calls take MBK_RENDER_DISTANCE_REL only: the
  * banding, supersampling and colour code of "Rendering" on these samples, as mbk_deep_xview_distance_render_* are for
- * extended-range views.  The ctx's table is the one of the MBK_DEEP_BLA count launches, keyed by the orbit's id and dcmax and
- * shared with them: launch once per (orbit, spans) before capturing, and expect alternating spans on one orbit to serialise.
+ * extended-range views.  The ctx's tables are those of the MBK_DEEP_BLA count launches, keyed by the orbit's id and dcmax and
+ * shared with them: launch once per (orbit, spans) before capturing, and expect three or more spans in turn on one orbit to
+ * serialise.
  */
 int mbk_deep_view_launch_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                       uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
@@ -1137,7 +1138,7 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
  * image).  MBK_ERR_INVALID, with nothing written: whatever mbk_view_render_* refuses for MBK_RENDER_SMOOTH, any other source,
  * threshold > 256, MBK_PRECISION_F32.  d_mask / h_mask may be NULL.
  *
- * Out of scope: Julia, deep and extended-range deep views (each is one more kind of sample launch on the same three steps); the
+ * Out of scope: Julia and extended-range deep views (each is one more kind of sample launch on the same three steps); the
  * bytes, distance and equalised sources; a distance-guided criterion, which would also catch filaments thinner than a pixel
  * inside a region of one colour (this criterion sees only what the s = 1 samples hit); sharding and slot forms.
  */
@@ -1152,6 +1153,47 @@ int mbk_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_view *view, uint32_
 int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, uint32_t width, uint32_t height,
                              const int32_t *base_counts, const double *base_smooth, const int32_t *fine_counts,
                              const double *fine_smooth, uint8_t *rgba, uint8_t *mask);
+
+/*
+ * Adaptive supersampling of deep views: the same for mbk_deep_view, with the plain step and with MBK_DEEP_BLA.  NOT in the
+ * reference; additive (the ABI version stays 5): no existing call, flag or default changes.  A deep sample costs thousands of
+ * perturbation steps, and mbk_deep_view_render_* at factor s pays s^2 of them for every pixel.
+ *
+ * Contract: that of "Adaptive supersampling" word for word (tests/adaptive_model.py; tests/test_deep_adaptive.py and
+ * tests/test_gpu_deep_adaptive.py hold the host twin and the GPU to it), with
+ *   base      B[y][x] the MBK_RENDER_SMOOTH colour of sample (x, y) of the W x H view, count and nu exactly as
+ *             mbk_deep_view_launch stores them;
+ *   refined   pixel: the pixel of mbk_deep_view_render_launch at factor s;
+ *   flags     0 or MBK_DEEP_BLA.  With the bit set both kinds of sample are those of MBK_DEEP_BLA: the base samples step with
+ *             the table of the W x H view's dcmax, the fine samples with the table of the (W s) x (H s) view's -- the two
+ *             differ for many shapes, since dcmax is formed from the half-widths in samples -- which is exactly what
+ *             mbk_deep_view_render_* with the flag uses at 1 and at s.
+ * So threshold 0 equals mbk_deep_view_render_* at s bit for bit, threshold 256 equals it at 1, s = 1 equals it at 1 at every
+ * threshold, and a window or a band is bit-identical to the same rectangle of the whole image.  The mask and the stats keep
+ * their meaning: the stats count the stored counts of the window's base samples plus the s^2 fine samples of each refined
+ * pixel, the halo is not counted, and with MBK_DEEP_BLA they follow the counts, not the steps executed.
+ *
+ * How it runs (csrc/mbk_deep_adaptive.h).  The three steps, the scratch layout, the band plan, the halo, the palette staging and
+ * _compute's mask placement are those above; the base pass is the deep sample launch and the refine kernel computes the listed
+ * pixels' fine samples by perturbation, one lane per sample, with the table's skips under MBK_DEEP_BLA (an orbit of length 1
+ * has no table: the flag changes nothing).  The ctx keeps TWO tables beside each orbit copy (see "Deep-zoom views with bilinear
+ * approximation"); a render with the flag acquires the base view's and the fine view's together before it enqueues anything,
+ * and neither takes the other's place (equal dcmax: one table).  A first call with a given (orbit, view, s) may therefore build
+ * and upload synchronously; after it the launch form performs no host synchronisation for as long as both tables stay
+ * resident -- until a launch on the same orbit brings a third dcmax -- and can be captured into a graph.
+ *
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_view_render_* refuses for MBK_RENDER_SMOOTH, any other source,
+ * threshold > 256, any flag but MBK_DEEP_BLA (MBK_DEEP_XBLA with a message of its own).  d_mask / h_mask may be NULL.
+ *
+ * Out of scope: mbk_deep_xview; Julia views; the equalised, bytes and MBK_RENDER_DISTANCE_REL sources; a distance-guided
+ * criterion; sharding and slot forms.
+ */
+int mbk_deep_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                         uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *d_rgba,
+                                         uint8_t *d_mask, void *hip_stream);
+int mbk_deep_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *h_rgba,
+                                          uint8_t *h_mask, mbk_stats *stats);
 
 /*
  * Count histograms and histogram-equalised colouring.  NOT in the reference; additive (the ABI version stays 5): no existing
