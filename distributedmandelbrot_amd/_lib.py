@@ -350,6 +350,12 @@ SIGNATURES = {
     "mbk_deep_view_render_adaptive_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,
                                                         C.POINTER(mbk_render_spec), C.c_uint32, C.c_void_p, C.c_void_p,
                                                         C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_render_adaptive_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                        C.POINTER(mbk_render_spec), C.c_uint32, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]),
+    "mbk_deep_xview_render_adaptive_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                         C.POINTER(mbk_render_spec), C.c_uint32, C.c_void_p, C.c_void_p,
+                                                         C.POINTER(mbk_stats)]),
     "mbk_counts_histogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_view_histogram_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_deep_view_histogram_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32,

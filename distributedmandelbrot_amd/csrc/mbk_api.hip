@@ -45,6 +45,7 @@
 #include "mbk_density.h"
 #include "mbk_adaptive.h"
 #include "mbk_deep_adaptive.h"
+#include "mbk_deep_wide_adaptive.h"
 
 using mbk::Axis;
 using mbk::ReduceOut;
@@ -222,14 +223,22 @@ struct mbk_ctx {
     // deep-zoom views: this ctx's device copies of the orbits it has used, by orbit id (deep_copy)
     // beside each, the bilinear-approximation tables of the two dcmax it was last launched with (MBK_DEEP_BLA; bla_copy: an
     // adaptive render needs the base view's and the fine view's at once) and the wide table, once a wide view has been
-    // launched on the orbit (wide_copy); beside that, the wide bilinear-approximation table of the last dcmax an MBK_DEEP_XBLA
-    // launch brought (xbla_copy)
+    // launched on the orbit (wide_copy); beside that, the wide bilinear-approximation tables of the two dcmax the MBK_DEEP_XBLA
+    // launches last brought (xbla_copy: the same rule, for the same reason)
     struct BlaSlot {
         bool has;
         uint64_t dcmax_bits;
         uint64_t used;                 // bla_clock at the last launch that asked for it: the smaller one is replaced
         double *d_rc;
         double4 *d_ab;
+    };
+    struct XblaSlot {
+        bool has;
+        uint64_t dcmax_bits;           // dcmax's mantissa
+        int32_t dcmax_exp;             // ... and exponent
+        uint64_t used;                 // xbla_clock at the last launch that asked for it: the smaller one is replaced
+        int32_t *d_ke;
+        mbk::WideBlaEntry *d_ab;
     };
     struct DeepCopy {
         uint64_t id;
@@ -239,12 +248,9 @@ struct mbk_ctx {
         uint64_t bla_clock;
         uint32_t levels;               // (the levels and their offsets depend on M alone: the same for every dcmax)
         uint32_t off[mbk::kBlaMaxLevels];
-        bool has_xbla;
-        uint64_t xdcmax_bits;          // dcmax's mantissa
-        int32_t xdcmax_exp;            // ... and exponent
-        int32_t *d_xke;
-        mbk::WideBlaEntry *d_xab;
-        uint32_t xlevels;
+        XblaSlot xbla[2];
+        uint64_t xbla_clock;
+        uint32_t xlevels;              // (as levels and off: of M alone)
         uint32_t xoff[mbk::kBlaMaxLevels];
     };
     std::vector<DeepCopy> deep;
@@ -415,8 +421,10 @@ static void free_deep_copy(mbk_ctx::DeepCopy &c)
         if (b.d_ab) (void)hipFree(b.d_ab);
     }
     if (c.d_wide) (void)hipFree(c.d_wide);
-    if (c.d_xke) (void)hipFree(c.d_xke);
-    if (c.d_xab) (void)hipFree(c.d_xab);
+    for (mbk_ctx::XblaSlot &b : c.xbla) {
+        if (b.d_ke) (void)hipFree(b.d_ke);
+        if (b.d_ab) (void)hipFree(b.d_ab);
+    }
     c = mbk_ctx::DeepCopy();
 }
 
@@ -3042,10 +3050,22 @@ static mbk::WideReal wide_view_dcmax(const mbk_deep_xview *v)
     return mbk::wide_dcmax(deep_dc(0u, v->width, v->range_r), deep_dc(0u, v->height, v->range_i), v->exp2);
 }
 
+// the resident wide table of `dcmax` beside the copy, or NULL
+static mbk_ctx::XblaSlot *xbla_find(mbk_ctx::DeepCopy *c, const mbk::WideReal &dcmax)
+{
+    for (mbk_ctx::XblaSlot &b : c->xbla)
+        if (b.has && b.dcmax_bits == dcmax_key(dcmax.f) && b.dcmax_exp == dcmax.e) return &b;
+    return nullptr;
+}
+
 // This ctx's device copy of `orbit` with its wide table (wide_copy) and the wide bilinear-approximation table of `dcmax`
-// beside it: bla_copy's rule -- built on the host and uploaded when the copy has none or has another dcmax's, synchronously,
-// and after the device has drained, since a launch that reads the table it replaces may still be queued (mbk.h).  M >= 2.
-static int xbla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideReal &dcmax, const mbk_ctx::DeepCopy **out)
+// beside it: bla_copy's rule.  A copy holds two tables, keyed by dcmax's mantissa bits and exponent.  A table that is not
+// resident is built on the host and uploaded, synchronously, into a free place or over the table asked for least recently --
+// never over `keep` --, and that only after the device has drained, since a launch that reads the table it replaces may still
+// be queued (mbk.h).  The second place is allocated when a second dcmax arrives.  *out and *table point into ctx->deep: good
+// until the next call.  M >= 2.
+static int xbla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideReal &dcmax, const mbk_ctx::DeepCopy **out,
+                     const mbk_ctx::XblaSlot **table, const mbk_ctx::XblaSlot *keep = nullptr)
 {
     const mbk::WideEntry *d_orbit = nullptr;
     int rc = wide_copy(ctx, orbit, &d_orbit);
@@ -3054,29 +3074,46 @@ static int xbla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideR
     rc = deep_copy(ctx, orbit, &c);
     if (rc != MBK_OK) return rc;
     *out = c;
-    uint64_t bits;
-    std::memcpy(&bits, &dcmax.f, sizeof(bits));
-    if (c->has_xbla && c->xdcmax_bits == bits && c->xdcmax_exp == dcmax.e) return MBK_OK;
+    mbk_ctx::XblaSlot *b = xbla_find(c, dcmax);
+    if (b) {
+        b->used = ++c->xbla_clock;
+        *table = b;
+        return MBK_OK;
+    }
+    for (mbk_ctx::XblaSlot &x : c->xbla) {
+        if (&x == keep) continue;
+        if (!b || (b->has && (!x.has || x.used < b->used))) b = &x;
+    }
     mbk::WideBlaTable t;
     try {
         mbk::build_wide_bla_table(orbit->o.wide, orbit->o.length, dcmax, &t);
     } catch (const std::bad_alloc &) {
         return fail(ctx, MBK_ERR_NOMEM, "out of host memory for the wide bilinear-approximation table");
     }
-    if (c->has_xbla) MBK_HIP(ctx, hipDeviceSynchronize());
-    c->has_xbla = false;
-    if (!c->d_xke) {   // the sizes depend on M alone: allocated once per copy
-        MBK_HIP(ctx, hipMalloc((void **)&c->d_xke, t.ke.size() * sizeof(int32_t)));
-        MBK_HIP(ctx, hipMalloc((void **)&c->d_xab, t.ab.size() * sizeof(mbk::WideBlaEntry)));
-    }
-    MBK_HIP(ctx, hipMemcpy(c->d_xke, t.ke.data(), t.ke.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    MBK_HIP(ctx, hipMemcpy(c->d_xab, t.ab.data(), t.ab.size() * sizeof(mbk::WideBlaEntry), hipMemcpyHostToDevice));
+    if (b->has) MBK_HIP(ctx, hipDeviceSynchronize());
+    b->has = false;
+    // the sizes depend on M alone: allocated once per place
+    if (!b->d_ke) MBK_HIP(ctx, hipMalloc((void **)&b->d_ke, t.ke.size() * sizeof(int32_t)));
+    if (!b->d_ab) MBK_HIP(ctx, hipMalloc((void **)&b->d_ab, t.ab.size() * sizeof(mbk::WideBlaEntry)));
+    MBK_HIP(ctx, hipMemcpy(b->d_ke, t.ke.data(), t.ke.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    MBK_HIP(ctx, hipMemcpy(b->d_ab, t.ab.data(), t.ab.size() * sizeof(mbk::WideBlaEntry), hipMemcpyHostToDevice));
     c->xlevels = t.levels;
     std::memcpy(c->xoff, t.off, sizeof(c->xoff));
-    c->xdcmax_bits = bits;
-    c->xdcmax_exp = dcmax.e;
-    c->has_xbla = true;
+    b->dcmax_bits = dcmax_key(dcmax.f);
+    b->dcmax_exp = dcmax.e;
+    b->used = ++c->xbla_clock;
+    b->has = true;
+    *table = b;
     return MBK_OK;
+}
+
+// the table of a launch in a wide kernel's arguments
+static void fill_xbla_table(mbk::DeepWideBlaArgs &a, const mbk_ctx::DeepCopy *c, const mbk_ctx::XblaSlot *table)
+{
+    a.ke = table->d_ke;
+    a.ab = table->d_ab;
+    a.levels = c->xlevels;
+    std::memcpy(a.off, c->xoff, sizeof(a.off));
 }
 
 // the wide kernel on device pointers (validated by the caller), on `stream`; xbla: MBK_DEEP_XBLA (an orbit of length 1 has no
@@ -3085,9 +3122,10 @@ static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk
                             int32_t *d_counts, uint8_t *d_bytes, double *d_smooth, hipStream_t stream, bool xbla = false)
 {
     const mbk_ctx::DeepCopy *c = nullptr;
+    const mbk_ctx::XblaSlot *slot = nullptr;
     const mbk::WideEntry *d_orbit = nullptr;
     const bool table = xbla && orbit->o.length >= 2u;
-    int rc = table ? xbla_copy(ctx, orbit, wide_view_dcmax(v), &c) : wide_copy(ctx, orbit, &d_orbit);
+    int rc = table ? xbla_copy(ctx, orbit, wide_view_dcmax(v), &c, &slot) : wide_copy(ctx, orbit, &d_orbit);
     if (rc != MBK_OK) return rc;
     mbk::DeepWideBlaArgs b;
     std::memset(&b, 0, sizeof(b));
@@ -3095,10 +3133,7 @@ static int launch_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk
     fill_deep_wide_args(a, table ? c->d_wide : d_orbit, orbit, v, mrd);
     fill_outputs(a, mrd, d_counts, d_bytes, d_smooth);
     if (table) {
-        b.ke = c->d_xke;
-        b.ab = c->d_xab;
-        b.levels = c->xlevels;
-        std::memcpy(b.off, c->xoff, sizeof(b.off));
+        fill_xbla_table(b, c, slot);
         hipLaunchKernelGGL(mbk::deep_wide_bla_kernel, block_grid(a), dim3(64), 0, stream, b);
     } else {
         hipLaunchKernelGGL(mbk::deep_wide_kernel, block_grid(a), dim3(64), 0, stream, a);
@@ -3486,16 +3521,14 @@ static int launch_deep_wide_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *or
 {
     if (orbit->o.length < 2u) return launch_deep_wide_distance(ctx, orbit, v, mrd, d_counts, d_rel, stream);
     const mbk_ctx::DeepCopy *c = nullptr;
-    int rc = xbla_copy(ctx, orbit, wide_view_dcmax(v), &c);
+    const mbk_ctx::XblaSlot *slot = nullptr;
+    int rc = xbla_copy(ctx, orbit, wide_view_dcmax(v), &c, &slot);
     if (rc != MBK_OK) return rc;
     mbk::DeepWideDistanceBlaArgs a;
     std::memset(&a, 0, sizeof(a));
     fill_deep_wide_args(a.b.v, c->d_wide, orbit, v, mrd);
     a.b.v.counts = d_counts;
-    a.b.ke = c->d_xke;
-    a.b.ab = c->d_xab;
-    a.b.levels = c->xlevels;
-    std::memcpy(a.b.off, c->xoff, sizeof(a.b.off));
+    fill_xbla_table(a.b, c, slot);
     a.range_r = v->range_r;
     a.rel = d_rel;
     hipLaunchKernelGGL(mbk::deep_wide_distance_bla_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
@@ -4373,8 +4406,9 @@ int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double 
     return resolve_host(spec, true, h_lut, lut_len, width, height, counts, nullptr, smooth, rgba);
 }
 
-// ---- adaptive supersampling (mbk.h "Adaptive supersampling" and "Adaptive supersampling of deep views"; mbk_adaptive.h,
-// mbk_deep_adaptive.h): plain and deep views, MBK_RENDER_SMOOTH ----------------------------------------------------------
+// ---- adaptive supersampling (mbk.h "Adaptive supersampling", "Adaptive supersampling of deep views" and "Adaptive
+// supersampling of extended-range deep views"; mbk_adaptive.h, mbk_deep_adaptive.h, mbk_deep_wide_adaptive.h): plain, deep and
+// extended-range deep views, MBK_RENDER_SMOOTH -------------------------------------------------------------------------------
 
 // Everything an adaptive render can refuse, before anything is allocated, enqueued or written: its own rules, then the smooth
 // render's for the sample view at s (render_check) and the sample launch's for the base view.
@@ -4386,7 +4420,12 @@ static int adaptive_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t 
     if (threshold > 256u) return fail(ctx, MBK_ERR_INVALID, "threshold must lie in [0, 256]");
     if (t.kind == Target::kDeep && (flags & MBK_DEEP_XBLA))
         return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA belongs to extended-range deep views, which adaptive supersampling does not cover (a deep view takes MBK_DEEP_BLA)");
-    int rc = render_check(ctx, t, mrd, flags, spec, out);
+    int rc;
+    if (t.kind == Target::kWide && (flags & MBK_DEEP_BLA)) {   // refused in validate_deep_wide's words, not the render rules'
+        rc = target_check(ctx, t, mrd, flags);
+        if (rc != MBK_OK) return rc;
+    }
+    rc = render_check(ctx, t, mrd, flags, spec, out);
     if (rc != MBK_OK) return rc;
     return target_check(ctx, target_samples(t, 1u, 0u, 0u, t.g.width, t.g.height), mrd, flags);
 }
@@ -4408,28 +4447,46 @@ static BandPlan adaptive_band_plan(uint32_t ncols, uint32_t nrows, uint32_t max_
     return p;
 }
 
-// The tables of a checked adaptive render of a deep view with MBK_DEEP_BLA, acquired TOGETHER before the render enqueues
-// anything: the base pass steps with the table of the W x H view's dcmax, the refine kernel with that of the (W s) x (H s)
-// view's, and neither may take the other's place (bla_copy's `keep`); equal dcmax are one table.  Once both are resident this
-// finds them and waits for nothing.  fine: the refine kernel's table, copied out of the ctx; rc stays NULL where the refine
-// kernel takes the plain step (no flag, an orbit of length 1) or does not run (s = 1, threshold 256: the base pass looks its
-// own table up, as every deep launch does).
-static int adaptive_tables(mbk_ctx *ctx, const Target &t, uint32_t flags, uint32_t s, uint32_t threshold, mbk::DeepBlaArgs *fine)
+// The refine kernel's table of an adaptive render, copied out of the ctx (adaptive_tables): deep.rc / wide.ke stay NULL where
+// the refine kernel takes the plain step or does not run.
+struct AdaptiveFine {
+    mbk::DeepBlaArgs deep;         // kDeep, MBK_DEEP_BLA
+    mbk::DeepWideBlaArgs wide;     // kWide, MBK_DEEP_XBLA
+};
+
+// The tables of a checked adaptive render of a deep view with MBK_DEEP_BLA, or of an extended-range deep view with
+// MBK_DEEP_XBLA, acquired TOGETHER before the render enqueues anything: the base pass steps with the table of the W x H view's
+// dcmax, the refine kernel with that of the (W s) x (H s) view's, and neither may take the other's place (bla_copy's and
+// xbla_copy's `keep`); equal dcmax are one table.  Once both are resident this finds them and waits for nothing.  fine: the
+// refine kernel's table, copied out of the ctx; the pointers stay NULL where the refine kernel takes the plain step (no flag, an
+// orbit of length 1) or does not run (s = 1, threshold 256: the base pass looks its own table up, as every deep launch does).
+static int adaptive_tables(mbk_ctx *ctx, const Target &t, uint32_t flags, uint32_t s, uint32_t threshold, AdaptiveFine *fine)
 {
     std::memset(fine, 0, sizeof(*fine));
-    if (t.kind != Target::kDeep || !(flags & MBK_DEEP_BLA) || t.orbit->o.length < 2u || s == 1u || threshold == 256u) return MBK_OK;
+    const bool deep = t.kind == Target::kDeep && (flags & MBK_DEEP_BLA), wide = t.kind == Target::kWide && (flags & MBK_DEEP_XBLA);
+    if ((!deep && !wide) || t.orbit->o.length < 2u || s == 1u || threshold == 256u) return MBK_OK;
     const Target b = target_samples(t, 1u, 0u, 0u, t.g.width, t.g.height), f = target_samples(t, s, 0u, 0u, t.g.width, t.g.height);
-    const double dc_base = deep_dcmax(&b.deep), dc_fine = deep_dcmax(&f.deep);
     mbk_ctx::DeepCopy *c = nullptr;
     int rc = deep_copy(ctx, t.orbit, &c);
     if (rc != MBK_OK) return rc;
     const mbk_ctx::DeepCopy *cc = nullptr;
+    if (wide) {
+        const mbk::WideReal dc_base = wide_view_dcmax(&b.wide), dc_fine = wide_view_dcmax(&f.wide);
+        const mbk_ctx::XblaSlot *tb = nullptr, *tf = nullptr;
+        rc = xbla_copy(ctx, t.orbit, dc_base, &cc, &tb, xbla_find(c, dc_fine));
+        if (rc != MBK_OK) return rc;
+        rc = xbla_copy(ctx, t.orbit, dc_fine, &cc, &tf, tb);
+        if (rc != MBK_OK) return rc;
+        fill_xbla_table(fine->wide, cc, tf);
+        return MBK_OK;
+    }
+    const double dc_base = deep_dcmax(&b.deep), dc_fine = deep_dcmax(&f.deep);
     const mbk_ctx::BlaSlot *tb = nullptr, *tf = nullptr;
     rc = bla_copy(ctx, t.orbit, dc_base, &cc, &tb, bla_find(c, dc_fine));
     if (rc != MBK_OK) return rc;
     rc = bla_copy(ctx, t.orbit, dc_fine, &cc, &tf, tb);
     if (rc != MBK_OK) return rc;
-    fill_bla_table(*fine, cc, tf);
+    fill_bla_table(fine->deep, cc, tf);
     return MBK_OK;
 }
 
@@ -4466,12 +4523,48 @@ static int launch_deep_refine(mbk_ctx *ctx, const Target &t, uint32_t s, uint32_
     return MBK_OK;
 }
 
+// the wide refine grid's waves per SIMD: what all eight instantiations hold at once (65 .. 81 VGPRs: 5 to 7)
+static const uint32_t kWideRefineWaves = 5u;
+
+// The refine step of an extended-range deep view's band: launch_deep_refine's twin in the wide number system
+// (mbk_deep_wide_adaptive.h), on the wide orbit table, with the skips of `fine` where it holds a table.
+static int launch_deep_wide_refine(mbk_ctx *ctx, const Target &t, uint32_t s, uint32_t x0, uint32_t y0, uint32_t nc, uint32_t nr, uint32_t mrd,
+                                   const mbk::DeepWideBlaArgs &fine, const mbk::AdaptiveClassifyArgs &a, uint32_t *d_words, hipStream_t stream)
+{
+    const mbk::WideEntry *d_orbit = nullptr;
+    int rc = wide_copy(ctx, t.orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    const Target samples = target_samples(t, s, x0, y0, nc, nr);
+    mbk::DeepWideAdaptiveRefineArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.b = fine;
+    fill_deep_wide_args(f.b.v, d_orbit, t.orbit, &samples.wide, mrd);
+    f.nc = nc;
+    f.list = a.list;
+    f.len = d_words;
+    f.cursor = d_words + 1;
+    f.out = a.out;
+    f.out_pitch = a.out_pitch;
+    f.stats = a.stats;
+    f.pal = a.pal;
+    // kWideRefineWaves waves per SIMD, which every instantiation's registers allow at once (profiles/deep_wide_adaptive/README.md
+    // has the compiler's table); no more workgroups than groups the fullest list can hold
+    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
+    const uint32_t per_group = 64u / (s * s);
+    const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
+    const dim3 grid((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * kWideRefineWaves));
+    if (fine.ke) mbk::launch_deep_wide_adaptive_refine<true>(s, grid, stream, f);
+    else mbk::launch_deep_wide_adaptive_refine<false>(s, grid, stream, f);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // A checked adaptive render (adaptive_check) onto the device image d_out (ncols x nrows words) and, if not NULL, the device
 // mask d_mask (ncols x nrows bytes), on `stream`.  stat: the slot whose reduction scratch the classify and refine kernels add
 // their samples' statistics to and whose ev_k1 marks the last kernel (_compute), or NULL.  fine: adaptive_tables' (deep views).
 static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                         uint32_t threshold, uint32_t *d_out, uint8_t *d_mask, hipStream_t stream, Slot *stat,
-                        const mbk::DeepBlaArgs *fine = nullptr)
+                        const AdaptiveFine *fine = nullptr)
 {
     const uint32_t s = spec->supersample;
     StreamScratch *sc = nullptr;
@@ -4539,7 +4632,10 @@ static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t fl
         // 3. refine: the fine samples of the listed pixels (at s = 1 a refined pixel is its base pixel: nothing to do), by the
         // kernel of the kind
         if (s > 1u && threshold < 256u && t.kind == Target::kDeep) {
-            rc = launch_deep_refine(ctx, t, s, x0, y0, nc, nr, mrd, *fine, a, d_words, stream);
+            rc = launch_deep_refine(ctx, t, s, x0, y0, nc, nr, mrd, fine->deep, a, d_words, stream);
+            if (rc != MBK_OK) return rc;
+        } else if (s > 1u && threshold < 256u && t.kind == Target::kWide) {
+            rc = launch_deep_wide_refine(ctx, t, s, x0, y0, nc, nr, mrd, fine->wide, a, d_words, stream);
             if (rc != MBK_OK) return rc;
         } else if (s > 1u && threshold < 256u) {
             mbk::AdaptiveRefineArgs f;
@@ -4585,7 +4681,7 @@ static int adaptive_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
-    mbk::DeepBlaArgs fine;
+    AdaptiveFine fine;
     rc = adaptive_tables(ctx, t, flags, spec->supersample, threshold, &fine);
     if (rc != MBK_OK) return rc;
     return adaptive_run(ctx, t, mrd, flags, spec, threshold, (uint32_t *)d_rgba, d_mask, (hipStream_t)hip_stream, nullptr, &fine);
@@ -4599,7 +4695,7 @@ static int adaptive_compute(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_
     if (rc != MBK_OK) return rc;
     rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
-    mbk::DeepBlaArgs fine;
+    AdaptiveFine fine;
     rc = adaptive_tables(ctx, t, flags, spec->supersample, threshold, &fine);
     if (rc != MBK_OK) return rc;
     Slot &sl = ctx->s[0];
@@ -4647,6 +4743,20 @@ int mbk_deep_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *or
                                           uint8_t *h_mask, mbk_stats *stats)
 {
     return adaptive_compute(ctx, deep_target(orbit, view), mrd, flags, spec, threshold, h_rgba, h_mask, stats);
+}
+
+int mbk_deep_xview_render_adaptive_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *d_rgba,
+                                          uint8_t *d_mask, void *hip_stream)
+{
+    return adaptive_launch(ctx, wide_target(orbit, view), mrd, flags, spec, threshold, d_rgba, d_mask, hip_stream);
+}
+
+int mbk_deep_xview_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *h_rgba,
+                                           uint8_t *h_mask, mbk_stats *stats)
+{
+    return adaptive_compute(ctx, wide_target(orbit, view), mrd, flags, spec, threshold, h_rgba, h_mask, stats);
 }
 
 int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, uint32_t width, uint32_t height,

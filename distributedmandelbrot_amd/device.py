@@ -1658,7 +1658,7 @@ class MandelbrotDevice:
     @staticmethod
     def _adaptive_deep(view) -> None:
         if not isinstance(view, DeepView):
-            raise ValueError("adaptive supersampling of deep views is implemented for a DeepView only (no WideDeepView)")
+            raise ValueError("render_deep_view_adaptive takes a DeepView (a WideDeepView: render_wide_view_adaptive)")
 
     def render_deep_view_adaptive(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, supersample: int, threshold: int,
                                   window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None, want_mask: bool = False,
@@ -1692,6 +1692,46 @@ class MandelbrotDevice:
         self._check(self._lib.mbk_deep_view_render_adaptive_launch(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_BLA if bla else 0,
                                                                    C.byref(spec), int(threshold), d_rgba or None, d_mask or None,
                                                                    stream or None))
+
+    # -- adaptive supersampling of extended-range deep views (include/mbk.h, the section of that name): a WideDeepView --
+    @staticmethod
+    def _adaptive_wide(view) -> None:
+        if not isinstance(view, WideDeepView):
+            raise ValueError("render_wide_view_adaptive takes a WideDeepView (a DeepView: render_deep_view_adaptive)")
+
+    def render_wide_view_adaptive(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, supersample: int, threshold: int,
+                                  window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None, want_mask: bool = False,
+                                  xbla: bool = False):
+        """render_deep_view_adaptive for a WideDeepView: render_deep_view(wide_view, source="smooth") that computes the s x s
+        samples only for the pixels whose s = 1 colour differs from a neighbour's by `threshold` or more.  threshold 0 is
+        render_deep_view at `supersample` bit for bit, 256 is render_deep_view at 1.  xbla: both kinds of sample are those of
+        compute_deep_view(xbla=True), each with the table of its own view (W x H, and s times that); the first call with a
+        given (orbit, view, supersample) builds and uploads what is missing of the two.  Returns (rgba, TileStats) or, with
+        want_mask, (rgba, mask, TileStats), as render_view_adaptive."""
+        self._adaptive_wide(view)
+        cv = self._cdeep(view, window)
+        rgba = self._render_out(cv, out)
+        mask = np.empty((cv.nrows, cv.ncols), np.uint8) if want_mask else None
+        spec = palette.spec("smooth", supersample, max_band_rows)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_render_adaptive_compute(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_XBLA if xbla else 0,
+                                                                     C.byref(spec), int(threshold), rgba.ctypes.data,
+                                                                     mask.ctypes.data if want_mask else None, C.byref(st)))
+        return (rgba, mask, _stats(st)) if want_mask else (rgba, _stats(st))
+
+    def launch_render_wide_view_adaptive(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, supersample: int,
+                                         threshold: int, d_rgba: int, d_mask: int = 0, stream: int = 0, window=None,
+                                         max_band_rows: int = 0, xbla: bool = False) -> None:
+        """Asynchronous form into a DEVICE buffer of nrows * ncols * 4 bytes and, with d_mask, a DEVICE mask of nrows * ncols
+        bytes, on ``stream`` (0 = HIP's null stream).  The first launch of an (orbit, view, supersample) uploads the wide orbit
+        table and, with xbla, builds and uploads its tables synchronously; later ones wait for nothing while both stay
+        resident."""
+        self._adaptive_wide(view)
+        cv = self._cdeep(view, window)
+        spec = palette.spec("smooth", supersample, max_band_rows)
+        self._check(self._lib.mbk_deep_xview_render_adaptive_launch(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_XBLA if xbla else 0,
+                                                                    C.byref(spec), int(threshold), d_rgba or None, d_mask or None,
+                                                                    stream or None))
 
     # -- count histograms (include/mbk.h, "Count histograms and histogram-equalised colouring") ------
     def view_histogram(self, view: View, mrd: int, *, window=None, kernel: str = "default", precision: str = "f64",

@@ -571,12 +571,13 @@ int mbk_deep_xview_count_host(const mbk_deep_orbit *orbit, const mbk_deep_xview 
  *             equals the truth on every sampled pixel of the five cases of tests/test_deep_wide.py (spans 2^-1100 and 2^-3000
  *             on c = i and on a Misiurewicz point, and the centre 1e-400).  The cap is the wide contract's: >= 99 % of pixels.
  *
- * The ctx keeps the device copy of one such table beside each orbit copy's wide table, keyed by the orbit's id and dcmax
- * (the bits of its mantissa and its exponent, which carries exp2): 4 + 48 bytes per entry, fewer than 2 (M - 1) entries.  It
- * follows the rule of the MBK_DEEP_BLA table: built on the host and uploaded on the first MBK_DEEP_XBLA launch of the orbit
- * on the ctx, and REBUILT whenever a launch brings another dcmax -- synchronously, and the rebuild first synchronises the
- * device, since a queued launch may still read the table it replaces.  Launch once per (orbit, spans) before capturing, and
- * expect alternating spans on one orbit to serialise.  The table is freed with the orbit copies.
+ * The ctx keeps the device copies of up to two such tables beside each orbit copy's wide table, keyed by the orbit's id and
+ * dcmax (the bits of its mantissa and its exponent, which carries exp2): 4 + 48 bytes per entry, fewer than 2 (M - 1) entries
+ * each.  They follow the rule of the MBK_DEEP_BLA tables: a table is built on the host and uploaded, synchronously, by the first
+ * MBK_DEEP_XBLA launch on the ctx that brings its dcmax (the second place is allocated only then); once both places are taken
+ * it goes over the table asked for least recently, and that first synchronises the device, since a queued launch may still
+ * read the table it replaces.  Launch once per (orbit, spans) before capturing, and expect three or more dcmax in turn on one
+ * orbit to serialise.  The tables are freed with the orbit copies.
  */
 #define MBK_DEEP_XBLA 0x10000u
 /* Host twins for the CPU tests, compiled from the functions the builder and the kernel use: no ctx, no device.  `view` gives
@@ -940,9 +941,9 @@ int mbk_deep_xview_nucleus_host(const mbk_deep_orbit *orbit, const mbk_deep_xvie
  * and MBK_DEEP_BLA each with a message of its own: the name selects the rule --, an orbit longer than 2^31 and whatever
  * mbk_deep_xview_launch refuses.  The render calls take MBK_RENDER_DISTANCE_REL only: banding, supersampling, colour,
  * statistics and refusals are those of mbk_deep_xview_distance_render_*; the sample view at s x is a full view of its own and
- * has a table of its own, as for MBK_DEEP_XBLA.  The ctx's table is the one of the MBK_DEEP_XBLA count launches, keyed by the
- * orbit's id and dcmax and shared with them: launch once per (orbit, spans) before capturing, and expect alternating spans on
- * one orbit to serialise.
+ * has a table of its own, as for MBK_DEEP_XBLA.  The ctx's tables are those of the MBK_DEEP_XBLA count launches, keyed by the
+ * orbit's id and dcmax and shared with them: launch once per (orbit, spans) before capturing, and expect three or more spans
+ * in turn on one orbit to serialise.
  */
 int mbk_deep_xview_launch_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
                                         uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream);
@@ -1138,7 +1139,8 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
  * image).  MBK_ERR_INVALID, with nothing written: whatever mbk_view_render_* refuses for MBK_RENDER_SMOOTH, any other source,
  * threshold > 256, MBK_PRECISION_F32.  d_mask / h_mask may be NULL.
  *
- * Out of scope: Julia and extended-range deep views (each is one more kind of sample launch on the same three steps); the
+ * Out of scope: Julia views (one more kind of sample launch on the same three steps; deep and extended-range deep views have
+ * sections of their own below); the
  * bytes, distance and equalised sources; a distance-guided criterion, which would also catch filaments thinner than a pixel
  * inside a region of one colour (this criterion sees only what the s = 1 samples hit); sharding and slot forms.
  */
@@ -1185,8 +1187,8 @@ int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, ui
  * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_view_render_* refuses for MBK_RENDER_SMOOTH, any other source,
  * threshold > 256, any flag but MBK_DEEP_BLA (MBK_DEEP_XBLA with a message of its own).  d_mask / h_mask may be NULL.
  *
- * Out of scope: mbk_deep_xview; Julia views; the equalised, bytes and MBK_RENDER_DISTANCE_REL sources; a distance-guided
- * criterion; sharding and slot forms.
+ * Out of scope: Julia views; the equalised, bytes and MBK_RENDER_DISTANCE_REL sources; a distance-guided criterion; sharding
+ * and slot forms.  (mbk_deep_xview: the next section.)
  */
 int mbk_deep_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                          uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *d_rgba,
@@ -1194,6 +1196,49 @@ int mbk_deep_view_render_adaptive_launch(mbk_ctx *ctx, const mbk_deep_orbit *orb
 int mbk_deep_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                           uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *h_rgba,
                                           uint8_t *h_mask, mbk_stats *stats);
+
+/*
+ * Adaptive supersampling of extended-range deep views: the same for mbk_deep_xview, with the plain wide step and with
+ * MBK_DEEP_XBLA.  NOT in the reference; additive (the ABI version stays 5): no existing call, flag or default changes.  A wide
+ * sample is the most expensive in the library -- every step aligns with ldexp and renormalises with frexp, and the orbits are
+ * the longest -- and mbk_deep_xview_render_* at factor s pays s^2 of them for every pixel.
+ *
+ * Contract: that of "Adaptive supersampling" word for word (tests/adaptive_model.py; tests/test_deep_wide_adaptive.py and
+ * tests/test_gpu_deep_wide_adaptive.py hold the shares and the GPU to it), with
+ *   base      B[y][x] the MBK_RENDER_SMOOTH colour of sample (x, y) of the W x H view, count and nu exactly as
+ *             mbk_deep_xview_launch stores them, with MBK_DEEP_XBLA if set;
+ *   refined   pixel: the pixel of mbk_deep_xview_render_launch at factor s;
+ *   flags     0 or MBK_DEEP_XBLA.  With the bit set both kinds of sample are those of MBK_DEEP_XBLA: the base samples step with
+ *             the table of the W x H view's dcmax, the fine samples with the table of the (W s) x (H s) view's -- 65 x 45 at
+ *             exp2 -1100 differs from its fine view at every s, 67 x 45 at none -- which is exactly what
+ *             mbk_deep_xview_render_* with the flag uses at 1 and at s.
+ * So threshold 0 equals mbk_deep_xview_render_* at s bit for bit, threshold 256 equals it at 1, s = 1 equals it at 1 at every
+ * threshold, and a window or a band is bit-identical to the same rectangle of the whole image.  The mask and the stats keep
+ * their meaning: the stats count the stored counts of the window's base samples plus the s^2 fine samples of each refined
+ * pixel, the halo is not counted, and with MBK_DEEP_XBLA they follow the counts, not the steps executed.
+ *
+ * How it runs (csrc/mbk_deep_wide_adaptive.h).  The three steps, the scratch layout, the band plan, the halo, the palette
+ * staging and _compute's mask placement are those above; the base pass is the wide sample launch and the refine kernel computes
+ * the listed pixels' fine samples in the wide number system, one lane per sample, with the table's skips under MBK_DEEP_XBLA
+ * (an orbit of length 1 has no table: the flag changes nothing).  The ctx keeps TWO wide tables beside each orbit copy (see
+ * "Extended-range deep views with bilinear approximation"); a render with the flag acquires the base view's and the fine
+ * view's together before it enqueues anything, and neither takes the other's place (equal dcmax: one table).  A first call
+ * with a given (orbit, view, s) may therefore upload the wide orbit table and build and upload the tables synchronously; after
+ * it the launch form performs no host synchronisation for as long as both tables stay resident -- until a launch on the same
+ * orbit brings a third dcmax.
+ *
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_xview_render_* refuses for MBK_RENDER_SMOOTH, any other source,
+ * threshold > 256, any flag but MBK_DEEP_XBLA (MBK_DEEP_BLA in the words of mbk_deep_xview_launch).  d_mask / h_mask may be
+ * NULL.
+ *
+ * Out of scope: Julia views; the equalised, bytes and distance sources; a distance-guided criterion; sharding and slot forms.
+ */
+int mbk_deep_xview_render_adaptive_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *d_rgba,
+                                          uint8_t *d_mask, void *hip_stream);
+int mbk_deep_xview_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, uint32_t threshold, uint8_t *h_rgba,
+                                           uint8_t *h_mask, mbk_stats *stats);
 
 /*
  * Count histograms and histogram-equalised colouring.  NOT in the reference; additive (the ABI version stays 5): no existing
