@@ -106,6 +106,12 @@ class mbk_interior_render_spec(C.Structure):
                 ("unknown", C.c_uint8 * 4), ("outside", C.c_uint8 * 4), ("scale", C.c_double), ("max_band_rows", C.c_uint32)]
 
 
+class mbk_relief_spec(C.Structure):
+    _fields_ = [("supersample", C.c_uint32), ("palette", C.c_void_p), ("palette_len", C.c_uint32), ("inside", C.c_uint8 * 4),
+                ("scale", C.c_double), ("offset", C.c_double), ("light_x", C.c_double), ("light_y", C.c_double),
+                ("height", C.c_double), ("max_band_rows", C.c_uint32)]
+
+
 class mbk_density_target(C.Structure):
     _fields_ = [("start_r", C.c_double), ("start_i", C.c_double), ("range_r", C.c_double), ("range_i", C.c_double),
                 ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -424,6 +430,18 @@ SIGNATURES = {
                                                    C.POINTER(mbk_interior_render_spec), C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_interior_resolve_host": (C.c_int, [C.POINTER(mbk_interior_render_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "mbk_view_launch_normal": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "mbk_view_compute_normal": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_normal_value_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double)]),
+    "mbk_relief_shade_host": (C.c_uint32, [C.c_double] * 5),
+    "mbk_view_relief_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                C.POINTER(mbk_relief_spec), C.c_void_p, C.c_void_p]),
+    "mbk_view_relief_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                 C.POINTER(mbk_relief_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_relief_resolve_host": (C.c_int, [C.POINTER(mbk_relief_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "mbk_view_density_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_view_density_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,

@@ -33,6 +33,7 @@
 #include "mbk_render.h"
 #include "mbk_chunks.h"
 #include "mbk_distance.h"
+#include "mbk_relief.h"
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
 #include "mbk_deep_distance_bla.h"
@@ -1520,16 +1521,18 @@ static int sync_end(mbk_ctx *ctx, int rc, mbk_stats *stats, bool have_bytes, boo
 // launch(d_counts, d_values, stream) enqueues the kernels that write both.  with_tail (interior views): the device values are
 // followed by px int32 (the periods, at d_values + px), which the launch writes too; they go to h_tail, and h_values and h_tail
 // may each be NULL.  per_px (atom periods and Newton seeds): that many binary64 values per pixel, the tail after all of them.
+// h_more (normals with distance estimates; not with a tail): px more binary64 values follow the per_px * px on the device, at
+// d_values + per_px * px, which the launch writes too; they go to h_more.
 template <typename Launch>
 static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch,
-                          bool with_tail = false, int32_t *h_tail = nullptr, size_t per_px = 1u)
+                          bool with_tail = false, int32_t *h_tail = nullptr, size_t per_px = 1u, double *h_more = nullptr)
 {
     Slot &sl = ctx->s[0];
     auto enqueue = [&]() -> int {
         int rc = ensure_buffers(ctx, sl, px);
         if (rc != MBK_OK) return rc;
         const size_t vals = per_px * px;
-        const size_t cap = with_tail ? vals + (px + 1u) / 2u : vals;   // (in binary64 values)
+        const size_t cap = with_tail ? vals + (px + 1u) / 2u : (h_more ? vals + px : vals);   // (in binary64 values)
         rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, cap, cap * sizeof(double));
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
@@ -1541,6 +1544,7 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         if (h_values) MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, vals * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_tail) MBK_HIP(ctx, hipMemcpyAsync(h_tail, ctx->d_smooth + vals, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
+        if (h_more) MBK_HIP(ctx, hipMemcpyAsync(h_more, ctx->d_smooth + vals, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
         ctx->last_px = 0;   // (no bytes on the device: mbk_serialize_last has nothing to read)
@@ -2357,6 +2361,106 @@ int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, 
 double mbk_distance_value_host(double mag, double dmag, int32_t count)
 {
     return mbk::distance_value(mag, dmag, count);
+}
+
+// ---- normals for relief shading (mbk_relief.h; mbk.h "Relief shading") -------------------------------------------------
+
+// Everything a normal launch can refuse, before anything is allocated, enqueued or written: what a distance launch refuses,
+// and every flag that is no kernel selector.
+static int normal_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, bool *safe)
+{
+    int rc = distance_check(ctx, view, mrd, flags, safe);
+    if (rc != MBK_OK) return rc;
+    if (flags & ~(uint32_t)MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "normals take kernel selection only (binary64, no other flag)");
+    return MBK_OK;
+}
+
+// The relief kernel on a checked view.  d_counts_in: the two-pass form on these counts; NULL: the one-pass form, which writes
+// its counts to d_counts_out where that is given.  d_distance may be null.
+static int launch_relief_kernel(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, bool safe, const int32_t *d_counts_in,
+                                int32_t *d_counts_out, double *d_normal, double *d_distance, hipStream_t stream)
+{
+    const bool one_pass = d_counts_in == nullptr;
+    mbk::ReliefArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_window(a, v);
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.mrd = (int32_t)mrd;
+    a.counts_in = d_counts_in;
+    a.counts_out = one_pass ? d_counts_out : nullptr;
+    a.normal = d_normal;
+    a.distance = d_distance;
+    const dim3 grid(a.blocks_x * ((v->nrows + 7u) / 8u)), block(64);   // (at most 2^31 / 64 blocks: validate_view)
+    if (one_pass) {
+        if (safe) hipLaunchKernelGGL((mbk::relief_kernel<false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mbk::relief_kernel<true, true>), grid, block, 0, stream, a);
+    } else {
+        if (safe) hipLaunchKernelGGL((mbk::relief_kernel<false, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((mbk::relief_kernel<true, false>), grid, block, 0, stream, a);
+    }
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// A checked launch, in the two forms of launch_distance: kernel "asm" in one pass; every other selector has the escape kernels
+// it names write the counts (into the stream's scratch when the caller wants none) and runs the two-pass form on them.
+static int launch_normal(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags, bool safe, int32_t *d_counts,
+                         double *d_normal, double *d_distance, hipStream_t stream)
+{
+    const uint32_t kernel = flags & MBK_KERNEL_MASK;
+    if (kernel == MBK_KERNEL_ASM) return launch_relief_kernel(ctx, v, mrd, safe, nullptr, d_counts, d_normal, d_distance, stream);
+    const size_t px = (size_t)v->ncols * v->nrows;
+    if (!d_counts) {
+        StreamScratch *sc = nullptr;
+        int rc = get_scratch(ctx, stream, &sc);
+        if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
+        if (rc != MBK_OK) return rc;
+        d_counts = sc->d_dist_counts;
+    }
+    int rc = launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+    if (rc != MBK_OK) return rc;
+    return launch_relief_kernel(ctx, v, mrd, safe, d_counts, nullptr, d_normal, d_distance, stream);
+}
+
+int mbk_view_launch_normal(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *d_counts, double *d_normal,
+                           double *d_distance, void *hip_stream)
+{
+    if (!ctx || !d_normal) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = normal_check(ctx, view, mrd, flags, &safe);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_normal & 7u) return fail(ctx, MBK_ERR_INVALID, "d_normal must be 8-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_normal(ctx, view, mrd, flags, safe, d_counts, d_normal, d_distance, (hipStream_t)hip_stream);
+}
+
+int mbk_view_compute_normal(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *h_counts, double *h_normal,
+                            double *h_distance, mbk_stats *stats)
+{
+    if (!ctx || !view || !h_normal) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = normal_check(ctx, view, mrd, flags, &safe);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    const size_t px = (size_t)view->ncols * view->nrows;
+    return compute_values(ctx, px, mrd, h_counts, h_normal, stats,
+                          [&](int32_t *d_counts, double *d_normal, hipStream_t stream) {
+                              return launch_normal(ctx, view, mrd, flags, safe, d_counts, d_normal, h_distance ? d_normal + 2u * px : nullptr, stream);
+                          },
+                          false, nullptr, 2u, h_distance);
+}
+
+int mbk_normal_value_host(double zr, double zi, double dr, double di, int32_t count, double out[2])
+{
+    if (!out) return fail(nullptr, MBK_ERR_INVALID, "out is NULL");
+    mbk::normal_value(zr, zi, dr, di, count, out);
+    return MBK_OK;
+}
+
+uint32_t mbk_relief_shade_host(double nx, double ny, double lx, double ly, double h)
+{
+    return mbk::relief_shade(nx, ny, lx, ly, h);
 }
 
 // ---- interior views (mbk_interior.h; mbk.h "Interior views") -----------------------------------------------------------
@@ -3748,6 +3852,7 @@ struct Outputs {
     bool distance;
     int32_t *period;   // interior views (plain views only): values is then the interior distance estimate
     bool interior;
+    double *normals;   // relief renders (plain views only): the normals of the samples, beside counts and nu
 };
 
 // The launch of a checked target (target_check) on device pointers, on `stream`: the one place that knows which kernels serve
@@ -3784,7 +3889,12 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
         return launch_distance(ctx, &t.view, mrd, flags, safe, o.counts, o.values, stream);
     }
     const uint32_t want = (o.counts ? MBK_WANT_COUNTS : 0u) | (o.bytes ? MBK_WANT_BYTES : 0u);
-    return launch_tile(ctx, &t.view, mrd, (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES)) | want, o.counts, o.bytes, stream, o.values);
+    int rc = launch_tile(ctx, &t.view, mrd, (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES)) | want, o.counts, o.bytes, stream, o.values);
+    if (rc != MBK_OK || !o.normals) return rc;
+    bool safe = false;   // (a relief band: the two-pass normal kernel on the counts the smooth launch has just written)
+    rc = validate_view(ctx, &t.view, &safe);
+    if (rc != MBK_OK) return rc;
+    return launch_relief_kernel(ctx, &t.view, mrd, safe, o.counts, nullptr, o.normals, nullptr, stream);
 }
 
 // The three forms of a count call on a target: device pointers on a stream, host pointers synchronously, host pointers on a slot.
@@ -3998,6 +4108,7 @@ static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint
     p.lut = nullptr;
     p.lut_mrd = 0u;
     p.unknown = p.outside = 0u;
+    p.light_x = p.light_y = p.height = 0.0;
     return p;
 }
 
@@ -4005,6 +4116,8 @@ static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint
 // lets through (validate_render_spec), and its two extra colours.
 static const uint32_t kRenderSourceInterior = 0x100u;
 struct InteriorColours { uint32_t unknown, outside; };
+// A relief render inside the render machinery: an MBK_RENDER_SMOOTH spec, and the light it has no field for.
+struct ReliefLight { double x, y, height; };
 
 // The stream's device palette: uploaded when it differs from what the device copy holds, after the launches that read that.
 static int stream_palette(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const uint8_t *palette, uint32_t len)
@@ -4101,7 +4214,7 @@ static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 // reduction scratch adds up the statistics of the samples and whose ev_k1 marks the last resolve kernel (_compute), or NULL.
 static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                       uint32_t *d_out, hipStream_t stream, Slot *stat, const double *h_lut = nullptr, uint32_t lut_len = 0u,
-                      const InteriorColours *interior = nullptr)
+                      const InteriorColours *interior = nullptr, const ReliefLight *relief = nullptr)
 {
     const uint32_t s = spec->supersample;
     const bool dist = spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL;   // (deep views: rel in place of de, the same colour rule)
@@ -4119,17 +4232,18 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         if (rc != MBK_OK) return rc;
     }
 
-    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (interior ? 16u : (smooth ? 12u : (stat ? 5u : 1u))), spec->max_band_rows);
+    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (relief ? 28u : (interior ? 16u : (smooth ? 12u : (stat ? 5u : 1u)))), spec->max_band_rows);
     const size_t cap_samples = plan.cap_px() * s * s;
-    // layout: SMOOTH nu | counts (interior: de | counts | periods); BYTES counts (statistics only) | bytes
+    // layout: SMOOTH nu | counts (interior: de | counts | periods; relief: nu | counts | normals); BYTES counts (statistics only) | bytes
     const size_t off2 = smooth ? round_up_256(cap_samples * 8u) : (stat ? round_up_256(cap_samples * 4u) : 0u);
-    const size_t off3 = off2 + round_up_256(cap_samples * 4u);   // (interior only)
-    const size_t need = interior ? off3 + cap_samples * 4u : off2 + (smooth ? cap_samples * 4u : cap_samples);
+    const size_t off3 = off2 + round_up_256(cap_samples * 4u);   // (interior and relief only)
+    const size_t need = relief ? off3 + cap_samples * 16u : (interior ? off3 + cap_samples * 4u : off2 + (smooth ? cap_samples * 4u : cap_samples));
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
     if (rc != MBK_OK) return rc;
     uint8_t *base = (uint8_t *)sc->d_render;
     const Outputs samples = {smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr), smooth ? nullptr : base + off2,
-                             smooth ? (double *)base : nullptr, dist, interior ? (int32_t *)(base + off3) : nullptr, interior != nullptr};
+                             smooth ? (double *)base : nullptr, dist, interior ? (int32_t *)(base + off3) : nullptr, interior != nullptr,
+                             relief ? (double *)(base + off3) : nullptr};
     const double *d_lut = eq ? sc->d_lut : nullptr;
     const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
 
@@ -4146,6 +4260,7 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         a.counts = samples.counts;
         a.smooth = samples.values;
         a.period = samples.period;
+        a.normal = samples.normals;
         a.bytes = samples.bytes;
         a.out = d_out + (size_t)r * t.g.ncols + c;
         a.pitch = (uint64_t)nc * s;
@@ -4162,10 +4277,17 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
             a.pal.unknown = interior->unknown;
             a.pal.outside = interior->outside;
         }
+        if (relief) {
+            a.pal.light_x = relief->x;
+            a.pal.light_y = relief->y;
+            a.pal.height = relief->height;
+        }
         const uint64_t pieces = (uint64_t)a.chunks_x * nr;
         const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
         if (interior)
             mbk::launch_resolve<true, mbk::kRuleInterior>(s, grid, use_lds ? lds : 0u, stream, a);
+        else if (relief)
+            mbk::launch_resolve<true, mbk::kRuleRelief>(s, grid, use_lds ? lds : 0u, stream, a);
         else if (dist)
             mbk::launch_resolve<true, mbk::kRuleDistance>(s, grid, use_lds ? lds : 0u, stream, a);
         else if (eq)
@@ -4195,7 +4317,7 @@ static int render_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
 // A checked render synchronously into a host image on slot 0: what follows the refusals of a *_render_compute call.
 static int render_compute_checked(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                                   uint8_t *h_rgba, mbk_stats *stats, const double *h_lut, uint32_t lut_len,
-                                  const InteriorColours *interior = nullptr)
+                                  const InteriorColours *interior = nullptr, const ReliefLight *relief = nullptr)
 {
     int rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
@@ -4207,7 +4329,7 @@ static int render_compute_checked(mbk_ctx *ctx, const Target &t, uint32_t mrd, u
         // the bands add their statistics up in the slot's reduction scratch: cleared once, here
         MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len, interior);
+        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len, interior, relief);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
@@ -4870,6 +4992,96 @@ int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t wid
     pal.unknown = colours.unknown;
     pal.outside = colours.outside;
     mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, de, rgba, mbk::kRuleInterior, period);
+    return MBK_OK;
+}
+
+// ---- relief renders (mbk.h "Relief shading"): calls of their own on the render machinery above -------------------------
+
+// The spec as the render machinery reads it: an MBK_RENDER_SMOOTH render of the same palette; and the light.
+static mbk_render_spec relief_render_spec(const mbk_relief_spec *spec, ReliefLight *light)
+{
+    mbk_render_spec r = {};
+    r.source = MBK_RENDER_SMOOTH;
+    r.supersample = spec->supersample;
+    r.palette = spec->palette;
+    r.palette_len = spec->palette_len;
+    std::memcpy(r.inside, spec->inside, sizeof(r.inside));
+    r.scale = spec->scale;
+    r.offset = spec->offset;
+    r.max_band_rows = spec->max_band_rows;
+    light->x = spec->light_x;
+    light->y = spec->light_y;
+    light->height = spec->height;
+    return r;
+}
+
+// What a relief spec adds to an MBK_RENDER_SMOOTH one (validate_render_spec checks the rest): the light and the height.
+static int validate_relief_light(mbk_ctx *ctx, const mbk_relief_spec *spec)
+{
+    if (!(std::fabs(spec->light_x) <= 1.0) || !(std::fabs(spec->light_y) <= 1.0))
+        return fail(ctx, MBK_ERR_INVALID, "light_x and light_y must lie in [-1, 1]");
+    if (!(spec->height >= 0.0) || !(spec->height <= 0x1p10)) return fail(ctx, MBK_ERR_INVALID, "height must lie in [0, 2^10]");
+    return MBK_OK;
+}
+
+// Everything a relief render can refuse, before anything is allocated, enqueued or written: what an MBK_RENDER_SMOOTH render
+// of the view refuses, MBK_PRECISION_F32 among it, and a light or a height out of range.
+static int relief_render_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_relief_spec *spec, const void *out,
+                               mbk_render_spec *r, ReliefLight *light)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!spec) return fail(ctx, MBK_ERR_INVALID, "render spec is NULL");
+    *r = relief_render_spec(spec, light);
+    int rc = render_check(ctx, t, mrd, flags, r, out);
+    if (rc != MBK_OK) return rc;
+    return validate_relief_light(ctx, spec);
+}
+
+int mbk_view_relief_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_relief_spec *spec,
+                                  uint8_t *d_rgba, void *hip_stream)
+{
+    const Target t = view_target(view);
+    mbk_render_spec r;
+    ReliefLight light;
+    int rc = relief_render_check(ctx, t, mrd, flags, spec, d_rgba, &r, &light);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, &light);
+}
+
+int mbk_view_relief_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_relief_spec *spec,
+                                   uint8_t *h_rgba, mbk_stats *stats)
+{
+    const Target t = view_target(view);
+    mbk_render_spec r;
+    ReliefLight light;
+    int rc = relief_render_check(ctx, t, mrd, flags, spec, h_rgba, &r, &light);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, &r, h_rgba, stats, nullptr, 0u, nullptr, &light);
+}
+
+int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_t height, const int32_t *counts, const double *smooth,
+                            const double *normals, uint8_t *rgba)
+{
+    if (!spec) return fail(nullptr, MBK_ERR_INVALID, "render spec is NULL");
+    ReliefLight light;
+    const mbk_render_spec r = relief_render_spec(spec, &light);
+    int rc = validate_render_spec(nullptr, &r);
+    if (rc == MBK_OK) rc = validate_relief_light(nullptr, spec);
+    if (rc != MBK_OK) return rc;
+    if (!rgba) return fail(nullptr, MBK_ERR_INVALID, "output pointer is NULL");
+    const uint32_t s = spec->supersample;
+    if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
+        return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
+    if (!counts || !smooth || !normals) return fail(nullptr, MBK_ERR_INVALID, "the sample arrays are NULL");
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    mbk::RenderPalette pal = render_palette(&r, words.data());
+    pal.light_x = light.x;
+    pal.light_y = light.y;
+    pal.height = light.height;
+    mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, smooth, rgba, mbk::kRuleRelief, nullptr, normals);
     return MBK_OK;
 }
 

@@ -1,6 +1,6 @@
 // mbk_render.h -- views to RGBA8 images (include/mbk.h, "Rendering"): the colour of one sample and the resolve of a pixel's
 // s x s samples, written once as __host__ __device__ functions that the resolve kernel and mbk_render_resolve_host share, and
-// the kernel itself (four rules for the binary64 samples: smooth, distance, equalised, interior).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
+// the kernel itself (five rules for the binary64 samples: smooth, distance, equalised, interior, relief).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
 //
 // Everything after the samples is integer arithmetic or exact binary64: t = fl(fl(nu * scale) + offset) are two rounded
 // operations (the translation unit is compiled with -ffp-contract=off), floor(t) and (t - floor(t)) * 256 are exact for
@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mbk_histogram.h"
+#include "mbk_relief.h"
 
 namespace mbk {
 
@@ -26,11 +27,13 @@ struct RenderPalette {
     const double *lut;   // MBK_RENDER_EQUALIZED: the equalisation table, lut_mrd + 2 entries
     uint32_t lut_mrd;
     uint32_t unknown, outside;   // interior renders: the colours of a sample with no period and of one that escapes
+    double light_x, light_y, height;   // relief renders (mbk.h "Relief shading")
 };
 
 // How a binary64 sample becomes a colour: the three rules of the sources that share the (count, value) sample layout.
-// kRuleInterior (mbk.h "Interior views") reads a third array, the periods, beside the same two.
-enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2, kRuleInterior = 3 };
+// kRuleInterior (mbk.h "Interior views") reads a third array, the periods, beside the same two; kRuleRelief (mbk.h "Relief
+// shading") the normals, two binary64 per sample.
+enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2, kRuleInterior = 3, kRuleRelief = 4 };
 
 // Two colour channels at a time: a word holds channels 0 and 2 (or 1 and 3) in its 16-bit halves.
 __host__ __device__ inline uint32_t render_even(uint32_t c) { return c & 0x00ff00ffu; }
@@ -96,6 +99,14 @@ __host__ __device__ inline uint32_t render_colour_equalized(const RenderPalette 
     return render_colour_distance(p, entries, count, equalize_value(p.lut, p.lut_mrd, nu));
 }
 
+// R, G and B of `base` scaled by f / 256, 0 <= f <= 256: (channel f + 128) >> 8.  Alpha is the base's.
+__host__ __device__ inline uint32_t render_dim(uint32_t base, uint32_t f)
+{
+    const uint32_t even = ((render_even(base) * f + 0x00800080u) >> 8) & 0x00ff00ffu;   // R, B
+    const uint32_t green = ((((base >> 8) & 0xffu) * f + 128u) >> 8) & 0xffu;
+    return even | (green << 8) | (base & 0xff000000u);
+}
+
 // The colour of one interior sample: `outside` if it escapes, `unknown` without a period; otherwise the palette entry of the
 // period (cyclic, 1 <= n <= 65536) with R, G, B scaled by f / 256, f = 256 from t = fl(de scale) >= 1 up (+inf included),
 // floor(256 t) below (exact: t < 1).  de is never NaN or negative.  Alpha is the entry's.
@@ -107,9 +118,16 @@ __host__ __device__ inline uint32_t render_colour_interior(const RenderPalette &
     const uint32_t base = entries[(uint32_t)(period - 1) % p.n];
     const double t = de * p.scale;
     const uint32_t f = t >= 1.0 ? 256u : (uint32_t)(t * 256.0);
-    const uint32_t even = ((render_even(base) * f + 0x00800080u) >> 8) & 0x00ff00ffu;   // R, B
-    const uint32_t green = ((((base >> 8) & 0xffu) * f + 128u) >> 8) & 0xffu;
-    return even | (green << 8) | (base & 0xff000000u);
+    return render_dim(base, f);
+}
+
+// The colour of one relief sample: `inside`, unshaded, if the count is 0; otherwise the MBK_RENDER_SMOOTH colour with R, G, B
+// scaled by q / 256, q the shade of the sample's normal (relief_shade).
+__host__ __device__ inline uint32_t render_colour_relief(const RenderPalette &p, const uint32_t *entries, int32_t count, double nu, double nx,
+                                                         double ny)
+{
+    if (count == 0) return p.inside;
+    return render_dim(render_colour_smooth(p, entries, count, nu), relief_shade(nx, ny, p.light_x, p.light_y, p.height));
 }
 
 template <int RULE>
@@ -147,6 +165,7 @@ struct RenderArgs {
     const int32_t *counts;   // MBK_RENDER_SMOOTH
     const double *smooth;
     const int32_t *period;   // kRuleInterior
+    const double *normal;    // kRuleRelief: [sample][2]
     const uint8_t *bytes;    // MBK_RENDER_BYTES
     uint32_t *out;
     uint64_t pitch, out_pitch;
@@ -191,7 +210,8 @@ __device__ inline void render_load_smooth(const RenderArgs &a, uint64_t at, doub
 // contiguous stretch of the image.  The grid is sized to the chip and every workgroup takes pieces in turn, which is what
 // makes staging the palette in LDS worth its loads.  Pure streaming: s^2 x (12 | 1) bytes in, 4 bytes out per pixel.
 // RULE (with SMOOTH): what the binary64 samples are -- nu, distance estimates (render_colour_distance) or nu for the
-// equalisation table (render_colour_equalized); same loads, same layout.
+// equalisation table (render_colour_equalized); same loads, same layout.  kRuleInterior and kRuleRelief read one more array
+// per sample (the periods; the normals, 16 bytes) straight from global memory.
 template <bool SMOOTH, int S, int RULE = kRuleSmooth>
 __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const RenderArgs a)
 {
@@ -220,7 +240,10 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
                 for (int sx = 0; sx < S; ++sx) {
                     if constexpr (RULE == kRuleInterior)
                         sum.add(render_colour_interior(a.pal, entries, cnt[sx], a.period[at + sx], nu[sx]));
-                    else
+                    else if constexpr (RULE == kRuleRelief) {   // (16-byte aligned: the band's base is, and a sample is 16 bytes)
+                        const double2 nv = reinterpret_cast<const double2 *>(a.normal)[at + sx];
+                        sum.add(render_colour_relief(a.pal, entries, cnt[sx], nu[sx], nv.x, nv.y));
+                    } else
                         sum.add(render_colour<RULE>(a.pal, entries, cnt[sx], nu[sx]));
                 }
             }
@@ -277,7 +300,7 @@ inline void launch_resolve(uint32_t s, dim3 grid, size_t lds, hipStream_t stream
 // The same rule on the host, for caller-supplied samples of (width * s) x (height * s): mbk_render_resolve_host.
 inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, uint32_t s, uint32_t width, uint32_t height,
                                 const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba,
-                                int rule = kRuleSmooth, const int32_t *period = nullptr)
+                                int rule = kRuleSmooth, const int32_t *period = nullptr, const double *normal = nullptr)
 {
     const uint64_t pitch = (uint64_t)width * s;
     for (uint32_t y = 0; y < height; ++y)
@@ -288,6 +311,7 @@ inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, ui
                     const uint64_t at = ((uint64_t)y * s + sy) * pitch + (uint64_t)x * s + sx;
                     sum.add(!smooth_source            ? pal.entries[bytes[at]]
                             : rule == kRuleInterior  ? render_colour_interior(pal, pal.entries, counts[at], period[at], smooth[at])
+                            : rule == kRuleRelief    ? render_colour_relief(pal, pal.entries, counts[at], smooth[at], normal[2u * at], normal[2u * at + 1u])
                             : rule == kRuleDistance  ? render_colour_distance(pal, pal.entries, counts[at], smooth[at])
                             : rule == kRuleEqualized ? render_colour_equalized(pal, pal.entries, counts[at], smooth[at])
                                                      : render_colour_smooth(pal, pal.entries, counts[at], smooth[at]));

@@ -833,6 +833,21 @@ def interior_host(c, mrd: int) -> Tuple[int, int, int, float]:
     return int(n.value), int(p.value), int(cl.value), float(de.value)
 
 
+def normal_value_host(zr: float, zi: float, dr: float, di: float, count: int) -> Tuple[float, float]:
+    """mbk_normal_value_host: the unit normal (nx, ny) at one final state (include/mbk.h, "Relief shading") on the host, from
+    the function the kernel uses; (0, 0) is the flat normal."""
+    lib = L.load()
+    out = (C.c_double * 2)()
+    _check(lib, lib.mbk_normal_value_host(float(zr), float(zi), float(dr), float(di), int(count), out))
+    return float(out[0]), float(out[1])
+
+
+def relief_shade_host(nx: float, ny: float, lx: float, ly: float, h: float) -> int:
+    """mbk_relief_shade_host: the brightness q in [0, 256] of a sample with normal (nx, ny) under the light (lx, ly) at
+    height h."""
+    return int(L.load().mbk_relief_shade_host(float(nx), float(ny), float(lx), float(ly), float(h)))
+
+
 def _interior_spec(palette, supersample, unknown, outside, scale, max_band_rows):
     """(mbk_interior_render_spec, the palette array it points into) for a palette of uint8[n, 4] entries, entry k the colour
     of period k + 1."""
@@ -1160,6 +1175,56 @@ class MandelbrotDevice:
         spec, pal = _interior_spec(palette, supersample, unknown, outside, scale, max_band_rows)
         self._check(self._lib.mbk_view_interior_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
                                                               d_rgba or None, stream or None))
+
+    # -- relief shading (include/mbk.h, "Relief shading") -------------------------------------------
+    def compute_view_normals(self, view: View, mrd: int, *, window=None, kernel: str = "default", want_distance: bool = False):
+        """Unit normals of the exterior potential (not in the reference): the direction of z / (dz/dc) at the final state of
+        compute_view_distance, (0, 0) -- the flat normal -- for never-escaped pixels and where the state has overflowed.  The
+        counts are those of compute_view.  kernel as for compute_view_distance; both forms store the same values.
+        Returns (counts int32[nrows,ncols], normals float64[nrows,ncols,2], TileStats), with want_distance
+        (counts, normals, distance float64[nrows,ncols], TileStats): the bits compute_view_distance stores."""
+        cv = self._cview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        counts = np.empty(shape, np.int32)
+        normals = np.empty(shape + (2,), np.float64)
+        dist = np.empty(shape, np.float64) if want_distance else None
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_compute_normal(self._h, C.byref(cv), mrd, L.KERNELS[kernel], counts.ctypes.data,
+                                                      normals.ctypes.data, dist.ctypes.data if want_distance else None, C.byref(st)))
+        return (counts, normals, dist, _stats(st)) if want_distance else (counts, normals, _stats(st))
+
+    def launch_view_normals(self, view: View, mrd: int, *, d_normals: int, d_counts: int = 0, d_distance: int = 0, stream: int = 0,
+                            window=None, kernel: str = "default") -> None:
+        """Asynchronous form on DEVICE pointers (float64 x 2 / int32 / float64 per pixel of the window; d_counts and d_distance
+        may be 0) on ``stream`` (0 = HIP's null stream)."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_view_launch_normal(self._h, C.byref(cv), mrd, L.KERNELS[kernel], d_counts or None,
+                                                     d_normals or None, d_distance or None, stream or None))
+
+    def render_view_relief(self, view: View, mrd: int, *, palette, light_deg: float = 45.0, height: float = 1.5,
+                           supersample: int = 1, window=None, max_band_rows: int = 0, kernel: str = "default", light=None,
+                           out: Optional[np.ndarray] = None):
+        """The view as a relief: the "smooth" colouring of render_view (image.Palette, its scale and offset) with R, G, B of
+        every escaped sample scaled by how its normal faces a light from the direction light_deg (degrees, counter-clockwise
+        from the positive real axis) at `height` above the plane -- filaments and spirals stand out as ridges.  height 0 is the
+        harshest light, a large height flattens it.  light: the doubles (lx, ly) in place of (cos, sin) of light_deg.
+        Supersampling, windows and bands as for render_view.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples)."""
+        cv = self._cview(view, window)
+        spec = palette.relief_spec(supersample, light_deg, height, max_band_rows, light=light)
+        img = self._render_out(cv, out)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_relief_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                             img.ctypes.data, C.byref(st)))
+        return img, _stats(st)
+
+    def launch_render_view_relief(self, view: View, mrd: int, *, palette, d_rgba: int, light_deg: float = 45.0, height: float = 1.5,
+                                  supersample: int = 1, stream: int = 0, window=None, max_band_rows: int = 0,
+                                  kernel: str = "default", light=None) -> None:
+        """Asynchronous relief render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream``."""
+        cv = self._cview(view, window)
+        spec = palette.relief_spec(supersample, light_deg, height, max_band_rows, light=light)
+        self._check(self._lib.mbk_view_relief_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                            d_rgba or None, stream or None))
 
     def serialize_last(self) -> Tuple[bytes, int]:
         """The last tile's quantised bytes exactly as DataChunk.Serialize (DataChunk.cs:173-206) would

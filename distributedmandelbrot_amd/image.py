@@ -142,6 +142,16 @@ class Palette:
         return L.mbk_density_render_spec(L.DENSITY_MODES[mode], int(factor), self.entries.ctypes.data, len(self),
                                          float(self.scale), float(self.offset))
 
+    def relief_spec(self, supersample: int, light_deg: float = 45.0, height: float = 1.5, max_band_rows: int = 0, *,
+                    light=None) -> L.mbk_relief_spec:
+        """The C struct of a relief render (include/mbk.h, "Relief shading"): this palette as for source "smooth", lit from
+        the direction light_deg (degrees, counter-clockwise from the positive real axis) by a light `height` above the plane.
+        light: the doubles (lx, ly) themselves in place of (cos, sin) of light_deg.  It points into self.entries, which the
+        caller keeps alive for the call."""
+        lx, ly = light if light is not None else (float(np.cos(np.deg2rad(light_deg))), float(np.sin(np.deg2rad(light_deg))))
+        return L.mbk_relief_spec(int(supersample), self.entries.ctypes.data, len(self), (C.c_uint8 * 4)(*self.inside),
+                                 float(self.scale), float(self.offset), float(lx), float(ly), float(height), int(max_band_rows))
+
     @staticmethod
     def _ramp(near, far, n: int) -> np.ndarray:
         x = np.arange(n, dtype=np.float64)[:, None] / (n - 1)
@@ -211,6 +221,26 @@ def resolve_host(palette: Palette, source: str, supersample: int, width: int, he
                                                    out.ctypes.data)
     else:
         st = lib.mbk_render_resolve_host(C.byref(spec), width, height, *ptrs, out.ctypes.data)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return out
+
+
+def relief_resolve_host(palette: Palette, supersample: int, width: int, height_px: int, *, counts, smooth, normals,
+                        light_deg: float = 45.0, height: float = 1.5, light=None) -> np.ndarray:
+    """mbk_relief_resolve_host: shade, colour and resolve caller-supplied samples of (height_px s, width s) on the host --
+    counts, nu and normals[..., 2] -- with the code the relief resolve kernel is compiled from, without a device."""
+    lib = L.load()
+    out = np.empty((height_px, width, 4), np.uint8)
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    nu = np.ascontiguousarray(smooth, dtype=np.float64)
+    nrm = np.ascontiguousarray(normals, dtype=np.float64)
+    samples = width * height_px * supersample * supersample
+    if c.size != samples or nu.size != samples or nrm.size != 2 * samples:
+        raise ValueError("sample arrays must hold (height * s) x (width * s) elements, the normals two each")
+    spec = palette.relief_spec(supersample, light_deg, height, light=light)
+    st = lib.mbk_relief_resolve_host(C.byref(spec), width, height_px, c.ctypes.data, nu.ctypes.data, nrm.ctypes.data, out.ctypes.data)
     if st != L.MBK_OK:
         from .device import MbkError
         raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())

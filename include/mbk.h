@@ -1683,6 +1683,87 @@ int mbk_view_interior_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_
 int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
                               const int32_t *period, const double *de, uint8_t *rgba);
 
+/*
+ * Relief shading: unit normals of the exterior potential and renders lit from one side.  NOT in the reference; additive (the
+ * ABI version stays 5): no existing call changes.  Every colouring above is one scalar per sample through a palette and cannot
+ * show slope.  The state of "Distance estimates" holds more than the magnitude 2 |z| ln |z| / |d|: z / d points along the
+ * gradient of the exterior potential G(c) = lim 2^-k ln |z_k|, the surface normal of the picture of G as a height field.
+ * Lighting the smooth colouring with it makes filaments and spirals stand out as ridges.  For plain views (mbk_view) only.
+ *
+ * Contract (exact; tests/relief_model.py restates it in numpy, tests/test_relief.py and tests/test_gpu_relief.py hold the host
+ * twins and the GPU to it).  Binary64, every operation rounded on its own.
+ *   state     exactly that of "Distance estimates": z_0 = c, d_0 = (1, 0), the same step, the same count n, the same run-on (up
+ *             to 64 uncounted steps or until mag >= 2^32).
+ *   normal    at the final state (zr, zi, dr, di) of a pixel with n > 0: wr = fl(fl(zr dr) + fl(zi di)),
+ *             wi = fl(fl(zi dr) - fl(zr di)) -- z conj(d), which has the direction of z / d; m = fl(fl(wr^2) + fl(wi^2)).  If
+ *             not m > 0, or m = +inf, the FLAT normal (0, 0) is stored: that covers a NaN, underflow to 0 and overflow.
+ *             Otherwise s = fl(sqrt(m)) and (nx, ny) = (fl(wr / s), fl(wi / s)).  Division and square root are the correctly
+ *             rounded ones and there is no logarithm, so device, host twin and numpy agree on every bit, the sign of a zero
+ *             component included.  n = 0 stores (0, 0).  A NaN is never stored.  mrd 0 and 1 run no step: every normal is
+ *             (0, 0).
+ *   shade     of a sample under a light (lx, ly) at height h: g = fl(fl(nx lx) + fl(ny ly)), t = fl(fl(g + h) / fl(1 + h));
+ *             q = 0 unless t > 0, q = 256 where t >= 1, q = floor(256 t) otherwise (exact).  A flat normal therefore takes the
+ *             neutral brightness floor(256 h / (1 + h)).  lx, ly finite with |lx|, |ly| <= 1 (the cosine and sine of an angle,
+ *             as a rule, but the contract is on the doubles); h finite with 0 <= h <= 2^10.
+ *   colour    of a sample: `inside`, unshaded, if its count is 0.  Otherwise base is the MBK_RENDER_SMOOTH colour of
+ *             (count, nu) with the spec's palette, scale and offset (cyclic, 2 <= palette_len <= 65536, the same ranges), and
+ *             each of R, G, B becomes (base q + 128) >> 8; alpha is the base's.
+ *   rendering resolve, supersampling set (1, 2, 3, 4, 8), output layout, banding under MBK_RENDER_BAND_BYTES, the palette's
+ *             wait-on-change rule and the statistics of _compute are those of "Rendering".  Samples are 28 bytes: int32 count,
+ *             binary64 nu, two binary64 for the normal.
+ * Windows of a view are bit-identical to the whole view; any max_band_rows gives the same image.
+ *
+ * Held to the mathematics (tests/test_relief.py): the same recurrences with mpmath at 384 bits, from the same binary64 c, give
+ * the unit vector of z / d; the model's normal differs from it by 1.4e-15 at c = 0.37 + 0.6i (n = 17), by 3.3e-14 at
+ * c = -1.75 + 0.02i (n = 12) and by 6.0e-5 at c = -0.7436438860371587 + 0.1318259043091895i (n = 1194, next to the
+ * boundary): rounding in d is amplified exactly as in the distance estimate.
+ *
+ * Two forms (csrc/mbk_relief.h), those of the distance kernel, storing identical bits: MBK_KERNEL_DEFAULT / _SCAN / _GROUP
+ * have the count kernels write the counts (into d_counts, or into scratch the ctx keeps per stream when d_counts is NULL) and
+ * run each escaped pixel for exactly its count in a second pass; MBK_KERNEL_ASM carries the derivative in one per-step pass.
+ * mbk_view_launch_normal: asynchronous, DEVICE pointers on the caller's stream; d_normal holds two binary64 per pixel of the
+ * window, (nx, ny), 8-byte aligned; d_counts and d_distance may be NULL.  d_distance receives the distance estimate of the
+ * same final state: the bits mbk_view_launch_distance stores.  Nothing is written outside the window-sized buffers.
+ * mbk_view_compute_normal: synchronous into HOST buffers on slot 0 (the slot-0 rule applies), the same pointer rules, stats as
+ * for mbk_view_compute_distance.
+ * mbk_normal_value_host / mbk_relief_shade_host: the normal of one final state and the shade q of one sample on the HOST,
+ * compiled from the functions the kernels use.
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_view_launch_distance refuses (MBK_PRECISION_F32, MBK_KERNEL_SIMPLE /
+ * _REFILL, mrd >= 2^31, a bad view), any flag bit that is no kernel selector, a NULL normal pointer.
+ *
+ * Relief renders are calls of their own, not an MBK_RENDER_* source.  A band computes the samples of mbk_view_launch_smooth
+ * (counts and nu, with the kernel `flags` select), runs the two-pass normal kernel on those counts and resolves.
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_view_render_* refuses for MBK_RENDER_SMOOTH, a NULL spec, palette or
+ * output pointer, a light or a height that is not finite or lies outside its range.
+ * mbk_relief_resolve_host: colour and resolve on the HOST for caller-supplied samples of (width s) x (height s); `normals`
+ * holds two binary64 per sample.
+ *
+ * Out of scope: deep, extended-range and Julia views; adaptive supersampling; equalised or distance base colours; sharding and
+ * slot forms; specular terms.
+ */
+typedef struct mbk_relief_spec {
+    uint32_t supersample;   /* 1, 2, 3, 4, 8 */
+    const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
+    uint32_t palette_len;   /* 2 .. 65536 */
+    uint8_t inside[4];      /* the colour of a sample that never escapes; not shaded */
+    double scale, offset;   /* as for MBK_RENDER_SMOOTH */
+    double light_x, light_y; /* the light's direction in the plane, each in [-1, 1] */
+    double height;          /* the light's height above the plane, 0 .. 2^10 */
+    uint32_t max_band_rows; /* 0 = the library's choice; any value gives the same image */
+} mbk_relief_spec;
+int mbk_view_launch_normal(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *d_counts,
+                           double *d_normal, double *d_distance, void *hip_stream);
+int mbk_view_compute_normal(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, int32_t *h_counts,
+                            double *h_normal, double *h_distance, mbk_stats *stats);
+int mbk_normal_value_host(double zr, double zi, double dr, double di, int32_t count, double out[2]);
+uint32_t mbk_relief_shade_host(double nx, double ny, double lx, double ly, double h);
+int mbk_view_relief_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_relief_spec *spec,
+                                  uint8_t *d_rgba, void *hip_stream);
+int mbk_view_relief_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_relief_spec *spec,
+                                   uint8_t *h_rgba, mbk_stats *stats);
+int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                            const double *smooth, const double *normals, uint8_t *rgba);
+
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
 #define MBK_CODEC_RLE 0x01u
