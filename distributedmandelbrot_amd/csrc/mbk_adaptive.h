@@ -7,6 +7,14 @@
 // kernel (colour, base image, mask, list of refined pixels) and the refine kernel (the fine samples of the listed pixels, one
 // lane per sample, on the hand-scheduled loops seeded per lane as mbk_julia.h seeds them).  The length of the list never
 // reaches the host.
+//
+// The refine kernels of all kinds of view are adaptive_walk around a sampler (here the plain view's; mbk_deep_adaptive.h,
+// mbk_deep_wide_adaptive.h).  The sampler contract: the walk calls sample(valid, row, col, sx, sy) once per group of the list
+// with EVERY lane of the wave present -- `valid` says whether the lane holds sample (sx, sy) of the listed pixel (row, col) of
+// the band -- and takes back that sample's count and |z|^2.  A sampler may therefore take wave-level decisions (ballots, a
+// grouped bailout test) at its top level, and must then give its lanes without a sample something harmless to run; whatever it
+// runs under `if (valid)` is an ordinary divergent loop from which no wave-uniform value may be taken.  What it returns for
+// an invalid lane is ignored.  The colour, the sums across a group (whole wave again) and the statistics are the walk's.
 #pragma once
 
 #include <vector>
@@ -15,9 +23,6 @@
 #include "mbk_render.h"
 
 namespace mbk {
-
-// a non-zero |c_i| below this takes the literal doubling; the value of mbk_api.hip's kSafeImagMin
-constexpr double kAdaptiveSafeImagMin = 0x1p-900;
 
 // The per-channel maxima of |p.ch - q.ch| over the pairs added, two channels to a word as RenderSum holds them: the 16-bit
 // halves are subtracted, made positive and folded in by packed instructions, so that a pixel's eight neighbours cost eight
@@ -191,13 +196,9 @@ __global__ __launch_bounds__(256) void adaptive_classify_kernel(const AdaptiveCl
 
 // ---- refine: the s x s samples of the listed pixels ------------------------------------------------------------------
 
-struct AdaptiveRefineArgs {
-    Axis re, im;             // the axes of the (W s) x (H s) view
-    uint32_t px0, py0;       // the band's first pixel in the W x H view
+// What the walk of the list needs, whatever the kind of view: the refine kernels' arguments all embed it.
+struct AdaptiveWalkArgs {
     uint32_t nc;             // the band's columns (a list entry is row * nc + col)
-    int32_t mrd;
-    uint32_t exact_steps;    // the grouped loop: steps tested one by one first; its cycle test's window (as TileArgs)
-    uint32_t cyc_window;
     const uint32_t *list;
     const uint32_t *len;     // DEVICE memory: the host never learns it
     uint32_t *cursor;        // the next chunk of the list to hand out (zeroed by the host before the launch)
@@ -230,28 +231,26 @@ __device__ __forceinline__ uint32_t adaptive_group_sum(uint32_t v, uint32_t firs
 // exterior a few: equal shares of the list would not be equal shares of the work).
 constexpr uint32_t kAdaptiveChunksPerWave = 4;
 
-// A grid sized to the chip; every wave takes chunks of the list from a cursor until the list is exhausted, and walks a chunk
-// in groups of G = floor(64 / s^2) listed pixels: one lane per sample.  The count and |z|^2 of a sample are the bits the tile
-// kernels store for it (block_pixel): the coordinates are axis_value's, a wave that holds a non-zero |c_i| below 2^-900 takes
-// the literal doubling (for every other c_i both doublings round alike, mbk_api.hip kSafeImagMin), and a wave within 1e-9 of
-// the ring |c| = 2 takes the per-step test.  kGroup = 0: the per-step loop throughout; 8: 8-step groups with the cycle test,
-// which retires the samples inside the set early and yields the same counts.  Lanes without a sample (the 64th at s = 3, a
-// part-filled last group) run c = 4, which leaves at step 1, and store nothing.
-template <int S, int kGroup>
-__global__ __launch_bounds__(256) void adaptive_refine_kernel(const AdaptiveRefineArgs p)
+// The walk of a refine kernel (256-thread workgroups), for supersampling S and mrd the view's: a grid sized to the chip; every
+// wave takes chunks of the list from a cursor until the list is exhausted, and walks a chunk in groups of G = floor(64 / s^2)
+// listed pixels, one lane per sample.  Per group every lane calls the sampler (the contract is at the top of this file); the
+// walk colours the samples, sums the colours across a group with the whole wave present, stores the mean and adds the samples
+// to the statistics.  Lanes without a sample (the 64th at s = 3, a part-filled last group) add colour 0 and store nothing.
+template <int S, typename Sampler>
+__device__ __forceinline__ void adaptive_walk(const AdaptiveWalkArgs &w, int32_t mrd, Sampler sample)
 {
     constexpr uint32_t S2 = (uint32_t)(S * S), G = 64u / S2;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t g = lane / S2, sub = lane - g * S2, sy = sub / (uint32_t)S, sx = sub - sy * (uint32_t)S;
-    const uint32_t n = *p.len;   // wave-uniform
+    const uint32_t n = *w.len;   // wave-uniform
     const uint32_t groups = n / G + (n % G != 0u ? 1u : 0u);
     const uint32_t chunks = gridDim.x * 4u * kAdaptiveChunksPerWave;
     const uint32_t per_chunk = groups / chunks + 1u;   // groups per request
-    const unsigned long long cap = p.mrd > 1 ? (unsigned long long)p.mrd - 1ull : 0ull;
+    const unsigned long long cap = mrd > 1 ? (unsigned long long)mrd - 1ull : 0ull;
     unsigned long long iters = 0, never = 0;
     for (;;) {
         uint32_t chunk = 0u;
-        if (lane == 0u) chunk = atomicAdd(p.cursor, 1u);
+        if (lane == 0u) chunk = atomicAdd(w.cursor, 1u);
         chunk = (uint32_t)__builtin_amdgcn_readfirstlane((int)chunk);
         const uint64_t first = (uint64_t)chunk * per_chunk;
         if (first >= (uint64_t)groups) break;
@@ -260,55 +259,91 @@ __global__ __launch_bounds__(256) void adaptive_refine_kernel(const AdaptiveRefi
             const uint64_t at = (uint64_t)grp * G + g;
             const bool valid = g < G && at < (uint64_t)n;
             uint32_t row = 0u, col = 0u;
-            double cr = 4.0, ci = 0.0;
             if (valid) {
-                const uint32_t idx = p.list[at];
-                row = idx / p.nc;
-                col = idx - row * p.nc;
-                cr = axis_value(p.re, (p.px0 + col) * (uint32_t)S + sx);
-                ci = axis_value(p.im, (p.py0 + row) * (uint32_t)S + sy);
+                const uint32_t idx = w.list[at];
+                row = idx / w.nc;
+                col = idx - row * w.nc;
             }
-            double m = 0.0;
-            int32_t count;
-            const bool literal = __ballot(ci != 0.0 && __builtin_fabs(ci) < kAdaptiveSafeImagMin) != 0ull;
-            if (literal)
-                count = escape_count_asm_from<false>(cr, ci, cr, ci, p.mrd, &m);
-            else if (kGroup == 0 || wave_touches_ring(cr, ci))
-                count = escape_count_asm_from<true>(cr, ci, cr, ci, p.mrd, &m);
-            else
-                count = escape_count_group_from<8, true>(cr, ci, cr, ci, p.mrd, &m, p.exact_steps, p.cyc_window);
-            const uint32_t colour = valid ? render_colour_smooth(p.pal, p.pal.entries, count, smooth_value(count, m)) : 0u;
+            const EscapeSample f = sample(valid, row, col, sx, sy);
+            const uint32_t colour = valid ? render_colour_smooth(w.pal, w.pal.entries, f.count, smooth_value(f.count, f.mag)) : 0u;
+            // every lane of the wave is here
             RenderSum sum;
             sum.even = adaptive_group_sum<S2>(render_even(colour), g * S2);
             sum.odd = adaptive_group_sum<S2>(render_odd(colour), g * S2);
             if (valid) {
-                if (sub == 0u) p.out[(uint64_t)row * p.out_pitch + col] = sum.mean(S2);
-                iters += count > 0 ? (unsigned long long)count : cap;
-                never += count == 0 ? 1ull : 0ull;
+                if (sub == 0u) w.out[(uint64_t)row * w.out_pitch + col] = sum.mean(S2);
+                iters += f.count > 0 ? (unsigned long long)f.count : cap;
+                never += f.count == 0 ? 1ull : 0ull;
             }
         }
     }
-    if (p.stats) {
+    if (w.stats) {
         iters = wave_sum_u64(iters);
         never = wave_sum_u64(never);
         if (lane == 0u) {
-            ReduceOut *out = &p.stats[(blockIdx.x * 4u + (threadIdx.x >> 6)) % kReduceSlots].r;
+            ReduceOut *out = &w.stats[(blockIdx.x * 4u + (threadIdx.x >> 6)) % kReduceSlots].r;
             if (iters) atomicAdd(&out->pixel_iterations, iters);
             if (never) atomicAdd(&out->never_pixels, never);
         }
     }
 }
 
-template <int kGroup>
-inline void launch_adaptive_refine(uint32_t s, dim3 grid, hipStream_t stream, const AdaptiveRefineArgs &a)
+// Family: the refine kernels of a kind of view -- Args, and kernel<S> the instantiation for supersampling S
+template <typename Family>
+inline void launch_adaptive_refine(uint32_t s, dim3 grid, hipStream_t stream, const typename Family::Args &a)
 {
     const dim3 block(256);
     switch (s) {
-        case 2: hipLaunchKernelGGL((adaptive_refine_kernel<2, kGroup>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((adaptive_refine_kernel<3, kGroup>), grid, block, 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((adaptive_refine_kernel<4, kGroup>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((adaptive_refine_kernel<8, kGroup>), grid, block, 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((Family::template kernel<2>), grid, block, 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((Family::template kernel<3>), grid, block, 0, stream, a); break;
+        case 4: hipLaunchKernelGGL((Family::template kernel<4>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((Family::template kernel<8>), grid, block, 0, stream, a); break;
     }
 }
+
+// ---- the plain view's refine kernel ----------------------------------------------------------------------------------------
+
+struct AdaptiveRefineArgs {
+    AdaptiveWalkArgs w;
+    Axis re, im;             // the axes of the (W s) x (H s) view
+    uint32_t px0, py0;       // the band's first pixel in the W x H view
+    int32_t mrd;
+    uint32_t exact_steps;    // the grouped loop: steps tested one by one first; its cycle test's window (as TileArgs)
+    uint32_t cyc_window;
+};
+
+// The count and |z|^2 of a sample are the bits the tile kernels store for it (block_pixel): the coordinates are axis_value's, a
+// wave that holds a non-zero |c_i| below 2^-900 takes the literal doubling (for every other c_i both doublings round alike,
+// kSafeImagMin), and a wave within 1e-9 of the ring |c| = 2 takes the per-step test.  kGroup = 0: the per-step loop throughout;
+// 8: 8-step groups with the cycle test, which retires the samples inside the set early and yields the same counts.  These
+// three decisions are the wave's, taken with every lane present; lanes without a sample run c = 4, which leaves at step 1.
+template <int S, int kGroup>
+__global__ __launch_bounds__(256) void adaptive_refine_kernel(const AdaptiveRefineArgs p)
+{
+    adaptive_walk<S>(p.w, p.mrd, [&p](bool valid, uint32_t row, uint32_t col, uint32_t sx, uint32_t sy) {
+        double cr = 4.0, ci = 0.0;
+        if (valid) {
+            cr = axis_value(p.re, (p.px0 + col) * (uint32_t)S + sx);
+            ci = axis_value(p.im, (p.py0 + row) * (uint32_t)S + sy);
+        }
+        double m = 0.0;
+        int32_t count;
+        const bool literal = __ballot(ci != 0.0 && __builtin_fabs(ci) < kSafeImagMin) != 0ull;
+        if (literal)
+            count = escape_count_asm_from<false>(cr, ci, cr, ci, p.mrd, &m);
+        else if (kGroup == 0 || wave_touches_ring(cr, ci))
+            count = escape_count_asm_from<true>(cr, ci, cr, ci, p.mrd, &m);
+        else
+            count = escape_count_group_from<8, true>(cr, ci, cr, ci, p.mrd, &m, p.exact_steps, p.cyc_window);
+        return EscapeSample{count, m};
+    });
+}
+
+template <int kGroup>
+struct AdaptiveRefine {
+    using Args = AdaptiveRefineArgs;
+    template <int S>
+    static constexpr auto kernel = adaptive_refine_kernel<S, kGroup>;
+};
 
 }   // namespace mbk

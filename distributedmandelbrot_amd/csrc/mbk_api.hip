@@ -53,6 +53,7 @@ using mbk::ReduceOut;
 using mbk::ReduceSlot;
 using mbk::TileArgs;
 using mbk::WorkQueues;
+using mbk::kSafeImagMin;   // (mbk_kernels.h: the literal-doubling threshold, which the refine kernel tests on the device)
 
 // Dispatch lists per stream, used in turn.  Two were enough to let the pre-pass of launch L + 1 run beside the tile kernel of
 // launch L -- but a second queue gets no wave slot on a chip full of single-wave workgroups until the tile kernel's grid is
@@ -334,10 +335,6 @@ static bool axis_end_is_regular(const Axis &a)
 // Coordinates must stay far from overflow so that no inf-inf = NaN can appear before the bailout
 // test fires (the hand-scheduled kernels compare the high word of |z|^2 as an integer).
 static const double kMaxCoord = 0x1p500;
-// fma(2, zr*zi, ci) == fl(fl((2*zr)*zi) + ci) unless zr*zi is subnormal AND ci is so small that
-// the last bit of a subnormal survives the addition.  |ci| >= 2^-900 (or ci == 0, where zi stays
-// exactly 0) rules that out; otherwise use the literal (2*zr)*zi instantiation.
-static const double kSafeImagMin = 0x1p-900;
 
 // A multiplier coprime to n near n * (golden ratio - 1): id -> (id * m) mod n is a bijection that
 // sends neighbouring ids far apart.
@@ -4612,8 +4609,62 @@ static int adaptive_tables(mbk_ctx *ctx, const Target &t, uint32_t flags, uint32
     return MBK_OK;
 }
 
-// The refine step of a deep view's band: the fine samples of the listed pixels by perturbation (mbk_deep_adaptive.h), with the
-// skips of `fine` where it holds a table.  (x0, y0, nc, nr): the band in the W x H view.
+// The waves per SIMD a refine grid asks for: what every instantiation of the kind's kernel holds at once by its registers
+// (profiles/refine_walk/README.md has the compiler's table).
+static const uint32_t kPlainRefineWaves = 6u;   // 43 .. 77 VGPRs: 6 or 7
+static const uint32_t kDeepRefineWaves = 5u;    // 73 .. 85 VGPRs: 5 or 6
+static const uint32_t kWideRefineWaves = 5u;    // 65 .. 81 VGPRs: 5 to 7
+
+// What the walk of a refine kernel takes over from the band's classify launch.  d_words: the list's length and the cursor.
+static mbk::AdaptiveWalkArgs refine_walk_args(const mbk::AdaptiveClassifyArgs &a, uint32_t *d_words)
+{
+    mbk::AdaptiveWalkArgs w;
+    std::memset(&w, 0, sizeof(w));
+    w.nc = a.nc;
+    w.list = a.list;
+    w.len = d_words;
+    w.cursor = d_words + 1;
+    w.out = a.out;
+    w.out_pitch = a.out_pitch;
+    w.stats = a.stats;
+    w.pal = a.pal;
+    return w;
+}
+
+// The grid of a refine kernel on an nc x nr band: `waves` waves per SIMD -- one 256-thread workgroup per CU each --, and no
+// more workgroups than groups the fullest list can hold.
+static dim3 refine_grid(const mbk_ctx *ctx, uint32_t s, uint32_t nc, uint32_t nr, uint32_t waves)
+{
+    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
+    const uint32_t per_group = 64u / (s * s);
+    const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
+    return dim3((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * waves));
+}
+
+// The refine step of a plain view's band: the fine samples of the listed pixels on the hand-scheduled loops (mbk_adaptive.h).
+// (x0, y0, nc, nr): the band in the W x H view; a: the band's classify launch.
+static int launch_plain_refine(mbk_ctx *ctx, const Target &t, uint32_t s, uint32_t x0, uint32_t y0, uint32_t nc, uint32_t nr, uint32_t mrd,
+                               bool per_step, const mbk::AdaptiveClassifyArgs &a, uint32_t *d_words, hipStream_t stream)
+{
+    mbk::AdaptiveRefineArgs f;
+    std::memset(&f, 0, sizeof(f));
+    f.w = refine_walk_args(a, d_words);
+    f.re = make_axis(t.view.start_r, t.view.range_r, t.g.width * s);
+    f.im = make_axis(t.view.start_i, t.view.range_i, t.g.height * s);
+    f.px0 = x0;
+    f.py0 = y0;
+    f.mrd = (int32_t)mrd;
+    f.exact_steps = ctx->opt[MBK_OPT_EXACT_STEPS];
+    f.cyc_window = ctx->opt[MBK_OPT_CYCLE_WINDOW];
+    const dim3 grid = refine_grid(ctx, s, nc, nr, kPlainRefineWaves);
+    if (per_step) mbk::launch_adaptive_refine<mbk::AdaptiveRefine<0>>(s, grid, stream, f);
+    else mbk::launch_adaptive_refine<mbk::AdaptiveRefine<8>>(s, grid, stream, f);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// The refine step of a deep view's band: the fine samples by perturbation (mbk_deep_adaptive.h), with the skips of `fine` where
+// it holds a table.
 static int launch_deep_refine(mbk_ctx *ctx, const Target &t, uint32_t s, uint32_t x0, uint32_t y0, uint32_t nc, uint32_t nr, uint32_t mrd,
                               const mbk::DeepBlaArgs &fine, const mbk::AdaptiveClassifyArgs &a, uint32_t *d_words, hipStream_t stream)
 {
@@ -4623,30 +4674,15 @@ static int launch_deep_refine(mbk_ctx *ctx, const Target &t, uint32_t s, uint32_
     const Target samples = target_samples(t, s, x0, y0, nc, nr);
     mbk::DeepAdaptiveRefineArgs f;
     std::memset(&f, 0, sizeof(f));
+    f.w = refine_walk_args(a, d_words);
     f.b = fine;
     fill_deep_args(f.b.v, c->d, t.orbit, &samples.deep, mrd);
-    f.nc = nc;
-    f.list = a.list;
-    f.len = d_words;
-    f.cursor = d_words + 1;
-    f.out = a.out;
-    f.out_pitch = a.out_pitch;
-    f.stats = a.stats;
-    f.pal = a.pal;
-    // 5 waves per SIMD, which every instantiation's registers allow at once (74 .. 85 VGPRs: 5 or 6); no more workgroups than
-    // groups the fullest list can hold
-    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
-    const uint32_t per_group = 64u / (s * s);
-    const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
-    const dim3 grid((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * 5u));
-    if (fine.rc) mbk::launch_deep_adaptive_refine<true>(s, grid, stream, f);
-    else mbk::launch_deep_adaptive_refine<false>(s, grid, stream, f);
+    const dim3 grid = refine_grid(ctx, s, nc, nr, kDeepRefineWaves);
+    if (fine.rc) mbk::launch_adaptive_refine<mbk::DeepAdaptiveRefine<true>>(s, grid, stream, f);
+    else mbk::launch_adaptive_refine<mbk::DeepAdaptiveRefine<false>>(s, grid, stream, f);
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
 }
-
-// the wide refine grid's waves per SIMD: what all eight instantiations hold at once (65 .. 81 VGPRs: 5 to 7)
-static const uint32_t kWideRefineWaves = 5u;
 
 // The refine step of an extended-range deep view's band: launch_deep_refine's twin in the wide number system
 // (mbk_deep_wide_adaptive.h), on the wide orbit table, with the skips of `fine` where it holds a table.
@@ -4659,24 +4695,12 @@ static int launch_deep_wide_refine(mbk_ctx *ctx, const Target &t, uint32_t s, ui
     const Target samples = target_samples(t, s, x0, y0, nc, nr);
     mbk::DeepWideAdaptiveRefineArgs f;
     std::memset(&f, 0, sizeof(f));
+    f.w = refine_walk_args(a, d_words);
     f.b = fine;
     fill_deep_wide_args(f.b.v, d_orbit, t.orbit, &samples.wide, mrd);
-    f.nc = nc;
-    f.list = a.list;
-    f.len = d_words;
-    f.cursor = d_words + 1;
-    f.out = a.out;
-    f.out_pitch = a.out_pitch;
-    f.stats = a.stats;
-    f.pal = a.pal;
-    // kWideRefineWaves waves per SIMD, which every instantiation's registers allow at once (profiles/deep_wide_adaptive/README.md
-    // has the compiler's table); no more workgroups than groups the fullest list can hold
-    const uint32_t cus = (uint32_t)std::max(ctx->prop.multiProcessorCount, 1);
-    const uint32_t per_group = 64u / (s * s);
-    const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
-    const dim3 grid((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * kWideRefineWaves));
-    if (fine.ke) mbk::launch_deep_wide_adaptive_refine<true>(s, grid, stream, f);
-    else mbk::launch_deep_wide_adaptive_refine<false>(s, grid, stream, f);
+    const dim3 grid = refine_grid(ctx, s, nc, nr, kWideRefineWaves);
+    if (fine.ke) mbk::launch_adaptive_refine<mbk::DeepWideAdaptiveRefine<true>>(s, grid, stream, f);
+    else mbk::launch_adaptive_refine<mbk::DeepWideAdaptiveRefine<false>>(s, grid, stream, f);
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
 }
@@ -4753,38 +4777,11 @@ static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t fl
         MBK_HIP(ctx, hipGetLastError());
         // 3. refine: the fine samples of the listed pixels (at s = 1 a refined pixel is its base pixel: nothing to do), by the
         // kernel of the kind
-        if (s > 1u && threshold < 256u && t.kind == Target::kDeep) {
-            rc = launch_deep_refine(ctx, t, s, x0, y0, nc, nr, mrd, fine->deep, a, d_words, stream);
+        if (s > 1u && threshold < 256u) {
+            if (t.kind == Target::kDeep) rc = launch_deep_refine(ctx, t, s, x0, y0, nc, nr, mrd, fine->deep, a, d_words, stream);
+            else if (t.kind == Target::kWide) rc = launch_deep_wide_refine(ctx, t, s, x0, y0, nc, nr, mrd, fine->wide, a, d_words, stream);
+            else rc = launch_plain_refine(ctx, t, s, x0, y0, nc, nr, mrd, per_step, a, d_words, stream);
             if (rc != MBK_OK) return rc;
-        } else if (s > 1u && threshold < 256u && t.kind == Target::kWide) {
-            rc = launch_deep_wide_refine(ctx, t, s, x0, y0, nc, nr, mrd, fine->wide, a, d_words, stream);
-            if (rc != MBK_OK) return rc;
-        } else if (s > 1u && threshold < 256u) {
-            mbk::AdaptiveRefineArgs f;
-            std::memset(&f, 0, sizeof(f));
-            f.re = make_axis(t.view.start_r, t.view.range_r, t.g.width * s);
-            f.im = make_axis(t.view.start_i, t.view.range_i, t.g.height * s);
-            f.px0 = x0;
-            f.py0 = y0;
-            f.nc = nc;
-            f.mrd = (int32_t)mrd;
-            f.exact_steps = ctx->opt[MBK_OPT_EXACT_STEPS];
-            f.cyc_window = ctx->opt[MBK_OPT_CYCLE_WINDOW];
-            f.list = d_list;
-            f.len = d_words;
-            f.cursor = d_words + 1;
-            f.out = a.out;
-            f.out_pitch = t.g.ncols;
-            f.stats = d_red;
-            f.pal = a.pal;
-            // 6 waves per SIMD, which every instantiation's registers allow at once; no more workgroups than groups the
-            // fullest list can hold
-            const uint32_t per_group = 64u / (s * s);
-            const uint64_t groups = ((uint64_t)nc * nr + per_group - 1u) / per_group;
-            const dim3 grid((uint32_t)std::min<uint64_t>((groups + 3u) / 4u, (uint64_t)cus * 6u));
-            if (per_step) mbk::launch_adaptive_refine<0>(s, grid, stream, f);
-            else mbk::launch_adaptive_refine<8>(s, grid, stream, f);
-            MBK_HIP(ctx, hipGetLastError());
         }
         if (stat && is_last) MBK_HIP(ctx, hipEventRecord(stat->ev_k1, stream));
         return MBK_OK;

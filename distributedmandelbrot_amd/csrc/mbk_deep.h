@@ -75,11 +75,13 @@ __host__ __device__ __forceinline__ bool deep_rebase(double mg, double dzr, doub
     return mg < dm;
 }
 
-__global__ __launch_bounds__(64) void deep_view_kernel(DeepArgs p)
+// The escape loop of the sample at offset dc: its count and |z|^2 at the escaping step (0, 0 for a sample that stays).  Written
+// once for deep_view_kernel and the refine kernel of an adaptive render (mbk_deep_adaptive.h), whose samples must be the bits
+// this launch stores.  The four escape functions return by value on purpose: with count and mag as reference out-parameters the
+// stores through them sit in the loop while the function is optimised on its own, before it is inlined, and deep_view_kernel's
+// loop comes out restructured (profiles/refine_walk/README.md).
+__device__ __forceinline__ EscapeSample deep_escape(const DeepArgs &p, double dcr, double dci)
 {
-    const DeepPixel px = deep_pixel(p);
-    if (!px.inside) return;
-    const double dcr = px.dcr, dci = px.dci;
     double dzr, dzi, zr, zi;
     OrbitCursor<double4> c(p.orbit, p.z1, p.M, deep_start(p.z1.x, p.z1.y, p.M, dcr, dci, dzr, dzi, zr, zi));
     int32_t count = 0;
@@ -104,10 +106,18 @@ __global__ __launch_bounds__(64) void deep_view_kernel(DeepArgs p)
         }
         c.prefetch();
     }
+    return EscapeSample{count, mag};
+}
+
+__global__ __launch_bounds__(64) void deep_view_kernel(DeepArgs p)
+{
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const EscapeSample e = deep_escape(p, px.dcr, px.dci);
     const size_t o = (size_t)px.lr * p.ncols + px.lc;
-    if (p.counts) p.counts[o] = count;
-    if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
-    if (p.smooth) p.smooth[o] = smooth_value(count, mag);
+    if (p.counts) p.counts[o] = e.count;
+    if (p.bytes) p.bytes[o] = quantise(e.count, p.mrd, p.quant_wide, p.quant_rcp);
+    if (p.smooth) p.smooth[o] = smooth_value(e.count, e.mag);
 }
 
 }  // namespace mbk

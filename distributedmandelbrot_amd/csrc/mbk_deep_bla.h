@@ -161,12 +161,11 @@ struct DeepBlaArgs {
     uint32_t off[kBlaMaxLevels];     // level l starts at off[l]
 };
 
-__global__ __launch_bounds__(64) void deep_bla_kernel(DeepBlaArgs q)
+// The escape loop of the sample at offset dc with the table's skips (M >= 2), as deep_escape is the plain one: written once for
+// deep_bla_kernel and the refine kernel of an adaptive render (mbk_deep_adaptive.h).
+__device__ __forceinline__ EscapeSample deep_bla_escape(const DeepBlaArgs &q, double dcr, double dci)
 {
     const DeepArgs &p = q.v;
-    const DeepPixel px = deep_pixel(p);
-    if (!px.inside) return;
-    const double dcr = px.dcr, dci = px.dci;
     double dzr = dcr, dzi = dci;
     BlaCursor<double4, double> c(p.orbit, p.z1, p.M, q.rc, 0.0);   // the radius is level 0's rc; 0 at m == 0
     int32_t count = 0;
@@ -199,10 +198,19 @@ __global__ __launch_bounds__(64) void deep_bla_kernel(DeepBlaArgs q)
         }
         c.prefetch();
     }
+    return EscapeSample{count, mag};
+}
+
+__global__ __launch_bounds__(64) void deep_bla_kernel(DeepBlaArgs q)
+{
+    const DeepArgs &p = q.v;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const EscapeSample e = deep_bla_escape(q, px.dcr, px.dci);
     const size_t o = (size_t)px.lr * p.ncols + px.lc;
-    if (p.counts) p.counts[o] = count;
-    if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
-    if (p.smooth) p.smooth[o] = smooth_value(count, mag);
+    if (p.counts) p.counts[o] = e.count;
+    if (p.bytes) p.bytes[o] = quantise(e.count, p.mrd, p.quant_wide, p.quant_rcp);
+    if (p.smooth) p.smooth[o] = smooth_value(e.count, e.mag);
 }
 
 // One pixel on the host, from the functions the kernel uses: the count, |z|^2 at the escaping step, and the number of steps

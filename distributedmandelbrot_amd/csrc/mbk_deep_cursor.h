@@ -31,7 +31,16 @@ struct DeepPixel {
     bool inside;         // false: the lane is past the window's edge and has nothing to do
 };
 
-// One lane per pixel, one 8x8 block per single-wave workgroup, image order.  Args: DeepArgs or DeepWideArgs.
+// The offset of pixel (lc, lr) of the window: dc = fl(fl(k - (W-1)/2) * s); the subtraction is exact (|k| < 2^32, a half-integer
+// at most).  Args: DeepArgs or DeepWideArgs.
+template <typename Args>
+__device__ __forceinline__ void deep_offset(const Args &p, uint32_t lc, uint32_t lr, double &dcr, double &dci)
+{
+    dcr = ((double)(p.col0 + lc) - p.half_r) * p.step_r;
+    dci = ((double)(p.row0 + lr) - p.half_i) * p.step_i;
+}
+
+// One lane per pixel, one 8x8 block per single-wave workgroup, image order.
 template <typename Args>
 __device__ __forceinline__ DeepPixel deep_pixel(const Args &p)
 {
@@ -41,9 +50,7 @@ __device__ __forceinline__ DeepPixel deep_pixel(const Args &p)
     px.lc = bx * 8u + (lane & 7u);
     px.lr = by * 8u + (lane >> 3);
     px.inside = px.lc < p.ncols && px.lr < p.nrows;
-    // dc = fl(fl(k - (W-1)/2) * s): the subtraction is exact (|k| < 2^32, a half-integer at most)
-    px.dcr = ((double)(p.col0 + px.lc) - p.half_r) * p.step_r;
-    px.dci = ((double)(p.row0 + px.lr) - p.half_i) * p.step_i;
+    deep_offset(p, px.lc, px.lr, px.dcr, px.dci);
     return px;
 }
 

@@ -126,11 +126,11 @@ __host__ __device__ __forceinline__ uint32_t wide_start(const WideEntry &z1, uin
     return 0u;
 }
 
-__global__ __launch_bounds__(64) void deep_wide_kernel(DeepWideArgs p)
+// The escape loop of the sample at offset dc 2^exp2: its count and |z|^2 at the escaping step as a plain binary64 (0, 0 for a
+// sample that stays), by value as deep_escape (mbk_deep.h).  Written once for deep_wide_kernel and the refine kernel of an
+// adaptive render (mbk_deep_wide_adaptive.h), whose samples must be the bits this launch stores.
+__device__ __forceinline__ EscapeSample deep_wide_escape(const DeepWideArgs &p, double dcr, double dci)
 {
-    const DeepPixel px = deep_pixel(p);
-    if (!px.inside) return;
-    const double dcr = px.dcr, dci = px.dci;
     const int32_t exp2 = p.exp2;
     double wr, wi, zr, zi, mg;
     int32_t q, t;
@@ -155,10 +155,18 @@ __global__ __launch_bounds__(64) void deep_wide_kernel(DeepWideArgs p)
         }
         c.prefetch();
     }
+    return EscapeSample{count, mag};
+}
+
+__global__ __launch_bounds__(64) void deep_wide_kernel(DeepWideArgs p)
+{
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const EscapeSample e = deep_wide_escape(p, px.dcr, px.dci);
     const size_t o = (size_t)px.lr * p.ncols + px.lc;
-    if (p.counts) p.counts[o] = count;
-    if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
-    if (p.smooth) p.smooth[o] = smooth_value(count, mag);
+    if (p.counts) p.counts[o] = e.count;
+    if (p.bytes) p.bytes[o] = quantise(e.count, p.mrd, p.quant_wide, p.quant_rcp);
+    if (p.smooth) p.smooth[o] = smooth_value(e.count, e.mag);
 }
 
 // One pixel on the host, from the functions the kernel uses: the count and |z|^2 at the escaping step (0 for count 0).

@@ -201,12 +201,11 @@ struct DeepWideBlaArgs {
     uint32_t off[kBlaMaxLevels];     // level l starts at off[l]
 };
 
-__global__ __launch_bounds__(64) void deep_wide_bla_kernel(DeepWideBlaArgs a)
+// The escape loop of the sample at offset dc 2^exp2 with the table's skips (M >= 2), as deep_wide_escape is the plain one:
+// written once for deep_wide_bla_kernel and the refine kernel of an adaptive render (mbk_deep_wide_adaptive.h).
+__device__ __forceinline__ EscapeSample deep_wide_bla_escape(const DeepWideBlaArgs &a, double dcr, double dci)
 {
     const DeepWideArgs &p = a.v;
-    const DeepPixel px = deep_pixel(p);
-    if (!px.inside) return;
-    const double dcr = px.dcr, dci = px.dci;
     const int32_t exp2 = p.exp2;
     double wr, wi;
     int32_t q;
@@ -243,10 +242,19 @@ __global__ __launch_bounds__(64) void deep_wide_bla_kernel(DeepWideBlaArgs a)
         }
         c.prefetch();
     }
+    return EscapeSample{count, mag};
+}
+
+__global__ __launch_bounds__(64) void deep_wide_bla_kernel(DeepWideBlaArgs a)
+{
+    const DeepWideArgs &p = a.v;
+    const DeepPixel px = deep_pixel(p);
+    if (!px.inside) return;
+    const EscapeSample e = deep_wide_bla_escape(a, px.dcr, px.dci);
     const size_t o = (size_t)px.lr * p.ncols + px.lc;
-    if (p.counts) p.counts[o] = count;
-    if (p.bytes) p.bytes[o] = quantise(count, p.mrd, p.quant_wide, p.quant_rcp);
-    if (p.smooth) p.smooth[o] = smooth_value(count, mag);
+    if (p.counts) p.counts[o] = e.count;
+    if (p.bytes) p.bytes[o] = quantise(e.count, p.mrd, p.quant_wide, p.quant_rcp);
+    if (p.smooth) p.smooth[o] = smooth_value(e.count, e.mag);
 }
 
 // One pixel on the host, from the functions the kernel uses: the count, |z|^2 at the escaping step, and the number of steps

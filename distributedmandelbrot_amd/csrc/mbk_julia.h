@@ -47,10 +47,8 @@ struct JuliaArgs {
     double *smooth;        // may be null
 };
 
-// |c_i| below this takes the literal doubling (see above); the value of mbk_api.hip's kSafeImagMin
-constexpr double kJuliaSafeImagMin = 0x1p-900;
-
-__host__ __device__ inline bool julia_needs_literal(double ci) { return !(__builtin_fabs(ci) >= kJuliaSafeImagMin); }
+// |c_i| below kSafeImagMin (mbk_kernels.h) takes the literal doubling (see above)
+__host__ __device__ inline bool julia_needs_literal(double ci) { return !(__builtin_fabs(ci) >= kSafeImagMin); }
 
 // May a launch with this parameter use the grouped bailout test?  (host arithmetic; the rounding of c2 is 1e-7 of the margin)
 inline bool julia_grouped_ok(double cr, double ci) { return cr * cr + ci * ci < 4.0 - 1e-9; }

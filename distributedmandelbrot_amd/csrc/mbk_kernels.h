@@ -36,6 +36,11 @@ struct Axis {
     uint32_t step_is_zero;  // numpy: y = (k/div)*delta instead of k*step
 };
 
+// fma(2, zr*zi, ci) == fl(fl((2*zr)*zi) + ci) unless zr*zi is subnormal AND ci is so small that
+// the last bit of a subnormal survives the addition.  |ci| >= 2^-900 (or ci == 0, where zi stays
+// exactly 0) rules that out; otherwise use the literal (2*zr)*zi instantiation.
+constexpr double kSafeImagMin = 0x1p-900;
+
 struct ReduceSlot;   // (below: partial results of the statistics reduction)
 
 constexpr uint32_t kSpillLevels = 12;    // SPILL: checkpoints told apart in the list's order (a block's count word: lanes | level << 8; mbk_spill.h)
@@ -151,6 +156,13 @@ __device__ __forceinline__ double smooth_value(int32_t count, double m)
 {
     return count > 0 ? (double)count + 1.0 - log2(0.5 * log(m)) : 0.0;
 }
+
+// What an escape loop yields where it is a function of its own (the deep views' loops, the samplers of mbk_adaptive.h): the
+// count, and |z|^2 at the escaping step as smooth_value takes it; 0, 0 for a sample that never escaped.
+struct EscapeSample {
+    int32_t count;
+    double mag;
+};
 
 // The reference loop for one pixel.  kFmaDouble selects how fl(2*zr*zi + ci) is formed.
 template <bool kFmaDouble>

@@ -123,6 +123,24 @@ def test_windows_and_bands_equal_the_same_rectangle_of_the_whole_image(gpu, name
             assert (st.pixel_iterations, st.never_pixels) == _stats_model(gpu, name, s, whole_mask), (s, rows)
 
 
+# One listed pixel is a list shorter than one group of the refine kernel's walk at s = 2, 3, 4 (16, 7, 4 pixels to a group) and
+# three end inside a group; at s = 8 a pixel is a group.  Inside the view; touching its right and its bottom edge.
+TINY_WINDOWS = [(33, 22, 1, 1), (W - 3, H - 1, 3, 1)]
+
+
+@pytest.mark.parametrize("s", [2, 3, 4, 8])
+def test_lists_shorter_than_a_group_equal_the_same_pixels_of_the_full_render(gpu, s):
+    name = "inset-boundary"
+    view, mrd, _ = _view(name)
+    full, _ = gpu.render_view(view, mrd, palette=PAL, supersample=s)
+    everything = np.ones((H, W), bool)
+    for window in TINY_WINDOWS:
+        c0, r0, nc, nr = window
+        img, st = gpu.render_view_adaptive(view, mrd, palette=PAL, supersample=s, threshold=0, window=window)
+        assert np.array_equal(img, full[r0:r0 + nr, c0:c0 + nc]), window
+        assert (st.pixel_iterations, st.never_pixels) == _stats_model(gpu, name, s, everything, window), window
+
+
 def test_a_view_inside_the_main_cardioid_refines_nothing(gpu):
     view, mrd = View(-0.25, -0.05 * H / W, 0.1, 0.1 * H / W, W, H), 200
     for s in (2, 8):

@@ -134,6 +134,25 @@ def test_windows_and_bands_equal_the_same_rectangle_of_the_whole_image(gpu, name
             assert (st.pixel_iterations, st.never_pixels) == _stats_model(gpu, name, s, whole_mask, bla), (s, rows)
 
 
+# One listed pixel is a list shorter than one group of the refine kernel's walk at s = 2, 3, 4 (16, 7, 4 pixels to a group) and
+# three end inside a group; at s = 8 a pixel is a group.  Inside the 67 x 45 view; touching its right and its bottom edge.
+TINY_WINDOWS = [(33, 22, 1, 1), (64, 44, 3, 1)]
+
+
+@pytest.mark.parametrize("bla", [False, True], ids=["plain", "bla"])
+@pytest.mark.parametrize("s", [2, 3, 4, 8])
+def test_lists_shorter_than_a_group_equal_the_same_pixels_of_the_full_render(gpu, s, bla):
+    name = "i-30"
+    orbit, view, mrd, pal, _ = K.case(name)
+    full, _ = gpu.render_deep_view(orbit, view, mrd, palette=pal, supersample=s, bla=bla)
+    everything = np.ones((view.height, view.width), bool)
+    for window in TINY_WINDOWS:
+        c0, r0, nc, nr = window
+        img, st = gpu.render_deep_view_adaptive(orbit, view, mrd, palette=pal, supersample=s, threshold=0, window=window, bla=bla)
+        assert np.array_equal(img, full[r0:r0 + nr, c0:c0 + nc]), window
+        assert (st.pixel_iterations, st.never_pixels) == _stats_model(gpu, name, s, everything, bla, window), window
+
+
 def test_both_tables_of_a_render_stay_resident_and_a_third_span_takes_only_one_place(gpu):
     """Three dcmax in turn on one orbit (the two of an adaptive render, then a plain launch's, then the two again) and another
     orbit's render in between: every result is its model's, and the first render comes back bit for bit."""
