@@ -1550,6 +1550,22 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
     return sync_end(ctx, enqueue(), stats, false);
 }
 
+// The first pass of a two-pass launch (distance estimates, normals, interior views) of px pixels on `stream`:
+// count_launch(counts) has the escape kernels write the counts the second pass runs on -- the caller's, or the stream's scratch
+// when the caller wants none; *d_counts is where they are.
+template <typename CountLaunch>
+static int launch_count_pass(mbk_ctx *ctx, size_t px, hipStream_t stream, int32_t **d_counts, CountLaunch count_launch)
+{
+    if (!*d_counts) {
+        StreamScratch *sc = nullptr;
+        int rc = get_scratch(ctx, stream, &sc);
+        if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
+        if (rc != MBK_OK) return rc;
+        *d_counts = sc->d_dist_counts;
+    }
+    return count_launch(*d_counts);
+}
+
 // MBK_WANT_* flags need the pointers they fill
 static int check_wanted(mbk_ctx *ctx, uint32_t flags, const void *counts, const void *bytes)
 {
@@ -2297,16 +2313,10 @@ static int launch_distance(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32
 {
     const uint32_t kernel = flags & MBK_KERNEL_MASK;
     const bool one_pass = kernel == MBK_KERNEL_ASM;
-    const size_t px = (size_t)v->ncols * v->nrows;
     if (!one_pass) {
-        if (!d_counts) {
-            StreamScratch *sc = nullptr;
-            int rc = get_scratch(ctx, stream, &sc);
-            if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
-            if (rc != MBK_OK) return rc;
-            d_counts = sc->d_dist_counts;
-        }
-        int rc = launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+        int rc = launch_count_pass(ctx, (size_t)v->ncols * v->nrows, stream, &d_counts, [&](int32_t *counts) {
+            return launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, counts, nullptr, stream);
+        });
         if (rc != MBK_OK) return rc;
     }
     mbk::DistanceArgs a;
@@ -2327,32 +2337,6 @@ static int launch_distance(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32
     }
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
-}
-
-int mbk_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
-                             int32_t *d_counts, double *d_distance, void *hip_stream)
-{
-    if (!ctx || !d_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
-    bool safe = false;
-    int rc = distance_check(ctx, view, mrd, flags, &safe);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_distance(ctx, view, mrd, flags, safe, d_counts, d_distance, (hipStream_t)hip_stream);
-}
-
-int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
-                              int32_t *h_counts, double *h_distance, mbk_stats *stats)
-{
-    if (!ctx || !view || !h_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
-    bool safe = false;
-    int rc = distance_check(ctx, view, mrd, flags & (MBK_KERNEL_MASK | MBK_DEEP_XBLA), &safe);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_distance, stats,
-                          [&](int32_t *d_counts, double *d_distance, hipStream_t stream) {
-                              return launch_distance(ctx, view, mrd, flags & MBK_KERNEL_MASK, safe, d_counts, d_distance, stream);
-                          });
 }
 
 double mbk_distance_value_host(double mag, double dmag, int32_t count)
@@ -2406,15 +2390,9 @@ static int launch_normal(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t
 {
     const uint32_t kernel = flags & MBK_KERNEL_MASK;
     if (kernel == MBK_KERNEL_ASM) return launch_relief_kernel(ctx, v, mrd, safe, nullptr, d_counts, d_normal, d_distance, stream);
-    const size_t px = (size_t)v->ncols * v->nrows;
-    if (!d_counts) {
-        StreamScratch *sc = nullptr;
-        int rc = get_scratch(ctx, stream, &sc);
-        if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
-        if (rc != MBK_OK) return rc;
-        d_counts = sc->d_dist_counts;
-    }
-    int rc = launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+    int rc = launch_count_pass(ctx, (size_t)v->ncols * v->nrows, stream, &d_counts, [&](int32_t *counts) {
+        return launch_tile(ctx, v, mrd, kernel | MBK_WANT_COUNTS, counts, nullptr, stream);
+    });
     if (rc != MBK_OK) return rc;
     return launch_relief_kernel(ctx, v, mrd, safe, d_counts, nullptr, d_normal, d_distance, stream);
 }
@@ -2480,15 +2458,9 @@ static int interior_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint
 static int launch_interior(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags, bool safe, int32_t *d_counts,
                            int32_t *d_period, double *d_distance, hipStream_t stream)
 {
-    const size_t px = (size_t)v->ncols * v->nrows;
-    if (!d_counts) {
-        StreamScratch *sc = nullptr;
-        int rc = get_scratch(ctx, stream, &sc);
-        if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
-        if (rc != MBK_OK) return rc;
-        d_counts = sc->d_dist_counts;
-    }
-    int rc = launch_tile(ctx, v, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, d_counts, nullptr, stream);
+    int rc = launch_count_pass(ctx, (size_t)v->ncols * v->nrows, stream, &d_counts, [&](int32_t *counts) {
+        return launch_tile(ctx, v, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, counts, nullptr, stream);
+    });
     if (rc != MBK_OK) return rc;
     mbk::InteriorArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -3113,12 +3085,14 @@ static int wide_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideE
     return MBK_OK;
 }
 
+static const char kNoWideBla[] = "MBK_DEEP_BLA is not implemented for extended-range deep views";   // (the count and the distance calls)
+
 static int validate_deep_wide(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd, uint32_t flags)
 {
     return validate_deep_view(
         ctx, orbit, v, mrd, flags,
         [&]() -> int {
-            if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
+            if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, kNoWideBla);
             if (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES | MBK_DEEP_XBLA))
                 return fail(ctx, MBK_ERR_INVALID, "extended-range deep views take MBK_WANT_COUNTS / MBK_WANT_BYTES only (no kernel selection, no fp32)");
             if ((flags & MBK_DEEP_XBLA) && orbit->o.length > (1u << 31))
@@ -3336,34 +3310,6 @@ static int launch_deep_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const
     hipLaunchKernelGGL(mbk::deep_distance_kernel, block_grid(a.v), dim3(64), 0, stream, a);
     MBK_HIP(ctx, hipGetLastError());
     return MBK_OK;
-}
-
-int mbk_deep_view_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
-                                  uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
-    int rc = validate_deep(ctx, orbit, view, mrd, 0u);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_deep_distance(ctx, orbit, view, mrd, d_counts, d_rel, (hipStream_t)hip_stream);
-}
-
-int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
-                                   uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
-    int rc = validate_deep(ctx, orbit, view, mrd, 0u);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_rel, stats,
-                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
-                              return launch_deep_distance(ctx, orbit, view, mrd, d_counts, d_rel, stream);
-                          });
 }
 
 double mbk_deep_distance_value_host(double mag, double dmagD, int32_t e, double range_r, int32_t count)
@@ -3637,42 +3583,6 @@ static int launch_deep_wide_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *or
     return MBK_OK;
 }
 
-// Everything a wide distance call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
-static int wide_distance_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags)
-{
-    if (flags & MBK_DEEP_XBLA)
-        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is not implemented for extended-range deep distance estimates");
-    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
-    if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance estimates take no flags (no kernel selection, no fp32)");
-    return validate_deep_wide(ctx, orbit, view, mrd, 0u);
-}
-
-int mbk_deep_xview_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                   uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = wide_distance_check(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_deep_wide_distance(ctx, orbit, view, mrd, d_counts, d_rel, (hipStream_t)hip_stream);
-}
-
-int mbk_deep_xview_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                    uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = wide_distance_check(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_rel, stats,
-                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
-                              return launch_deep_wide_distance(ctx, orbit, view, mrd, d_counts, d_rel, stream);
-                          });
-}
-
 // host twins (mbk_deep_wide_distance.h): no ctx, no device
 int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
                                  int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel)
@@ -3766,15 +3676,6 @@ static int launch_julia(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i,
     return MBK_OK;
 }
 
-// Everything a Julia distance call can refuse, before anything is allocated, enqueued or written: its own flag rule (kernel
-// selection only), then the rules of the count launch.
-static int julia_distance_check(mbk_ctx *ctx, const mbk_view *v, double c_r, double c_i, uint32_t mrd, uint32_t flags)
-{
-    if (flags & ~(uint32_t)MBK_KERNEL_MASK)
-        return fail(ctx, MBK_ERR_INVALID, "Julia distance estimates take kernel selection only (binary64; no MBK_LAZY_UNIFORM, no MBK_DEEP_BLA / MBK_DEEP_XBLA)");
-    return julia_check(ctx, v, c_r, c_i, mrd, flags);
-}
-
 // A checked launch (mbk_julia_distance.h).  Kernel "asm": one pass, the derivative rides in a per-step escape loop.  Every
 // other selector: launch_julia with that selector writes the counts, then the derivative pass runs each escaped pixel for
 // exactly its count.  The doubling is the count launch's (julia_needs_literal), so both passes walk the same z.
@@ -3783,16 +3684,10 @@ static int launch_julia_distance(mbk_ctx *ctx, const mbk_view *v, double c_r, do
 {
     const uint32_t kernel = flags & MBK_KERNEL_MASK;
     const bool one_pass = kernel == MBK_KERNEL_ASM;
-    const size_t px = (size_t)v->ncols * v->nrows;
     if (!one_pass) {
-        if (!d_counts) {
-            StreamScratch *sc = nullptr;
-            int rc = get_scratch(ctx, stream, &sc);
-            if (rc == MBK_OK) rc = grow(ctx, sc->d_dist_counts, sc->dist_cap_px, px, px * sizeof(int32_t));
-            if (rc != MBK_OK) return rc;
-            d_counts = sc->d_dist_counts;
-        }
-        int rc = launch_julia(ctx, v, c_r, c_i, mrd, kernel, d_counts, nullptr, nullptr, stream);
+        int rc = launch_count_pass(ctx, (size_t)v->ncols * v->nrows, stream, &d_counts, [&](int32_t *counts) {
+            return launch_julia(ctx, v, c_r, c_i, mrd, kernel, counts, nullptr, nullptr, stream);
+        });
         if (rc != MBK_OK) return rc;
     }
     mbk::JuliaDistanceArgs a;
@@ -3868,7 +3763,7 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
                                               : launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream);
             return launch_deep(ctx, t.orbit, &t.deep, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_BLA) != 0);
         case Target::kJulia:
-            if (o.distance)   // (reached from mbk_julia_view_distance_render_* alone: mbk_julia_view_render_* refuses the source)
+            if (o.distance)   // (reached from the Julia distance calls alone: mbk_julia_view_render_* refuses the source)
                 return launch_julia_distance(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.values, stream);
             return launch_julia(ctx, &t.view, t.c_r, t.c_i, mrd, flags, o.counts, o.bytes, o.values, stream);
         case Target::kPlain: break;
@@ -4004,32 +3899,6 @@ int mbk_julia_count_host(double z_r, double z_i, double c_r, double c_i, uint32_
 }
 
 // ---- distance estimates for Julia views (mbk_julia_distance.h; mbk.h, the section of that name) ------------------------
-
-int mbk_julia_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
-                                   int32_t *d_counts, double *d_distance, void *hip_stream)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!d_distance) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = julia_distance_check(ctx, view, c_r, c_i, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return launch_julia_distance(ctx, view, c_r, c_i, mrd, flags, d_counts, d_distance, (hipStream_t)hip_stream);
-}
-
-int mbk_julia_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
-                                    int32_t *h_counts, double *h_distance, mbk_stats *stats)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!h_distance) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = julia_distance_check(ctx, view, c_r, c_i, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    return compute_values(ctx, (size_t)view->ncols * view->nrows, mrd, h_counts, h_distance, stats,
-                          [&](int32_t *d_counts, double *d_distance, hipStream_t stream) {
-                              return launch_julia_distance(ctx, view, c_r, c_i, mrd, flags, d_counts, d_distance, stream);
-                          });
-}
 
 int mbk_julia_distance_host(double z_r, double z_i, double c_r, double c_i, uint32_t mrd, int32_t *count, int32_t *extra,
                             double *zr, double *zi, double *dr, double *di, double *mag, double *dmag, double *de)
@@ -4173,19 +4042,28 @@ static const RenderRules kRenderRules[4] = {
      "distance estimates are not implemented for extended-range deep views", "distance estimates are not implemented for extended-range deep views"},
 };
 
+// What every render refuses of its output and of the view's geometry at supersample s, before the rules of the sample launch
+// see the samples: target_samples needs a view, spans that fit 32 bits and a window inside the view.
+static int render_geometry_check(mbk_ctx *ctx, const Target &t, uint32_t s, const void *out)
+{
+    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
+    if (!t.has_view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
+    if ((uint64_t)t.g.width * s > 0xffffffffull || (uint64_t)t.g.height * s > 0xffffffffull)
+        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
+    if ((uint64_t)t.g.col0 + t.g.ncols > t.g.width || (uint64_t)t.g.row0 + t.g.nrows > t.g.height)
+        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    return MBK_OK;
+}
+
 // Everything a render can refuse, before anything is allocated, enqueued or written.
 static int render_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                         const void *out, bool equalized = false, const double *h_lut = nullptr, uint32_t lut_len = 0u)
 {
     int rc = validate_render_spec(ctx, spec, equalized);
     if (rc != MBK_OK) return rc;
-    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!t.has_view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     const uint32_t s = spec->supersample;
-    if ((uint64_t)t.g.width * s > 0xffffffffull || (uint64_t)t.g.height * s > 0xffffffffull)
-        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t.g.col0 + t.g.ncols > t.g.width || (uint64_t)t.g.row0 + t.g.nrows > t.g.height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    rc = render_geometry_check(ctx, t, s, out);
+    if (rc != MBK_OK) return rc;
     const bool dist = spec->source == MBK_RENDER_DISTANCE;
     const bool rel = spec->source == MBK_RENDER_DISTANCE_REL;
     const bool smooth = spec->source == MBK_RENDER_SMOOTH || dist || rel || equalized;   // (the distance samples obey the smooth launch's rules)
@@ -4934,14 +4812,10 @@ static int interior_render_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mr
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
     int rc = validate_interior_spec(ctx, spec);
     if (rc != MBK_OK) return rc;
-    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
     *t = view_target(view);
     const uint32_t s = spec->supersample;
-    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
-        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
+    rc = render_geometry_check(ctx, *t, s, out);
+    if (rc != MBK_OK) return rc;
     const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
     bool safe = false;
     return interior_check(ctx, &samples.view, mrd, flags, &safe);
@@ -5082,172 +4956,275 @@ int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_
     return MBK_OK;
 }
 
-// ---- distance renders of extended-range deep views (mbk.h "Distance estimates for extended-range deep views"): calls of
-// their own on the render machinery above; mbk_deep_xview_render_* keeps refusing the distance sources ---------------------
+// ---- the distance calls (mbk.h, the six "Distance estimates ..." sections; DESIGN.md "One target, four kinds of view"): the
+// value calls of six rules on one scaffold, and the renders of the four rules that have calls of their own on another (plain
+// views and deep views without skips render through mbk_view_render_* / mbk_deep_view_render_*, which refuse the other four) ---
 
-// Everything such a render can refuse, before anything is allocated, enqueued or written.
-static int wide_distance_render_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
-                                      const mbk_render_spec *spec, const void *out, Target *t)
+// A rule.  check: everything its calls can refuse beyond the NULL pointers, before anything is allocated, enqueued or written,
+// on the target of a value call or on the samples of a render.  launch_flags: what the launch takes beyond the caller's flags
+// (which the check has passed): the skips that the rule's name selects.  source, other_source: the one source the rule's renders
+// take and the text that refuses every other; a rule without renders of its own has neither.
+struct DistanceRule {
+    int (*check)(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags);
+    uint32_t launch_flags;
+    uint32_t source;
+    const char *other_source;
+};
+
+static int plain_distance_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    bool safe = false;   // (target_launch derives it again)
+    return distance_check(ctx, t.has_view ? &t.view : nullptr, mrd, flags, &safe);
+}
+
+// its own flag rule (kernel selection only), then the rules of the count launch
+static int julia_distance_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    if (flags & ~(uint32_t)MBK_KERNEL_MASK)
+        return fail(ctx, MBK_ERR_INVALID, "Julia distance estimates take kernel selection only (binary64; no MBK_LAZY_UNIFORM, no MBK_DEEP_BLA / MBK_DEEP_XBLA)");
+    return target_check(ctx, t, mrd, flags);
+}
+
+// The deep rules take no flags, then the rules of the count launch with `skips`: the flag of the count calls that the rule's
+// name implies (the table's indices must fit), or none.
+static int deep_no_flags_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, uint32_t skips)
+{
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
+    return target_check(ctx, t, mrd, skips);
+}
+
+static int deep_distance_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    return deep_no_flags_check(ctx, t, mrd, flags, 0u);
+}
+
+static int deep_distance_bla_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    if (flags & MBK_DEEP_BLA)
+        return fail(ctx, MBK_ERR_INVALID, "the _distance_bla calls take no flags: the name selects the rule (MBK_DEEP_BLA is a flag of the count calls)");
+    return deep_no_flags_check(ctx, t, mrd, flags, MBK_DEEP_BLA);
+}
+
+// the same for the extended-range rules, which name MBK_DEEP_BLA as the count calls do
+static int wide_no_flags_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, uint32_t skips)
+{
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, kNoWideBla);
+    if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance estimates take no flags (no kernel selection, no fp32)");
+    return target_check(ctx, t, mrd, skips);
+}
+
+static int wide_distance_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    if (flags & MBK_DEEP_XBLA)
+        return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is not implemented for extended-range deep distance estimates");
+    return wide_no_flags_check(ctx, t, mrd, flags, 0u);
+}
+
+static int wide_distance_xbla_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags)
+{
+    if (flags & MBK_DEEP_XBLA)
+        return fail(ctx, MBK_ERR_INVALID, "the _distance_xbla calls take no flags: the name selects the rule (MBK_DEEP_XBLA is a flag of the count calls)");
+    return wide_no_flags_check(ctx, t, mrd, flags, MBK_DEEP_XBLA);
+}
+
+static const DistanceRule kPlainDistance = {plain_distance_check, 0u, 0u, nullptr};
+static const DistanceRule kJuliaDistance = {julia_distance_check, 0u, MBK_RENDER_DISTANCE, "Julia distance renders take MBK_RENDER_DISTANCE only"};
+static const DistanceRule kDeepDistance = {deep_distance_check, 0u, 0u, nullptr};
+static const DistanceRule kDeepDistanceBla = {deep_distance_bla_check, MBK_DEEP_BLA, MBK_RENDER_DISTANCE_REL,
+                                              "deep distance renders with bilinear approximation take MBK_RENDER_DISTANCE_REL only"};
+static const DistanceRule kWideDistance = {wide_distance_check, 0u, MBK_RENDER_DISTANCE_REL,
+                                           "extended-range deep distance renders take MBK_RENDER_DISTANCE_REL only"};
+static const DistanceRule kWideDistanceXbla = {wide_distance_xbla_check, MBK_DEEP_XBLA, MBK_RENDER_DISTANCE_REL,
+                                               "extended-range deep distance renders with bilinear approximation take MBK_RENDER_DISTANCE_REL only"};
+
+// The two forms of a value call: device pointers on a stream, host pointers synchronously.  The counts pointer may be NULL.
+static int distance_values_check(mbk_ctx *ctx, const DistanceRule &rule, const Target &t, uint32_t mrd, uint32_t flags, const void *values)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!values) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
+    return rule.check(ctx, t, mrd, flags);
+}
+
+static int distance_values_launch(mbk_ctx *ctx, const DistanceRule &rule, const Target &t, uint32_t mrd, uint32_t flags, int32_t *d_counts,
+                                  double *d_values, void *hip_stream)
+{
+    int rc = distance_values_check(ctx, rule, t, mrd, flags, d_values);
+    if (rc != MBK_OK) return rc;
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return target_launch(ctx, t, mrd, flags | rule.launch_flags, Outputs{d_counts, nullptr, d_values, true}, (hipStream_t)hip_stream);
+}
+
+static int distance_values_compute(mbk_ctx *ctx, const DistanceRule &rule, const Target &t, uint32_t mrd, uint32_t flags, int32_t *h_counts,
+                                   double *h_values, mbk_stats *stats)
+{
+    int rc = distance_values_check(ctx, rule, t, mrd, flags, h_values);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    return compute_values(ctx, (size_t)t.g.ncols * t.g.nrows, mrd, h_counts, h_values, stats,
+                          [&](int32_t *d_counts, double *d_values, hipStream_t stream) {
+                              return target_launch(ctx, t, mrd, flags | rule.launch_flags, Outputs{d_counts, nullptr, d_values, true}, stream);
+                          });
+}
+
+// Everything a render of a rule's own can refuse, before anything is allocated, enqueued or written; then its two forms, on the
+// render machinery above.
+static int distance_render_check(mbk_ctx *ctx, const DistanceRule &rule, const Target &t, uint32_t mrd, uint32_t flags,
+                                 const mbk_render_spec *spec, const void *out)
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
     int rc = validate_render_spec(ctx, spec);
     if (rc != MBK_OK) return rc;
-    if (spec->source != MBK_RENDER_DISTANCE_REL)
-        return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance renders take MBK_RENDER_DISTANCE_REL only");
-    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    *t = wide_target(orbit, view);
-    const uint32_t s = spec->supersample;
-    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
-        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
-    return wide_distance_check(ctx, orbit, &samples.wide, mrd, flags);
+    if (spec->source != rule.source) return fail(ctx, MBK_ERR_INVALID, rule.other_source);
+    rc = render_geometry_check(ctx, t, spec->supersample, out);
+    if (rc != MBK_OK) return rc;
+    return rule.check(ctx, target_samples(t, spec->supersample, t.g.col0, t.g.row0, t.g.ncols, t.g.nrows), mrd, flags);
 }
 
-int mbk_deep_xview_distance_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                          uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+static int distance_render_launch(mbk_ctx *ctx, const DistanceRule &rule, const Target &t, uint32_t mrd, uint32_t flags,
+                                  const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
 {
-    Target t;
-    int rc = wide_distance_render_check(ctx, orbit, view, mrd, flags, spec, d_rgba, &t);
+    int rc = distance_render_check(ctx, rule, t, mrd, flags, spec, d_rgba);
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+    return render_run(ctx, t, mrd, flags | rule.launch_flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
 }
 
-int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                           uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+static int distance_render_compute(mbk_ctx *ctx, const DistanceRule &rule, const Target &t, uint32_t mrd, uint32_t flags,
+                                   const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
 {
-    Target t;
-    int rc = wide_distance_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
+    int rc = distance_render_check(ctx, rule, t, mrd, flags, spec, h_rgba);
     if (rc != MBK_OK) return rc;
-    return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, nullptr, 0u);
+    return render_compute_checked(ctx, t, mrd, flags | rule.launch_flags, spec, h_rgba, stats, nullptr, 0u);
 }
 
-// ---- distance renders of Julia views (mbk.h "Distance estimates for Julia views"): calls of their own in the same way;
-// mbk_julia_view_render_* keeps refusing the distance sources ------------------------------------------------------------
-
-// Everything such a render can refuse, before anything is allocated, enqueued or written.
-static int julia_distance_render_check(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
-                                       const mbk_render_spec *spec, const void *out, Target *t)
+// The plain pair has one text of its own for its NULL pointers, and its compute form counts the view among them.
+int mbk_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                             int32_t *d_counts, double *d_distance, void *hip_stream)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_render_spec(ctx, spec);
-    if (rc != MBK_OK) return rc;
-    if (spec->source != MBK_RENDER_DISTANCE) return fail(ctx, MBK_ERR_INVALID, "Julia distance renders take MBK_RENDER_DISTANCE only");
-    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    *t = julia_target(view, c_r, c_i);
-    const uint32_t s = spec->supersample;
-    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
-        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
-    return julia_distance_check(ctx, &samples.view, c_r, c_i, mrd, flags);
+    if (!ctx || !d_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    return distance_values_launch(ctx, kPlainDistance, view_target(view), mrd, flags, d_counts, d_distance, hip_stream);
+}
+
+// (only the kernel selector and MBK_DEEP_XBLA reach the rule: this form serves every other flag, MBK_PRECISION_F32 among them)
+int mbk_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
+                              int32_t *h_counts, double *h_distance, mbk_stats *stats)
+{
+    if (!ctx || !view || !h_distance) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    return distance_values_compute(ctx, kPlainDistance, view_target(view), mrd, flags & (MBK_KERNEL_MASK | MBK_DEEP_XBLA), h_counts, h_distance, stats);
+}
+
+int mbk_julia_view_launch_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                   int32_t *d_counts, double *d_distance, void *hip_stream)
+{
+    return distance_values_launch(ctx, kJuliaDistance, julia_target(view, c_r, c_i), mrd, flags, d_counts, d_distance, hip_stream);
+}
+
+int mbk_julia_view_compute_distance(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
+                                    int32_t *h_counts, double *h_distance, mbk_stats *stats)
+{
+    return distance_values_compute(ctx, kJuliaDistance, julia_target(view, c_r, c_i), mrd, flags, h_counts, h_distance, stats);
 }
 
 int mbk_julia_view_distance_render_launch(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
                                           const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
 {
-    Target t;
-    int rc = julia_distance_render_check(ctx, view, c_r, c_i, mrd, flags, spec, d_rgba, &t);
-    if (rc != MBK_OK) return rc;
-    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+    return distance_render_launch(ctx, kJuliaDistance, julia_target(view, c_r, c_i), mrd, flags, spec, d_rgba, hip_stream);
 }
 
 int mbk_julia_view_distance_render_compute(mbk_ctx *ctx, const mbk_view *view, double c_r, double c_i, uint32_t mrd, uint32_t flags,
                                            const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
 {
-    Target t;
-    int rc = julia_distance_render_check(ctx, view, c_r, c_i, mrd, flags, spec, h_rgba, &t);
-    if (rc != MBK_OK) return rc;
-    return render_compute_checked(ctx, t, mrd, flags, spec, h_rgba, stats, nullptr, 0u);
+    return distance_render_compute(ctx, kJuliaDistance, julia_target(view, c_r, c_i), mrd, flags, spec, h_rgba, stats);
 }
 
-// ---- distance estimates for deep views with bilinear approximation (mbk.h, the section of that name): calls of their own on
-// the launch, the value scaffold and the render machinery above; the calls without _bla keep refusing MBK_DEEP_BLA -----------
-
-// Everything such a call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
-static int deep_distance_bla_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags)
+int mbk_deep_view_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
 {
-    if (flags & MBK_DEEP_BLA)
-        return fail(ctx, MBK_ERR_INVALID, "the _distance_bla calls take no flags: the name selects the rule (MBK_DEEP_BLA is a flag of the count calls)");
-    if (flags) return fail(ctx, MBK_ERR_INVALID, "deep distance estimates take no flags (no kernel selection, no fp32)");
-    return validate_deep(ctx, orbit, view, mrd, MBK_DEEP_BLA);
+    return distance_values_launch(ctx, kDeepDistance, deep_target(orbit, view), mrd, flags, d_counts, d_rel, hip_stream);
+}
+
+int mbk_deep_view_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    return distance_values_compute(ctx, kDeepDistance, deep_target(orbit, view), mrd, flags, h_counts, h_rel, stats);
 }
 
 int mbk_deep_view_launch_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                       uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = deep_distance_bla_check(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return target_launch(ctx, deep_target(orbit, view), mrd, MBK_DEEP_BLA, Outputs{d_counts, nullptr, d_rel, true}, (hipStream_t)hip_stream);
+    return distance_values_launch(ctx, kDeepDistanceBla, deep_target(orbit, view), mrd, flags, d_counts, d_rel, hip_stream);
 }
 
 int mbk_deep_view_compute_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                        uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
 {
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = deep_distance_bla_check(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    const Target t = deep_target(orbit, view);
-    return compute_values(ctx, (size_t)t.g.ncols * t.g.nrows, mrd, h_counts, h_rel, stats,
-                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
-                              return target_launch(ctx, t, mrd, MBK_DEEP_BLA, Outputs{d_counts, nullptr, d_rel, true}, stream);
-                          });
-}
-
-// Everything such a render can refuse, before anything is allocated, enqueued or written.
-static int deep_distance_bla_render_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
-                                          const mbk_render_spec *spec, const void *out, Target *t)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_render_spec(ctx, spec);
-    if (rc != MBK_OK) return rc;
-    if (spec->source != MBK_RENDER_DISTANCE_REL)
-        return fail(ctx, MBK_ERR_INVALID, "deep distance renders with bilinear approximation take MBK_RENDER_DISTANCE_REL only");
-    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    *t = deep_target(orbit, view);
-    const uint32_t s = spec->supersample;
-    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
-        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
-    return deep_distance_bla_check(ctx, orbit, &samples.deep, mrd, flags);
+    return distance_values_compute(ctx, kDeepDistanceBla, deep_target(orbit, view), mrd, flags, h_counts, h_rel, stats);
 }
 
 int mbk_deep_view_distance_bla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                              uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
 {
-    Target t;
-    int rc = deep_distance_bla_render_check(ctx, orbit, view, mrd, flags, spec, d_rgba, &t);
-    if (rc != MBK_OK) return rc;
-    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return render_run(ctx, t, mrd, MBK_DEEP_BLA, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
+    return distance_render_launch(ctx, kDeepDistanceBla, deep_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream);
 }
 
 int mbk_deep_view_distance_bla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                               uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
 {
-    Target t;
-    int rc = deep_distance_bla_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
-    if (rc != MBK_OK) return rc;
-    return render_compute_checked(ctx, t, mrd, MBK_DEEP_BLA, spec, h_rgba, stats, nullptr, 0u);
+    return distance_render_compute(ctx, kDeepDistanceBla, deep_target(orbit, view), mrd, flags, spec, h_rgba, stats);
 }
+
+int mbk_deep_xview_launch_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                   uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
+{
+    return distance_values_launch(ctx, kWideDistance, wide_target(orbit, view), mrd, flags, d_counts, d_rel, hip_stream);
+}
+
+int mbk_deep_xview_compute_distance(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                    uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    return distance_values_compute(ctx, kWideDistance, wide_target(orbit, view), mrd, flags, h_counts, h_rel, stats);
+}
+
+int mbk_deep_xview_distance_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                          uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    return distance_render_launch(ctx, kWideDistance, wide_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream);
+}
+
+int mbk_deep_xview_distance_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                           uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    return distance_render_compute(ctx, kWideDistance, wide_target(orbit, view), mrd, flags, spec, h_rgba, stats);
+}
+
+int mbk_deep_xview_launch_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                        uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
+{
+    return distance_values_launch(ctx, kWideDistanceXbla, wide_target(orbit, view), mrd, flags, d_counts, d_rel, hip_stream);
+}
+
+int mbk_deep_xview_compute_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                         uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
+{
+    return distance_values_compute(ctx, kWideDistanceXbla, wide_target(orbit, view), mrd, flags, h_counts, h_rel, stats);
+}
+
+int mbk_deep_xview_distance_xbla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                               uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    return distance_render_launch(ctx, kWideDistanceXbla, wide_target(orbit, view), mrd, flags, spec, d_rgba, hip_stream);
+}
+
+int mbk_deep_xview_distance_xbla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                                uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    return distance_render_compute(ctx, kWideDistanceXbla, wide_target(orbit, view), mrd, flags, spec, h_rgba, stats);
+}
+
+// ---- distance estimates for deep views with bilinear approximation (mbk_deep_distance_bla.h; mbk.h, the section of that
+// name): the calls stand with the distance calls, above ----------------------------------------------------------------------
 
 // host twins (mbk_deep_distance_bla.h): no ctx, no device
 int mbk_deep_distance_bla_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
@@ -5274,87 +5251,8 @@ int mbk_deep_distance_bla_skip_host(double A_r, double A_i, double B_r, double B
     return MBK_OK;
 }
 
-// ---- distance estimates for extended-range deep views with bilinear approximation (mbk.h, the section of that name): calls
-// of their own on the launch, the value scaffold and the render machinery above; the calls without _xbla keep refusing
-// MBK_DEEP_XBLA ------------------------------------------------------------------------------------------------------------
-
-// Everything such a call can refuse beyond the view's own rules, before anything is allocated, enqueued or written.
-static int wide_distance_xbla_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags)
-{
-    if (flags & MBK_DEEP_XBLA)
-        return fail(ctx, MBK_ERR_INVALID, "the _distance_xbla calls take no flags: the name selects the rule (MBK_DEEP_XBLA is a flag of the count calls)");
-    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is not implemented for extended-range deep views");
-    if (flags) return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance estimates take no flags (no kernel selection, no fp32)");
-    return validate_deep_wide(ctx, orbit, view, mrd, MBK_DEEP_XBLA);
-}
-
-int mbk_deep_xview_launch_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                        uint32_t flags, int32_t *d_counts, double *d_rel, void *hip_stream)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!d_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = wide_distance_xbla_check(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return target_launch(ctx, wide_target(orbit, view), mrd, MBK_DEEP_XBLA, Outputs{d_counts, nullptr, d_rel, true}, (hipStream_t)hip_stream);
-}
-
-int mbk_deep_xview_compute_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                         uint32_t flags, int32_t *h_counts, double *h_rel, mbk_stats *stats)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    if (!h_rel) return fail(ctx, MBK_ERR_INVALID, "NULL value pointer");
-    int rc = wide_distance_xbla_check(ctx, orbit, view, mrd, flags);
-    if (rc != MBK_OK) return rc;
-    rc = sync_begin(ctx);
-    if (rc != MBK_OK) return rc;
-    const Target t = wide_target(orbit, view);
-    return compute_values(ctx, (size_t)t.g.ncols * t.g.nrows, mrd, h_counts, h_rel, stats,
-                          [&](int32_t *d_counts, double *d_rel, hipStream_t stream) {
-                              return target_launch(ctx, t, mrd, MBK_DEEP_XBLA, Outputs{d_counts, nullptr, d_rel, true}, stream);
-                          });
-}
-
-// Everything such a render can refuse, before anything is allocated, enqueued or written.
-static int wide_distance_xbla_render_check(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                           uint32_t flags, const mbk_render_spec *spec, const void *out, Target *t)
-{
-    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
-    int rc = validate_render_spec(ctx, spec);
-    if (rc != MBK_OK) return rc;
-    if (spec->source != MBK_RENDER_DISTANCE_REL)
-        return fail(ctx, MBK_ERR_INVALID, "extended-range deep distance renders with bilinear approximation take MBK_RENDER_DISTANCE_REL only");
-    if (!out) return fail(ctx, MBK_ERR_INVALID, "output pointer is NULL");
-    if (!view) return fail(ctx, MBK_ERR_INVALID, "view is NULL");
-    *t = wide_target(orbit, view);
-    const uint32_t s = spec->supersample;
-    if ((uint64_t)t->g.width * s > 0xffffffffull || (uint64_t)t->g.height * s > 0xffffffffull)
-        return fail(ctx, MBK_ERR_INVALID, "width or height times supersample does not fit 32 bits");
-    if ((uint64_t)t->g.col0 + t->g.ncols > t->g.width || (uint64_t)t->g.row0 + t->g.nrows > t->g.height)
-        return fail(ctx, MBK_ERR_INVALID, "window exceeds the view");
-    const Target samples = target_samples(*t, s, t->g.col0, t->g.row0, t->g.ncols, t->g.nrows);
-    return wide_distance_xbla_check(ctx, orbit, &samples.wide, mrd, flags);
-}
-
-int mbk_deep_xview_distance_xbla_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                               uint32_t flags, const mbk_render_spec *spec, uint8_t *d_rgba, void *hip_stream)
-{
-    Target t;
-    int rc = wide_distance_xbla_render_check(ctx, orbit, view, mrd, flags, spec, d_rgba, &t);
-    if (rc != MBK_OK) return rc;
-    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
-    MBK_HIP(ctx, hipSetDevice(ctx->device));
-    return render_run(ctx, t, mrd, MBK_DEEP_XBLA, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
-}
-
-int mbk_deep_xview_distance_xbla_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
-                                                uint32_t flags, const mbk_render_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
-{
-    Target t;
-    int rc = wide_distance_xbla_render_check(ctx, orbit, view, mrd, flags, spec, h_rgba, &t);
-    if (rc != MBK_OK) return rc;
-    return render_compute_checked(ctx, t, mrd, MBK_DEEP_XBLA, spec, h_rgba, stats, nullptr, 0u);
-}
+// ---- distance estimates for extended-range deep views with bilinear approximation (mbk_deep_wide_distance_bla.h; mbk.h, the
+// section of that name): the calls stand with the distance calls, above ------------------------------------------------------
 
 // host twins (mbk_deep_wide_distance_bla.h): no ctx, no device
 int mbk_deep_xview_distance_xbla_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,

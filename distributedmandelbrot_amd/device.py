@@ -1108,21 +1108,12 @@ class MandelbrotDevice:
         are those of compute_view.  kernel "asm" takes the one-pass form, every other selector computes the counts with that
         kernel first and the derivative in a second pass; both store the same values.
         Returns (distance float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
-        cv = self._cview(view, window)
-        shape = (cv.nrows, cv.ncols)
-        dist = np.empty(shape, np.float64)
-        counts = np.empty(shape, np.int32)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_view_compute_distance(self._h, C.byref(cv), mrd, L.KERNELS[kernel],
-                                                        counts.ctypes.data, dist.ctypes.data, C.byref(st)))
-        return dist, counts, _stats(st)
+        return self._distance_values("compute", "plain", view, mrd, window, kernel=kernel)
 
     def launch_view_distance(self, view: View, mrd: int, *, d_distance: int, d_counts: int = 0, stream: int = 0,
                              window=None, kernel: str = "default") -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
-        cv = self._cview(view, window)
-        self._check(self._lib.mbk_view_launch_distance(self._h, C.byref(cv), mrd, L.KERNELS[kernel],
-                                                       d_counts or None, d_distance, stream or None))
+        self._distance_values("launch", "plain", view, mrd, window, d_values=d_distance, d_counts=d_counts, stream=stream, kernel=kernel)
 
     # -- interior views (include/mbk.h, "Interior views") -------------------------------------------
     def compute_view_interior(self, view: View, mrd: int, *, window=None, kernel: str = "default", want_counts: bool = True,
@@ -1318,6 +1309,55 @@ class MandelbrotDevice:
             return getattr(self._lib, "mbk_julia_view_" + name), (C.byref(cv), float(c[0]), float(c[1])), L.KERNELS[kernel]
         return getattr(self._lib, "mbk_view_" + name), (C.byref(cv),), L.KERNELS[kernel] | L.PRECISIONS[precision]
 
+    # The distance rules (include/mbk.h, the "Distance estimates ..." sections): the C value calls of each, the renders of its own
+    # and the one source they take (plain views and deep views without skips render through render_view / render_deep_view).
+    _DISTANCE_RULES = {
+        "plain": ("mbk_view_{}_distance", None, None),
+        "julia": ("mbk_julia_view_{}_distance", "mbk_julia_view_distance_render_{}", "distance"),
+        "deep": ("mbk_deep_view_{}_distance", None, None),
+        "deep_bla": ("mbk_deep_view_{}_distance_bla", "mbk_deep_view_distance_bla_render_{}", "distance_rel"),
+        "wide": ("mbk_deep_xview_{}_distance", "mbk_deep_xview_distance_render_{}", "distance_rel"),
+        "wide_xbla": ("mbk_deep_xview_{}_distance_xbla", "mbk_deep_xview_distance_xbla_render_{}", "distance_rel"),
+    }
+
+    def _distance_args(self, rule: str, view, window, *, orbit=None, c=None, kernel: str = "default"):
+        """(the C view of the rule's kind, the arguments between the ctx and mrd, the flags): as _kind_fn names a kind, and only
+        the rules without an orbit select a kernel."""
+        if orbit is not None:
+            cv = _cxview(view, window) if rule.startswith("wide") else self._cdeep(view, window)
+            return cv, (orbit._h, C.byref(cv)), 0
+        cv = self._cview(view, window)
+        return cv, (C.byref(cv),) + ((float(c[0]), float(c[1])) if c is not None else ()), L.KERNELS[kernel]
+
+    def _distance_values(self, form: str, rule: str, view, mrd: int, window, *, d_values: int = 0, d_counts: int = 0, stream: int = 0,
+                         **kind):
+        """compute_*_distance* (form "compute": returns (values float64[nrows,ncols], counts int32[nrows,ncols], TileStats)) and
+        launch_*_distance* (form "launch": into d_values and, where given, d_counts on `stream`) of any rule."""
+        cv, lead, flags = self._distance_args(rule, view, window, **kind)
+        fn = getattr(self._lib, self._DISTANCE_RULES[rule][0].format(form))
+        if form == "launch":
+            self._check(fn(self._h, *lead, mrd, flags, d_counts or None, d_values or None, stream or None))
+            return None
+        shape = (cv.nrows, cv.ncols)
+        values = np.empty(shape, np.float64)
+        counts = np.empty(shape, np.int32)
+        st = L.mbk_stats()
+        self._check(fn(self._h, *lead, mrd, flags, counts.ctypes.data, values.ctypes.data, C.byref(st)))
+        return values, counts, _stats(st)
+
+    def _distance_render(self, form: str, rule: str, view, mrd: int, palette, supersample, window, max_band_rows, *, out=None,
+                         d_rgba: int = 0, stream: int = 0, **kind):
+        """render_*_distance* (form "compute": into the host array `out`, returns (rgba, TileStats)) and launch_render_*_distance*
+        (form "launch": into d_rgba on `stream`) of the rules that have renders of their own."""
+        cv, lead, flags = self._distance_args(rule, view, window, **kind)
+        _, name, source = self._DISTANCE_RULES[rule]
+        rgba = self._render_out(cv, out) if form == "compute" else None
+        spec = palette.spec(source, supersample, max_band_rows)
+        st = L.mbk_stats()
+        tail = (rgba.ctypes.data, C.byref(st)) if form == "compute" else (d_rgba or None, stream or None)
+        self._check(getattr(self._lib, name.format(form))(self._h, *lead, mrd, flags, C.byref(spec), *tail))
+        return (rgba, _stats(st)) if form == "compute" else None
+
     def _render(self, form: str, view, mrd: int, palette, source, supersample, window, max_band_rows, lut, histogram, *, out=None,
                 d_rgba: int = 0, stream: int = 0, **kind):
         """render_* (form "compute": into the host array `out`, returns (rgba, TileStats)) and launch_render_* (form "launch":
@@ -1395,22 +1435,13 @@ class MandelbrotDevice:
         fraction of the view's real span (rel * (width - 1) is the distance in pixels); 0 for never-escaped pixels.  The counts
         are those of compute_deep_view.  Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
         self._deep_fn(view, "compute_distance", source="distance_rel")   # (a WideDeepView: compute_wide_view_distance)
-        cv = self._cdeep(view, window)
-        shape = (cv.nrows, cv.ncols)
-        rel = np.empty(shape, np.float64)
-        counts = np.empty(shape, np.int32)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_compute_distance(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
-                                                             rel.ctypes.data, C.byref(st)))
-        return rel, counts, _stats(st)
+        return self._distance_values("compute", "deep", view, mrd, window, orbit=orbit)
 
     def launch_deep_view_distance(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
                                   stream: int = 0, window=None) -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
         self._deep_fn(view, "launch_distance", source="distance_rel")
-        cv = self._cdeep(view, window)
-        self._check(self._lib.mbk_deep_view_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
-                                                            d_rel or None, stream or None))
+        self._distance_values("launch", "deep", view, mrd, window, d_values=d_rel, d_counts=d_counts, stream=stream, orbit=orbit)
 
     # -- locating minibrots (include/mbk.h, "Locating minibrots in deep views") --
     @staticmethod
@@ -1510,45 +1541,28 @@ class MandelbrotDevice:
         is within 1e-4 of the truth on the project's cases (tests/deep_distance_bla_model.py has the measured figures).
         Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
         self._plain_deep(view)
-        cv = self._cdeep(view, window)
-        shape = (cv.nrows, cv.ncols)
-        rel = np.empty(shape, np.float64)
-        counts = np.empty(shape, np.int32)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_compute_distance_bla(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
-                                                                 rel.ctypes.data, C.byref(st)))
-        return rel, counts, _stats(st)
+        return self._distance_values("compute", "deep_bla", view, mrd, window, orbit=orbit)
 
     def launch_deep_view_distance_bla(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
                                       stream: int = 0, window=None) -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream).  The
         first launch of a view's spans on an orbit builds and uploads the table synchronously."""
         self._plain_deep(view)
-        cv = self._cdeep(view, window)
-        self._check(self._lib.mbk_deep_view_launch_distance_bla(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
-                                                                d_rel or None, stream or None))
+        self._distance_values("launch", "deep_bla", view, mrd, window, d_values=d_rel, d_counts=d_counts, stream=stream, orbit=orbit)
 
     def render_deep_view_distance_bla(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, supersample: int = 1,
                                       window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
         """The view as an RGBA8 image coloured by that estimate (source "distance_rel"; Palette.deep_distance), as
         render_deep_view(source="distance_rel") does without skips.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
         self._plain_deep(view)
-        cv = self._cdeep(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec("distance_rel", supersample, max_band_rows)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_view_distance_bla_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                                        rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._distance_render("compute", "deep_bla", view, mrd, palette, supersample, window, max_band_rows, out=out, orbit=orbit)
 
     def launch_render_deep_view_distance_bla(self, orbit: DeepOrbit, view: DeepView, mrd: int, *, palette, d_rgba: int,
                                              supersample: int = 1, stream: int = 0, window=None, max_band_rows: int = 0) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
         self._plain_deep(view)
-        cv = self._cdeep(view, window)
-        spec = palette.spec("distance_rel", supersample, max_band_rows)
-        self._check(self._lib.mbk_deep_view_distance_bla_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                                       d_rgba or None, stream or None))
+        self._distance_render("launch", "deep_bla", view, mrd, palette, supersample, window, max_band_rows, d_rgba=d_rgba, stream=stream,
+                              orbit=orbit)
 
     # -- distance estimates for extended-range deep views (include/mbk.h, the section of that name): calls of their own --
     def compute_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, window=None):
@@ -1556,41 +1570,24 @@ class MandelbrotDevice:
         an int32 exponent), so neither a span of 2^-3000 nor an orbit that returns to within 1e-400 of 0 loses it.  The value
         is rel = de / (range_r 2^exp2), the distance as a fraction of the view's real span; the counts are those of
         compute_deep_view.  Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
-        cv = _cxview(view, window)
-        shape = (cv.nrows, cv.ncols)
-        rel = np.empty(shape, np.float64)
-        counts = np.empty(shape, np.int32)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_xview_compute_distance(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
-                                                              rel.ctypes.data, C.byref(st)))
-        return rel, counts, _stats(st)
+        return self._distance_values("compute", "wide", view, mrd, window, orbit=orbit)
 
     def launch_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
                                   stream: int = 0, window=None) -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
-        cv = _cxview(view, window)
-        self._check(self._lib.mbk_deep_xview_launch_distance(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
-                                                             d_rel or None, stream or None))
+        self._distance_values("launch", "wide", view, mrd, window, d_values=d_rel, d_counts=d_counts, stream=stream, orbit=orbit)
 
     def render_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, supersample: int = 1,
                                   window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
         """The view as an RGBA8 image coloured by its distance estimate (source "distance_rel"; Palette.deep_distance), as
         render_deep_view(source="distance_rel") does for a DeepView.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
-        cv = _cxview(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec("distance_rel", supersample, max_band_rows)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_xview_distance_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                                     rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._distance_render("compute", "wide", view, mrd, palette, supersample, window, max_band_rows, out=out, orbit=orbit)
 
     def launch_render_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, d_rgba: int,
                                          supersample: int = 1, stream: int = 0, window=None, max_band_rows: int = 0) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
-        cv = _cxview(view, window)
-        spec = palette.spec("distance_rel", supersample, max_band_rows)
-        self._check(self._lib.mbk_deep_xview_distance_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                                    d_rgba or None, stream or None))
+        self._distance_render("launch", "wide", view, mrd, palette, supersample, window, max_band_rows, d_rgba=d_rgba, stream=stream,
+                              orbit=orbit)
 
     # -- distance estimates for extended-range deep views with bilinear approximation (include/mbk.h, the section of that
     # name): calls of their own; compute_wide_view_distance keeps its rule and the flag stays refused there --
@@ -1599,42 +1596,25 @@ class MandelbrotDevice:
         derivative follows d -> A d + B, from the table the count launches use.  The counts are those of
         compute_deep_view(xbla=True); tests/deep_wide_distance_bla_model.py has the measured error of rel.
         Returns (rel float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
-        cv = _cxview(view, window)
-        shape = (cv.nrows, cv.ncols)
-        rel = np.empty(shape, np.float64)
-        counts = np.empty(shape, np.int32)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_xview_compute_distance_xbla(self._h, orbit._h, C.byref(cv), mrd, 0, counts.ctypes.data,
-                                                                   rel.ctypes.data, C.byref(st)))
-        return rel, counts, _stats(st)
+        return self._distance_values("compute", "wide_xbla", view, mrd, window, orbit=orbit)
 
     def launch_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, d_rel: int, d_counts: int = 0,
                                        stream: int = 0, window=None) -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream).  The
         first launch of a view's spans on an orbit builds and uploads the table synchronously."""
-        cv = _cxview(view, window)
-        self._check(self._lib.mbk_deep_xview_launch_distance_xbla(self._h, orbit._h, C.byref(cv), mrd, 0, d_counts or None,
-                                                                  d_rel or None, stream or None))
+        self._distance_values("launch", "wide_xbla", view, mrd, window, d_values=d_rel, d_counts=d_counts, stream=stream, orbit=orbit)
 
     def render_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, supersample: int = 1,
                                        window=None, max_band_rows: int = 0, out: Optional[np.ndarray] = None):
         """The view as an RGBA8 image coloured by that estimate (source "distance_rel"; Palette.deep_distance), as
         render_wide_view_distance does without skips.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
-        cv = _cxview(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec("distance_rel", supersample, max_band_rows)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_deep_xview_distance_xbla_render_compute(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                                          rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._distance_render("compute", "wide_xbla", view, mrd, palette, supersample, window, max_band_rows, out=out, orbit=orbit)
 
     def launch_render_wide_view_distance_xbla(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, d_rgba: int,
                                               supersample: int = 1, stream: int = 0, window=None, max_band_rows: int = 0) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
-        cv = _cxview(view, window)
-        spec = palette.spec("distance_rel", supersample, max_band_rows)
-        self._check(self._lib.mbk_deep_xview_distance_xbla_render_launch(self._h, orbit._h, C.byref(cv), mrd, 0, C.byref(spec),
-                                                                         d_rgba or None, stream or None))
+        self._distance_render("launch", "wide_xbla", view, mrd, palette, supersample, window, max_band_rows, d_rgba=d_rgba, stream=stream,
+                              orbit=orbit)
 
     # -- rendering (include/mbk.h, "Rendering") ---------------------------------------------------
     def _render_out(self, cv, out):
@@ -1948,41 +1928,24 @@ class MandelbrotDevice:
         kernel "asm" takes the one-pass form; "default" and "group" compute the counts with that kernel first and the
         derivative in a second pass; all store the same values.  A pixel at exactly 0 (the critical point) that escapes has
         derivative 0 and stores +inf.  Returns (distance float64[nrows,ncols], counts int32[nrows,ncols], TileStats)."""
-        cv = self._cview(view, window)
-        shape = (cv.nrows, cv.ncols)
-        dist = np.empty(shape, np.float64)
-        counts = np.empty(shape, np.int32)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_julia_view_compute_distance(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
-                                                              counts.ctypes.data, dist.ctypes.data, C.byref(st)))
-        return dist, counts, _stats(st)
+        return self._distance_values("compute", "julia", view, mrd, window, c=c, kernel=kernel)
 
     def launch_julia_view_distance(self, view: View, c, mrd: int, *, d_distance: int, d_counts: int = 0, stream: int = 0,
                                    window=None, kernel: str = "default") -> None:
         """Asynchronous form on DEVICE pointers (float64 / int32 of the window's size) on ``stream`` (0 = HIP's null stream)."""
-        cv = self._cview(view, window)
-        self._check(self._lib.mbk_julia_view_launch_distance(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd, L.KERNELS[kernel],
-                                                             d_counts or None, d_distance or None, stream or None))
+        self._distance_values("launch", "julia", view, mrd, window, d_values=d_distance, d_counts=d_counts, stream=stream, c=c, kernel=kernel)
 
     def render_julia_view_distance(self, view: View, c, mrd: int, *, palette, supersample: int = 1, window=None,
                                    kernel: str = "default", max_band_rows: int = 0, out: Optional[np.ndarray] = None):
         """The Julia set of c as an RGBA8 image coloured by its distance estimate (source "distance"; Palette.distance), as
         render_view(source="distance") does for a plain view.  Returns (rgba uint8[nrows, ncols, 4], TileStats)."""
-        cv = self._cview(view, window)
-        rgba = self._render_out(cv, out)
-        spec = palette.spec("distance", supersample, max_band_rows)
-        st = L.mbk_stats()
-        self._check(self._lib.mbk_julia_view_distance_render_compute(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
-                                                                     L.KERNELS[kernel], C.byref(spec), rgba.ctypes.data, C.byref(st)))
-        return rgba, _stats(st)
+        return self._distance_render("compute", "julia", view, mrd, palette, supersample, window, max_band_rows, out=out, c=c, kernel=kernel)
 
     def launch_render_julia_view_distance(self, view: View, c, mrd: int, *, palette, d_rgba: int, supersample: int = 1,
                                           stream: int = 0, window=None, kernel: str = "default", max_band_rows: int = 0) -> None:
         """Asynchronous render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream`` (0 = HIP's null stream)."""
-        cv = self._cview(view, window)
-        spec = palette.spec("distance", supersample, max_band_rows)
-        self._check(self._lib.mbk_julia_view_distance_render_launch(self._h, C.byref(cv), float(c[0]), float(c[1]), mrd,
-                                                                    L.KERNELS[kernel], C.byref(spec), d_rgba or None, stream or None))
+        self._distance_render("launch", "julia", view, mrd, palette, supersample, window, max_band_rows, d_rgba=d_rgba, stream=stream, c=c,
+                              kernel=kernel)
 
     # -- stored chunks (include/mbk.h, "Stored chunks") ---------------------------------------------
     def decode_chunk(self, stream, n: int = L.MBK_CHUNK_BYTES, out: Optional[np.ndarray] = None):
