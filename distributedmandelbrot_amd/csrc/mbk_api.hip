@@ -37,6 +37,7 @@
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
 #include "mbk_deep_distance_bla.h"
+#include "mbk_deep_relief.h"
 #include "mbk_deep_nucleus.h"
 #include "mbk_deep_wide_nucleus.h"
 #include "mbk_deep_wide_distance_bla.h"
@@ -1519,17 +1520,19 @@ static int sync_end(mbk_ctx *ctx, int rc, mbk_stats *stats, bool have_bytes, boo
 // followed by px int32 (the periods, at d_values + px), which the launch writes too; they go to h_tail, and h_values and h_tail
 // may each be NULL.  per_px (atom periods and Newton seeds): that many binary64 values per pixel, the tail after all of them.
 // h_more (normals with distance estimates; not with a tail): px more binary64 values follow the per_px * px on the device, at
-// d_values + per_px * px, which the launch writes too; they go to h_more.
+// d_values + per_px * px, which the launch writes too; they go to h_more.  h_more2 (deep normals: nu in h_more, rel here): px
+// further values behind those, at d_values + (per_px + 1) * px whether or not h_more is given.
 template <typename Launch>
 static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch,
-                          bool with_tail = false, int32_t *h_tail = nullptr, size_t per_px = 1u, double *h_more = nullptr)
+                          bool with_tail = false, int32_t *h_tail = nullptr, size_t per_px = 1u, double *h_more = nullptr,
+                          double *h_more2 = nullptr)
 {
     Slot &sl = ctx->s[0];
     auto enqueue = [&]() -> int {
         int rc = ensure_buffers(ctx, sl, px);
         if (rc != MBK_OK) return rc;
         const size_t vals = per_px * px;
-        const size_t cap = with_tail ? vals + (px + 1u) / 2u : (h_more ? vals + px : vals);   // (in binary64 values)
+        const size_t cap = with_tail ? vals + (px + 1u) / 2u : (h_more2 ? vals + 2u * px : (h_more ? vals + px : vals));   // (in binary64 values)
         rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, cap, cap * sizeof(double));
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
@@ -1542,6 +1545,7 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
         if (h_values) MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, vals * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_tail) MBK_HIP(ctx, hipMemcpyAsync(h_tail, ctx->d_smooth + vals, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         if (h_more) MBK_HIP(ctx, hipMemcpyAsync(h_more, ctx->d_smooth + vals, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        if (h_more2) MBK_HIP(ctx, hipMemcpyAsync(h_more2, ctx->d_smooth + vals + px, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
         ctx->last_px = 0;   // (no bytes on the device: mbk_serialize_last has nothing to read)
@@ -3541,6 +3545,41 @@ static int launch_deep_distance_bla(mbk_ctx *ctx, const mbk_deep_orbit *orbit, c
     return MBK_OK;
 }
 
+// ---- relief shading for deep views (mbk_deep_relief.h; mbk.h "Relief shading for deep views"): the launch; the entry points
+// follow the relief renders, below -------------------------------------------------------------------------------------------
+
+// the one-pass deep relief kernel on device pointers (validated by the caller), on `stream`; d_counts, d_smooth and d_rel may be
+// null.  bla: MBK_DEEP_BLA, on the table of the count launches (bla_copy); an orbit of length 1 has none and takes the plain kernel
+static int launch_deep_relief(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *v, uint32_t mrd, bool bla,
+                              int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel, hipStream_t stream)
+{
+    bla = bla && orbit->o.length >= 2u;
+    const mbk_ctx::DeepCopy *c = nullptr;
+    const mbk_ctx::BlaSlot *table = nullptr;
+    int rc;
+    if (bla) {
+        rc = bla_copy(ctx, orbit, deep_dcmax(v), &c, &table);
+    } else {
+        mbk_ctx::DeepCopy *plain = nullptr;
+        rc = deep_copy(ctx, orbit, &plain);
+        c = plain;
+    }
+    if (rc != MBK_OK) return rc;
+    mbk::DeepReliefArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_deep_args(a.b.v, c->d, orbit, v, mrd);
+    a.b.v.counts = d_counts;
+    a.b.v.smooth = d_smooth;
+    if (bla) fill_bla_table(a.b, c, table);
+    a.range_r = v->range_r;
+    a.normal = d_normal;
+    a.rel = d_rel;
+    if (bla) hipLaunchKernelGGL(mbk::deep_relief_bla_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(mbk::deep_relief_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // ---- distance estimates for extended-range deep views (mbk_deep_wide_distance.h; mbk.h, the section of that name) -------
 
 // the wide distance kernel on device pointers (validated by the caller), on `stream`
@@ -3744,7 +3783,8 @@ struct Outputs {
     bool distance;
     int32_t *period;   // interior views (plain views only): values is then the interior distance estimate
     bool interior;
-    double *normals;   // relief renders (plain views only): the normals of the samples, beside counts and nu
+    double *normals;   // relief (plain and deep views): the normals of the samples, beside counts and nu
+    double *rel;       // deep normals: the distance estimate of the same final state, beside nu in `values`
 };
 
 // The launch of a checked target (target_check) on device pointers, on `stream`: the one place that knows which kernels serve
@@ -3758,6 +3798,8 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
                                                : launch_deep_wide_distance(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream);
             return launch_deep_wide(ctx, t.orbit, &t.wide, mrd, o.counts, o.bytes, o.values, stream, (flags & MBK_DEEP_XBLA) != 0);
         case Target::kDeep:
+            if (o.normals)   // (one pass for counts, nu, normals and rel: a deep sample is paid once)
+                return launch_deep_relief(ctx, t.orbit, &t.deep, mrd, (flags & MBK_DEEP_BLA) != 0, o.counts, o.normals, o.values, o.rel, stream);
             if (o.distance)   // (MBK_DEEP_BLA reaches here from the _distance_bla calls alone: every public distance call refuses it)
                 return (flags & MBK_DEEP_BLA) ? launch_deep_distance_bla(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream)
                                               : launch_deep_distance(ctx, t.orbit, &t.deep, mrd, o.counts, o.values, stream);
@@ -4953,6 +4995,97 @@ int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_
     pal.light_y = light.y;
     pal.height = light.height;
     mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, smooth, rgba, mbk::kRuleRelief, nullptr, normals);
+    return MBK_OK;
+}
+
+// ---- relief shading for deep views (mbk_deep_relief.h; mbk.h "Relief shading for deep views"): the value calls on the
+// scaffold of the value calls, the renders on the relief render path above ---------------------------------------------------
+
+// Everything a deep normal call can refuse, before anything is allocated, enqueued or written: the NULL pointers, every flag but
+// MBK_DEEP_BLA, then the rules of the count launch under the same flag (the table's indices must fit).
+static int deep_normal_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const void *normal)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!normal) return fail(ctx, MBK_ERR_INVALID, "NULL normal pointer");
+    if (flags & ~(uint32_t)MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "deep normals take MBK_DEEP_BLA only (no kernel selection, no fp32)");
+    return target_check(ctx, t, mrd, flags);
+}
+
+int mbk_deep_view_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                                int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel, void *hip_stream)
+{
+    const Target t = deep_target(orbit, view);
+    int rc = deep_normal_check(ctx, t, mrd, flags, d_normal);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_normal & 7u) return fail(ctx, MBK_ERR_INVALID, "d_normal must be 8-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return target_launch(ctx, t, mrd, flags, Outputs{d_counts, nullptr, d_smooth, false, nullptr, false, d_normal, d_rel}, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_view_compute_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                                 int32_t *h_counts, double *h_normal, double *h_smooth, double *h_rel, mbk_stats *stats)
+{
+    const Target t = deep_target(orbit, view);
+    int rc = deep_normal_check(ctx, t, mrd, flags, h_normal);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    // the device values: 2 px binary64 (the normals), then px (nu), then px (rel)
+    const size_t px = (size_t)t.g.ncols * t.g.nrows;
+    return compute_values(ctx, px, mrd, h_counts, h_normal, stats,
+                          [&](int32_t *d_counts, double *d_normal, hipStream_t stream) {
+                              return target_launch(ctx, t, mrd, flags,
+                                                   Outputs{d_counts, nullptr, h_smooth ? d_normal + 2u * px : nullptr, false, nullptr, false,
+                                                           d_normal, h_rel ? d_normal + 3u * px : nullptr},
+                                                   stream);
+                          },
+                          false, nullptr, 2u, h_smooth, h_rel);
+}
+
+int mbk_deep_view_relief_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                                       const mbk_relief_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    const Target t = deep_target(orbit, view);
+    mbk_render_spec r;
+    ReliefLight light;
+    int rc = relief_render_check(ctx, t, mrd, flags, spec, d_rgba, &r, &light);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, &light);
+}
+
+int mbk_deep_view_relief_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd, uint32_t flags,
+                                        const mbk_relief_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    const Target t = deep_target(orbit, view);
+    mbk_render_spec r;
+    ReliefLight light;
+    int rc = relief_render_check(ctx, t, mrd, flags, spec, h_rgba, &r, &light);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, &r, h_rgba, stats, nullptr, 0u, nullptr, &light);
+}
+
+// host twin (the loop of mbk_deep_distance_bla.h's, the epilogue of mbk_deep_relief.h): no ctx, no device.  flags 0: no table,
+// the plain rule
+int mbk_deep_normal_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd, uint32_t flags,
+                         int32_t *count, int32_t *extra, double *zp_r, double *zp_i, double *D_r, double *D_i, int32_t *e, double normal[2],
+                         double *nu, uint64_t *steps_executed)
+{
+    if (!count || !extra || !zp_r || !zp_i || !D_r || !D_i || !e || !normal || !nu || !steps_executed)
+        return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    if (flags & ~(uint32_t)MBK_DEEP_BLA) return fail(nullptr, MBK_ERR_INVALID, "deep normals take MBK_DEEP_BLA only (no kernel selection, no fp32)");
+    mbk::BlaTable t;
+    int rc = (flags & MBK_DEEP_BLA) ? bla_host_table(orbit, view, &t) : validate_deep(nullptr, orbit, view, 0u, 0u);
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    double mag = 0.0, escaped = 0.0;   // (the final mag is the distance twin's to report)
+    mbk::deep_distance_bla_host(orbit->o.table, orbit->o.length, t, dc.r, dc.i, (int64_t)mrd, count, extra, &mag, D_r, D_i, e, steps_executed,
+                                zp_r, zp_i, &escaped);
+    mbk::normal_value(*zp_r, *zp_i, *D_r, *D_i, *count, normal);
+    *nu = mbk::smooth_value(*count, escaped);
     return MBK_OK;
 }
 

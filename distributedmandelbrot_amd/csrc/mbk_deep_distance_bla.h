@@ -128,9 +128,11 @@ __global__ __launch_bounds__(64) void deep_distance_bla_kernel(DeepDistanceBlaAr
 
 // One pixel on the host, from the functions the kernel uses: the count, the run-on steps taken, the final mag (0 for count 0),
 // the final D 2^e and the number of steps executed in the count loop (a skip is one).  `orbit` as for build_bla_table; with no
-// table (M <= 1) this is the rule of "Distance estimates for deep views".
+// table (M <= 1, or a table without levels) this is the rule of "Distance estimates for deep views".  For the relief twin
+// (mbk_deep_normal_host), each where given: the final zp, and |z|^2 of the escaping step, before the run-on (0 for count 0).
 inline void deep_distance_bla_host(const std::vector<double> &orbit, uint32_t M, const BlaTable &t, double dcr, double dci, int64_t mrd,
-                                   int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e_out, uint64_t *steps)
+                                   int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e_out, uint64_t *steps,
+                                   double *zp_r = nullptr, double *zp_i = nullptr, double *escaped = nullptr)
 {
     const double *Z = orbit.data();
     double dzr, dzi, zpr, zpi;
@@ -171,10 +173,13 @@ inline void deep_distance_bla_host(const std::vector<double> &orbit, uint32_t M,
             m = 0u;
         }
     }
+    if (escaped) *escaped = *mag;
     if (*count > 0) *extra = deep_run_on(Z, M, m, dcr, dci, dzr, dzi, zpr, zpi, *mag, Dr, Di, e, one);
     *D_r = Dr;
     *D_i = Di;
     *e_out = e;
+    if (zp_r) *zp_r = zpr;
+    if (zp_i) *zp_i = zpi;
 }
 
 }  // namespace mbk

@@ -151,8 +151,9 @@ __device__ __forceinline__ uint8_t quantise(int32_t count, const TileArgs &p)
 // that tripped the test: the tests hold nu to the correctly rounded value of the formula at that m within
 // 2.57 ulp(nu) + 3.38 * 2^-52 (glibc's libm: 1.57 and 1.38; include/mbk.h).  Measured on gfx950:
 // 1.570 ulp(nu) at n = 1, m = 11337031.25 and 1.379 * 2^-52 at n = 1, m = 75820.85571289062.
-// m == +inf (|z_1|^2 overflowed, |c| above ~1e77) gives -inf, never NaN.
-__device__ __forceinline__ double smooth_value(int32_t count, double m)
+// m == +inf (|z_1|^2 overflowed, |c| above ~1e77) gives -inf, never NaN.  __host__ too: mbk_deep_normal_host calls it, with
+// the host's libm.
+__host__ __device__ __forceinline__ double smooth_value(int32_t count, double m)
 {
     return count > 0 ? (double)count + 1.0 - log2(0.5 * log(m)) : 0.0;
 }

@@ -1738,8 +1738,8 @@ int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t wid
  * mbk_relief_resolve_host: colour and resolve on the HOST for caller-supplied samples of (width s) x (height s); `normals`
  * holds two binary64 per sample.
  *
- * Out of scope: deep, extended-range and Julia views; adaptive supersampling; equalised or distance base colours; sharding and
- * slot forms; specular terms.
+ * Out of scope: extended-range and Julia views (deep views: "Relief shading for deep views", below); adaptive supersampling;
+ * equalised or distance base colours; sharding and slot forms; specular terms.
  */
 typedef struct mbk_relief_spec {
     uint32_t supersample;   /* 1, 2, 3, 4, 8 */
@@ -1763,6 +1763,77 @@ int mbk_view_relief_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t 
                                    uint8_t *h_rgba, mbk_stats *stats);
 int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
                             const double *smooth, const double *normals, uint8_t *rgba);
+
+/*
+ * Relief shading for deep views: the same normals and lit renders for mbk_deep_view, with the plain step and with the skips of
+ * MBK_DEEP_BLA.  NOT in the reference; additive (the ABI version stays 5): no existing call changes.  At a span of 1e-60 a
+ * count or nu picture is dense bands; slope lighting is what makes filaments and spirals readable there, and it is nearly free:
+ * the deep distance kernels already end every escaped pixel with its full z and the derivative D 2^e in registers.
+ *
+ * Contract (exact; tests/deep_relief_model.py restates it in numpy, tests/test_deep_relief.py and tests/test_gpu_deep_relief.py
+ * hold the host twin and the GPU to it).  Binary64, every operation rounded on its own.
+ *   state     flags 0: exactly that of "Distance estimates for deep views"; flags MBK_DEEP_BLA: exactly that of "Distance
+ *             estimates for deep views with bilinear approximation" -- the same start, step (and skip), rescale rule, count n,
+ *             run-on and final (zp, D, e), zp being the pixel's full z = fl(Z_m + dz) of the last step run.
+ *   normal    normal_value(zp.r, zp.i, D_r, D_i, n) as "Relief shading" defines it on (z, d): the same products, the same
+ *             flat-normal rule, the correctly rounded square root and division.  e is NOT used: the direction of z conj(d)
+ *             does not depend on the scale of d, so D stands for d = D 2^e and a view at e = 768 needs nothing more than one
+ *             at e = 0.  m = |zp conj(D)|^2 cannot overflow: the rescale rules leave max(|D_r|, |D_i|) < 2^256 and the run-on
+ *             stops at the first |zp|^2 >= 2^32, reached from below 2^32, so |zp|^2 < 2^65 and m < 2^(65 + 514) < 2^580.
+ *             m CAN underflow to 0, and the normal of an escaped pixel is then flat; |zp| >= 2 there, so it needs
+ *             max(|D_r|, |D_i|) < 2^-538, and nothing in the rules forbids that.  The plain step rescales downwards only: a step
+ *             from |zp| < 1/2 shrinks D and e does not fall.  The skip's upward rescale is applied once per skip, by 2^256,
+ *             and only while e >= 256: it brings max(|D_r|, |D_i|) back to 2^-256 or above only from 2^-512 or above.  With
+ *             e < 256 such a D is a true |d| < 2^-282 -- the pixel sits on a critical point of z_n(c), where the gradient has
+ *             no direction and rel is +inf or overflows; with e >= 256 it takes 282 binades of decay after the last restoring
+ *             skip.  Neither occurs on the project's cases (the tests assert that every escaped pixel's normal is a unit
+ *             vector); where it does, (0, 0) is the defined result.
+ *   nu        smooth_value(n, mag) with the mag of the ESCAPING step, before the run-on: the bits mbk_deep_view_launch stores
+ *             as smooth values under the same flags.
+ *   rel       (optional output) the bits mbk_deep_view_launch_distance stores; with MBK_DEEP_BLA those of
+ *             mbk_deep_view_launch_distance_bla.
+ *   shade, colour, resolve, banding, statistics: those of "Relief shading" and "Rendering".  A sample is 28 bytes.
+ *             mbk_relief_spec and mbk_relief_resolve_host serve as they are.
+ * Windows of a view are bit-identical to the whole view (the table of MBK_DEEP_BLA is the FULL view's); any max_band_rows
+ * gives the same image.  mrd 0 and 1 run no step: every count and nu is 0 and every normal flat.  Where no skip is ever taken
+ * (M <= 1, or offsets that never pass the radius test) MBK_DEEP_BLA changes no bit.
+ * Held to the mathematics (tests/test_deep_relief.py): d' = 2 z d + 1, z' = z^2 + c in mpmath at the orbit's precision + 128
+ * bits from the exact pixel coordinate give the unit vector of z / d; the model's normal is within 4 x MEASURED_NORMAL of it
+ * (tests/deep_relief_model.py, measured per case with and without skips) on the escaped picks whose count and run-on agree.
+ *
+ * ONE pass (csrc/mbk_deep_relief.h): the loops of the deep distance kernels with another epilogue; a deep sample costs
+ * thousands of perturbation steps and is paid once, whatever is asked for.  With M <= 1 the flag changes nothing.
+ * mbk_deep_view_launch_normal: asynchronous, DEVICE pointers on the caller's stream.  d_normal: two binary64 per pixel of the
+ * window, 8-byte aligned, required; d_counts (int32), d_smooth (nu) and d_rel (binary64 each) may be NULL.  Nothing is written
+ * outside the window-sized buffers.  flags: 0 or MBK_DEEP_BLA -- the calls are new, so the flag is taken on the one name.  The
+ * table is the one the MBK_DEEP_BLA count launches build and share, under their first-launch rule: launch once per (orbit,
+ * spans) before capturing.
+ * mbk_deep_view_compute_normal: synchronous into HOST buffers on slot 0 (the slot-0 rule applies), the same pointer rules;
+ * pixel_iterations counts the reference's iterations (count, or mrd - 1 for 0), not the steps executed and not the run-on.
+ * mbk_deep_view_relief_render_launch / _compute: a band runs the one-pass kernel for counts, nu and normals and resolves with
+ * the relief rule.
+ * mbk_deep_normal_host: one pixel (col, row) of the FULL view on the HOST, compiled from the functions the kernels use: count,
+ * run-on steps, final zp, D and e, the normal, nu, and the steps executed in the count loop (a skip is one).
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_view_launch_distance refuses for the view, the orbit and mrd (with
+ * MBK_DEEP_BLA also an orbit longer than 2^31); any flag bit other than MBK_DEEP_BLA; ranges below 2^-960 (an extended-range
+ * view has no call here); a NULL normal, spec, palette or output pointer; a light or a height outside the ranges of "Relief
+ * shading".
+ *
+ * Out of scope: extended-range (mbk_deep_xview) and Julia views; adaptive supersampling; sharding and slot forms.
+ */
+int mbk_deep_view_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                uint32_t flags, int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel,
+                                void *hip_stream);
+int mbk_deep_view_compute_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                 uint32_t flags, int32_t *h_counts, double *h_normal, double *h_smooth, double *h_rel,
+                                 mbk_stats *stats);
+int mbk_deep_view_relief_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                       uint32_t flags, const mbk_relief_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_view_relief_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
+                                        uint32_t flags, const mbk_relief_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+int mbk_deep_normal_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
+                         uint32_t flags, int32_t *count, int32_t *extra, double *zp_r, double *zp_i, double *D_r, double *D_i,
+                         int32_t *e, double normal[2], double *nu, uint64_t *steps_executed);
 
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
