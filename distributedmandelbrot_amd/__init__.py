@@ -19,10 +19,10 @@ There is no CPU fallback anywhere in this package.
 from .device import DeepOrbit, DeepView, DensityStats, DensityTarget, MandelbrotDevice, MbkError, TileStats, View, WideDeepView, device_count  # noqa: F401
 from .device import deep_distance_bla_host, deep_distance_bla_skip_host, deep_normal_host  # noqa: F401
 from .device import Nucleus, NucleusError, deep_nucleus_host, locate_nucleus, pick_nucleus_seed, refine_nucleus  # noqa: F401
-from .device import locate_wide_nucleus, pick_wide_nucleus_seed, wide_nucleus_host, wide_nucleus_precision_bits  # noqa: F401
+from .device import locate_wide_nucleus, pick_wide_nucleus_seed, wide_normal_host, wide_nucleus_host, wide_nucleus_precision_bits  # noqa: F401
 from .image import Palette, write_png  # noqa: F401
 
 __all__ = ["DeepOrbit", "DeepView", "DensityStats", "DensityTarget", "MandelbrotDevice", "MbkError", "Nucleus", "NucleusError", "Palette",
            "TileStats", "View", "WideDeepView", "deep_distance_bla_host", "deep_distance_bla_skip_host", "deep_normal_host",
            "deep_nucleus_host", "device_count", "locate_nucleus", "locate_wide_nucleus", "pick_nucleus_seed", "pick_wide_nucleus_seed", "refine_nucleus",
-           "wide_nucleus_host", "wide_nucleus_precision_bits", "write_png"]
+           "wide_normal_host", "wide_nucleus_host", "wide_nucleus_precision_bits", "write_png"]

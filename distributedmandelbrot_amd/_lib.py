@@ -454,6 +454,18 @@ SIGNATURES = {
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "mbk_deep_xview_launch_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_compute_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_relief_render_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                      C.POINTER(mbk_relief_spec), C.c_void_p, C.c_void_p]),
+    "mbk_deep_xview_relief_render_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32,
+                                                       C.POINTER(mbk_relief_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_deep_xview_normal_host": (C.c_int, [C.c_void_p, C.POINTER(mbk_deep_xview), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "mbk_view_density_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mbk_view_density_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.POINTER(mbk_density_target), C.c_uint32, C.c_uint32,

@@ -41,6 +41,7 @@
 #include "mbk_deep_nucleus.h"
 #include "mbk_deep_wide_nucleus.h"
 #include "mbk_deep_wide_distance_bla.h"
+#include "mbk_deep_wide_relief.h"
 #include "mbk_deep_wide_distance.h"
 #include "mbk_julia.h"
 #include "mbk_julia_distance.h"
@@ -3622,6 +3623,36 @@ static int launch_deep_wide_distance_xbla(mbk_ctx *ctx, const mbk_deep_orbit *or
     return MBK_OK;
 }
 
+// ---- relief shading for extended-range deep views (mbk_deep_wide_relief.h; mbk.h, the section of that name): the launch; the
+// entry points follow those of the deep views, below --------------------------------------------------------------------------
+
+// the one-pass wide relief kernel on device pointers (validated by the caller), on `stream`; d_counts, d_smooth and d_rel may be
+// null.  xbla: MBK_DEEP_XBLA, on the table of the count launches (xbla_copy: acquired before anything is enqueued); an orbit of
+// length 1 has none and takes the plain kernel
+static int launch_deep_wide_relief(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *v, uint32_t mrd, bool xbla,
+                                   int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel, hipStream_t stream)
+{
+    xbla = xbla && orbit->o.length >= 2u;
+    const mbk_ctx::DeepCopy *c = nullptr;
+    const mbk_ctx::XblaSlot *slot = nullptr;
+    const mbk::WideEntry *d_orbit = nullptr;
+    int rc = xbla ? xbla_copy(ctx, orbit, wide_view_dcmax(v), &c, &slot) : wide_copy(ctx, orbit, &d_orbit);
+    if (rc != MBK_OK) return rc;
+    mbk::DeepWideReliefArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_deep_wide_args(a.b.v, xbla ? c->d_wide : d_orbit, orbit, v, mrd);
+    a.b.v.counts = d_counts;
+    a.b.v.smooth = d_smooth;
+    if (xbla) fill_xbla_table(a.b, c, slot);
+    a.range_r = v->range_r;
+    a.normal = d_normal;
+    a.rel = d_rel;
+    if (xbla) hipLaunchKernelGGL(mbk::deep_wide_relief_xbla_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL(mbk::deep_wide_relief_kernel, block_grid(a.b.v), dim3(64), 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
 // host twins (mbk_deep_wide_distance.h): no ctx, no device
 int mbk_deep_xview_distance_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
                                  int32_t *count, int32_t *extra, double *mag, double *D_r, double *D_i, int32_t *e, double *rel)
@@ -3783,8 +3814,8 @@ struct Outputs {
     bool distance;
     int32_t *period;   // interior views (plain views only): values is then the interior distance estimate
     bool interior;
-    double *normals;   // relief (plain and deep views): the normals of the samples, beside counts and nu
-    double *rel;       // deep normals: the distance estimate of the same final state, beside nu in `values`
+    double *normals;   // relief (plain, deep and extended-range deep views): the normals of the samples, beside counts and nu
+    double *rel;       // deep and extended-range deep normals: the distance estimate of the same final state, beside nu in `values`
 };
 
 // The launch of a checked target (target_check) on device pointers, on `stream`: the one place that knows which kernels serve
@@ -3793,6 +3824,8 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
 {
     switch (t.kind) {
         case Target::kWide:
+            if (o.normals)   // (one pass for counts, nu, normals and rel: a wide sample is paid once)
+                return launch_deep_wide_relief(ctx, t.orbit, &t.wide, mrd, (flags & MBK_DEEP_XBLA) != 0, o.counts, o.normals, o.values, o.rel, stream);
             if (o.distance)   // (MBK_DEEP_XBLA reaches here from the _distance_xbla calls alone: every other distance call refuses it)
                 return (flags & MBK_DEEP_XBLA) ? launch_deep_wide_distance_xbla(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream)
                                                : launch_deep_wide_distance(ctx, t.orbit, &t.wide, mrd, o.counts, o.values, stream);
@@ -5084,6 +5117,118 @@ int mbk_deep_normal_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view,
     double mag = 0.0, escaped = 0.0;   // (the final mag is the distance twin's to report)
     mbk::deep_distance_bla_host(orbit->o.table, orbit->o.length, t, dc.r, dc.i, (int64_t)mrd, count, extra, &mag, D_r, D_i, e, steps_executed,
                                 zp_r, zp_i, &escaped);
+    mbk::normal_value(*zp_r, *zp_i, *D_r, *D_i, *count, normal);
+    *nu = mbk::smooth_value(*count, escaped);
+    return MBK_OK;
+}
+
+// ---- relief shading for extended-range deep views (mbk_deep_wide_relief.h; mbk.h, the section of that name): the calls of the
+// deep views on a Target of kind kWide ------------------------------------------------------------------------------------------
+
+// What the wide relief calls refuse of their flags: MBK_DEEP_BLA in validate_deep_wide's words, every flag but MBK_DEEP_XBLA
+static int wide_normal_flags_check(mbk_ctx *ctx, uint32_t flags)
+{
+    if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, kNoWideBla);
+    if (flags & ~(uint32_t)MBK_DEEP_XBLA)
+        return fail(ctx, MBK_ERR_INVALID, "extended-range deep normals take MBK_DEEP_XBLA only (no kernel selection, no fp32)");
+    return MBK_OK;
+}
+
+// Everything a wide normal call can refuse, before anything is allocated, enqueued or written: the NULL pointers, the flags,
+// then the rules of the count launch under the same flag (the table's indices must fit).
+static int wide_normal_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const void *normal)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!normal) return fail(ctx, MBK_ERR_INVALID, "NULL normal pointer");
+    int rc = wide_normal_flags_check(ctx, flags);
+    if (rc != MBK_OK) return rc;
+    return target_check(ctx, t, mrd, flags);
+}
+
+// relief_render_check behind the flag rules of the wide normal calls
+static int wide_relief_render_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_relief_spec *spec, const void *out,
+                                    mbk_render_spec *r, ReliefLight *light)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    int rc = wide_normal_flags_check(ctx, flags);
+    if (rc != MBK_OK) return rc;
+    return relief_render_check(ctx, t, mrd, flags, spec, out, r, light);
+}
+
+int mbk_deep_xview_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                                 int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel, void *hip_stream)
+{
+    const Target t = wide_target(orbit, view);
+    int rc = wide_normal_check(ctx, t, mrd, flags, d_normal);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_normal & 7u) return fail(ctx, MBK_ERR_INVALID, "d_normal must be 8-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return target_launch(ctx, t, mrd, flags, Outputs{d_counts, nullptr, d_smooth, false, nullptr, false, d_normal, d_rel}, (hipStream_t)hip_stream);
+}
+
+int mbk_deep_xview_compute_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                                  int32_t *h_counts, double *h_normal, double *h_smooth, double *h_rel, mbk_stats *stats)
+{
+    const Target t = wide_target(orbit, view);
+    int rc = wide_normal_check(ctx, t, mrd, flags, h_normal);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    // the device values: 2 px binary64 (the normals), then px (nu), then px (rel)
+    const size_t px = (size_t)t.g.ncols * t.g.nrows;
+    return compute_values(ctx, px, mrd, h_counts, h_normal, stats,
+                          [&](int32_t *d_counts, double *d_normal, hipStream_t stream) {
+                              return target_launch(ctx, t, mrd, flags,
+                                                   Outputs{d_counts, nullptr, h_smooth ? d_normal + 2u * px : nullptr, false, nullptr, false,
+                                                           d_normal, h_rel ? d_normal + 3u * px : nullptr},
+                                                   stream);
+                          },
+                          false, nullptr, 2u, h_smooth, h_rel);
+}
+
+int mbk_deep_xview_relief_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                                        const mbk_relief_spec *spec, uint8_t *d_rgba, void *hip_stream)
+{
+    const Target t = wide_target(orbit, view);
+    mbk_render_spec r;
+    ReliefLight light;
+    int rc = wide_relief_render_check(ctx, t, mrd, flags, spec, d_rgba, &r, &light);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, &light);
+}
+
+int mbk_deep_xview_relief_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd, uint32_t flags,
+                                         const mbk_relief_spec *spec, uint8_t *h_rgba, mbk_stats *stats)
+{
+    const Target t = wide_target(orbit, view);
+    mbk_render_spec r;
+    ReliefLight light;
+    int rc = wide_relief_render_check(ctx, t, mrd, flags, spec, h_rgba, &r, &light);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, &r, h_rgba, stats, nullptr, 0u, nullptr, &light);
+}
+
+// host twin (the loop of mbk_deep_wide_distance_bla.h's, the epilogue of mbk_deep_wide_relief.h): no ctx, no device.  flags 0:
+// no table, the plain rule
+int mbk_deep_xview_normal_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row, uint32_t mrd,
+                               uint32_t flags, int32_t *count, int32_t *extra, double *zp_r, double *zp_i, int32_t *zp_t, double *D_r,
+                               double *D_i, int32_t *e, double normal[2], double *nu, uint64_t *steps_executed)
+{
+    if (!count || !extra || !zp_r || !zp_i || !zp_t || !D_r || !D_i || !e || !normal || !nu || !steps_executed)
+        return fail(nullptr, MBK_ERR_INVALID, "NULL argument");
+    int rc = wide_normal_flags_check(nullptr, flags);
+    if (rc != MBK_OK) return rc;
+    mbk::WideBlaTable t;
+    rc = (flags & MBK_DEEP_XBLA) ? xbla_host_table(orbit, view, &t) : validate_deep_wide(nullptr, orbit, view, 0u, 0u);
+    if (rc != MBK_OK) return rc;
+    if (mrd > orbit->o.mrd) return fail(nullptr, MBK_ERR_INVALID, "mrd exceeds the mrd the reference orbit was computed for");
+    const PixelDc dc = pixel_dc(view, col, row);
+    if (dc.rc != MBK_OK) return dc.rc;
+    double mag = 0.0, escaped = 0.0;   // (the final mag is the distance twin's to report)
+    mbk::wide_distance_bla_host(orbit->o.wide, orbit->o.length, t, dc.r, dc.i, view->exp2, (int64_t)mrd, count, extra, &mag, D_r, D_i, e,
+                                steps_executed, zp_r, zp_i, zp_t, &escaped);
     mbk::normal_value(*zp_r, *zp_i, *D_r, *D_i, *count, normal);
     *nu = mbk::smooth_value(*count, escaped);
     return MBK_OK;

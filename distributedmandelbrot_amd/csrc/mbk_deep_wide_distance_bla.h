@@ -147,11 +147,14 @@ __global__ __launch_bounds__(64, 8) void deep_wide_distance_bla_kernel(DeepWideD
 }
 
 // One pixel on the host, from the functions the kernel uses: the count, the run-on steps taken, the final |z|^2 (0 for count
-// 0), the final derivative D 2^e and the number of steps executed in the count loop (a skip is one).  With no table (M <= 1)
-// this is the rule of "Distance estimates for extended-range deep views".
+// 0), the final derivative D 2^e and the number of steps executed in the count loop (a skip is one).  With no table (M <= 1,
+// or a table without levels) this is the rule of "Distance estimates for extended-range deep views".  For the relief twin
+// (mbk_deep_xview_normal_host), each where given: the final zp = (zr, zi) 2^t, and |z|^2 of the escaping step, before the
+// run-on (0 for count 0).
 inline void wide_distance_bla_host(const std::vector<WideEntry> &orbit, uint32_t M, const WideBlaTable &tb, double dcr, double dci,
                                    int32_t exp2, int64_t mrd, int32_t *count, int32_t *extra, double *mag, double *Dr_out,
-                                   double *Di_out, int32_t *e_out, uint64_t *steps)
+                                   double *Di_out, int32_t *e_out, uint64_t *steps, double *zr_out = nullptr, double *zi_out = nullptr,
+                                   int32_t *t_out = nullptr, double *escaped = nullptr)
 {
     const WideEntry *Z = orbit.data();
     double wr, wi, zr, zi, mg;
@@ -190,10 +193,14 @@ inline void wide_distance_bla_host(const std::vector<WideEntry> &orbit, uint32_t
             m = 0u;
         }
     }
+    if (escaped) *escaped = *mag;
     if (*count > 0) *extra = wide_run_on(Z, M, m, dcr, dci, exp2, wr, wi, q, zr, zi, t, mg, *mag, Dr, Di, e);
     *Dr_out = Dr;
     *Di_out = Di;
     *e_out = e;
+    if (zr_out) *zr_out = zr;
+    if (zi_out) *zi_out = zi;
+    if (t_out) *t_out = t;
 }
 
 }  // namespace mbk

@@ -432,7 +432,12 @@ def deep_distance_bla_skip_host(A_r: float, A_i: float, B_r: float, B_i: float, 
 def _no_wide_relief(view) -> None:
     if not isinstance(view, DeepView):
         raise MbkError(L.MBK_ERR_INVALID, "relief shading is implemented for a DeepView only: a WideDeepView (spans below 2^-960) "
-                                          "has no normals yet")
+                                          "takes compute_wide_view_normals / render_wide_view_relief / wide_normal_host")
+
+
+def _wide_relief_only(view, name: str, deep_name: str) -> None:
+    if not isinstance(view, WideDeepView):
+        raise ValueError(f"{name} takes a WideDeepView (a DeepView: {deep_name})")
 
 
 def deep_normal_host(orbit: "DeepOrbit", view: "DeepView", pixels, mrd: int, bla: bool = False) -> dict:
@@ -456,6 +461,33 @@ def deep_normal_host(orbit: "DeepOrbit", view: "DeepView", pixels, mrd: int, bla
                                              L.MBK_DEEP_BLA if bla else 0, C.byref(n), C.byref(x), C.byref(zr), C.byref(zi),
                                              C.byref(dr), C.byref(di), C.byref(e), nrm, C.byref(nu), C.byref(s)))
         for key, v in (("n", n), ("extra", x), ("zpr", zr), ("zpi", zi), ("Dr", dr), ("Di", di), ("e", e), ("nu", nu), ("steps", s)):
+            out[key][j] = v.value
+        out["normal"][j] = nrm[0], nrm[1]
+    return out
+
+
+def wide_normal_host(orbit: "DeepOrbit", view: "WideDeepView", pixels, mrd: int, xbla: bool = False, window=None) -> dict:
+    """mbk_deep_xview_normal_host on the pixels (row-major indices of the FULL view), on the host, from the functions the
+    kernels use (include/mbk.h, "Relief shading for extended-range deep views"): the dict of deep_normal_host -- zpr, zpi the
+    mantissas of the final z -- plus t (int64: z = (zpr, zpi) 2^t; d = (Dr, Di) 2^e).  A window changes nothing: the table of
+    xbla is the full view's."""
+    _wide_relief_only(view, "wide_normal_host", "deep_normal_host")
+    lib = L.load()
+    cv = _cxview(view, window)
+    pixels = np.asarray(pixels, np.int64).ravel()
+    out = {k: np.empty(pixels.size, t) for k, t in (("n", np.int32), ("extra", np.int32), ("zpr", np.float64), ("zpi", np.float64),
+                                                   ("t", np.int64), ("Dr", np.float64), ("Di", np.float64), ("e", np.int64),
+                                                   ("nu", np.float64), ("steps", np.int64))}
+    out["normal"] = np.empty((pixels.size, 2), np.float64)
+    n, x, t, e, s = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+    zr, zi, dr, di, nu = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    nrm = (C.c_double * 2)()
+    for j, k in enumerate(pixels):
+        _check(lib, lib.mbk_deep_xview_normal_host(orbit._h, C.byref(cv), int(k % view.width), int(k // view.width), int(mrd),
+                                                   L.MBK_DEEP_XBLA if xbla else 0, C.byref(n), C.byref(x), C.byref(zr), C.byref(zi),
+                                                   C.byref(t), C.byref(dr), C.byref(di), C.byref(e), nrm, C.byref(nu), C.byref(s)))
+        for key, v in (("n", n), ("extra", x), ("zpr", zr), ("zpi", zi), ("t", t), ("Dr", dr), ("Di", di), ("e", e), ("nu", nu),
+                       ("steps", s)):
             out[key][j] = v.value
         out["normal"][j] = nrm[0], nrm[1]
     return out
@@ -1653,6 +1685,67 @@ class MandelbrotDevice:
         spec = palette.relief_spec(supersample, light_deg, height, max_band_rows, light=light)
         self._check(self._lib.mbk_deep_view_relief_render_launch(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_BLA if bla else 0,
                                                                  C.byref(spec), d_rgba or None, stream or None))
+
+    # -- relief shading for extended-range deep views (include/mbk.h, the section of that name): calls of their own, one pass
+    # per sample; the compute_deep_view_normals family keeps refusing a WideDeepView --
+    def compute_wide_view_normals(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, window=None, xbla: bool = False,
+                                  want_smooth: bool = False, want_distance: bool = False):
+        """compute_deep_view_normals for a WideDeepView: unit normals of the exterior potential from the state
+        compute_wide_view_distance (xbla: compute_wide_view_distance_xbla) ends with -- neither the exponent of z nor that of
+        the derivative enters the direction.  (0, 0) for never-escaped pixels, and for no escaped one.  The counts are those of
+        compute_deep_view(xbla=xbla); want_smooth adds its smooth values, want_distance the rel of the distance call, each bit
+        for bit, from the same single pass.
+        Returns (counts int32[nrows,ncols], normals float64[nrows,ncols,2], [smooth float64[nrows,ncols],]
+        [rel float64[nrows,ncols],] TileStats)."""
+        _wide_relief_only(view, "compute_wide_view_normals", "compute_deep_view_normals")
+        cv = _cxview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        counts = np.empty(shape, np.int32)
+        normals = np.empty(shape + (2,), np.float64)
+        smooth = np.empty(shape, np.float64) if want_smooth else None
+        rel = np.empty(shape, np.float64) if want_distance else None
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_compute_normal(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_XBLA if xbla else 0,
+                                                            counts.ctypes.data, normals.ctypes.data,
+                                                            smooth.ctypes.data if want_smooth else None,
+                                                            rel.ctypes.data if want_distance else None, C.byref(st)))
+        return (counts, normals) + ((smooth,) if want_smooth else ()) + ((rel,) if want_distance else ()) + (_stats(st),)
+
+    def launch_wide_view_normals(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, d_normals: int, d_counts: int = 0,
+                                 d_smooth: int = 0, d_rel: int = 0, stream: int = 0, window=None, xbla: bool = False) -> None:
+        """Asynchronous form on DEVICE pointers (float64 x 2 / int32 / float64 / float64 per pixel of the window; d_counts,
+        d_smooth and d_rel may be 0) on ``stream`` (0 = HIP's null stream).  With xbla the first launch of a view's spans on an
+        orbit builds and uploads the table synchronously."""
+        _wide_relief_only(view, "launch_wide_view_normals", "launch_deep_view_normals")
+        cv = _cxview(view, window)
+        self._check(self._lib.mbk_deep_xview_launch_normal(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_XBLA if xbla else 0,
+                                                           d_counts or None, d_normals or None, d_smooth or None, d_rel or None,
+                                                           stream or None))
+
+    def render_wide_view_relief(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, light_deg: float = 45.0,
+                                height: float = 1.5, light=None, supersample: int = 1, window=None, max_band_rows: int = 0,
+                                xbla: bool = False, out: Optional[np.ndarray] = None):
+        """The extended-range view as a relief: render_view_relief's light on render_deep_view's "smooth" colouring, every
+        sample computed once.  xbla: the samples are those of the s-times view under compute_deep_view(xbla=True), with that
+        view's own table.  Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples)."""
+        _wide_relief_only(view, "render_wide_view_relief", "render_deep_view_relief")
+        cv = _cxview(view, window)
+        spec = palette.relief_spec(supersample, light_deg, height, max_band_rows, light=light)
+        img = self._render_out(cv, out)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_deep_xview_relief_render_compute(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_XBLA if xbla else 0,
+                                                                   C.byref(spec), img.ctypes.data, C.byref(st)))
+        return img, _stats(st)
+
+    def launch_render_wide_view_relief(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, palette, d_rgba: int,
+                                       light_deg: float = 45.0, height: float = 1.5, light=None, supersample: int = 1,
+                                       stream: int = 0, window=None, max_band_rows: int = 0, xbla: bool = False) -> None:
+        """Asynchronous relief render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream``."""
+        _wide_relief_only(view, "launch_render_wide_view_relief", "launch_render_deep_view_relief")
+        cv = _cxview(view, window)
+        spec = palette.relief_spec(supersample, light_deg, height, max_band_rows, light=light)
+        self._check(self._lib.mbk_deep_xview_relief_render_launch(self._h, orbit._h, C.byref(cv), mrd, L.MBK_DEEP_XBLA if xbla else 0,
+                                                                  C.byref(spec), d_rgba or None, stream or None))
 
     # -- distance estimates for extended-range deep views (include/mbk.h, the section of that name): calls of their own --
     def compute_wide_view_distance(self, orbit: DeepOrbit, view: WideDeepView, mrd: int, *, window=None):

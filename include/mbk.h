@@ -1738,8 +1738,8 @@ int mbk_interior_resolve_host(const mbk_interior_render_spec *spec, uint32_t wid
  * mbk_relief_resolve_host: colour and resolve on the HOST for caller-supplied samples of (width s) x (height s); `normals`
  * holds two binary64 per sample.
  *
- * Out of scope: extended-range and Julia views (deep views: "Relief shading for deep views", below); adaptive supersampling;
- * equalised or distance base colours; sharding and slot forms; specular terms.
+ * Out of scope: Julia views (deep and extended-range deep views: the two sections below); adaptive supersampling; equalised or
+ * distance base colours; sharding and slot forms; specular terms.
  */
 typedef struct mbk_relief_spec {
     uint32_t supersample;   /* 1, 2, 3, 4, 8 */
@@ -1819,7 +1819,8 @@ int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_
  * view has no call here); a NULL normal, spec, palette or output pointer; a light or a height outside the ranges of "Relief
  * shading".
  *
- * Out of scope: extended-range (mbk_deep_xview) and Julia views; adaptive supersampling; sharding and slot forms.
+ * Out of scope: Julia views (extended-range views: "Relief shading for extended-range deep views", below); adaptive
+ * supersampling; sharding and slot forms.
  */
 int mbk_deep_view_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t mrd,
                                 uint32_t flags, int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel,
@@ -1834,6 +1835,84 @@ int mbk_deep_view_relief_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbi
 int mbk_deep_normal_host(const mbk_deep_orbit *orbit, const mbk_deep_view *view, uint32_t col, uint32_t row, uint32_t mrd,
                          uint32_t flags, int32_t *count, int32_t *extra, double *zp_r, double *zp_i, double *D_r, double *D_i,
                          int32_t *e, double normal[2], double *nu, uint64_t *steps_executed);
+
+/*
+ * Relief shading for extended-range deep views: the same normals and lit renders for mbk_deep_xview (spans below 2^-960), with
+ * the plain wide step and with the skips of MBK_DEEP_XBLA.  NOT in the reference; additive (the ABI version stays 5): no
+ * existing call changes.  Past 2^-960 a count or nu picture is dense bands and slope lighting is what keeps filaments
+ * readable; it is nearly free, since the wide distance kernels already end every escaped pixel with its full z = (zr, zi) 2^t
+ * and the derivative d = (Dr, Di) 2^e in registers.
+ *
+ * Contract (exact; tests/deep_wide_relief_model.py restates it in numpy, tests/test_deep_wide_relief.py and
+ * tests/test_gpu_deep_wide_relief.py hold the host twin and the GPU to it).  Binary64 mantissas, every operation rounded on its
+ * own.
+ *   state     flags 0: exactly that of "Distance estimates for extended-range deep views"; flags MBK_DEEP_XBLA: exactly that
+ *             of "Distance estimates for extended-range deep views with bilinear approximation" -- the same start, step (and
+ *             skip), count n, run-on and final (zr, zi, t, Dr, Di, e): zp = (zr, zi) 2^t is step (e)'s sum of the last step
+ *             run, on its nominal exponent, not renormalised.
+ *   normal    normal_value(zr, zi, Dr, Di, n) as "Relief shading" defines it on (z, d): the same products, the same
+ *             flat-normal rule, the correctly rounded square root and division.  Neither t nor e is used: the direction of
+ *             z conj(d) depends on the scale of neither factor.
+ *   bound     m = |(zr, zi) conj((Dr, Di))|^2 of an escaped pixel with D != 0 lies in (2^-68, 2^5): it can neither overflow
+ *             nor underflow.  Above: zr and zi are each the sum of two aligned mantissas below 1 in magnitude, so
+ *             |zr|, |zi| < 2; max(|Dr|, |Di|) < 1; each of the two sums of products is below 4 and m < 32.  Below: the
+ *             escaping |z|^2 >= 4 as computed, so |z| >= 2 (1 - 2^-50), and |z| does not shrink in the run-on, which stops
+ *             at the first |z|^2 >= 2^32, reached from below 2^32 with |c| < 3: |z| < 2^32 + 3.  The orbit ends at its first
+ *             |Z_M|^2 >= 4, so |Z_m| < 6 and its exponent xe <= 3; |dz| <= |z| + |Z_m| < 2^33 gives q <= 33.  t = max(xe, q)
+ *             <= 33, so |(zr, zi)|^2 = |z|^2 2^(-2t) > 2^-65; the larger component of D is at least 1/2, |D|^2 >= 1/4; the
+ *             roundings of the four products, two sums, two squares and the last sum move m by a relative 2^-49 at most
+ *             (one of the two sums of products may cancel; the other then carries m).  So the flat normal of an escaped pixel
+ *             means D == 0 exactly -- 2 z d = -1 to the last bit at the step before, the critical point where the gradient
+ *             has no direction -- and the 2^-538 caveat of "Relief shading for deep views" has no counterpart.  The tests
+ *             assert that no escaped pixel of any case is flat.
+ *   nu        smooth_value(n, mag) with the mag of the ESCAPING step, before the run-on: the bits mbk_deep_xview_launch
+ *             stores as smooth values under the same flags.
+ *   rel       (optional output) the bits mbk_deep_xview_launch_distance stores; with MBK_DEEP_XBLA those of
+ *             mbk_deep_xview_launch_distance_xbla.
+ *   shade, colour, resolve, banding, statistics: those of "Relief shading" and "Rendering".  A sample is 28 bytes.
+ *             mbk_relief_spec and mbk_relief_resolve_host serve as they are.
+ * Wherever the plain deep contract meets no subnormal, the normal is the one "Relief shading for deep views" stores, bit for
+ * bit (scaling by a power of two is exact).  Windows of a view are bit-identical to the whole view (the table of MBK_DEEP_XBLA
+ * is the FULL view's; for a render at supersample s, the sample view's own); any max_band_rows gives the same image.  mrd 0
+ * and 1 run no step: every count and nu is 0 and every normal flat.  Where no skip is ever
+ * taken (M <= 1, or offsets that never pass the radius test) MBK_DEEP_XBLA changes no bit.
+ * Held to the mathematics (tests/test_deep_wide_relief.py): d' = 2 z d + 1, z' = z^2 + c in mpmath at the orbit's precision +
+ * 128 bits from the exact pixel coordinate give the unit vector of z / d; the model's normal is within 4 x MEASURED_NORMAL of
+ * it (tests/deep_wide_relief_model.py, measured per case with and without skips) on the escaped picks whose count and run-on
+ * agree.
+ *
+ * ONE pass (csrc/mbk_deep_wide_relief.h): the loops of the wide distance kernels with another epilogue; a wide sample costs
+ * thousands of wide steps and is paid once, whatever is asked for.
+ * mbk_deep_xview_launch_normal: asynchronous, DEVICE pointers on the caller's stream.  d_normal: two binary64 per pixel of the
+ * window, 8-byte aligned, required; d_counts (int32), d_smooth (nu) and d_rel (binary64 each) may be NULL.  Nothing is written
+ * outside the window-sized buffers.  flags: 0 or MBK_DEEP_XBLA.  The table is the one the MBK_DEEP_XBLA count launches build
+ * and share (two per orbit), under their first-launch rule: launch once per (orbit, spans) before capturing.
+ * mbk_deep_xview_compute_normal: synchronous into HOST buffers on slot 0 (the slot-0 rule applies), the same pointer rules.
+ * mbk_deep_xview_relief_render_launch / _compute: a band runs the one-pass kernel for counts, nu and normals and resolves
+ * with the relief rule.
+ * mbk_deep_xview_normal_host: one pixel (col, row) of the FULL view on the HOST, compiled from the functions the kernels use:
+ * count, run-on steps, final zp = (zp_r, zp_i) 2^zp_t, D and e, the normal, nu (through the host's logarithms), and the steps
+ * executed in the count loop (a skip is one).  No ctx, no device.
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_xview_launch refuses for the view, the orbit and mrd under the same
+ * flags; MBK_DEEP_BLA, in the count calls' words; any other flag bit than MBK_DEEP_XBLA; a NULL normal, spec, palette or
+ * output pointer; a misaligned d_normal or d_rgba; a light or a height outside the ranges of "Relief shading".
+ *
+ * Out of scope: adaptive supersampling of relief renders; Julia views; stored chunks; sharding and slot forms.
+ */
+int mbk_deep_xview_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                 uint32_t flags, int32_t *d_counts, double *d_normal, double *d_smooth, double *d_rel,
+                                 void *hip_stream);
+int mbk_deep_xview_compute_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                  uint32_t flags, int32_t *h_counts, double *h_normal, double *h_smooth, double *h_rel,
+                                  mbk_stats *stats);
+int mbk_deep_xview_relief_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                        uint32_t flags, const mbk_relief_spec *spec, uint8_t *d_rgba, void *hip_stream);
+int mbk_deep_xview_relief_render_compute(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t mrd,
+                                         uint32_t flags, const mbk_relief_spec *spec, uint8_t *h_rgba, mbk_stats *stats);
+int mbk_deep_xview_normal_host(const mbk_deep_orbit *orbit, const mbk_deep_xview *view, uint32_t col, uint32_t row,
+                               uint32_t mrd, uint32_t flags, int32_t *count, int32_t *extra, double *zp_r, double *zp_i,
+                               int32_t *zp_t, double *D_r, double *D_i, int32_t *e, double normal[2], double *nu,
+                               uint64_t *steps_executed);
 
 /* Codec codes of DataChunkSerializer.cs (Raw :20, RLE :54). */
 #define MBK_CODEC_RAW 0x00u
