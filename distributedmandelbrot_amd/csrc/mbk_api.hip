@@ -69,7 +69,10 @@ static const int kOrderRing = 3;
 // stream) can run while the tile kernels of the launches before it still read the others
 struct OrderRing {
     uint32_t *d_order[kOrderRing] = {};
-    uint32_t *d_ctl = nullptr;    // 8 words per list: the units pre-pass' counters (H, V, M | late M, settled H, ticket), zero between launches
+    uint32_t *d_capture = nullptr;   // the list of every launch captured into a graph on this stream (acquire_order_list), as large as the
+                                     // others: written and read on the caller's stream alone, never handed to the pre-pass stream
+    uint32_t *d_ctl = nullptr;    // 8 words per list (the ring's, then the capture list's): the units pre-pass' counters (H, V, M | late M,
+                                  // settled H, ticket), zero between launches
     bool ctl_dirty = true;        // the counters must be cleared (on the pre-pass' own stream) before the next pre-pass: never used
                                   // yet, or a launch failed after its pre-pass was enqueued and may have left a ticket behind
     size_t order_cap = 0;         // regions
@@ -88,6 +91,8 @@ struct OrderRing {
             d_order[k] = nullptr;
             done_valid[k] = false;
         }
+        if (d_capture) (void)hipFree(d_capture);
+        d_capture = nullptr;
         order_cap = 0;
     }
     void drop_aux()   // the stream and the events that tie it to the caller's
@@ -258,6 +263,7 @@ struct mbk_ctx {
         uint32_t xoff[mbk::kBlaMaxLevels];
     };
     std::vector<DeepCopy> deep;
+    bool capturing = false;          // the stream of the launch form being served is capturing a graph (CaptureScope)
     hipDeviceProp_t prop;
     std::string err;
 };
@@ -283,6 +289,57 @@ static int fail(mbk_ctx *ctx, int code, const std::string &msg)
                         std::string(#call) + ": " + hipGetErrorString(e_));                 \
         }                                                                                   \
     } while (0)
+
+// ---- graph capture (mbk.h "Graph capture"; DESIGN.md "Graph capture") --------------------------------------------------------
+
+// Is `stream` capturing a graph?  One host call that enqueues nothing.  A status the runtime will not give (the legacy stream
+// beside another stream's capture) counts as "no": that call is then no part of any graph.
+static bool stream_capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// Every *_launch form opens one of these on the caller's stream before it acquires or enqueues anything: while it lives,
+// ctx->capturing tells the steps below -- which do not all see the stream -- that nothing may synchronise, allocate, free or
+// copy synchronously, and that everything goes to the caller's stream.  The synchronous and the slot forms open none: their
+// streams are the ctx' own and never capture.
+struct CaptureScope {
+    mbk_ctx *ctx;
+    CaptureScope(mbk_ctx *c, hipStream_t stream) : ctx(c) { ctx->capturing = stream_capturing(stream); }
+    ~CaptureScope() { ctx->capturing = false; }
+    CaptureScope(const CaptureScope &) = delete;
+    CaptureScope &operator=(const CaptureScope &) = delete;
+};
+
+// The refusal of a call that cannot be served inside a capture.  The places that return it do so before they allocate or
+// enqueue anything, so the caller's capture stays valid.
+static int refuse_capture(mbk_ctx *ctx, const char *why)
+{
+    return fail(ctx, MBK_ERR_INVALID, std::string("graph capture: ") + why + " (mbk.h \"Graph capture\")");
+}
+
+// Control words inside the stream's scratch (a dispatch list's cursors, the length of the adaptive list, the density band
+// counters) put to zero ahead of the kernels that count in them.  Outside a capture a hipMemsetAsync, as ever.  Inside a capture
+// a one-workgroup kernel: the second replay of a graph that held the 12-byte memset of a list's cursors ran classify_blocks_kernel
+// on the totals the first replay had left -- its light entries, filled in from the back of the list, then leave the list, which
+// is a memory fault (tests/test_gpu_graph.py, the ordered "asm" case; profiles/graph_capture/README.md) -- so as far as that
+// evidence goes a memset node of a few bytes in the middle of an allocation is not something a replay can rest on, while kernel
+// nodes replay in order (the units pre-pass, whose kernel restores its own counters, had passed every replay).
+static int clear_words(mbk_ctx *ctx, uint32_t *words, uint32_t n, hipStream_t stream)
+{
+    if (!ctx->capturing) {
+        MBK_HIP(ctx, hipMemsetAsync(words, 0, (size_t)n * sizeof(uint32_t), stream));
+        return MBK_OK;
+    }
+    hipLaunchKernelGGL(mbk::clear_words_kernel, dim3(1), dim3(64), 0, stream, words, n);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
 
 // ---- host arithmetic (individually rounded; `volatile` keeps the compiler honest at any -O) ----
 
@@ -460,6 +517,7 @@ static int get_scratch(mbk_ctx *ctx, hipStream_t stream, StreamScratch **out)
             *out = &sc;
             return MBK_OK;
         }
+    if (ctx->capturing) return refuse_capture(ctx, "the first call of this ctx on a stream allocates its scratch: make the same call once outside the capture");
     if (ctx->scratch.size() >= kMaxStreamScratch) {
         MBK_HIP(ctx, hipDeviceSynchronize());
         for (StreamScratch &sc : ctx->scratch) free_scratch(sc);
@@ -618,14 +676,47 @@ struct OrderList {
     ~OrderList() { if (sc && !whole) sc->ring.ctl_dirty = true; }
 };
 
+// What keeps a captured launch from taking the capture list of `ring`, or NULL.
+static const char *capture_list_missing(const OrderRing &ring, uint32_t nblocks, bool units)
+{
+    if (nblocks > ring.order_cap || !ring.d_capture)
+        return "the stream's dispatch lists must grow for this window: make the same call, or a larger one, once outside the capture";
+    if (units && (!ring.d_ctl || ring.ctl_dirty))
+        return "the units pre-pass' counters must be cleared behind a drain: make the same call once outside the capture";
+    return nullptr;
+}
+
+static bool capture_list_ready(const mbk_ctx *ctx, hipStream_t stream, uint32_t nblocks, bool units)
+{
+    for (const StreamScratch &sc : ctx->scratch)
+        if (sc.stream == stream) return capture_list_missing(sc.ring, nblocks, units) == nullptr;
+    return false;
+}
+
 // Step 2, the ring of `stream`: brings it into the state MBK_OPT_PREPASS_OVERLAP asks for (a change drains both streams), grows
 // the lists to `nblocks` entries, takes the next one in turn and makes the pre-pass stream wait for that list's last reader.
-static int acquire_order_list(mbk_ctx *ctx, hipStream_t stream, uint32_t nblocks, OrderList *out)
+//
+// While `stream` captures a graph (ctx->capturing) none of that happens.  The launch takes the ring's capture list, which no
+// launch outside a capture ever takes, and its pre-pass goes to the caller's stream as under MBK_OPT_PREPASS_OVERLAP = 0, whatever
+// the option says: the graph is one chain, and a replay writes and reads a list that only work ordered on this stream touches --
+// a list of the ring would by then belong to a later launch, whose pre-pass on the auxiliary stream waits for the ring's own
+// readers only.  The ring's turn, its mode, its auxiliary stream and its events stay as they are.  A list that would have to
+// grow, or (units: the units pre-pass) control words that would have to be allocated or cleared behind a drain, refuse the launch.
+static int acquire_order_list(mbk_ctx *ctx, hipStream_t stream, uint32_t nblocks, bool units, OrderList *out)
 {
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
     OrderRing &ring = sc->ring;
+    if (ctx->capturing) {
+        if (const char *why = capture_list_missing(ring, nblocks, units)) return refuse_capture(ctx, why);
+        out->k = (unsigned)kOrderRing;
+        out->list = ring.d_capture;
+        out->pre = stream;
+        out->overlap = false;
+        out->sc = sc;
+        return MBK_OK;
+    }
     // MBK_OPT_PREPASS_OVERLAP: 0 the pre-pass runs on the caller's stream, in order (one queue, no event: +4..5 us per cfg2
     // launch back to back, profiles/r06/prepass_modes_ab.txt); 1 / 2 on an auxiliary stream (2: at the highest priority), tied
     // to the tile kernel by events.  (Round 6 also tried it as an ANY-ORDER launch on the caller's stream -- an AQL packet
@@ -675,6 +766,7 @@ static int acquire_order_list(mbk_ctx *ctx, hipStream_t stream, uint32_t nblocks
         // | its settled H entries (mbk_units.h: units_settled_base)
         for (int k = 0; k < kOrderRing; ++k)
             MBK_HIP(ctx, hipMalloc((void **)&ring.d_order[k], mbk::units_list_words(nblocks) * sizeof(uint32_t)));
+        MBK_HIP(ctx, hipMalloc((void **)&ring.d_capture, mbk::units_list_words(nblocks) * sizeof(uint32_t)));
         ring.order_cap = nblocks;
     }
     // Pre-pass of THIS launch on the aux stream: it depends on the window only, not on anything the caller's
@@ -705,8 +797,9 @@ static int enqueue_units_prepass(mbk_ctx *ctx, TileArgs &a, const BlockLaunchPla
     const double settle_thr = hs ? std::pow(10.0, -(double)hs) : 0.0;
     // the pre-pass' six counters live apart from the lists (whose layout moves with the window's size), are zeroed once
     // here and put back to zero by the pre-pass itself (mbk_units.h: classify_units_kernel)
+    // (inside a capture neither branch is taken: acquire_order_list has refused the launch that would need one)
     if (!ring.d_ctl) {
-        MBK_HIP(ctx, hipMalloc((void **)&ring.d_ctl, (size_t)kOrderRing * 8u * sizeof(uint32_t)));
+        MBK_HIP(ctx, hipMalloc((void **)&ring.d_ctl, (size_t)(kOrderRing + 1) * 8u * sizeof(uint32_t)));
         ring.ctl_dirty = true;
     }
     if (ring.ctl_dirty) {
@@ -715,7 +808,7 @@ static int enqueue_units_prepass(mbk_ctx *ctx, TileArgs &a, const BlockLaunchPla
         // still be running there and on the caller's stream; also after a failed launch (OrderList)
         if (ring.aux) MBK_HIP(ctx, hipStreamSynchronize(ring.aux));
         MBK_HIP(ctx, hipStreamSynchronize(stream));
-        MBK_HIP(ctx, hipMemsetAsync(ring.d_ctl, 0, (size_t)kOrderRing * 8u * sizeof(uint32_t), ol.pre));
+        MBK_HIP(ctx, hipMemsetAsync(ring.d_ctl, 0, (size_t)(kOrderRing + 1) * 8u * sizeof(uint32_t), ol.pre));
         ring.ctl_dirty = false;
     }
     uint32_t *ctl = ring.d_ctl + 8u * ol.k;
@@ -725,7 +818,9 @@ static int enqueue_units_prepass(mbk_ctx *ctx, TileArgs &a, const BlockLaunchPla
     // the stamps -- when an XCD dealt its last ids -- do not see; following them cost 0.3 % there, xcd_balance_ab.txt)
     // (and to a whole chip only: the stamps' "workgroup id mod 8 = XCD" is the dispatch order of 8 XCDs x 32 CUs -- a
     // partitioned device, CPX / DPX modes, deals differently: ADVICE r4)
-    const uint32_t balance = ctx->opt[MBK_OPT_XCD_BALANCE] == 1u && (p.cyc || ctx->prop.multiProcessorCount != 256)
+    // (and never inside a capture: the stamp slot and its tag belong to one enqueue -- a replay would write stale tags into the
+    // pinned slots that xcd_shares_update reads -- so a captured launch deals evenly and leaves the shares' bookkeeping alone)
+    const uint32_t balance = ctx->opt[MBK_OPT_XCD_BALANCE] == 1u && (p.cyc || ctx->prop.multiProcessorCount != 256 || ctx->capturing)
                                  ? 0u : ctx->opt[MBK_OPT_XCD_BALANCE];
     static const double kUneven[8] = {0.110, 0.140, 0.125, 0.120, 0.130, 0.125, 0.115, 0.135};
     if (balance == 1u && !sc->h_stamps) {
@@ -736,8 +831,9 @@ static int enqueue_units_prepass(mbk_ctx *ctx, TileArgs &a, const BlockLaunchPla
     if (balance == 1u) xcd_shares_update(ctx, *sc);
     mbk::XcdShares w;
     double f[8];
-    const uint32_t seq = ++sc->xcd_issued;
-    StreamScratch::SharesUsed &used = sc->xcd_ring[seq % kShareRing];
+    StreamScratch::SharesUsed captured;   // (a captured launch takes no number: it is no launch the stamps could tell of)
+    const uint32_t seq = ctx->capturing ? sc->xcd_issued : ++sc->xcd_issued;
+    StreamScratch::SharesUsed &used = ctx->capturing ? captured : sc->xcd_ring[seq % kShareRing];
     used.seq = seq;
     used.switches = ctx->stream_switches;
     for (uint32_t x = 0; x < 8u; ++x) {
@@ -761,7 +857,8 @@ static int enqueue_classify_prepass(mbk_ctx *ctx, const TileArgs &a, const Block
 {
     const uint32_t nblocks = p.grid.x;
     uint32_t *cursors = ol.list + nblocks;   // right behind the list: the tile kernel finds them at order[gridDim.x]
-    MBK_HIP(ctx, hipMemsetAsync(cursors, 0, 3 * sizeof(uint32_t), ol.pre));
+    const int rc = clear_words(ctx, cursors, 3u, ol.pre);
+    if (rc != MBK_OK) return rc;
     // the middle class: MBK_OPT_PROBE_MID's (dispatched between heavy and light) or, without one, MBK_OPT_M_LATE's
     // (order 3 only: boundary blocks whose centre escapes at step >= m_late, dispatched first)
     *mid_first = p.order_mode == 3 && ctx->opt[MBK_OPT_PROBE_MID] > p.probe_steps && ctx->opt[MBK_OPT_M_LATE] >= 2u &&
@@ -926,12 +1023,16 @@ static int enqueue_spill_second_pass(mbk_ctx *ctx, const TileArgs &a, const Spil
 
 // Launch the one-wave-per-block kernels ("asm" / "group", fp64 or fp32) for the window described by `a`
 // (a.col0/row0/ncols/nrows, output at a.out_*), optionally behind the heavy-first classify pre-pass: the steps above, in order.
-static int launch_blocks(mbk_ctx *ctx, TileArgs a, uint32_t kernel, bool safe, bool f32, hipStream_t stream, FuseStats *fuse = nullptr)
+// list_optional (inside a capture only; launch_tile: the default selector in place of the two-pass "scan"): where the capture
+// list is not there for the taking the launch goes in image order instead of being refused.
+static int launch_blocks(mbk_ctx *ctx, TileArgs a, uint32_t kernel, bool safe, bool f32, hipStream_t stream, FuseStats *fuse = nullptr,
+                         bool list_optional = false)
 {
-    const BlockLaunchPlan p = block_launch_plan(ctx, a, kernel, safe, f32);
+    BlockLaunchPlan p = block_launch_plan(ctx, a, kernel, safe, f32);
+    if (p.ordered && list_optional && ctx->capturing && !capture_list_ready(ctx, stream, p.grid.x, p.units)) p.ordered = p.units = false;
     OrderList ol;   // (once it holds a list, a failing return leaves the ring marked: ctl_dirty)
     if (p.ordered) {
-        int rc = acquire_order_list(ctx, stream, p.grid.x, &ol);
+        int rc = acquire_order_list(ctx, stream, p.grid.x, p.units, &ol);
         if (rc != MBK_OK) return rc;
         OrderRing &ring = ol.sc->ring;
         bool mid_first = false;
@@ -946,7 +1047,8 @@ static int launch_blocks(mbk_ctx *ctx, TileArgs a, uint32_t kernel, bool safe, b
         a.order_mid = mid_first ? 2u : (ctx->opt[MBK_OPT_PROBE_MID] <= p.probe_steps ? 1u : 0u);
     }
     SpillBuffers *spill = nullptr;
-    if (spill_wanted(ctx, a, p, kernel, safe, f32)) {
+    // (not inside a capture: the buffers may have to grow behind a drain, and every kernel stores the same results)
+    if (!ctx->capturing && spill_wanted(ctx, a, p, kernel, safe, f32)) {
         const int rc = acquire_spill(ctx, ol.sc, stream, a, p.grid.x, &spill);
         if (rc != MBK_OK) return rc;
     }
@@ -1027,6 +1129,7 @@ static void set_window_facts(TileArgs &a, bool f32, bool cyc, uint32_t sure_opti
 // Falls back to "group" for everything the narrow persistent kernel excludes (see mbk_persist.h).
 static int launch_refill(mbk_ctx *ctx, const TileArgs &a, bool safe, hipStream_t stream)
 {
+    if (ctx->capturing) return refuse_capture(ctx, "MBK_KERNEL_REFILL is not served inside a capture: take the default selector, group or asm");
     const bool eligible = !safe && a.mrd >= 2 && a.counts != nullptr && !a.re.step_is_zero &&
                           !a.im.step_is_zero && !window_may_touch_ring(a, 1e-6);
     // interior = whole 8x8 blocks that do not contain the last sample of either axis
@@ -1157,6 +1260,8 @@ static ScanKernel pick_todo_kernel(bool cyc) { return cyc ? mbk::tile_todo_kerne
 // todo lists (`qcap` ids each) and the size of pass 2, into `s`.
 static int acquire_scan_lists(mbk_ctx *ctx, hipStream_t stream, uint32_t qcap, double probe_share, mbk::ScanArgs &s, StreamScratch **out)
 {
+    // (launch_tile sends no captured launch here: the sets alternate per enqueue, and the hint below is read at enqueue time)
+    if (ctx->capturing) return refuse_capture(ctx, "the two-pass form of MBK_KERNEL_SCAN is not served inside a capture");
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, stream, &sc);
     if (rc != MBK_OK) return rc;
@@ -1312,7 +1417,7 @@ static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t f
     if (flags & MBK_DEEP_BLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_BLA is a flag of the deep view calls");
     if (flags & MBK_DEEP_XBLA) return fail(ctx, MBK_ERR_INVALID, "MBK_DEEP_XBLA is a flag of the extended-range deep view calls");
     if (fuse) fuse->fused = false;
-    if (stream != ctx->last_tile_stream) {
+    if (!ctx->capturing && stream != ctx->last_tile_stream) {   // (a capture runs nothing: no launch the shares could have felt)
         ctx->last_tile_stream = stream;
         ++ctx->stream_switches;
     }
@@ -1362,12 +1467,23 @@ static int launch_tile(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t f
             // by its 0.27 ns per workgroup and its stores, and "scan" wins (all-exterior tile: 29 us against 71).
             // Launches under 16 k blocks take "group", which for them is a single kernel in image order (cfg1: 20
             // us, scan 24).  heavy_share = 0 forces "group", 65536 forces "scan".
+            // Inside a capture (mbk.h "Graph capture") the two-pass form of "scan" is never taken: its two cursor sets alternate
+            // per ENQUEUE -- pass 1 of launch L clears the set of launch L + 1 -- so a capture, which enqueues without running,
+            // would leave the next launch a set nobody cleared, and a replay would append behind its own tails; the size of
+            // its pass 2 comes from a hint the host reads at enqueue time.  The selector "scan" is refused there, and the
+            // default takes "group" where it would take the two-pass form (every selector stores the same results) -- behind a
+            // dispatch list if the stream's lists are large enough, in image order otherwise: the warm call, which took
+            // "scan", was no occasion to grow them.  The finish-in-place form (one kernel, no scratch) stays the default's.
+            if (ctx->capturing && kernel == MBK_KERNEL_SCAN)
+                return refuse_capture(ctx, "MBK_KERNEL_SCAN is not served inside a capture: take the default selector, group or asm");
             if (kernel == MBK_KERNEL_DEFAULT && (uint64_t)((a.ncols + 7u) / 8u) * ((a.nrows + 7u) / 8u) < 16384u)
                 return launch_blocks(ctx, a, MBK_KERNEL_GROUP, safe, f32, stream);
             const double share = window_heavy_share(ctx, a);
             if (kernel == MBK_KERNEL_DEFAULT &&
                 (share * 65536.0 > (double)ctx->opt[MBK_OPT_HEAVY_SHARE] || ctx->opt[MBK_OPT_HEAVY_SHARE] == 0u))
                 return launch_blocks(ctx, a, MBK_KERNEL_GROUP, safe, f32, stream, fuse);
+            if (ctx->capturing && !(share == 0.0 && ctx->opt[MBK_OPT_SCAN_INLINE] != 0u))
+                return launch_blocks(ctx, a, MBK_KERNEL_GROUP, safe, f32, stream, nullptr, true);
             return f32 ? launch_scan_t<float>(ctx, a, safe, stream, share, fuse) : launch_scan_t<double>(ctx, a, safe, stream, share, fuse);
         }
         case MBK_KERNEL_GROUP:
@@ -1396,6 +1512,7 @@ template <typename T>
 static int grow(mbk_ctx *ctx, T *&p, size_t &cap, size_t need, size_t bytes)
 {
     if (need <= cap) return MBK_OK;
+    if (ctx->capturing) return refuse_capture(ctx, "the stream's scratch must grow for this call: make the same call, or a larger one, once outside the capture");
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
@@ -2051,6 +2168,7 @@ int mbk_view_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t f
 {
     if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return launch_tile(ctx, view, mrd, flags, d_counts, d_bytes, (hipStream_t)hip_stream);
 }
 
@@ -2276,6 +2394,7 @@ int mbk_view_launch_smooth(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uin
     if (!ctx || !d_smooth) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t f = (flags & (MBK_KERNEL_MASK | MBK_PRECISION_F32 | MBK_DEEP_XBLA)) | (d_counts ? MBK_WANT_COUNTS : 0u);
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return launch_tile(ctx, view, mrd, f, d_counts, nullptr, (hipStream_t)hip_stream, d_smooth);
 }
 
@@ -2411,6 +2530,7 @@ int mbk_view_launch_normal(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uin
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_normal & 7u) return fail(ctx, MBK_ERR_INVALID, "d_normal must be 8-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return launch_normal(ctx, view, mrd, flags, safe, d_counts, d_normal, d_distance, (hipStream_t)hip_stream);
 }
 
@@ -2490,6 +2610,7 @@ int mbk_view_interior_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, u
     int rc = interior_check(ctx, view, mrd, flags, &safe);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return launch_interior(ctx, view, mrd, flags, safe, d_counts, d_period, d_distance, (hipStream_t)hip_stream);
 }
 
@@ -2762,6 +2883,7 @@ int mbk_reduce_counts(mbk_ctx *ctx, const int32_t *d_counts, uint64_t n, uint32_
     if (!ctx || !d_counts || !stats) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)hip_stream;
+    if (stream_capturing(s)) return refuse_capture(ctx, "mbk_reduce_counts waits for its result and cannot be captured");
     // partial results live in the STREAM's scratch (not in slot 0's: a tile in flight on slot 0 reduces into those)
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, s, &sc);
@@ -2853,6 +2975,7 @@ static int deep_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, mbk_ctx::DeepCop
             *out = &c;
             return MBK_OK;
         }
+    if (ctx->capturing) return refuse_capture(ctx, "the reference orbit is not on the device, and its upload is synchronous: make the same call once outside the capture");
     if (ctx->deep.size() >= kMaxDeepCopies) {
         MBK_HIP(ctx, hipDeviceSynchronize());
         for (mbk_ctx::DeepCopy &c : ctx->deep) free_deep_copy(c);
@@ -2942,6 +3065,8 @@ static int bla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, double dcmax, con
         *table = b;
         return MBK_OK;
     }
+    if (ctx->capturing)
+        return refuse_capture(ctx, "the bilinear-approximation table of this view's dcmax is not on the device, and it is built and uploaded synchronously: make the same call once outside the capture");
     for (mbk_ctx::BlaSlot &x : c->bla) {
         if (&x == keep) continue;
         if (!b || (b->has && (!x.has || x.used < b->used))) b = &x;
@@ -3076,6 +3201,8 @@ static int wide_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideE
     int rc = deep_copy(ctx, orbit, &c);
     if (rc != MBK_OK) return rc;
     if (!c->d_wide) {
+        if (ctx->capturing)
+            return refuse_capture(ctx, "the wide reference orbit is not on the device, and its upload is synchronous: make the same call once outside the capture");
         const size_t bytes = orbit->o.wide.size() * sizeof(mbk::WideEntry);
         mbk::WideEntry *d = nullptr;
         MBK_HIP(ctx, hipMalloc((void **)&d, bytes));
@@ -3160,6 +3287,8 @@ static int xbla_copy(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const mbk::WideR
         *table = b;
         return MBK_OK;
     }
+    if (ctx->capturing)
+        return refuse_capture(ctx, "the wide bilinear-approximation table of this view's dcmax is not on the device, and it is built and uploaded synchronously: make the same call once outside the capture");
     for (mbk_ctx::XblaSlot &x : c->xbla) {
         if (&x == keep) continue;
         if (!b || (b->has && (!x.has || x.used < b->used))) b = &x;
@@ -3361,6 +3490,7 @@ int mbk_deep_view_launch_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, cons
     int rc = deep_nucleus_check(ctx, orbit, view, mrd, flags, d_period, d_delta);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return launch_deep_nucleus(ctx, orbit, view, mrd, d_counts, d_period, d_delta, (hipStream_t)hip_stream);
 }
 
@@ -3475,6 +3605,7 @@ int mbk_deep_xview_launch_nucleus(mbk_ctx *ctx, const mbk_deep_orbit *orbit, con
     int rc = wide_nucleus_check(ctx, orbit, view, mrd, flags, d_period, d_delta);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return launch_deep_wide_nucleus(ctx, orbit, view, mrd, d_counts, d_period, d_delta, (hipStream_t)hip_stream);
 }
 
@@ -3876,6 +4007,7 @@ static int target_view_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint3
     rc = check_wanted(ctx, flags, d_counts, d_bytes);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return target_launch(ctx, t, mrd, flags, Outputs{wc ? d_counts : nullptr, wb ? d_bytes : nullptr, d_smooth, false}, (hipStream_t)hip_stream);
 }
 
@@ -4065,6 +4197,8 @@ static int stream_palette(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, c
 {
     std::vector<uint32_t> words(len);
     for (uint32_t k = 0; k < len; ++k) words[k] = pack_rgba(palette + 4u * (size_t)k);
+    if (ctx->capturing && (!sc->d_palette || words != sc->palette))
+        return refuse_capture(ctx, "the palette differs from the one on the device, and its upload waits for the stream: make the same call once outside the capture");
     if (!sc->d_palette) MBK_HIP(ctx, hipMalloc((void **)&sc->d_palette, 65536u * sizeof(uint32_t)));
     if (words != sc->palette) {
         MBK_HIP(ctx, hipStreamSynchronize(stream));
@@ -4091,6 +4225,8 @@ static int validate_lut(mbk_ctx *ctx, const double *h_lut, uint32_t lut_len, uin
 static int stream_lut(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const double *h_lut, uint32_t lut_len)
 {
     if (sc->lut.size() == lut_len && std::memcmp(sc->lut.data(), h_lut, (size_t)lut_len * sizeof(double)) == 0) return MBK_OK;
+    if (ctx->capturing)
+        return refuse_capture(ctx, "the equalisation table differs from the one on the device, and its upload waits for the stream: make the same call once outside the capture");
     MBK_HIP(ctx, hipStreamSynchronize(stream));
     sc->lut.clear();
     int rc = grow(ctx, sc->d_lut, sc->lut_cap, lut_len, (size_t)lut_len * sizeof(double));
@@ -4261,6 +4397,7 @@ static int render_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return render_run(ctx, t, mrd, flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, h_lut, lut_len);
 }
 
@@ -4701,7 +4838,8 @@ static int adaptive_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t fl
         const uint32_t hc = ox + nc + (x0 + nc < t.g.width ? 1u : 0u), hr = oy + nr + (y0 + nr < t.g.height ? 1u : 0u);
         int rc = target_launch(ctx, target_samples(t, 1u, x0 - ox, y0 - oy, hc, hr), mrd, flags, samples, stream);
         if (rc != MBK_OK) return rc;
-        MBK_HIP(ctx, hipMemsetAsync(d_words, 0, 2u * sizeof(uint32_t), stream));
+        rc = clear_words(ctx, d_words, 2u, stream);
+        if (rc != MBK_OK) return rc;
         // 2. classify: base image, mask, list
         mbk::AdaptiveClassifyArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -4753,6 +4891,7 @@ static int adaptive_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     AdaptiveFine fine;
     rc = adaptive_tables(ctx, t, flags, spec->supersample, threshold, &fine);
     if (rc != MBK_OK) return rc;
@@ -4906,6 +5045,7 @@ int mbk_view_interior_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t
     InteriorColours colours;
     const mbk_render_spec r = interior_render_spec(spec, &colours);
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, &colours);
 }
 
@@ -4993,6 +5133,7 @@ int mbk_view_relief_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t m
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, &light);
 }
 
@@ -5052,6 +5193,7 @@ int mbk_deep_view_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, const
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_normal & 7u) return fail(ctx, MBK_ERR_INVALID, "d_normal must be 8-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return target_launch(ctx, t, mrd, flags, Outputs{d_counts, nullptr, d_smooth, false, nullptr, false, d_normal, d_rel}, (hipStream_t)hip_stream);
 }
 
@@ -5085,6 +5227,7 @@ int mbk_deep_view_relief_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbit
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, &light);
 }
 
@@ -5163,6 +5306,7 @@ int mbk_deep_xview_launch_normal(mbk_ctx *ctx, const mbk_deep_orbit *orbit, cons
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_normal & 7u) return fail(ctx, MBK_ERR_INVALID, "d_normal must be 8-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return target_launch(ctx, t, mrd, flags, Outputs{d_counts, nullptr, d_smooth, false, nullptr, false, d_normal, d_rel}, (hipStream_t)hip_stream);
 }
 
@@ -5196,6 +5340,7 @@ int mbk_deep_xview_relief_render_launch(mbk_ctx *ctx, const mbk_deep_orbit *orbi
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, &light);
 }
 
@@ -5329,6 +5474,7 @@ static int distance_values_launch(mbk_ctx *ctx, const DistanceRule &rule, const 
     int rc = distance_values_check(ctx, rule, t, mrd, flags, d_values);
     if (rc != MBK_OK) return rc;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return target_launch(ctx, t, mrd, flags | rule.launch_flags, Outputs{d_counts, nullptr, d_values, true}, (hipStream_t)hip_stream);
 }
 
@@ -5366,6 +5512,7 @@ static int distance_render_launch(mbk_ctx *ctx, const DistanceRule &rule, const 
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return render_run(ctx, t, mrd, flags | rule.launch_flags, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr);
 }
 
@@ -5668,6 +5815,7 @@ static int hist_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t fla
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_hist & 7u) return fail(ctx, MBK_ERR_INVALID, "d_hist must be 8-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return hist_run(ctx, t, mrd, flags, (unsigned long long *)d_hist, (hipStream_t)hip_stream, nullptr);
 }
 
@@ -5811,6 +5959,8 @@ static int density_run(mbk_ctx *ctx, const mbk_view *v, const mbk::DensityTarget
     const size_t need = mbk::kDensityCompact ? off2 + cap * 4u : cap * 4u;
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
     if (rc != MBK_OK) return rc;
+    if (mbk::kDensityCompact && !sc->d_density_bands && ctx->capturing)
+        return refuse_capture(ctx, "the first density call on this stream allocates its band counters: make the same call once outside the capture");
     if (mbk::kDensityCompact && !sc->d_density_bands)
         MBK_HIP(ctx, hipMalloc((void **)&sc->d_density_bands, 2u * mbk::kDensityBands * sizeof(uint32_t)));
     // (sc may move when a launch below adds a stream's scratch: not used past here)
@@ -5825,7 +5975,10 @@ static int density_run(mbk_ctx *ctx, const mbk_view *v, const mbk::DensityTarget
         sv.nrows = nr;
         int rc = launch_tile(ctx, &sv, mrd, kernel | MBK_WANT_COUNTS, d_counts, nullptr, stream);
         if (rc != MBK_OK) return rc;
-        if (mbk::kDensityCompact) MBK_HIP(ctx, hipMemsetAsync(d_bands, 0, 2u * mbk::kDensityBands * sizeof(uint32_t), stream));
+        if (mbk::kDensityCompact) {
+            rc = clear_words(ctx, d_bands, 2u * mbk::kDensityBands, stream);
+            if (rc != MBK_OK) return rc;
+        }
         mbk::DensityArgs a;
         std::memset(&a, 0, sizeof(a));
         fill_window(a, &sv);
@@ -5853,6 +6006,7 @@ int mbk_view_density_launch(mbk_ctx *ctx, const mbk_view *view, const mbk_densit
     if (rc != MBK_OK) return rc;
     if ((uintptr_t)d_density & 3u) return fail(ctx, MBK_ERR_INVALID, "d_density must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return density_run(ctx, view, dt, mrd, minc, maxc, flags & MBK_KERNEL_MASK, d_density, nullptr, (hipStream_t)hip_stream, nullptr);
 }
 
@@ -5902,6 +6056,7 @@ int mbk_density_max(mbk_ctx *ctx, const uint32_t *d_density, uint64_t n, uint32_
     if (n == 0) return MBK_OK;
     MBK_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = (hipStream_t)hip_stream;
+    if (stream_capturing(s)) return refuse_capture(ctx, "mbk_density_max waits for its result and cannot be captured");
     StreamScratch *sc = nullptr;
     int rc = get_scratch(ctx, s, &sc);
     if (rc != MBK_OK) return rc;
@@ -5984,6 +6139,7 @@ int mbk_density_render_launch(mbk_ctx *ctx, const uint32_t *d_density, uint32_t 
     if (rc != MBK_OK) return rc;
     if (((uintptr_t)d_density & 3u) || ((uintptr_t)d_rgba & 3u)) return fail(ctx, MBK_ERR_INVALID, "d_density and d_rgba must be 4-byte aligned");
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
     return density_render_run(ctx, d_density, width, height, spec, (uint32_t *)d_rgba, (hipStream_t)hip_stream);
 }
 
@@ -6275,6 +6431,8 @@ int mbk_chunk_decode_launch(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size
     const uint32_t why = stream_precheck(h_stream, size, n, &codec, &runs);
     if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    if (stream_capturing((hipStream_t)hip_stream))
+        return refuse_capture(ctx, "mbk_chunk_decode_launch reads its input from host memory at enqueue time and cannot be captured");
     StreamScratch *sc = nullptr;
     const int rc = get_scratch(ctx, (hipStream_t)hip_stream, &sc);
     if (rc != MBK_OK) return rc;
@@ -6294,6 +6452,8 @@ int mbk_chunk_render_launch(mbk_ctx *ctx, const uint8_t *h_stream, uint64_t size
     const uint32_t why = stream_precheck(h_stream, size, MBK_CHUNK_BYTES, &codec, &runs);
     if (why != MBK_STREAM_OK) return fail_stream(ctx, why);
     MBK_HIP(ctx, hipSetDevice(ctx->device));
+    if (stream_capturing((hipStream_t)hip_stream))
+        return refuse_capture(ctx, "mbk_chunk_render_launch reads its input from host memory at enqueue time and cannot be captured");
     return chunk_render_run(ctx, h_stream, size, codec, runs, spec, lk, (uint32_t *)d_rgba, pitch_px, d_status, false, nullptr,
                             nullptr, (hipStream_t)hip_stream);
 }

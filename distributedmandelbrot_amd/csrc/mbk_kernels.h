@@ -606,6 +606,13 @@ __global__ __launch_bounds__(1024) void classify_blocks_kernel(TileArgs p, uint3
     }
 }
 
+// A few control words put to zero by a kernel: what a launch that is being captured into a graph enqueues in place of a
+// hipMemsetAsync of those words (mbk_api.hip: clear_words).  One workgroup.
+__global__ __launch_bounds__(64) void clear_words_kernel(uint32_t *words, uint32_t n)
+{
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) words[k] = 0u;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Reduction over finished results: pixel-iterations, never-escaped pixels, all-zero / all-one byte
 // flags (DataChunk.cs:82,87).  HBM-bound, 4-5 B/pixel read once; not part of the timed hot loop.

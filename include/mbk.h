@@ -160,6 +160,51 @@ int mbk_datachunk_geometry(uint32_t level, uint32_t index_real, uint32_t index_i
 int mbk_view_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
                     int32_t *d_counts, uint8_t *d_bytes, void *hip_stream);
 
+/*
+ * Graph capture.  Every *_launch form of this header that works on DEVICE pointers alone may be called while its stream
+ * captures a graph (hipStreamBeginCapture in any mode, torch.cuda.graph), and the graph may be replayed any number of times:
+ * mbk_view_launch, _launch_smooth, _launch_distance, _launch_normal and mbk_view_interior_launch; the mbk_julia_view_*, the
+ * mbk_deep_view_* and the mbk_deep_xview_* launches (counts, smooth values, distance with and without a table, normals,
+ * nucleus); every *_render_launch, *_render_equalized_launch, *_render_adaptive_launch, *_relief_render_launch and
+ * *_distance*_render_launch, mbk_view_interior_render_launch and mbk_density_render_launch; the *_histogram_launch calls,
+ * mbk_counts_histogram and mbk_view_density_launch (these three ADD into the caller's table: n replays add n times).
+ * tests/test_gpu_graph.py captures and replays each of them; DESIGN.md "Graph capture" has what each enqueues.
+ *
+ * Inside a capture a call asks the stream for its status once (hipStreamIsCapturing) and then
+ *   - enqueues everything on the caller's stream, in order: the graph is one chain without branches.  The dispatch-order
+ *     pre-pass runs as under MBK_OPT_PREPASS_OVERLAP = 0 whatever the option says, into a list that only captured launches of
+ *     this stream use; the ctx' auxiliary stream, its events and the option's bookkeeping are not touched;
+ *   - takes MBK_OPT_XCD_BALANCE = 1 for 0 (the time stamps belong to one enqueue) and runs without the SPILL second pass;
+ *   - serves MBK_KERNEL_DEFAULT at every window size -- with "group" where it would take the two-pass form of "scan" outside a
+ *     capture -- and MBK_KERNEL_GROUP, _ASM and _SIMPLE as always.  Every selector stores the same counts, bytes and values, so
+ *     a replay stores what the call outside the capture stores, bit for bit;
+ *   - never synchronises, allocates, frees, copies synchronously or builds a table.  A call that would have to returns
+ *     MBK_ERR_INVALID with a message that begins "graph capture:" BEFORE it has allocated or enqueued anything: the caller's
+ *     capture stays valid, nothing is written, and the same call outside a capture succeeds.
+ *
+ * The warm-up rule.  What a captured call needs must already be there: make THE SAME CALL once outside a capture, on the same
+ * stream of the same ctx, with the same palette (and equalisation table), the same orbit and flags, and the same view and window
+ * or larger ones.  Refused inside a capture, each in its own words: the first call of a ctx on a stream; a window, a band or a
+ * view for which the stream's scratch (dispatch lists, count, render and density scratch) would have to grow; a palette or an
+ * equalisation table that differs from the one the stream's last render uploaded; an orbit whose copy (extended-range views: whose
+ * wide table) is not on the device; an MBK_DEEP_BLA / MBK_DEEP_XBLA view whose dcmax has no resident table; an "order 3" launch
+ * whose pre-pass counters were never cleared; MBK_KERNEL_SCAN and MBK_KERNEL_REFILL (their cursors and queues alternate or
+ * are sized per enqueue).  Never capturable, and refused in the same way: mbk_chunk_decode_launch and mbk_chunk_render_launch
+ * (they read HOST input at enqueue time), mbk_density_max and mbk_reduce_counts (they wait for their result).  The slot forms
+ * (*_submit, mbk_wait) and every *_compute form run on streams of the ctx' own and take no stream to capture.
+ *
+ * Replays.  A captured launch holds pointers into the scratch of its (ctx, stream) and into the ctx' orbit copies and tables, so
+ *   - a replay must be ORDERED against every other piece of work of the same ctx on the capture stream -- replay it on that
+ *     stream, or behind an event of it -- as two launches on one stream are;
+ *   - the graph stays valid until one of these calls is made on the ctx, and must not be replayed afterwards: a call on the
+ *     capture stream whose scratch need is larger than any before it (the scratch is freed and allocated anew); for a graph
+ *     that holds a render, a render on the capture stream with another palette or equalisation table (the stream's device copy
+ *     is overwritten in place: a replay would colour through the new one); a launch that
+ *     brings a THIRD dcmax to an orbit the graph uses with MBK_DEEP_BLA / MBK_DEEP_XBLA (the table asked for least recently is
+ *     overwritten); the use of a NINTH orbit (all copies are dropped); a launch on a 65th stream (all scratch is dropped);
+ *     mbk_destroy.  The library cannot see a graph and does not check this.
+ */
+
 /* Synchronous: launch + D2H into HOST buffers (either may be NULL according to flags) + stats.
  * Replaces WorkerCUDA.py:82-98 for a generic view. */
 int mbk_view_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
@@ -330,7 +375,8 @@ int mbk_view_submit(mbk_ctx *ctx, int slot, const mbk_view *view, uint32_t mrd, 
  * reused: 32 bytes x (M + 1) per copy (Z and 2Z, which is exact).  A copy lives until mbk_destroy -- or until a ctx holds 8
  * copies and needs a ninth: then the ctx synchronises the device (no launch that may read a copy is left) and frees all of
  * them.  Destroying an orbit does not free its copies.  The first launch of an orbit on a ctx allocates and copies
- * synchronously: launch once before capturing deep launches into a graph.
+ * synchronously: launch once before capturing deep launches into a graph ("Graph capture": inside a capture that first launch
+ * is refused).
  */
 typedef struct mbk_deep_orbit mbk_deep_orbit;
 
@@ -996,7 +1042,8 @@ int mbk_deep_xdistance_skip_host(double A_r, double A_i, int32_t a_e, double B_r
  * banding cannot change the image.  Beside the samples a stream keeps its palette on the device (<= 256 KiB), and _compute
  * keeps one device image of 4 bytes per output pixel of the largest window rendered, per ctx.  The palette is copied during
  * the call; a call whose palette or palette length differs from the previous render's on that stream first waits for the
- * stream (like an orbit's first launch: render once before capturing renders into a graph).
+ * stream (like an orbit's first launch: render once before capturing renders into a graph -- "Graph capture": inside a capture
+ * a render with another palette is refused).
  *
  * Out of scope: handing bands to several GPUs (sharding.py; a band of an image is a window, and windows are bit-identical,
  * so a follow-up can), slot / submit forms, gamma-aware averaging, and fusing the colouring into the escape kernels.
@@ -1130,7 +1177,9 @@ int mbk_render_resolve_host(const mbk_render_spec *spec, uint32_t width, uint32_
  * view, by the sample kernels the flags select; a classify kernel that colours them, writes B, the mask and a list of the
  * refined pixels; a refine kernel that computes the s^2 samples of each listed pixel, one lane per sample.  The length of the
  * list stays on the device: the launch form is asynchronous on the caller's stream, waits for nothing but the palette's
- * change (as every render) and can be captured into a graph after a first call.  Scratch: 12 bytes per base sample of the
+ * change (as every render) and, once the same call has been made outside a capture, can be captured into a graph at every
+ * size of band ("Graph capture" has the rules: the warm-up, what a capture changes in the base pass, how long a graph stays
+ * valid).  Scratch: 12 bytes per base sample of the
  * haloed band plus 4 per pixel of the band for the list, within MBK_RENDER_BAND_BYTES; max_band_rows keeps its meaning.
  * _compute keeps one byte per pixel for the mask behind the ctx' device image.
  *
@@ -1182,7 +1231,8 @@ int mbk_render_adaptive_host(const mbk_render_spec *spec, uint32_t threshold, ui
  * approximation"); a render with the flag acquires the base view's and the fine view's together before it enqueues anything,
  * and neither takes the other's place (equal dcmax: one table).  A first call with a given (orbit, view, s) may therefore build
  * and upload synchronously; after it the launch form performs no host synchronisation for as long as both tables stay
- * resident -- until a launch on the same orbit brings a third dcmax -- and can be captured into a graph.
+ * resident -- until a launch on the same orbit brings a third dcmax -- and can be captured into a graph ("Graph capture": a
+ * graph must not be replayed after that third dcmax either).
  *
  * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_view_render_* refuses for MBK_RENDER_SMOOTH, any other source,
  * threshold > 256, any flag but MBK_DEEP_BLA (MBK_DEEP_XBLA with a message of its own).  d_mask / h_mask may be NULL.
@@ -1225,7 +1275,7 @@ int mbk_deep_view_render_adaptive_compute(mbk_ctx *ctx, const mbk_deep_orbit *or
  * view's together before it enqueues anything, and neither takes the other's place (equal dcmax: one table).  A first call
  * with a given (orbit, view, s) may therefore upload the wide orbit table and build and upload the tables synchronously; after
  * it the launch form performs no host synchronisation for as long as both tables stay resident -- until a launch on the same
- * orbit brings a third dcmax.
+ * orbit brings a third dcmax -- and can be captured into a graph ("Graph capture", as above).
  *
  * MBK_ERR_INVALID, with nothing written: whatever mbk_deep_xview_render_* refuses for MBK_RENDER_SMOOTH, any other source,
  * threshold > 256, any flag but MBK_DEEP_XBLA (MBK_DEEP_BLA in the words of mbk_deep_xview_launch).  d_mask / h_mask may be

@@ -1,0 +1,775 @@
+"""Graph capture and replay of the launch forms (include/mbk.h, "Graph capture"; DESIGN.md, "Graph capture").
+
+Every other GPU test of a *_launch form issues it, synchronises and compares.  That shape cannot see host-side state that a launch
+consumes at enqueue time and a replay does not refresh (which dispatch list, which cursor set, which time-stamp slot), work that
+leaves the caller's stream, or a hidden synchronisation, allocation or synchronous copy on a path the header calls asynchronous.
+A capture in torch's default (global) error mode is invalidated by any such call, and a replay around other launches of the same
+ctx on the same stream stores something else if a launch depended on state of its enqueue.
+
+The pattern of a capturable case (_cycle): the launch once outside a capture into A, which must hold the bits of the synchronous
+form; the same launch captured into a sentinel-filled B with guard elements around it -- nothing may be written, a capture runs
+nothing; a replay: B holds A's bits and the guards are intact; another launch of the family on the same stream (one that takes a
+dispatch list, a cursor set, or the count / render scratch), then a replay: B again, and the interposed launch's own output is
+right; a third replay.  Accumulating calls (histograms, density) add once per replay instead.  A refusal (_refusal) leaves the
+capture valid and writes nothing: the stream is still capturing after it, a launch captured behind it replays correctly, and the
+refused call succeeds outside the capture.  Stale graphs are never replayed: the lifetime rules are documented, not provoked.
+
+Every test opens its own MandelbrotDevice, so that no other test grows the scratch under a live graph, and drops its graphs
+before the context closes.  The shapes are the smallest at which each path exists; a case is milliseconds of GPU work.
+"""
+import gc
+from dataclasses import dataclass
+from typing import Callable
+
+import numpy as np
+import pytest
+
+from distributedmandelbrot_amd import DeepOrbit, DeepView, DensityTarget, MandelbrotDevice, MbkError, Palette, View, WideDeepView
+from distributedmandelbrot_amd.image import equalize_lut
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 64
+SENTINEL = {"i4": -5, "u1": 0xA5, "f8": -77.0, "i8": 0x5A5A5A5A5A5A5A5A, "rgba": 0x5A5A5A5A}
+
+
+class Out:
+    """One device output of n elements with GUARD sentinel elements in front of and behind it."""
+
+    def __init__(self, kind: str, n: int):
+        import torch
+        dtype = {"i4": torch.int32, "u1": torch.uint8, "f8": torch.float64, "i8": torch.int64, "rgba": torch.int32}[kind]
+        self.n, self.sentinel = int(n), SENTINEL[kind]
+        self.t = torch.full((self.n + 2 * GUARD,), self.sentinel, dtype=dtype, device="cuda:0")
+
+    @property
+    def ptr(self) -> int:
+        return self.t[GUARD:].data_ptr()
+
+    def refill(self) -> None:
+        self.t.fill_(self.sentinel)
+
+    def zero_body(self) -> None:
+        self.t[GUARD:GUARD + self.n].zero_()
+
+    def body(self) -> np.ndarray:
+        return self.t.cpu().numpy()[GUARD:GUARD + self.n]
+
+    def guards_intact(self) -> bool:
+        h = self.t.cpu().numpy()
+        return bool((h[:GUARD] == self.sentinel).all() and (h[GUARD + self.n:] == self.sentinel).all())
+
+    def untouched(self) -> bool:
+        return bool((self.t.cpu().numpy() == self.sentinel).all())
+
+
+@dataclass
+class Case:
+    """A launch form on fixed arguments: outs() makes its device outputs, launch(dev, outs, stream) enqueues it on the hipStream_t
+    `stream`, want(dev) gives what the synchronous form stores for the same arguments, by output name."""
+    outs: Callable
+    launch: Callable
+    want: Callable
+    times: int = 1      # as an interposed launch: how often it is enqueued
+
+
+def _bytes(a) -> bytes:
+    return np.ascontiguousarray(a).tobytes()
+
+
+def _check(outs, want, what, factor: int = 1):
+    for name, o in outs.items():
+        assert o.guards_intact(), (what, name, "guard elements written")
+        if name not in want:
+            assert o.untouched(), (what, name)
+            continue
+        w = np.ascontiguousarray(want[name])
+        got = o.body()
+        if factor != 1:
+            w = (w.astype(np.uint64) * np.uint64(factor)).astype(w.dtype)
+        same = _bytes(got) == _bytes(w)
+        assert same, (what, name, int((np.frombuffer(_bytes(got), np.uint8) != np.frombuffer(_bytes(w), np.uint8)).sum()), "bytes differ")
+    assert set(want) <= set(outs), (what, set(want) - set(outs))
+
+
+def _all_untouched(outs) -> bool:
+    return all(o.untouched() for o in outs.values())
+
+
+def _refill(torch, outs) -> None:
+    for o in outs.values():
+        o.refill()
+    torch.cuda.synchronize()
+
+
+def _capture(torch, s, enqueue):
+    """enqueue() captured on the torch stream s in the default (global) error mode, the strictest."""
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        enqueue()
+    torch.cuda.synchronize()
+    return g
+
+
+def _replay(torch, s, g) -> None:
+    with torch.cuda.stream(s):      # ordered against the ctx' other work on the capture stream (mbk.h)
+        g.replay()
+    s.synchronize()
+
+
+def _drop(g) -> None:
+    g.reset()
+    del g
+    gc.collect()
+
+
+def _cycle(dev, case: Case, inter: Case):
+    """Steps 1 to 6 of the module's docstring for an overwriting launch."""
+    import torch
+    s = torch.cuda.Stream(device="cuda:0")
+    want, iwant = case.want(dev), inter.want(dev)
+    A, B, I = case.outs(), case.outs(), inter.outs()
+    torch.cuda.synchronize()
+    case.launch(dev, A, s.cuda_stream)
+    s.synchronize()
+    _check(A, want, "warm call")
+    g = _capture(torch, s, lambda: case.launch(dev, B, s.cuda_stream))
+    try:
+        assert _all_untouched(B), "a capture runs nothing"
+        _replay(torch, s, g)
+        _check(B, want, "replay 1")
+        _refill(torch, B)
+        for _ in range(inter.times):
+            inter.launch(dev, I, s.cuda_stream)
+        _replay(torch, s, g)
+        _check(B, want, "replay 2, behind another launch on the stream")
+        _check(I, iwant, "the interposed launch")
+        _refill(torch, B)
+        _replay(torch, s, g)
+        _check(B, want, "replay 3")
+    finally:
+        _drop(g)
+
+
+def _cycle_accumulate(dev, case: Case, inter: Case):
+    """The same for a call that ADDS into its table: zeroed once, n replays leave n times the single result."""
+    import torch
+    s = torch.cuda.Stream(device="cuda:0")
+    want, iwant = case.want(dev), inter.want(dev)
+    A, B, I = case.outs(), case.outs(), inter.outs()
+    for outs in (A, B, I):
+        for o in outs.values():
+            o.zero_body()
+    torch.cuda.synchronize()
+    case.launch(dev, A, s.cuda_stream)
+    s.synchronize()
+    _check(A, want, "warm call")
+    assert all(np.asarray(w).any() for w in want.values())
+    g = _capture(torch, s, lambda: case.launch(dev, B, s.cuda_stream))
+    try:
+        _check(B, want, "a capture runs nothing", factor=0)
+        _replay(torch, s, g)
+        _check(B, want, "replay 1")
+        for _ in range(inter.times):
+            inter.launch(dev, I, s.cuda_stream)
+        _replay(torch, s, g)
+        _check(B, want, "replay 2, behind another launch on the stream", factor=2)
+        _check(I, iwant, "the interposed launch", factor=inter.times)
+        _replay(torch, s, g)
+        _check(B, want, "replay 3", factor=3)
+    finally:
+        _drop(g)
+
+
+def _refusal(dev, bad: Case, good: Case, text: str):
+    """`bad` inside a capture of the stream s: MBK_ERR_INVALID whose message begins "graph capture:" and holds `text`, the stream
+    still capturing, nothing written; `good`, captured behind it, replays correctly; then `bad` succeeds outside the capture
+    and stores what its synchronous form stores (computed last: that form would bring what the refusal is about).  The warm call
+    of `good` is all the ctx has seen on the stream."""
+    import torch
+    s = torch.cuda.Stream(device="cuda:0")
+    gwant = good.want(dev)
+    R, B, W = bad.outs(), good.outs(), good.outs()
+    torch.cuda.synchronize()
+    good.launch(dev, W, s.cuda_stream)
+    s.synchronize()
+    _check(W, gwant, "warm call")
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        with pytest.raises(MbkError) as err:
+            bad.launch(dev, R, s.cuda_stream)
+        still = torch.cuda.is_current_stream_capturing()
+        good.launch(dev, B, s.cuda_stream)
+    torch.cuda.synchronize()
+    try:
+        assert still, "the refusal ended the capture"
+        assert err.value.status == 1 and "graph capture:" in str(err.value) and text in str(err.value), str(err.value)
+        assert _all_untouched(R) and _all_untouched(B)
+        _replay(torch, s, g)
+        _check(B, gwant, "the launch captured behind the refusal")
+        assert _all_untouched(R)
+    finally:
+        _drop(g)
+    bad.launch(dev, R, s.cuda_stream)
+    s.synchronize()
+    _check(R, bad.want(dev), "the refused call, outside the capture")
+
+
+# ---- plain views --------------------------------------------------------------------------------------------------------------
+
+SEAHORSE = ((-0.765, 0.085, 0.04, 0.04 * 44 / 66, 67, 45), 600)      # neither side a multiple of 8 (tests/test_gpu_relief.py)
+FULL = (-2.0, -1.5, 3.0, 3.0)
+
+
+def _px(v, window):
+    return (window[2] * window[3]) if window is not None else v[4] * v[5]
+
+
+def plain(v, mrd, kernel, outputs, window=None, times=1, precision="f64") -> Case:
+    """mbk_view_launch ("counts", "bytes", "counts+bytes") or mbk_view_launch_smooth ("smooth": nu and counts)."""
+    view, n = View(*v), _px(v, window)
+    if outputs == "smooth":
+        def want(dev):
+            nu, counts, _ = dev.compute_view_smooth(view, mrd, window=window, kernel=kernel)
+            return {"smooth": nu, "counts": counts}
+        return Case(lambda: {"smooth": Out("f8", n), "counts": Out("i4", n)},
+                    lambda dev, o, s: dev.launch_view_smooth(view, mrd, d_smooth=o["smooth"].ptr, d_counts=o["counts"].ptr, stream=s,
+                                                             window=window, kernel=kernel), want, times)
+    wc, wb = "counts" in outputs, "bytes" in outputs
+
+    def want(dev):
+        counts, byts, _ = dev.compute_view(view, mrd, window=window, want_counts=wc, want_bytes=wb, kernel=kernel, precision=precision)
+        return dict(([("counts", counts)] if wc else []) + ([("bytes", byts)] if wb else []))
+    return Case(lambda: dict(([("counts", Out("i4", n))] if wc else []) + ([("bytes", Out("u1", n))] if wb else [])),
+                lambda dev, o, s: dev.launch_view(view, mrd, d_counts=o["counts"].ptr if wc else 0, d_bytes=o["bytes"].ptr if wb else 0,
+                                                  stream=s, window=window, kernel=kernel, precision=precision), want, times)
+
+
+@pytest.mark.parametrize("outputs", ["counts+bytes", "bytes", "smooth"])
+@pytest.mark.parametrize("kernel", ["default", "group", "asm"])
+def test_plain_small_window(kernel, outputs):
+    """Under 16 384 blocks every selector is one kernel on the caller's stream.  Interposed: "scan" on a window of the view, whose
+    two-pass form takes a cursor set of the stream and turns scan_turn."""
+    v, mrd = SEAHORSE
+    with MandelbrotDevice(0) as dev:
+        _cycle(dev, plain(v, mrd, kernel, outputs), plain(v, mrd, "scan", "counts", window=(3, 5, 40, 33), times=2))
+
+
+def _ordered_mrd(dev):
+    return 2 * dev.get_option("probe_steps") + 2
+
+
+ORDERED = [("default", None), ("group", None), ("asm", None), ("group", "units")]
+
+
+@pytest.mark.parametrize("cycle_detect", [0, 1])
+@pytest.mark.parametrize("prepass_overlap", [0, 1, 2])
+@pytest.mark.parametrize("kernel,order", ORDERED, ids=["default", "group", "asm", "units"])
+def test_plain_ordered_path(kernel, order, prepass_overlap, cycle_detect):
+    """1024 x 1024 = exactly 16 384 blocks of 8 x 8 at the smallest mrd that takes a dispatch list: the pre-pass and the tile kernel
+    are two launches tied by a list.  Outside a capture the pre-pass of prepass_overlap 1 / 2 runs on the ctx' auxiliary stream into
+    a list of the stream's ring; a captured launch must carry its pre-pass in the graph, into a list no later launch takes.
+    Interposed: three launches of the same size on a window of a finer view of the same rectangle, which take every list of the
+    ring in turn -- the third replay then runs right behind them.  The expected counts are the same ctx' outside a capture
+    (tests/test_gpu_parity.py holds those to the oracle under every option used here)."""
+    with MandelbrotDevice(0) as dev:
+        dev.set_option("prepass_overlap", prepass_overlap)
+        dev.set_option("cycle_detect", cycle_detect)
+        if order == "units":
+            dev.set_option("order", 3)
+            dev.set_option("units_min_light", 0)
+        assert dev.get_option("order") >= 2
+        mrd = _ordered_mrd(dev)
+        case = plain(FULL + (1024, 1024), mrd, kernel, "counts")
+        inter = plain(FULL + (2048, 2048), mrd, kernel, "counts", window=(512, 512, 1024, 1024), times=3)
+        _cycle(dev, case, inter)
+        assert len(np.unique(case.want(dev)["counts"])) > 10
+
+
+def test_plain_ordered_bytes_and_xcd_balance():
+    """The units kernel with MBK_OPT_XCD_BALANCE = 1 (strict loops: where the option applies) and both outputs: inside a capture
+    the option acts as 0 -- the time-stamp slot and its tag belong to one enqueue -- and the results are those of every deal."""
+    with MandelbrotDevice(0) as dev:
+        for name, value in (("order", 3), ("units_min_light", 0), ("xcd_balance", 1), ("cycle_detect", 0)):
+            dev.set_option(name, value)
+        mrd = _ordered_mrd(dev)
+        _cycle(dev, plain(FULL + (1024, 1024), mrd, "group", "counts+bytes"),
+               plain(FULL + (2048, 2048), mrd, "group", "counts+bytes", window=(512, 512, 1024, 1024), times=3))
+
+
+def test_default_selector_where_it_would_take_scan():
+    """Outside a capture the default selector takes "scan" where the host probe finds little or nothing heavy.  A window wholly
+    outside |c| = 2.5 takes its finish-in-place form -- one kernel, which a capture keeps.  With heavy_share = 65536 ("always
+    scan") the full set takes the two-pass form, which a capture replaces by "group": in image order as long as the stream has no
+    dispatch lists (the warm call had no reason to grow them), behind the capture list once a "group" launch has."""
+    with MandelbrotDevice(0) as dev:
+        outside = (-3.5, 1.0, 1.0, 1.0, 1024, 1024)
+        _cycle(dev, plain(outside, 300, "default", "counts"), plain(outside, 300, "scan", "counts", window=(0, 0, 512, 512)))
+        assert (plain(outside, 300, "default", "counts").want(dev)["counts"] == 1).all()
+    with MandelbrotDevice(0) as dev:
+        dev.set_option("heavy_share", 65536)
+        v = FULL + (1024, 1024)
+        _cycle(dev, plain(v, 300, "default", "counts+bytes"), plain(v, 300, "scan", "counts", window=(0, 0, 512, 512)))
+        _cycle(dev, plain(v, 300, "default", "counts+bytes"), plain(v, 300, "group", "counts", times=3))
+
+
+# ---- two-pass plain calls and Julia views ------------------------------------------------------------------------------------------
+
+RAGGED = (5, 3, 21, 17)
+BLOCKS = ((-0.4, 0.2, 0.6, 0.6, 64, 64), 300)      # whole-interior 8 x 8 blocks and the edge (tests/test_gpu_relief.py)
+INTERIOR = ((-2.0, -1.5, 3.0, 3.0, 61, 45), 600)   # tests/test_gpu_interior.py
+JULIA = ((-1.7, -1.3, 3.4, 2.6, 64, 48), (-0.8, 0.156), 300)
+
+
+def distance(v, mrd, kernel, window=None, with_counts=True) -> Case:
+    view, n = View(*v), _px(v, window)
+
+    def want(dev):
+        de, counts, _ = dev.compute_view_distance(view, mrd, window=window, kernel=kernel)
+        return {"distance": de, "counts": counts} if with_counts else {"distance": de}
+    return Case(lambda: {"distance": Out("f8", n), "counts": Out("i4", n)},
+                lambda dev, o, s: dev.launch_view_distance(view, mrd, d_distance=o["distance"].ptr, d_counts=o["counts"].ptr if with_counts else 0,
+                                                           stream=s, window=window, kernel=kernel), want)
+
+
+def normals(v, mrd, kernel, window=None) -> Case:
+    """NULL d_counts: the counts of the two-pass form live in the stream's scratch."""
+    view, n = View(*v), _px(v, window)
+
+    def want(dev):
+        _, nrm, de, _ = dev.compute_view_normals(view, mrd, window=window, kernel=kernel, want_distance=True)
+        return {"normals": nrm, "distance": de}
+    return Case(lambda: {"normals": Out("f8", 2 * n), "distance": Out("f8", n)},
+                lambda dev, o, s: dev.launch_view_normals(view, mrd, d_normals=o["normals"].ptr, d_distance=o["distance"].ptr, stream=s,
+                                                          window=window, kernel=kernel), want)
+
+
+def interior(v, mrd, kernel, window=None) -> Case:
+    view, n = View(*v), _px(v, window)
+
+    def want(dev):
+        period, de, _, _ = dev.compute_view_interior(view, mrd, window=window, kernel=kernel)
+        return {"period": period, "distance": de}
+    return Case(lambda: {"period": Out("i4", n), "distance": Out("f8", n)},
+                lambda dev, o, s: dev.launch_view_interior(view, mrd, d_period=o["period"].ptr, d_distance=o["distance"].ptr, stream=s,
+                                                           window=window, kernel=kernel), want)
+
+
+def julia(v, c, mrd, kernel, window=None) -> Case:
+    view, n = View(*v), _px(v, window)
+
+    def want(dev):
+        counts, byts, nu, _ = dev.compute_julia_view(view, c, mrd, window=window, want_smooth=True, kernel=kernel)
+        return {"counts": counts, "bytes": byts, "smooth": nu}
+    return Case(lambda: {"counts": Out("i4", n), "bytes": Out("u1", n), "smooth": Out("f8", n)},
+                lambda dev, o, s: dev.launch_julia_view(view, c, mrd, d_counts=o["counts"].ptr, d_bytes=o["bytes"].ptr,
+                                                        d_smooth=o["smooth"].ptr, stream=s, window=window, kernel=kernel), want)
+
+
+def julia_distance(v, c, mrd, kernel, window=None) -> Case:
+    view, n = View(*v), _px(v, window)
+
+    def want(dev):
+        return {"distance": dev.compute_julia_view_distance(view, c, mrd, window=window, kernel=kernel)[0]}
+    return Case(lambda: {"distance": Out("f8", n)},
+                lambda dev, o, s: dev.launch_julia_view_distance(view, c, mrd, d_distance=o["distance"].ptr, stream=s, window=window,
+                                                                 kernel=kernel), want)
+
+
+@pytest.mark.parametrize("kernel", ["default", "asm"])
+@pytest.mark.parametrize("family", ["distance", "normals", "julia", "julia_distance"])
+def test_two_pass_calls_and_julia(family, kernel):
+    """Interposed: the two-pass form of the family on a ragged window without d_counts, through the stream's count scratch."""
+    with MandelbrotDevice(0) as dev:
+        if family == "distance":
+            _cycle(dev, distance(*SEAHORSE, kernel), distance(*SEAHORSE, "default", window=RAGGED, with_counts=False))
+        elif family == "normals":
+            _cycle(dev, normals(*BLOCKS, kernel), normals(*BLOCKS, "group", window=RAGGED))
+        elif family == "julia":
+            _cycle(dev, julia(*JULIA, kernel), julia_distance(*JULIA, "default", window=RAGGED))
+        else:
+            _cycle(dev, julia_distance(*JULIA, kernel), julia_distance(*JULIA, "group", window=RAGGED))
+
+
+@pytest.mark.parametrize("kernel", ["default", "group"])
+def test_interior(kernel):
+    with MandelbrotDevice(0) as dev:
+        _cycle(dev, interior(*INTERIOR, kernel), interior(*INTERIOR, "scan", window=RAGGED))
+        assert (interior(*INTERIOR, kernel).want(dev)["period"] > 0).sum() > 100
+
+
+# ---- deep and extended-range deep views ------------------------------------------------------------------------------------------
+
+_ORBITS = {}
+
+
+def _deep(w=64, h=64):
+    """(orbit, view, a view of the same orbit with another dcmax, mrd): the seahorse case of tests/test_gpu_deep_relief.py."""
+    if "deep" not in _ORBITS:
+        _ORBITS["deep"] = DeepOrbit("-0.77568377", "0.13646737", 3000, min_span=1e-12)
+    return _ORBITS["deep"], DeepView(1e-12, w, h), DeepView(2e-12, w, h), 3000
+
+
+def _wide(w=64, h=64):
+    """The same for an extended-range view: the case "i-1100" of tests/test_gpu_deep_wide_relief.py."""
+    if "wide" not in _ORBITS:
+        _ORBITS["wide"] = DeepOrbit("0", "1", 3000, min_span_exp2=WideDeepView(1.0, -1100, 64, 64).min_span_exp2)
+    return _ORBITS["wide"], WideDeepView(1.0, -1100, w, h), WideDeepView(1.0, -1099, w, h), 3000
+
+
+def deep(orbit, view, mrd, kind, table, window=None) -> Case:
+    """The launch forms of a deep or an extended-range deep view; table: MBK_DEEP_BLA / MBK_DEEP_XBLA."""
+    wide = isinstance(view, WideDeepView)
+    n = (window[2] * window[3]) if window is not None else view.width * view.height
+    flag = {"xbla": table} if wide else {"bla": table}
+    if kind == "counts":
+        def want(dev):
+            counts, _, nu, _ = dev.compute_deep_view(orbit, view, mrd, window=window, want_bytes=False, want_smooth=True, **flag)
+            return {"counts": counts, "smooth": nu}
+        return Case(lambda: {"counts": Out("i4", n), "smooth": Out("f8", n)},
+                    lambda dev, o, s: dev.launch_deep_view(orbit, view, mrd, d_counts=o["counts"].ptr, d_smooth=o["smooth"].ptr, stream=s,
+                                                           window=window, **flag), want)
+    if kind == "distance":
+        name = ("wide_view_distance" + ("_xbla" if table else "")) if wide else ("deep_view_distance" + ("_bla" if table else ""))
+
+        def want(dev):
+            rel, counts, _ = getattr(dev, "compute_" + name)(orbit, view, mrd, window=window)
+            return {"rel": rel, "counts": counts}
+        return Case(lambda: {"rel": Out("f8", n), "counts": Out("i4", n)},
+                    lambda dev, o, s: getattr(dev, "launch_" + name)(orbit, view, mrd, d_rel=o["rel"].ptr, d_counts=o["counts"].ptr, stream=s,
+                                                                     window=window), want)
+    if kind == "normals":
+        name = "wide_view_normals" if wide else "deep_view_normals"
+
+        def want(dev):
+            counts, nrm, nu, rel, _ = getattr(dev, "compute_" + name)(orbit, view, mrd, window=window, want_smooth=True, want_distance=True, **flag)
+            return {"counts": counts, "normals": nrm, "smooth": nu, "rel": rel}
+        return Case(lambda: {"counts": Out("i4", n), "normals": Out("f8", 2 * n), "smooth": Out("f8", n), "rel": Out("f8", n)},
+                    lambda dev, o, s: getattr(dev, "launch_" + name)(orbit, view, mrd, d_normals=o["normals"].ptr, d_counts=o["counts"].ptr,
+                                                                     d_smooth=o["smooth"].ptr, d_rel=o["rel"].ptr, stream=s, window=window,
+                                                                     **flag), want)
+    assert kind == "nucleus" and not table
+    name = "wide_view_nucleus" if wide else "deep_view_nucleus"
+
+    def want(dev):
+        period, delta, counts, _ = getattr(dev, "compute_" + name)(orbit, view, mrd, window=window)
+        return {"period": period, "delta": delta, "counts": counts}
+    return Case(lambda: {"period": Out("i4", n), "delta": Out("f8", 2 * n), "counts": Out("i4", n)},
+                lambda dev, o, s: getattr(dev, "launch_" + name)(orbit, view, mrd, d_period=o["period"].ptr, d_delta=o["delta"].ptr,
+                                                                 d_counts=o["counts"].ptr, stream=s, window=window), want)
+
+
+DEEP_KINDS = [("counts", False), ("counts", True), ("distance", False), ("distance", True), ("normals", False), ("normals", True),
+              ("nucleus", False)]
+
+
+@pytest.mark.parametrize("kind,table", DEEP_KINDS, ids=[k + ("-table" if t else "") for k, t in DEEP_KINDS])
+@pytest.mark.parametrize("family", ["deep", "wide"])
+def test_deep_and_wide_views(family, kind, table):
+    """Plain step and MBK_DEEP_BLA / MBK_DEEP_XBLA.  Interposed: the same call on the same orbit with a second dcmax -- the ctx
+    keeps two tables beside an orbit, so nothing the graph reads is evicted."""
+    orbit, view, view2, mrd = _deep() if family == "deep" else _wide()
+    with MandelbrotDevice(0) as dev:
+        _cycle(dev, deep(orbit, view, mrd, kind, table), deep(orbit, view2, mrd, kind, table, window=(3, 5, 40, 33)))
+        assert len(np.unique(deep(orbit, view, mrd, kind, table).want(dev)["counts"])) > 1
+
+
+# ---- renders -------------------------------------------------------------------------------------------------------------------
+
+RENDER_VIEW = ((-0.765, 0.085, 0.04, 0.04 * 27 / 39, 40, 28), 400)       # tests/test_gpu_relief.py
+BANDS = 10                                                                 # 28 rows: three bands
+
+
+def _render_palette():
+    rng = np.random.RandomState(11)
+    return Palette(rng.randint(0, 256, (53, 4)).astype(np.uint8), inside=(9, 8, 7, 200), scale=3.7, offset=0.25)
+
+
+def _image(n, mask=False):
+    return (lambda: {"rgba": Out("rgba", n), "mask": Out("u1", n)}) if mask else (lambda: {"rgba": Out("rgba", n)})
+
+
+def _rgba(img):
+    return {"rgba": np.ascontiguousarray(img).view(np.int32).ravel()}
+
+
+def render(kind_of_view, what, pal, *, s=2, rows=0, window=None, threshold=0, kernel="default", lut=None) -> Case:
+    """A render launch of a plain view ("plain"), the Julia set ("julia"), a deep view with MBK_DEEP_BLA ("deep") or an
+    extended-range view with MBK_DEEP_XBLA ("wide").  what: "smooth", "distance", "equalized" (with `lut`), "relief", "interior",
+    "adaptive".  The expected image is the synchronous form's."""
+    if kind_of_view in ("plain", "julia"):
+        view, mrd = View(*RENDER_VIEW[0]), RENDER_VIEW[1]
+        if kind_of_view == "julia":
+            view, c, mrd = View(*JULIA[0][:4], 40, 28), JULIA[1], JULIA[2]
+        orbit = None
+    else:
+        orbit, view, _, mrd = _deep(40, 28) if kind_of_view == "deep" else _wide(40, 28)
+    n = (window[2] * window[3]) if window is not None else view.width * view.height
+    common = dict(palette=pal, supersample=s, window=window, max_band_rows=rows)
+    table = {"deep": {"bla": True}, "wide": {"xbla": True}}.get(kind_of_view, {})
+    lead = (orbit, view, mrd) if orbit is not None else ((view, c, mrd) if kind_of_view == "julia" else (view, mrd))
+    if kind_of_view in ("plain", "julia"):
+        common["kernel"] = kernel
+    if what == "adaptive":
+        name = {"plain": "render_view_adaptive", "deep": "render_deep_view_adaptive", "wide": "render_wide_view_adaptive"}[kind_of_view]
+
+        def want(dev):
+            img, mask, _ = getattr(dev, name)(*lead, threshold=threshold, want_mask=True, **common, **table)
+            return dict(_rgba(img), mask=mask)
+        return Case(_image(n, mask=True),
+                    lambda dev, o, st: getattr(dev, "launch_" + name)(*lead, threshold=threshold, d_rgba=o["rgba"].ptr, d_mask=o["mask"].ptr,
+                                                                      stream=st, **common, **table), want)
+    if what == "relief":
+        name = {"plain": "render_view_relief", "deep": "render_deep_view_relief", "wide": "render_wide_view_relief"}[kind_of_view]
+        extra = dict(light_deg=200.0, height=0.75)
+    elif what == "interior":
+        name, extra = "render_view_interior", dict(scale=64.0)
+    elif what == "distance" and kind_of_view != "plain":
+        name = {"julia": "render_julia_view_distance", "deep": "render_deep_view_distance_bla", "wide": "render_wide_view_distance_xbla"}[kind_of_view]
+        extra, table = {}, {}
+    else:
+        name = {"plain": "render_view", "julia": "render_julia_view", "deep": "render_deep_view", "wide": "render_deep_view"}[kind_of_view]
+        extra = dict(source=what, **({"lut": lut} if what == "equalized" else {}))
+    return Case(_image(n), lambda dev, o, st: getattr(dev, "launch_" + name)(*lead, d_rgba=o["rgba"].ptr, stream=st, **common, **extra, **table),
+                lambda dev: _rgba(getattr(dev, name)(*lead, **common, **extra, **table)[0]))
+
+
+def _lut(dev, kind_of_view):
+    """The equalisation table of the whole view at output resolution: what the synchronous form takes when none is given."""
+    if kind_of_view == "plain":
+        return equalize_lut(dev.view_histogram(View(*RENDER_VIEW[0]), RENDER_VIEW[1]))
+    if kind_of_view == "julia":
+        return equalize_lut(dev.julia_view_histogram(View(*JULIA[0][:4], 40, 28), JULIA[1], JULIA[2]))
+    orbit, view, _, mrd = _deep(40, 28) if kind_of_view == "deep" else _wide(40, 28)
+    return equalize_lut(dev.deep_view_histogram(orbit, view, mrd, bla=kind_of_view == "deep", xbla=kind_of_view == "wide"))
+
+
+RENDERS = ([(k, w, 2, 0, 0) for k in ("plain", "deep", "wide") for w in ("smooth", "distance", "equalized", "relief")]
+           + [(k, "adaptive", s, t, 0) for k in ("plain", "deep", "wide") for s in (2, 3) for t in (16, 0)]
+           + [("julia", w, 2, 0, 0) for w in ("smooth", "distance", "equalized")]
+           + [("plain", "interior", 2, 0, 0)]
+           + [(k, w, 2, 16, BANDS) for k in ("plain", "deep", "wide") for w in ("smooth", "relief", "adaptive")])
+
+
+@pytest.mark.parametrize("kind_of_view,what,s,threshold,rows", RENDERS,
+                         ids=["-".join([k, w, f"s{s}"] + ([f"t{t}"] if w == "adaptive" else []) + (["bands"] if r else []))
+                              for k, w, s, t, r in RENDERS])
+def test_renders(kind_of_view, what, s, threshold, rows):
+    """40 x 28 images.  Interposed: a smooth render of a window at s = 1 with the same palette, through the same render scratch."""
+    pal = _render_palette()
+    with MandelbrotDevice(0) as dev:
+        lut = _lut(dev, kind_of_view) if what == "equalized" else None
+        case = render(kind_of_view, what, pal, s=s, rows=rows, threshold=threshold, lut=lut)
+        _cycle(dev, case, render(kind_of_view, "smooth", pal, s=1, window=(7, 5, 19, 13)))
+        # the case is no flat image: the smooth colourings blend 53 entries over hundreds of values, a distance or a period
+        # map holds the inside colour and a few entries at least; a threshold under 256 refines something
+        want = case.want(dev)
+        assert len(np.unique(want["rgba"])) > (3 if what in ("distance", "interior") else 50)
+        if what == "adaptive":
+            assert want["mask"].any() and (threshold > 0 or want["mask"].all())
+
+
+def test_density_render():
+    pal = _render_palette()
+    view, target, mrd = View(-2.0, -1.25, 3.0, 2.5, 40, 24), DensityTarget(-2.5, -2.5, 5.0, 5.0, 64, 48), 200
+    import torch
+    with MandelbrotDevice(0) as dev:
+        table = dev.compute_view_density(view, target, mrd)[0]
+        d_table = torch.from_numpy(table.view(np.int32).copy()).to("cuda:0")
+        assert table.max() > 3
+
+        def case(mode, factor):
+            n = (64 // factor) * (48 // factor)
+            return Case(_image(n), lambda dev, o, s: dev.launch_render_density(d_table.data_ptr(), 64, 48, palette=pal, d_rgba=o["rgba"].ptr,
+                                                                               mode=mode, factor=factor, stream=s),
+                        lambda dev: _rgba(dev.render_density(table, palette=pal, mode=mode, factor=factor)[0]))
+        _cycle(dev, case("sqrt", 2), case("linear", 1))
+
+
+# ---- accumulating calls ----------------------------------------------------------------------------------------------------------
+
+def histogram(kind_of_view, window=None) -> Case:
+    if kind_of_view == "plain":
+        lead, mrd, kw, name = (View(*SEAHORSE[0]), SEAHORSE[1]), SEAHORSE[1], {}, "view_histogram"
+    elif kind_of_view == "julia":
+        lead, mrd, kw, name = (View(*JULIA[0]), JULIA[1], JULIA[2]), JULIA[2], {}, "julia_view_histogram"
+    else:
+        orbit, view, _, mrd = _deep() if kind_of_view == "deep" else _wide()
+        lead, kw, name = (orbit, view, mrd), ({"bla": True} if kind_of_view == "deep" else {"xbla": True}), "deep_view_histogram"
+    return Case(lambda: {"hist": Out("i8", mrd)},
+                lambda dev, o, s: getattr(dev, "launch_" + name)(*lead, d_hist=o["hist"].ptr, stream=s, window=window, **kw),
+                lambda dev: {"hist": getattr(dev, name)(*lead, window=window, **kw).view(np.int64)})
+
+
+@pytest.mark.parametrize("kind_of_view", ["plain", "julia", "deep", "wide"])
+def test_histograms_accumulate_once_per_replay(kind_of_view):
+    with MandelbrotDevice(0) as dev:
+        _cycle_accumulate(dev, histogram(kind_of_view), histogram(kind_of_view, window=(3, 5, 40, 33)))
+
+
+def test_density_accumulates_once_per_replay():
+    view, target, mrd = View(-2.0, -1.25, 3.0, 2.5, 40, 24), DensityTarget(-2.5, -2.5, 5.0, 5.0, 64, 48), 200
+
+    def case(window):
+        return Case(lambda: {"table": Out("i4", 64 * 48)},
+                    lambda dev, o, s: dev.launch_view_density(view, target, mrd, d_density=o["table"].ptr, stream=s, window=window),
+                    lambda dev: {"table": dev.compute_view_density(view, target, mrd, window=window)[0].view(np.int32).ravel()})
+    with MandelbrotDevice(0) as dev:
+        _cycle_accumulate(dev, case(None), case((3, 5, 30, 17)))
+
+
+def test_counts_histogram():
+    """mbk_counts_histogram: device pointers alone, no scratch -- capturable on a cold ctx."""
+    import torch
+    rng = np.random.RandomState(5)
+    counts = rng.randint(0, 50, 5000).astype(np.int32)
+    d_counts = torch.from_numpy(counts).to("cuda:0")
+
+    def case(n):
+        return Case(lambda: {"hist": Out("i8", 50)},
+                    lambda dev, o, s: dev.counts_histogram(d_counts.data_ptr(), n, 50, o["hist"].ptr, stream=s),
+                    lambda dev: {"hist": np.bincount(counts[:n], minlength=50).astype(np.int64)})
+    with MandelbrotDevice(0) as dev:
+        _cycle_accumulate(dev, case(5000), case(1234))
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------
+
+def _small():
+    """A launch that needs nothing of the ctx: capturable behind any refusal, on a cold ctx too."""
+    return plain(SEAHORSE[0], SEAHORSE[1], "default", "counts")
+
+
+def test_refused_on_a_cold_ctx():
+    """No call has been made on the stream, no orbit has been used: every form that keeps scratch or reads an orbit copy is
+    refused; a small plain launch, which needs neither, is captured behind the refusal."""
+    pal = _render_palette()
+    orbit, view, _, mrd = _deep()
+    worbit, wview, _, _ = _wide()
+    for bad, text in ((lambda dev: render("plain", "smooth", pal), "first call"),
+                      (lambda dev: distance(*SEAHORSE, "default", with_counts=False), "first call"),
+                      (lambda dev: plain(FULL + (1024, 1024), _ordered_mrd(dev), "group", "counts"), "first call"),
+                      (lambda dev: deep(orbit, view, mrd, "counts", False), "reference orbit"),
+                      (lambda dev: deep(worbit, wview, mrd, "distance", False), "reference orbit")):
+        with MandelbrotDevice(0) as dev:
+            _refusal(dev, bad(dev), _small(), text)
+
+
+def test_refused_where_the_scratch_must_grow():
+    pal = _render_palette()
+    with MandelbrotDevice(0) as dev:
+        # the count scratch of the two-pass forms: warm on a window, whole view inside the capture
+        _refusal(dev, distance(*SEAHORSE, "default", with_counts=False), distance(*SEAHORSE, "default", window=RAGGED, with_counts=False),
+                 "scratch must grow")
+    with MandelbrotDevice(0) as dev:
+        _refusal(dev, render("plain", "smooth", pal, s=3), render("plain", "smooth", pal, s=1), "scratch must grow")
+    with MandelbrotDevice(0) as dev:
+        # the dispatch lists: warm at 16 384 blocks, 16 512 inside the capture
+        mrd = _ordered_mrd(dev)
+        _refusal(dev, plain(FULL + (1032, 1024), mrd, "group", "counts"), plain(FULL + (1024, 1024), mrd, "group", "counts"),
+                 "dispatch lists must grow")
+    with MandelbrotDevice(0) as dev:
+        # the units pre-pass' counters: the warm call took order 2, the captured one order 3
+        mrd = _ordered_mrd(dev)
+        dev.set_option("order", 2)
+        case = plain(FULL + (1024, 1024), mrd, "group", "counts")
+
+        def bad_launch(dev, o, s):
+            dev.set_option("order", 3)
+            dev.set_option("units_min_light", 0)
+            try:
+                case.launch(dev, o, s)
+            finally:
+                dev.set_option("order", 2)
+        _refusal(dev, Case(case.outs, bad_launch, case.want), case, "units pre-pass")
+
+
+def test_refused_with_another_palette_or_table():
+    pal = _render_palette()
+    other = Palette(pal.entries[::-1].copy(), inside=pal.inside, scale=pal.scale, offset=pal.offset)
+    with MandelbrotDevice(0) as dev:
+        _refusal(dev, render("plain", "smooth", other), render("plain", "smooth", pal), "palette differs")
+    with MandelbrotDevice(0) as dev:
+        lut = _lut(dev, "plain")
+        lut2 = np.sqrt(lut)
+        assert lut2.shape == lut.shape and (lut2 != lut).any() and lut2.min() >= 0.0 and lut2.max() <= 1.0
+        _refusal(dev, render("plain", "equalized", pal, lut=lut2), render("plain", "equalized", pal, lut=lut), "equalisation table differs")
+    with MandelbrotDevice(0) as dev:
+        import torch
+        table = np.arange(64 * 48, dtype=np.uint32).reshape(48, 64)
+        d_table = torch.from_numpy(table.view(np.int32).copy()).to("cuda:0")
+
+        def density(p):
+            return Case(_image(64 * 48), lambda dev, o, s: dev.launch_render_density(d_table.data_ptr(), 64, 48, palette=p, d_rgba=o["rgba"].ptr, stream=s),
+                        lambda dev: _rgba(dev.render_density(table, palette=p)[0]))
+        _refusal(dev, density(other), density(pal), "palette differs")
+
+
+def test_refused_without_a_resident_orbit_or_table():
+    for family in ("deep", "wide"):
+        orbit, view, view2, mrd = _deep() if family == "deep" else _wide()
+        text = "table of this view's dcmax"
+        with MandelbrotDevice(0) as dev:
+            # a dcmax that is not resident: the warm call brought the other view's table
+            _refusal(dev, deep(orbit, view2, mrd, "counts", True), deep(orbit, view, mrd, "counts", True), text)
+        with MandelbrotDevice(0) as dev:
+            _refusal(dev, deep(orbit, view2, mrd, "normals", True), deep(orbit, view, mrd, "distance", True), text)
+        with MandelbrotDevice(0) as dev:
+            # an orbit never used on the ctx
+            _refusal(dev, deep(orbit, view, mrd, "nucleus", False), _small(), "reference orbit")
+    with MandelbrotDevice(0) as dev:
+        # the orbit's plain copy is there, its wide table is not
+        orbit, view, _, mrd = _wide()
+        plain_view = DeepView(1e-280, 64, 64)
+        _refusal(dev, deep(orbit, view, mrd, "counts", False), deep(orbit, plain_view, mrd, "counts", False), "wide reference orbit")
+
+
+@pytest.mark.parametrize("kernel", ["scan", "refill"])
+def test_refused_selectors(kernel):
+    """The two-pass "scan" alternates its cursor sets per enqueue and sizes its second pass from a hint the host reads; "refill"
+    allocates its queues.  Both are refused inside a capture, through every call that takes a selector."""
+    text = "MBK_KERNEL_" + kernel.upper()
+    with MandelbrotDevice(0) as dev:
+        _refusal(dev, plain(*SEAHORSE, kernel, "counts"), plain(*SEAHORSE, "group", "counts"), text)
+    with MandelbrotDevice(0) as dev:
+        big = FULL + (1024, 1024)
+        _refusal(dev, plain(big, 300, kernel, "counts"), plain(big, 300, "default", "counts"), text)
+    if kernel == "scan":
+        pal = _render_palette()
+        for bad, good in ((distance(*SEAHORSE, "scan", with_counts=False), distance(*SEAHORSE, "default", with_counts=False)),
+                          (interior(*INTERIOR, "scan"), interior(*INTERIOR, "group")),
+                          (render("plain", "smooth", pal, kernel="scan"), render("plain", "smooth", pal))):
+            with MandelbrotDevice(0) as dev:
+                _refusal(dev, bad, good, text)
+
+
+def test_calls_that_cannot_be_captured():
+    """The chunk launches read HOST input at enqueue time; mbk_density_max and mbk_reduce_counts wait for their result."""
+    import torch
+    from distributedmandelbrot_amd import _lib as L
+    payload = np.random.RandomState(3).randint(0, 256, 4096).astype(np.uint8)
+    raw = bytes([L.MBK_CODEC_RAW]) + payload.tobytes()
+    one_run = bytes([L.MBK_CODEC_RLE]) + (L.MBK_CHUNK_BYTES).to_bytes(4, "little") + bytes([7])
+    values = np.random.RandomState(4).randint(0, 1000, 3000).astype(np.int32)
+    d_values = torch.from_numpy(values).to("cuda:0")
+    results = {}
+
+    def density_max(dev, o, s):
+        results["max"] = dev.density_max(d_values.data_ptr(), values.size, stream=s)
+
+    def reduce_counts(dev, o, s):
+        results["reduce"] = dev.reduce_counts(d_values.data_ptr(), values.size, 1000, stream=s)
+    cases = [
+        (Case(lambda: {"bytes": Out("u1", 4096)}, lambda dev, o, s: dev.launch_decode_chunk(raw, d_bytes=o["bytes"].ptr, n=4096, hip_stream=s),
+              lambda dev: {"bytes": payload}), "mbk_chunk_decode_launch"),
+        (Case(_image(64 * 64), lambda dev, o, s: dev.launch_render_chunk(one_run, d_rgba=o["rgba"].ptr, scale=64, hip_stream=s),
+              lambda dev: _rgba(dev.render_chunk(one_run, scale=64)[0])), "mbk_chunk_render_launch"),
+        (Case(lambda: {}, density_max, lambda dev: {}), "mbk_density_max"),
+        (Case(lambda: {}, reduce_counts, lambda dev: {}), "mbk_reduce_counts"),
+    ]
+    for bad, text in cases:
+        with MandelbrotDevice(0) as dev:
+            _refusal(dev, bad, _small(), text)
+    assert results["max"] == (int(values.max()), int(values.sum()))
+    st = results["reduce"]
+    assert st.never_pixels == int((values == 0).sum()) and st.pixel_iterations == int(np.where(values > 0, values, 999).astype(np.int64).sum())
