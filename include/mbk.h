@@ -205,6 +205,39 @@ int mbk_view_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t f
  *     mbk_destroy.  The library cannot see a graph and does not check this.
  */
 
+/*
+ * Streams.  Every *_launch form takes the caller's stream, and one ctx may have launches queued on any number of streams at
+ * once, from ONE host thread at a time (a ctx is not thread-safe).  tests/test_gpu_streams.py runs every form beside the others
+ * on 4 and on 12 streams, with the launches held back on the device so that they do overlap; DESIGN.md "Streams" has the table.
+ *
+ * Kept per (ctx, stream), made on the stream's first call and grown on demand: the dispatch lists with their pre-pass stream
+ * and events, the scan cursors and lists, the SPILL buffers, the sample scratch of renders, histograms and density views, the
+ * count scratch of the two-pass calls, the palette and the equalisation table of the last render, the density band counters,
+ * the chunk scratch, the XCD shares.  Two launches on different streams share none of it.  The ctx' own streams (the slots of
+ * *_submit and of the *_compute forms) take entries of the same table when a call on them needs scratch.
+ *
+ * A WARM launch form -- same or smaller window, same palette and table, resident orbit and dcmax -- enqueues and returns: it
+ * waits for nothing, whatever is queued on its stream or on others.  What does wait, and for what:
+ *   - the caller's stream (and the stream's pre-pass stream): dispatch lists, scan lists or SPILL buffers that must grow; the
+ *     first "order 3" launch of a stream; a change of MBK_OPT_PREPASS_OVERLAP since the stream's last ordered launch; a render
+ *     whose palette or equalisation table differs from the stream's last (the device copy is overwritten in place, behind the
+ *     renders that read it); mbk_density_max, mbk_reduce_counts, MBK_INFO_SPILL;
+ *   - the whole DEVICE, every stream of every ctx and of the caller's own work included: sample or count scratch that must grow
+ *     (the old buffer is freed, and hipFree waits for the device); an MBK_DEEP_BLA / MBK_DEEP_XBLA launch whose dcmax is not
+ *     resident while both places beside the orbit are taken (the table asked for least recently is overwritten; an adaptive
+ *     render keeps both of its own); the use of a NINTH orbit on a ctx that holds eight copies (all eight are freed); the first
+ *     call on a stream when the table already holds 64 streams, the ctx' own among them (the scratch of all 64 is freed and
+ *     made anew as the streams come back; a stream's palette and table are then uploaded again); mbk_destroy.
+ * A first call on a stream, an orbit's first launch and a table into a free place allocate and copy synchronously; the library
+ * waits for no launch there, and they may be made beside queued work of other streams.  Whether hipMalloc or a synchronous
+ * hipMemcpy waits for queued work is the runtime's to say: in the tests it did not, but for one such call in some thirty
+ * (profiles/streams/README.md).  The *_compute forms wait for their own result, and like any call they drain the device where
+ * one of the ctx' buffers must grow.
+ * A caller that creates streams without end pays the 64-stream drain again and again: keep a pool (PyTorch's holds 32 streams
+ * per priority).  Accumulating forms (the *_histogram_launch calls, mbk_counts_histogram, mbk_view_density_launch) add with
+ * device-wide atomics: any number of streams may add into one table, and the table holds the sum.
+ */
+
 /* Synchronous: launch + D2H into HOST buffers (either may be NULL according to flags) + stats.
  * Replaces WorkerCUDA.py:82-98 for a generic view. */
 int mbk_view_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags,
