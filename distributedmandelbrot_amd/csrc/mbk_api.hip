@@ -4620,7 +4620,9 @@ int mbk_render_resolve_equalized_host(const mbk_render_spec *spec, const double 
 // extended-range deep views, MBK_RENDER_SMOOTH -------------------------------------------------------------------------------
 
 // Everything an adaptive render can refuse, before anything is allocated, enqueued or written: its own rules, then the smooth
-// render's for the sample view at s (render_check) and the sample launch's for the base view.
+// render's for the sample view at s (render_check) and the sample launch's for the base samples of the output window: the base
+// samples are launched per band of that window's halo, and the whole view -- which may hold far more than the 2^31 pixels of a
+// window -- is never a launch.
 static int adaptive_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                           uint32_t threshold, const void *out)
 {
@@ -4636,7 +4638,7 @@ static int adaptive_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t 
     }
     rc = render_check(ctx, t, mrd, flags, spec, out);
     if (rc != MBK_OK) return rc;
-    return target_check(ctx, target_samples(t, 1u, 0u, 0u, t.g.width, t.g.height), mrd, flags);
+    return target_check(ctx, target_samples(t, 1u, t.g.col0, t.g.row0, t.g.ncols, t.g.nrows), mrd, flags);
 }
 
 // The bands of an adaptive render: per band the base samples of its halo (12 bytes each, the band grown by one pixel on each

@@ -83,6 +83,24 @@ typedef struct mbk_ctx mbk_ctx;
  * FULL view's linspace, so a banded view is bit-identical to the whole one.
  * Output layout: element (row-row0)*ncols + (col-col0); real is the fast axis (np.tile, :34),
  * imaginary the slow one (np.repeat, :35); row 0 is start_i.
+ *
+ * Limits (tests/test_geometry_limits.py, tests/test_gpu_geometry_limits.py, tests/test_gpu_large_outputs.py; the
+ * thresholds between the launch forms: DESIGN.md, "Geometric thresholds"):
+ *   samples per axis   width, height <= 2^32 - 1: a sample index is a uint32_t and is converted to binary64 as an
+ *                      unsigned number, exactly; col0 + ncols <= width and row0 + nrows <= height are checked in 64 bits.
+ *   pixels per window  ncols * nrows <= 2^31.  Protects the 32-bit lane offset the kernels add to a block's 64-bit base
+ *                      (at most 7 rows of the window, so below 2^31 elements), the block count (at most 2^25 blocks of
+ *                      8 x 8 pixels, a 32-bit grid) and the statistics (pixel_iterations < 2^62).  An output may well be
+ *                      larger than 2^32 BYTES (int32 counts of more than 2^30 pixels, float64 of more than 2^29): element
+ *                      offsets are 64-bit, or a 64-bit base plus a 32-bit offset that the kernel keeps below 2^32.
+ *   renders            width * s and height * s <= 2^32 - 1 for supersample s: the samples of a render are those of the
+ *                      view with s times as many samples per axis, and their indices must be uint32_t as well.
+ *   adaptive renders   the renders' limits; the base samples (s = 1) answer to the pixel limit for the output window, not for
+ *                      the whole view: a small window of a view of more than 2^31 pixels is served.
+ *   host resolve twins width * s and height * s < 2^31 for mbk_render_resolve_host, its equalized form and the adaptive
+ *                      resolve twins: they take whole sample arrays on the host, indexed in 64 bits from 31-bit sizes.
+ *   coordinates        finite, |x| <= 2^500 (MBK_PRECISION_F32: 2^60) for the start, the range and their sum: no inf - inf
+ *                      before the bailout test.
  */
 typedef struct mbk_view {
     double start_r, start_i;

@@ -61,3 +61,28 @@ def sample_stats(mask, mrd, s, base_counts, fine_counts, window=None):
     it_b, nv_b = totals(np.asarray(base_counts)[r0:r0 + nr, c0:c0 + nc])
     it_f, nv_f = totals(fine.transpose(0, 2, 1, 3)[m]) if s > 1 else (0, 0)
     return it_b + it_f, nv_b + nv_f
+
+
+def halo(window, width, height):
+    """The window (col0, row0, ncols, nrows) grown by one pixel on every side and clamped to the width x height view: the
+    rectangle of the s = 1 image that decides which of the window's pixels are refined."""
+    c0, r0, nc, nr = window
+    hc0, hr0 = max(c0 - 1, 0), max(r0 - 1, 0)
+    return hc0, hr0, min(c0 + nc + 1, width) - hc0, min(r0 + nr + 1, height) - hr0
+
+
+def render_adaptive_window(palette, inside, scale, offset, s, threshold, window, width, height, halo_counts, halo_nu, fine_counts,
+                           fine_nu):
+    """render_adaptive for a window of a width x height view without the view: halo_counts / halo_nu are the base samples of
+    halo(window, width, height), fine_counts / fine_nu the samples of the window at s (nrows * s by ncols * s).  A window pixel's
+    neighbours all lie in the halo rectangle unless they lie outside the view, and the rule looks at no others: refined_mask on
+    the halo rectangle, whose own border plays the view's where the view ends and is cut away where it does not, is the whole
+    view's mask on the window."""
+    c0, r0, nc, nr = window
+    hc0, hr0, hnc, hnr = halo(window, width, height)
+    assert np.asarray(halo_counts).shape == (hnr, hnc) and np.asarray(fine_counts).shape == (nr * s, nc * s)
+    base = base_image(palette, inside, scale, offset, halo_counts, halo_nu)
+    rows, cols = slice(r0 - hr0, r0 - hr0 + nr), slice(c0 - hc0, c0 - hc0 + nc)
+    mask = refined_mask(base, threshold)[rows, cols]
+    fine = M.render_smooth(palette, inside, scale, offset, s, fine_counts, fine_nu)
+    return np.where(mask[..., None], fine, base[rows, cols]), mask.astype(np.uint8)

@@ -72,10 +72,11 @@ def qualify(n, mrd, min_count=1, max_count=0):
     return (n >= min_count) & (n <= hi) & (n > 0)
 
 
-def accumulate(view, target, mrd, min_count=1, max_count=0, window=None, n=None):
+def accumulate(view, target, mrd, min_count=1, max_count=0, window=None, n=None, coords=None):
     """(table uint64[H, W], deposits, dropped, n) of a window.  The table is exact (no wrap at 2^32: the tests' tables are
-    far below it)."""
-    xs, ys = axes(view, window)
+    far below it).  coords: the window's (xs, ys) where the caller has them without the view's whole axes
+    (tests/geometry_model.py window_axes: a view of 2^32 - 1 samples)."""
+    xs, ys = coords if coords is not None else axes(view, window)
     cr, ci = np.meshgrid(xs, ys)
     if n is None:
         n = counts(cr, ci, mrd)

@@ -46,6 +46,29 @@ def _samples(rs, h, w, n):
 
 
 @pytest.mark.parametrize("s", M.SUPERSAMPLES)
+@pytest.mark.parametrize("w, h", SHAPES + [(40, 28)])
+def test_window_form_of_the_model_equals_the_whole_view_form(w, h, s):
+    """adaptive_model.render_adaptive_window (the window's fine samples and a one-pixel halo of the base samples) against
+    render_adaptive of the whole view, on the synthetic samples of the twin's test: the whole view as a window, every corner,
+    every edge, single pixels at the last column and row, and an interior window."""
+    rs = np.random.RandomState(1000 * s + 17 * w + h)
+    pal = _palette(rs)
+    bc, bn = _samples(rs, h, w, len(pal))
+    fc, fn = _samples(rs, h * s, w * s, len(pal))
+    windows = {(0, 0, w, h), (w - 1, h - 1, 1, 1), (0, 0, 1, 1), (w - 1, 0, 1, h), (0, h - 1, w, 1), (0, 0, (w + 1) // 2, (h + 1) // 2),
+               (w // 2, h // 2, w - w // 2, h - h // 2), (w // 3, h // 3, max(w // 3, 1), max(h // 3, 1))}
+    for thr in THRESHOLDS:
+        want, want_mask = A.render_adaptive(pal.entries, pal.inside, pal.scale, pal.offset, s, thr, bc, bn, fc, fn)
+        for window in windows:
+            c0, r0, nc, nr = window
+            hc0, hr0, hnc, hnr = A.halo(window, w, h)
+            got, mask = A.render_adaptive_window(pal.entries, pal.inside, pal.scale, pal.offset, s, thr, window, w, h,
+                                                 bc[hr0:hr0 + hnr, hc0:hc0 + hnc], bn[hr0:hr0 + hnr, hc0:hc0 + hnc],
+                                                 fc[r0 * s:(r0 + nr) * s, c0 * s:(c0 + nc) * s], fn[r0 * s:(r0 + nr) * s, c0 * s:(c0 + nc) * s])
+            assert np.array_equal(got, want[r0:r0 + nr, c0:c0 + nc]) and np.array_equal(mask, want_mask[r0:r0 + nr, c0:c0 + nc]), (thr, window)
+
+
+@pytest.mark.parametrize("s", M.SUPERSAMPLES)
 @pytest.mark.parametrize("w, h", SHAPES)
 def test_twin_equals_the_model_on_synthetic_samples(w, h, s):
     rs = np.random.RandomState(1000 * s + 17 * w + h)
