@@ -112,6 +112,17 @@ class mbk_relief_spec(C.Structure):
                 ("height", C.c_double), ("max_band_rows", C.c_uint32)]
 
 
+class mbk_stripe_state(C.Structure):
+    _fields_ = [("S", C.c_double), ("t_last", C.c_double), ("mag", C.c_double), ("v", C.c_double), ("n", C.c_int32),
+                ("N", C.c_int32), ("cnt", C.c_int32), ("reserved", C.c_int32)]
+
+
+class mbk_stripe_spec(C.Structure):
+    _fields_ = [("supersample", C.c_uint32), ("palette", C.c_void_p), ("palette_len", C.c_uint32), ("inside", C.c_uint8 * 4),
+                ("scale", C.c_double), ("offset", C.c_double), ("density", C.c_uint32), ("skip", C.c_uint32),
+                ("lo", C.c_double), ("gain", C.c_double), ("max_band_rows", C.c_uint32)]
+
+
 class mbk_density_target(C.Structure):
     _fields_ = [("start_r", C.c_double), ("start_i", C.c_double), ("range_r", C.c_double), ("range_i", C.c_double),
                 ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -441,6 +452,19 @@ SIGNATURES = {
     "mbk_view_relief_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
                                                  C.POINTER(mbk_relief_spec), C.c_void_p, C.POINTER(mbk_stats)]),
     "mbk_relief_resolve_host": (C.c_int, [C.POINTER(mbk_relief_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "mbk_view_launch_stripe": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mbk_view_compute_stripe": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_stripe_state_host": (C.c_int, [C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(mbk_stripe_state)]),
+    "mbk_stripe_value_host": (C.c_double, [C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32]),
+    "mbk_stripe_shade_host": (C.c_uint32, [C.c_double] * 3),
+    "mbk_view_stripe_render_launch": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                C.POINTER(mbk_stripe_spec), C.c_void_p, C.c_void_p]),
+    "mbk_view_stripe_render_compute": (C.c_int, [C.c_void_p, C.POINTER(mbk_view), C.c_uint32, C.c_uint32,
+                                                 C.POINTER(mbk_stripe_spec), C.c_void_p, C.POINTER(mbk_stats)]),
+    "mbk_stripe_resolve_host": (C.c_int, [C.POINTER(mbk_stripe_spec), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "mbk_deep_view_launch_normal": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(mbk_deep_view), C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

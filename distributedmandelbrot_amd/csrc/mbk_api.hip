@@ -34,6 +34,7 @@
 #include "mbk_chunks.h"
 #include "mbk_distance.h"
 #include "mbk_relief.h"
+#include "mbk_stripe.h"
 #include "mbk_interior.h"
 #include "mbk_deep_distance.h"
 #include "mbk_deep_distance_bla.h"
@@ -1639,18 +1640,19 @@ static int sync_end(mbk_ctx *ctx, int rc, mbk_stats *stats, bool have_bytes, boo
 // may each be NULL.  per_px (atom periods and Newton seeds): that many binary64 values per pixel, the tail after all of them.
 // h_more (normals with distance estimates; not with a tail): px more binary64 values follow the per_px * px on the device, at
 // d_values + per_px * px, which the launch writes too; they go to h_more.  h_more2 (deep normals: nu in h_more, rel here): px
-// further values behind those, at d_values + (per_px + 1) * px whether or not h_more is given.
+// further values behind those, at d_values + (per_px + 1) * px whether or not h_more is given.  more_per_px (the stripe state:
+// 32 bytes per pixel; not with h_more2): that many binary64 values per pixel in h_more.
 template <typename Launch>
 static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_counts, double *h_values, mbk_stats *stats, Launch launch,
                           bool with_tail = false, int32_t *h_tail = nullptr, size_t per_px = 1u, double *h_more = nullptr,
-                          double *h_more2 = nullptr)
+                          double *h_more2 = nullptr, size_t more_per_px = 1u)
 {
     Slot &sl = ctx->s[0];
     auto enqueue = [&]() -> int {
         int rc = ensure_buffers(ctx, sl, px);
         if (rc != MBK_OK) return rc;
         const size_t vals = per_px * px;
-        const size_t cap = with_tail ? vals + (px + 1u) / 2u : (h_more2 ? vals + 2u * px : (h_more ? vals + px : vals));   // (in binary64 values)
+        const size_t cap = with_tail ? vals + (px + 1u) / 2u : (h_more2 ? vals + 2u * px : (h_more ? vals + more_per_px * px : vals));   // (in binary64 values)
         rc = grow(ctx, ctx->d_smooth, ctx->smooth_cap_px, cap, cap * sizeof(double));
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
@@ -1662,7 +1664,7 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         if (h_values) MBK_HIP(ctx, hipMemcpyAsync(h_values, ctx->d_smooth, vals * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_tail) MBK_HIP(ctx, hipMemcpyAsync(h_tail, ctx->d_smooth + vals, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
-        if (h_more) MBK_HIP(ctx, hipMemcpyAsync(h_more, ctx->d_smooth + vals, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
+        if (h_more) MBK_HIP(ctx, hipMemcpyAsync(h_more, ctx->d_smooth + vals, more_per_px * px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_more2) MBK_HIP(ctx, hipMemcpyAsync(h_more2, ctx->d_smooth + vals + px, px * sizeof(double), hipMemcpyDeviceToHost, sl.stream));
         if (h_counts) MBK_HIP(ctx, hipMemcpyAsync(h_counts, sl.d_counts, px * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_c1, sl.stream));
@@ -1672,7 +1674,7 @@ static int compute_values(mbk_ctx *ctx, size_t px, uint32_t mrd, int32_t *h_coun
     return sync_end(ctx, enqueue(), stats, false);
 }
 
-// The first pass of a two-pass launch (distance estimates, normals, interior views) of px pixels on `stream`:
+// The first pass of a two-pass launch (distance estimates, normals, stripe averages, interior views) of px pixels on `stream`:
 // count_launch(counts) has the escape kernels write the counts the second pass runs on -- the caller's, or the stream's scratch
 // when the caller wants none; *d_counts is where they are.
 template <typename CountLaunch>
@@ -2561,6 +2563,116 @@ int mbk_normal_value_host(double zr, double zi, double dr, double di, int32_t co
 uint32_t mbk_relief_shade_host(double nx, double ny, double lx, double ly, double h)
 {
     return mbk::relief_shade(nx, ny, lx, ly, h);
+}
+
+// ---- stripe averages (mbk_stripe.h; mbk.h "Stripe-average colouring") --------------------------------------------------
+
+// Everything a stripe launch can refuse, before anything is allocated, enqueued or written: what a distance launch refuses,
+// kernel "asm" (there is no one-pass form), every flag that is no kernel selector, and a density out of range.
+static int stripe_check(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t density, uint32_t skip, bool *safe)
+{
+    int rc = distance_check(ctx, view, mrd, flags, safe);
+    if (rc != MBK_OK) return rc;
+    if (flags & ~(uint32_t)MBK_KERNEL_MASK) return fail(ctx, MBK_ERR_INVALID, "stripe averages take kernel selection only (binary64, no other flag)");
+    if ((flags & MBK_KERNEL_MASK) == MBK_KERNEL_ASM) return fail(ctx, MBK_ERR_INVALID, "stripe averages have no one-pass form: take the default selector, scan or group");
+    if (density < 1u || density > mbk::kStripeDensityMax) return fail(ctx, MBK_ERR_INVALID, "density must lie in 1 .. 16");
+    if (skip > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "skip must lie in 0 .. 2^31 - 1");
+    return MBK_OK;
+}
+
+// The stripe kernel on a checked view and the counts of its pixels.  d_state may be null.
+static int launch_stripe_kernel(mbk_ctx *ctx, const mbk_view *v, bool safe, uint32_t density, uint32_t skip, const int32_t *d_counts,
+                                double *d_stripe, double *d_state, hipStream_t stream)
+{
+    mbk::StripeArgs a;
+    std::memset(&a, 0, sizeof(a));
+    fill_window(a, v);
+    a.blocks_x = (v->ncols + 7u) / 8u;
+    a.density = density;
+    a.skip = skip;
+    a.counts_in = d_counts;
+    a.value = d_stripe;
+    a.state = d_state;
+    a.px = (uint64_t)v->ncols * v->nrows;
+    const dim3 grid(a.blocks_x * ((v->nrows + 7u) / 8u)), block(64);   // (at most 2^31 / 64 blocks: validate_view)
+    if (safe) hipLaunchKernelGGL(mbk::stripe_kernel<false>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(mbk::stripe_kernel<true>, grid, block, 0, stream, a);
+    MBK_HIP(ctx, hipGetLastError());
+    return MBK_OK;
+}
+
+// A checked launch: the escape kernels the selector names write the counts (into the stream's scratch when the caller wants
+// none), then the stripe kernel replays each escaped pixel for exactly its count.
+static int launch_stripe(mbk_ctx *ctx, const mbk_view *v, uint32_t mrd, uint32_t flags, bool safe, uint32_t density, uint32_t skip,
+                         int32_t *d_counts, double *d_stripe, double *d_state, hipStream_t stream)
+{
+    int rc = launch_count_pass(ctx, (size_t)v->ncols * v->nrows, stream, &d_counts, [&](int32_t *counts) {
+        return launch_tile(ctx, v, mrd, (flags & MBK_KERNEL_MASK) | MBK_WANT_COUNTS, counts, nullptr, stream);
+    });
+    if (rc != MBK_OK) return rc;
+    return launch_stripe_kernel(ctx, v, safe, density, skip, d_counts, d_stripe, d_state, stream);
+}
+
+int mbk_view_launch_stripe(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t density, uint32_t skip,
+                           int32_t *d_counts, double *d_stripe, void *d_state, void *hip_stream)
+{
+    if (!ctx || !d_stripe) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = stripe_check(ctx, view, mrd, flags, density, skip, &safe);
+    if (rc != MBK_OK) return rc;
+    if (((uintptr_t)d_stripe | (uintptr_t)d_state) & 7u) return fail(ctx, MBK_ERR_INVALID, "d_stripe and d_state must be 8-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
+    return launch_stripe(ctx, view, mrd, flags, safe, density, skip, d_counts, d_stripe, (double *)d_state, (hipStream_t)hip_stream);
+}
+
+int mbk_view_compute_stripe(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t density, uint32_t skip,
+                            int32_t *h_counts, double *h_stripe, void *h_state, mbk_stats *stats)
+{
+    if (!ctx || !view || !h_stripe) return fail(ctx, MBK_ERR_INVALID, "NULL argument");
+    bool safe = false;
+    int rc = stripe_check(ctx, view, mrd, flags, density, skip, &safe);
+    if (rc != MBK_OK) return rc;
+    rc = sync_begin(ctx);
+    if (rc != MBK_OK) return rc;
+    const size_t px = (size_t)view->ncols * view->nrows;
+    return compute_values(ctx, px, mrd, h_counts, h_stripe, stats,
+                          [&](int32_t *d_counts, double *d_stripe, hipStream_t stream) {
+                              return launch_stripe(ctx, view, mrd, flags, safe, density, skip, d_counts, d_stripe, h_state ? d_stripe + px : nullptr, stream);
+                          },
+                          false, nullptr, 1u, (double *)h_state, nullptr, 4u);
+}
+
+int mbk_stripe_state_host(double c_r, double c_i, uint32_t mrd, uint32_t density, uint32_t skip, mbk_stripe_state *out)
+{
+    if (!out) return fail(nullptr, MBK_ERR_INVALID, "out is NULL");
+    if (mrd > 0x7fffffffu) return fail(nullptr, MBK_ERR_INVALID, "mrd must fit int32 (calc_mb_value returns int32)");
+    if (density < 1u || density > mbk::kStripeDensityMax) return fail(nullptr, MBK_ERR_INVALID, "density must lie in 1 .. 16");
+    if (skip > 0x7fffffffu) return fail(nullptr, MBK_ERR_INVALID, "skip must lie in 0 .. 2^31 - 1");
+    // the literal doubling throughout: the contract's step, which the fused form equals wherever a launch takes it
+    double m = 0.0;
+    std::memset(out, 0, sizeof(*out));
+    out->n = mbk::julia_count<false>(c_r, c_i, c_r, c_i, (int32_t)mrd, &m);
+    if (out->n > 0) {
+        const mbk::StripeState st = mbk::stripe_replay<false>(c_r, c_i, out->n, density, skip);
+        out->N = st.N;
+        out->cnt = st.cnt;
+        out->S = st.S;
+        out->t_last = st.t_last;
+        out->mag = st.mag;
+    }
+    out->v = mbk::stripe_value(out->S, out->t_last, out->cnt, out->mag, out->n);
+    return MBK_OK;
+}
+
+double mbk_stripe_value_host(double S, double t_last, int32_t cnt, double mag, int32_t count)
+{
+    return mbk::stripe_value(S, t_last, cnt, mag, count);
+}
+
+uint32_t mbk_stripe_shade_host(double v, double lo, double gain)
+{
+    return mbk::stripe_shade(v, lo, gain);
 }
 
 // ---- interior views (mbk_interior.h; mbk.h "Interior views") -----------------------------------------------------------
@@ -3947,6 +4059,8 @@ struct Outputs {
     bool interior;
     double *normals;   // relief (plain, deep and extended-range deep views): the normals of the samples, beside counts and nu
     double *rel;       // deep and extended-range deep normals: the distance estimate of the same final state, beside nu in `values`
+    double *stripe;    // stripe renders (plain views only): the stripe averages of the samples, beside counts and nu
+    uint32_t density, skip;
 };
 
 // The launch of a checked target (target_check) on device pointers, on `stream`: the one place that knows which kernels serve
@@ -3988,10 +4102,11 @@ static int target_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
     }
     const uint32_t want = (o.counts ? MBK_WANT_COUNTS : 0u) | (o.bytes ? MBK_WANT_BYTES : 0u);
     int rc = launch_tile(ctx, &t.view, mrd, (flags & ~(MBK_WANT_COUNTS | MBK_WANT_BYTES)) | want, o.counts, o.bytes, stream, o.values);
-    if (rc != MBK_OK || !o.normals) return rc;
-    bool safe = false;   // (a relief band: the two-pass normal kernel on the counts the smooth launch has just written)
+    if (rc != MBK_OK || (!o.normals && !o.stripe)) return rc;
+    bool safe = false;   // (a relief or stripe band: the two-pass kernel on the counts the smooth launch has just written)
     rc = validate_view(ctx, &t.view, &safe);
     if (rc != MBK_OK) return rc;
+    if (o.stripe) return launch_stripe_kernel(ctx, &t.view, safe, o.density, o.skip, o.counts, o.stripe, nullptr, stream);
     return launch_relief_kernel(ctx, &t.view, mrd, safe, o.counts, nullptr, o.normals, nullptr, stream);
 }
 
@@ -4182,6 +4297,7 @@ static mbk::RenderPalette render_palette(const mbk_render_spec *spec, const uint
     p.lut_mrd = 0u;
     p.unknown = p.outside = 0u;
     p.light_x = p.light_y = p.height = 0.0;
+    p.stripe_lo = p.stripe_gain = 0.0;
     return p;
 }
 
@@ -4191,6 +4307,8 @@ static const uint32_t kRenderSourceInterior = 0x100u;
 struct InteriorColours { uint32_t unknown, outside; };
 // A relief render inside the render machinery: an MBK_RENDER_SMOOTH spec, and the light it has no field for.
 struct ReliefLight { double x, y, height; };
+// A stripe render inside the render machinery: an MBK_RENDER_SMOOTH spec, and what it has no field for.
+struct StripeShade { uint32_t density, skip; double lo, gain; };
 
 // The stream's device palette: uploaded when it differs from what the device copy holds, after the launches that read that.
 static int stream_palette(mbk_ctx *ctx, StreamScratch *sc, hipStream_t stream, const uint8_t *palette, uint32_t len)
@@ -4300,7 +4418,7 @@ static size_t round_up_256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 // reduction scratch adds up the statistics of the samples and whose ev_k1 marks the last resolve kernel (_compute), or NULL.
 static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                       uint32_t *d_out, hipStream_t stream, Slot *stat, const double *h_lut = nullptr, uint32_t lut_len = 0u,
-                      const InteriorColours *interior = nullptr, const ReliefLight *relief = nullptr)
+                      const InteriorColours *interior = nullptr, const ReliefLight *relief = nullptr, const StripeShade *stripe = nullptr)
 {
     const uint32_t s = spec->supersample;
     const bool dist = spec->source == MBK_RENDER_DISTANCE || spec->source == MBK_RENDER_DISTANCE_REL;   // (deep views: rel in place of de, the same colour rule)
@@ -4318,18 +4436,19 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         if (rc != MBK_OK) return rc;
     }
 
-    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (relief ? 28u : (interior ? 16u : (smooth ? 12u : (stat ? 5u : 1u)))), spec->max_band_rows);
+    const BandPlan plan = band_plan(t.g.ncols, t.g.nrows, (uint64_t)s * s * (relief ? 28u : stripe ? 20u : (interior ? 16u : (smooth ? 12u : (stat ? 5u : 1u)))), spec->max_band_rows);
     const size_t cap_samples = plan.cap_px() * s * s;
-    // layout: SMOOTH nu | counts (interior: de | counts | periods; relief: nu | counts | normals); BYTES counts (statistics only) | bytes
+    // layout: SMOOTH nu | counts (interior: de | counts | periods; relief: nu | counts | normals; stripe: nu | counts | v); BYTES counts (statistics only) | bytes
     const size_t off2 = smooth ? round_up_256(cap_samples * 8u) : (stat ? round_up_256(cap_samples * 4u) : 0u);
-    const size_t off3 = off2 + round_up_256(cap_samples * 4u);   // (interior and relief only)
-    const size_t need = relief ? off3 + cap_samples * 16u : (interior ? off3 + cap_samples * 4u : off2 + (smooth ? cap_samples * 4u : cap_samples));
+    const size_t off3 = off2 + round_up_256(cap_samples * 4u);   // (interior, relief and stripe only)
+    const size_t need = relief ? off3 + cap_samples * 16u : stripe ? off3 + cap_samples * 8u : (interior ? off3 + cap_samples * 4u : off2 + (smooth ? cap_samples * 4u : cap_samples));
     rc = grow(ctx, sc->d_render, sc->render_cap, need, need);
     if (rc != MBK_OK) return rc;
     uint8_t *base = (uint8_t *)sc->d_render;
     const Outputs samples = {smooth ? (int32_t *)(base + off2) : (stat ? (int32_t *)base : nullptr), smooth ? nullptr : base + off2,
                              smooth ? (double *)base : nullptr, dist, interior ? (int32_t *)(base + off3) : nullptr, interior != nullptr,
-                             relief ? (double *)(base + off3) : nullptr};
+                             relief ? (double *)(base + off3) : nullptr, nullptr, stripe ? (double *)(base + off3) : nullptr,
+                             stripe ? stripe->density : 0u, stripe ? stripe->skip : 0u};
     const double *d_lut = eq ? sc->d_lut : nullptr;
     const uint32_t *d_palette = sc->d_palette;   // (sc may move when a launch below adds a stream's scratch: not used past here)
 
@@ -4347,6 +4466,7 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
         a.smooth = samples.values;
         a.period = samples.period;
         a.normal = samples.normals;
+        a.stripe = samples.stripe;
         a.bytes = samples.bytes;
         a.out = d_out + (size_t)r * t.g.ncols + c;
         a.pitch = (uint64_t)nc * s;
@@ -4368,12 +4488,18 @@ static int render_run(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flag
             a.pal.light_y = relief->y;
             a.pal.height = relief->height;
         }
+        if (stripe) {
+            a.pal.stripe_lo = stripe->lo;
+            a.pal.stripe_gain = stripe->gain;
+        }
         const uint64_t pieces = (uint64_t)a.chunks_x * nr;
         const dim3 grid((uint32_t)std::min<uint64_t>(pieces, (uint64_t)cus * wg_per_cu));
         if (interior)
             mbk::launch_resolve<true, mbk::kRuleInterior>(s, grid, use_lds ? lds : 0u, stream, a);
         else if (relief)
             mbk::launch_resolve<true, mbk::kRuleRelief>(s, grid, use_lds ? lds : 0u, stream, a);
+        else if (stripe)
+            mbk::launch_resolve<true, mbk::kRuleStripe>(s, grid, use_lds ? lds : 0u, stream, a);
         else if (dist)
             mbk::launch_resolve<true, mbk::kRuleDistance>(s, grid, use_lds ? lds : 0u, stream, a);
         else if (eq)
@@ -4404,7 +4530,8 @@ static int render_launch(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t f
 // A checked render synchronously into a host image on slot 0: what follows the refusals of a *_render_compute call.
 static int render_compute_checked(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_render_spec *spec,
                                   uint8_t *h_rgba, mbk_stats *stats, const double *h_lut, uint32_t lut_len,
-                                  const InteriorColours *interior = nullptr, const ReliefLight *relief = nullptr)
+                                  const InteriorColours *interior = nullptr, const ReliefLight *relief = nullptr,
+                                  const StripeShade *stripe = nullptr)
 {
     int rc = sync_begin(ctx);
     if (rc != MBK_OK) return rc;
@@ -4416,7 +4543,7 @@ static int render_compute_checked(mbk_ctx *ctx, const Target &t, uint32_t mrd, u
         // the bands add their statistics up in the slot's reduction scratch: cleared once, here
         MBK_HIP(ctx, hipMemsetAsync(sl.d_red, 0, sizeof(ReduceSlot) * mbk::kReduceSlots, sl.stream));
         MBK_HIP(ctx, hipEventRecord(sl.ev_k0, sl.stream));
-        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len, interior, relief);
+        rc = render_run(ctx, t, mrd, flags, spec, ctx->d_rgba, sl.stream, &sl, h_lut, lut_len, interior, relief, stripe);
         if (rc != MBK_OK) return rc;
         MBK_HIP(ctx, hipEventRecord(sl.ev_c0, sl.stream));
         MBK_HIP(ctx, hipMemcpyAsync(h_rgba, ctx->d_rgba, px * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.stream));
@@ -5171,6 +5298,98 @@ int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_
     pal.light_y = light.y;
     pal.height = light.height;
     mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, smooth, rgba, mbk::kRuleRelief, nullptr, normals);
+    return MBK_OK;
+}
+
+// ---- stripe renders (mbk.h "Stripe-average colouring"): calls of their own on the render machinery above ---------------
+
+// The spec as the render machinery reads it: an MBK_RENDER_SMOOTH render of the same palette; and the stripe parameters.
+static mbk_render_spec stripe_render_spec(const mbk_stripe_spec *spec, StripeShade *shade)
+{
+    mbk_render_spec r = {};
+    r.source = MBK_RENDER_SMOOTH;
+    r.supersample = spec->supersample;
+    r.palette = spec->palette;
+    r.palette_len = spec->palette_len;
+    std::memcpy(r.inside, spec->inside, sizeof(r.inside));
+    r.scale = spec->scale;
+    r.offset = spec->offset;
+    r.max_band_rows = spec->max_band_rows;
+    shade->density = spec->density;
+    shade->skip = spec->skip;
+    shade->lo = spec->lo;
+    shade->gain = spec->gain;
+    return r;
+}
+
+// What a stripe spec adds to an MBK_RENDER_SMOOTH one (validate_render_spec checks the rest).
+static int validate_stripe_shade(mbk_ctx *ctx, const mbk_stripe_spec *spec)
+{
+    if (spec->density < 1u || spec->density > mbk::kStripeDensityMax) return fail(ctx, MBK_ERR_INVALID, "density must lie in 1 .. 16");
+    if (spec->skip > 0x7fffffffu) return fail(ctx, MBK_ERR_INVALID, "skip must lie in 0 .. 2^31 - 1");
+    if (!(spec->lo >= 0.0) || !(spec->lo <= 1.0)) return fail(ctx, MBK_ERR_INVALID, "lo must lie in [0, 1]");
+    if (!(spec->gain >= 0.0) || !(spec->gain <= 0x1p10)) return fail(ctx, MBK_ERR_INVALID, "gain must lie in [0, 2^10]");
+    return MBK_OK;
+}
+
+// Everything a stripe render can refuse, before anything is allocated, enqueued or written: what an MBK_RENDER_SMOOTH render
+// of the view refuses, MBK_PRECISION_F32 among it, and stripe parameters out of range.
+static int stripe_render_check(mbk_ctx *ctx, const Target &t, uint32_t mrd, uint32_t flags, const mbk_stripe_spec *spec, const void *out,
+                               mbk_render_spec *r, StripeShade *shade)
+{
+    if (!ctx) return fail(ctx, MBK_ERR_INVALID, "ctx is NULL");
+    if (!spec) return fail(ctx, MBK_ERR_INVALID, "render spec is NULL");
+    *r = stripe_render_spec(spec, shade);
+    int rc = render_check(ctx, t, mrd, flags, r, out);
+    if (rc != MBK_OK) return rc;
+    return validate_stripe_shade(ctx, spec);
+}
+
+int mbk_view_stripe_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_stripe_spec *spec,
+                                  uint8_t *d_rgba, void *hip_stream)
+{
+    const Target t = view_target(view);
+    mbk_render_spec r;
+    StripeShade shade;
+    int rc = stripe_render_check(ctx, t, mrd, flags, spec, d_rgba, &r, &shade);
+    if (rc != MBK_OK) return rc;
+    if ((uintptr_t)d_rgba & 3u) return fail(ctx, MBK_ERR_INVALID, "d_rgba must be 4-byte aligned");
+    MBK_HIP(ctx, hipSetDevice(ctx->device));
+    CaptureScope capture(ctx, (hipStream_t)hip_stream);
+    return render_run(ctx, t, mrd, flags, &r, (uint32_t *)d_rgba, (hipStream_t)hip_stream, nullptr, nullptr, 0u, nullptr, nullptr, &shade);
+}
+
+int mbk_view_stripe_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_stripe_spec *spec,
+                                   uint8_t *h_rgba, mbk_stats *stats)
+{
+    const Target t = view_target(view);
+    mbk_render_spec r;
+    StripeShade shade;
+    int rc = stripe_render_check(ctx, t, mrd, flags, spec, h_rgba, &r, &shade);
+    if (rc != MBK_OK) return rc;
+    return render_compute_checked(ctx, t, mrd, flags, &r, h_rgba, stats, nullptr, 0u, nullptr, nullptr, &shade);
+}
+
+int mbk_stripe_resolve_host(const mbk_stripe_spec *spec, uint32_t width, uint32_t height, const int32_t *counts, const double *smooth,
+                            const double *stripe, uint8_t *rgba)
+{
+    if (!spec) return fail(nullptr, MBK_ERR_INVALID, "render spec is NULL");
+    StripeShade shade;
+    const mbk_render_spec r = stripe_render_spec(spec, &shade);
+    int rc = validate_render_spec(nullptr, &r);
+    if (rc == MBK_OK) rc = validate_stripe_shade(nullptr, spec);
+    if (rc != MBK_OK) return rc;
+    if (!rgba) return fail(nullptr, MBK_ERR_INVALID, "output pointer is NULL");
+    const uint32_t s = spec->supersample;
+    if (width == 0 || height == 0 || (uint64_t)width * s >= (1ull << 31) || (uint64_t)height * s >= (1ull << 31))
+        return fail(nullptr, MBK_ERR_INVALID, "width and height must be > 0 and, times supersample, below 2^31");
+    if (!counts || !smooth || !stripe) return fail(nullptr, MBK_ERR_INVALID, "the sample arrays are NULL");
+    std::vector<uint32_t> words(spec->palette_len);
+    for (uint32_t k = 0; k < spec->palette_len; ++k) words[k] = pack_rgba(spec->palette + 4u * (size_t)k);
+    mbk::RenderPalette pal = render_palette(&r, words.data());
+    pal.stripe_lo = shade.lo;
+    pal.stripe_gain = shade.gain;
+    mbk::render_resolve_host(pal, true, s, width, height, counts, nullptr, smooth, rgba, mbk::kRuleStripe, nullptr, nullptr, stripe);
     return MBK_OK;
 }
 

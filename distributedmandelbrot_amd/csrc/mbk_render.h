@@ -1,6 +1,6 @@
 // mbk_render.h -- views to RGBA8 images (include/mbk.h, "Rendering"): the colour of one sample and the resolve of a pixel's
 // s x s samples, written once as __host__ __device__ functions that the resolve kernel and mbk_render_resolve_host share, and
-// the kernel itself (five rules for the binary64 samples: smooth, distance, equalised, interior, relief).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
+// the kernel itself (six rules for the binary64 samples: smooth, distance, equalised, interior, relief, stripe).  The samples come from the existing escape kernels, launched on a band's window; nothing here iterates.
 //
 // Everything after the samples is integer arithmetic or exact binary64: t = fl(fl(nu * scale) + offset) are two rounded
 // operations (the translation unit is compiled with -ffp-contract=off), floor(t) and (t - floor(t)) * 256 are exact for
@@ -14,6 +14,7 @@
 
 #include "mbk_histogram.h"
 #include "mbk_relief.h"
+#include "mbk_stripe.h"
 
 namespace mbk {
 
@@ -28,12 +29,13 @@ struct RenderPalette {
     uint32_t lut_mrd;
     uint32_t unknown, outside;   // interior renders: the colours of a sample with no period and of one that escapes
     double light_x, light_y, height;   // relief renders (mbk.h "Relief shading")
+    double stripe_lo, stripe_gain;     // stripe renders (mbk.h "Stripe-average colouring")
 };
 
 // How a binary64 sample becomes a colour: the three rules of the sources that share the (count, value) sample layout.
 // kRuleInterior (mbk.h "Interior views") reads a third array, the periods, beside the same two; kRuleRelief (mbk.h "Relief
-// shading") the normals, two binary64 per sample.
-enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2, kRuleInterior = 3, kRuleRelief = 4 };
+// shading") the normals, two binary64 per sample; kRuleStripe (mbk.h "Stripe-average colouring") the stripe values, one.
+enum RenderRule { kRuleSmooth = 0, kRuleDistance = 1, kRuleEqualized = 2, kRuleInterior = 3, kRuleRelief = 4, kRuleStripe = 5 };
 
 // Two colour channels at a time: a word holds channels 0 and 2 (or 1 and 3) in its 16-bit halves.
 __host__ __device__ inline uint32_t render_even(uint32_t c) { return c & 0x00ff00ffu; }
@@ -130,6 +132,14 @@ __host__ __device__ inline uint32_t render_colour_relief(const RenderPalette &p,
     return render_dim(render_colour_smooth(p, entries, count, nu), relief_shade(nx, ny, p.light_x, p.light_y, p.height));
 }
 
+// The colour of one stripe sample: `inside`, unshaded, if the count is 0; otherwise the MBK_RENDER_SMOOTH colour with R, G, B
+// scaled by q / 256, q the shade of the sample's stripe average (stripe_shade).
+__host__ __device__ inline uint32_t render_colour_stripe(const RenderPalette &p, const uint32_t *entries, int32_t count, double nu, double v)
+{
+    if (count == 0) return p.inside;
+    return render_dim(render_colour_smooth(p, entries, count, nu), stripe_shade(v, p.stripe_lo, p.stripe_gain));
+}
+
 template <int RULE>
 __host__ __device__ inline uint32_t render_colour(const RenderPalette &p, const uint32_t *entries, int32_t count, double value)
 {
@@ -166,6 +176,7 @@ struct RenderArgs {
     const double *smooth;
     const int32_t *period;   // kRuleInterior
     const double *normal;    // kRuleRelief: [sample][2]
+    const double *stripe;    // kRuleStripe: [sample]
     const uint8_t *bytes;    // MBK_RENDER_BYTES
     uint32_t *out;
     uint64_t pitch, out_pitch;
@@ -210,8 +221,8 @@ __device__ inline void render_load_smooth(const RenderArgs &a, uint64_t at, doub
 // contiguous stretch of the image.  The grid is sized to the chip and every workgroup takes pieces in turn, which is what
 // makes staging the palette in LDS worth its loads.  Pure streaming: s^2 x (12 | 1) bytes in, 4 bytes out per pixel.
 // RULE (with SMOOTH): what the binary64 samples are -- nu, distance estimates (render_colour_distance) or nu for the
-// equalisation table (render_colour_equalized); same loads, same layout.  kRuleInterior and kRuleRelief read one more array
-// per sample (the periods; the normals, 16 bytes) straight from global memory.
+// equalisation table (render_colour_equalized); same loads, same layout.  kRuleInterior, kRuleRelief and kRuleStripe read one
+// more array per sample (the periods; the normals, 16 bytes; the stripe values, 8) straight from global memory.
 template <bool SMOOTH, int S, int RULE = kRuleSmooth>
 __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const RenderArgs a)
 {
@@ -243,7 +254,9 @@ __global__ __launch_bounds__(kRenderThreads) void render_resolve_kernel(const Re
                     else if constexpr (RULE == kRuleRelief) {   // (16-byte aligned: the band's base is, and a sample is 16 bytes)
                         const double2 nv = reinterpret_cast<const double2 *>(a.normal)[at + sx];
                         sum.add(render_colour_relief(a.pal, entries, cnt[sx], nu[sx], nv.x, nv.y));
-                    } else
+                    } else if constexpr (RULE == kRuleStripe)
+                        sum.add(render_colour_stripe(a.pal, entries, cnt[sx], nu[sx], a.stripe[at + sx]));
+                    else
                         sum.add(render_colour<RULE>(a.pal, entries, cnt[sx], nu[sx]));
                 }
             }
@@ -300,7 +313,8 @@ inline void launch_resolve(uint32_t s, dim3 grid, size_t lds, hipStream_t stream
 // The same rule on the host, for caller-supplied samples of (width * s) x (height * s): mbk_render_resolve_host.
 inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, uint32_t s, uint32_t width, uint32_t height,
                                 const int32_t *counts, const uint8_t *bytes, const double *smooth, uint8_t *rgba,
-                                int rule = kRuleSmooth, const int32_t *period = nullptr, const double *normal = nullptr)
+                                int rule = kRuleSmooth, const int32_t *period = nullptr, const double *normal = nullptr,
+                                const double *stripe = nullptr)
 {
     const uint64_t pitch = (uint64_t)width * s;
     for (uint32_t y = 0; y < height; ++y)
@@ -312,6 +326,7 @@ inline void render_resolve_host(const RenderPalette &pal, bool smooth_source, ui
                     sum.add(!smooth_source            ? pal.entries[bytes[at]]
                             : rule == kRuleInterior  ? render_colour_interior(pal, pal.entries, counts[at], period[at], smooth[at])
                             : rule == kRuleRelief    ? render_colour_relief(pal, pal.entries, counts[at], smooth[at], normal[2u * at], normal[2u * at + 1u])
+                            : rule == kRuleStripe    ? render_colour_stripe(pal, pal.entries, counts[at], smooth[at], stripe[at])
                             : rule == kRuleDistance  ? render_colour_distance(pal, pal.entries, counts[at], smooth[at])
                             : rule == kRuleEqualized ? render_colour_equalized(pal, pal.entries, counts[at], smooth[at])
                                                      : render_colour_smooth(pal, pal.entries, counts[at], smooth[at]));

@@ -912,6 +912,36 @@ def relief_shade_host(nx: float, ny: float, lx: float, ly: float, h: float) -> i
     return int(L.load().mbk_relief_shade_host(float(nx), float(ny), float(lx), float(ly), float(h)))
 
 
+def stripe_state_host(c, mrd: int, *, density: int = 5, skip: int = 0) -> dict:
+    """mbk_stripe_state_host: the exact stripe state of one pixel by coordinate on the host (include/mbk.h, "Stripe-average
+    colouring"): {"n", "N", "S", "t_last", "mag", "cnt", "v"}."""
+    lib = L.load()
+    st = L.mbk_stripe_state()
+    _check(lib, lib.mbk_stripe_state_host(float(c[0]), float(c[1]), int(mrd), int(density), int(skip), C.byref(st)))
+    return {"n": int(st.n), "N": int(st.N), "S": float(st.S), "t_last": float(st.t_last), "mag": float(st.mag),
+            "cnt": int(st.cnt), "v": float(st.v)}
+
+
+def stripe_value_host(S: float, t_last: float, cnt: int, mag: float, count: int) -> float:
+    """mbk_stripe_value_host: the value v of one exact state on the host, from the function the kernel uses."""
+    return float(L.load().mbk_stripe_value_host(float(S), float(t_last), int(cnt), float(mag), int(count)))
+
+
+def stripe_shade_host(v: float, lo: float, gain: float) -> int:
+    """mbk_stripe_shade_host: the brightness q in [0, 256] of a sample with stripe average v."""
+    return int(L.load().mbk_stripe_shade_host(float(v), float(lo), float(gain)))
+
+
+def stripe_state_arrays(buf: np.ndarray, shape) -> dict:
+    """The five arrays of a stripe state buffer (32 bytes per pixel: S, t_last, mag as float64, then N, cnt as int32), as
+    views of ``buf`` (uint8, 32 * px bytes) shaped ``shape``."""
+    px = int(shape[0]) * int(shape[1])
+    f = buf[:24 * px].view(np.float64)
+    i = buf[24 * px:32 * px].view(np.int32)
+    return {"S": f[:px].reshape(shape), "t_last": f[px:2 * px].reshape(shape), "mag": f[2 * px:3 * px].reshape(shape),
+            "N": i[:px].reshape(shape), "cnt": i[px:].reshape(shape)}
+
+
 def _interior_spec(palette, supersample, unknown, outside, scale, max_band_rows):
     """(mbk_interior_render_spec, the palette array it points into) for a palette of uint8[n, 4] entries, entry k the colour
     of period k + 1."""
@@ -1279,6 +1309,57 @@ class MandelbrotDevice:
         cv = self._cview(view, window)
         spec = palette.relief_spec(supersample, light_deg, height, max_band_rows, light=light)
         self._check(self._lib.mbk_view_relief_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                            d_rgba or None, stream or None))
+
+    # -- stripe-average colouring (include/mbk.h, "Stripe-average colouring") -----------------------
+    def compute_view_stripes(self, view: View, mrd: int, *, density: int = 5, skip: int = 0, window=None, kernel: str = "default",
+                             want_state: bool = False):
+        """Stripe averages (not in the reference): per pixel the mean of 1/2 + 1/2 sin(density arg z_k) over its own orbit,
+        the first ``skip`` points left out, interpolated across the escape bands; 0 for never-escaped pixels.  The counts are
+        those of compute_view.  kernel: "default", "scan" or "group".
+        Returns (counts int32[nrows,ncols], v float64[nrows,ncols], TileStats), with want_state
+        (counts, v, state, TileStats): state is the dict of stripe_state_arrays (S, t_last, mag, N, cnt)."""
+        cv = self._cview(view, window)
+        shape = (cv.nrows, cv.ncols)
+        counts = np.empty(shape, np.int32)
+        v = np.empty(shape, np.float64)
+        buf = np.empty(32 * cv.nrows * cv.ncols, np.uint8) if want_state else None
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_compute_stripe(self._h, C.byref(cv), mrd, L.KERNELS[kernel], int(density), int(skip),
+                                                      counts.ctypes.data, v.ctypes.data, buf.ctypes.data if want_state else None,
+                                                      C.byref(st)))
+        return (counts, v, stripe_state_arrays(buf, shape), _stats(st)) if want_state else (counts, v, _stats(st))
+
+    def launch_view_stripes(self, view: View, mrd: int, *, d_stripe: int, d_counts: int = 0, d_state: int = 0, density: int = 5,
+                            skip: int = 0, stream: int = 0, window=None, kernel: str = "default") -> None:
+        """Asynchronous form on DEVICE pointers (float64 / int32 / 32 bytes per pixel of the window; d_counts and d_state may
+        be 0) on ``stream`` (0 = HIP's null stream).  d_state has the layout of stripe_state_arrays."""
+        cv = self._cview(view, window)
+        self._check(self._lib.mbk_view_launch_stripe(self._h, C.byref(cv), mrd, L.KERNELS[kernel], int(density), int(skip),
+                                                     d_counts or None, d_stripe or None, d_state or None, stream or None))
+
+    def render_view_stripes(self, view: View, mrd: int, *, palette, density: int = 5, skip: int = 0, lo: float = 0.35,
+                            gain: float = 1.0, supersample: int = 1, window=None, max_band_rows: int = 0, kernel: str = "default",
+                            out: Optional[np.ndarray] = None):
+        """The view with stripes: the "smooth" colouring of render_view (image.Palette, its scale and offset) with R, G, B of
+        every escaped sample scaled by its stripe average -- ``lo`` is the brightness of the darkest stripe, ``gain`` the
+        contrast about the middle (0 gives one neutral brightness).  Supersampling, windows and bands as for render_view.
+        Returns (rgba uint8[nrows, ncols, 4], TileStats over the samples)."""
+        cv = self._cview(view, window)
+        spec = palette.stripe_spec(supersample, density, skip, lo, gain, max_band_rows)
+        img = self._render_out(cv, out)
+        st = L.mbk_stats()
+        self._check(self._lib.mbk_view_stripe_render_compute(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
+                                                             img.ctypes.data, C.byref(st)))
+        return img, _stats(st)
+
+    def launch_render_view_stripes(self, view: View, mrd: int, *, palette, d_rgba: int, density: int = 5, skip: int = 0,
+                                   lo: float = 0.35, gain: float = 1.0, supersample: int = 1, stream: int = 0, window=None,
+                                   max_band_rows: int = 0, kernel: str = "default") -> None:
+        """Asynchronous stripe render into a DEVICE buffer of nrows * ncols * 4 bytes on ``stream``."""
+        cv = self._cview(view, window)
+        spec = palette.stripe_spec(supersample, density, skip, lo, gain, max_band_rows)
+        self._check(self._lib.mbk_view_stripe_render_launch(self._h, C.byref(cv), mrd, L.KERNELS[kernel], C.byref(spec),
                                                             d_rgba or None, stream or None))
 
     def serialize_last(self) -> Tuple[bytes, int]:

@@ -152,6 +152,15 @@ class Palette:
         return L.mbk_relief_spec(int(supersample), self.entries.ctypes.data, len(self), (C.c_uint8 * 4)(*self.inside),
                                  float(self.scale), float(self.offset), float(lx), float(ly), float(height), int(max_band_rows))
 
+    def stripe_spec(self, supersample: int, density: int = 5, skip: int = 0, lo: float = 0.35, gain: float = 1.0,
+                    max_band_rows: int = 0) -> L.mbk_stripe_spec:
+        """The C struct of a stripe render (include/mbk.h, "Stripe-average colouring"): this palette as for source "smooth",
+        shaded by the stripe average of density `density` with the first `skip` orbit points left out; `lo` the brightness of
+        the darkest stripe, `gain` the contrast.  It points into self.entries, which the caller keeps alive for the call."""
+        return L.mbk_stripe_spec(int(supersample), self.entries.ctypes.data, len(self), (C.c_uint8 * 4)(*self.inside),
+                                 float(self.scale), float(self.offset), int(density), int(skip), float(lo), float(gain),
+                                 int(max_band_rows))
+
     @staticmethod
     def _ramp(near, far, n: int) -> np.ndarray:
         x = np.arange(n, dtype=np.float64)[:, None] / (n - 1)
@@ -241,6 +250,26 @@ def relief_resolve_host(palette: Palette, supersample: int, width: int, height_p
         raise ValueError("sample arrays must hold (height * s) x (width * s) elements, the normals two each")
     spec = palette.relief_spec(supersample, light_deg, height, light=light)
     st = lib.mbk_relief_resolve_host(C.byref(spec), width, height_px, c.ctypes.data, nu.ctypes.data, nrm.ctypes.data, out.ctypes.data)
+    if st != L.MBK_OK:
+        from .device import MbkError
+        raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())
+    return out
+
+
+def stripe_resolve_host(palette: Palette, supersample: int, width: int, height_px: int, *, counts, smooth, stripe,
+                        density: int = 5, skip: int = 0, lo: float = 0.35, gain: float = 1.0) -> np.ndarray:
+    """mbk_stripe_resolve_host: shade, colour and resolve caller-supplied samples of (height_px s, width s) on the host --
+    counts, nu and stripe averages -- with the code the stripe resolve kernel is compiled from, without a device."""
+    lib = L.load()
+    out = np.empty((height_px, width, 4), np.uint8)
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    nu = np.ascontiguousarray(smooth, dtype=np.float64)
+    v = np.ascontiguousarray(stripe, dtype=np.float64)
+    samples = width * height_px * supersample * supersample
+    if c.size != samples or nu.size != samples or v.size != samples:
+        raise ValueError("sample arrays must hold (height * s) x (width * s) elements")
+    spec = palette.stripe_spec(supersample, density, skip, lo, gain)
+    st = lib.mbk_stripe_resolve_host(C.byref(spec), width, height_px, c.ctypes.data, nu.ctypes.data, v.ctypes.data, out.ctypes.data)
     if st != L.MBK_OK:
         from .device import MbkError
         raise MbkError(st, (lib.mbk_last_error(None) or b"").decode())

@@ -1866,6 +1866,106 @@ int mbk_relief_resolve_host(const mbk_relief_spec *spec, uint32_t width, uint32_
                             const double *smooth, const double *normals, uint8_t *rgba);
 
 /*
+ * Stripe-average colouring: a statistic taken along a pixel's own orbit, and renders shaded by it.  NOT in the reference;
+ * additive (the ABI version stays 5): no existing call changes.  Every colouring above is a function of a pixel's final state;
+ * the stripe average (Harkonen) is the mean of 1/2 + 1/2 sin(s arg z_k) over the orbit, interpolated across the escape bands so
+ * that the picture is continuous -- the striped, feathered exteriors of Mandelbrot renderers.  For an integer density s,
+ * sin(s arg z) is the imaginary part of (z / |z|)^s: one square root, two divisions and s - 1 complex products, all correctly
+ * rounded, no libm call per step.  For plain views (mbk_view) only.
+ *
+ * Contract (exact; tests/stripe_model.py restates it in numpy, tests/test_stripe.py and tests/test_gpu_stripe.py hold the host
+ * twins and the GPU to it).  Binary64, every operation rounded on its own.  Uniform per launch: the density s in 1 .. 16 and
+ * skip in 0 .. 2^31 - 1, the number of leading orbit points left out of the average.
+ *   orbit     z_0 = c, the recurrence and the count n of mbk_view_launch, unchanged.  The run-on is that of "Distance estimates":
+ *             a pixel with n > 0 runs on, uncounted, until mag = fl(fl(zr^2) + fl(zi^2)) >= 2^32 or 64 further steps.
+ *             N = n + run-on steps is the index of the last point.
+ *   term      of a point z_k, 1 <= k <= N: if not mag_k > 0, or mag_k = +inf, t_k = 0.5 (that covers NaN and 0).  Otherwise
+ *             r = fl(sqrt(mag_k)), u = (fl(zr / r), fl(zi / r)), p = u, then s - 1 times
+ *             p <- (fl(fl(p.r u.r) - fl(p.i u.i)), fl(fl(p.r u.i) + fl(p.i u.r))), and t_k = fl(0.5 + fl(0.5 p.i)).
+ *   sum       S adds t_k for k = skip + 1 .. N in ascending order, one rounded addition each; cnt = max(0, N - skip);
+ *             t_last = t_N if cnt > 0, else 0.  The exact state of a pixel is (n, N, S, t_last, mag_N, cnt); a pixel with
+ *             n = 0 has the all-zero state.
+ *   value     v = 0 if n = 0; 0.5 if cnt = 0; S if cnt = 1.  Otherwise a1 = fl(S / cnt), a0 = fl(fl(S - t_last) / (cnt - 1)),
+ *             d = fl(1 - fl(log2(fl(fl(ln mag_N) / LB)))) with LB the binary64 nearest 32 ln 2; d = 0 unless d >= 0 (a NaN,
+ *             mag = inf), d = 1 where d > 1 (the 64-step cap: c = -2); v = fl(a0 + fl(fl(a1 - a0) d)).  a0 comes from
+ *             S - t_last, not from a second running sum.  ln and log2 are the device's (ocml) on the device and the C
+ *             library's on the host; everything else is exact.  A NaN is never stored.
+ *   shade     of a sample, lo in [0, 1] and gain finite in [0, 2^10]: w = fl(0.5 + fl(gain fl(v - 0.5))) clamped to [0, 1],
+ *             t = fl(lo + fl(fl(1 - lo) w)), q = floor(256 t), or 256 where t >= 1.
+ *   colour    of a sample: `inside`, unshaded, if its count is 0.  Otherwise base is the MBK_RENDER_SMOOTH colour of
+ *             (count, nu) with the spec's palette, scale and offset, and each of R, G, B becomes (base q + 128) >> 8, exactly
+ *             as the relief rule scales; alpha is the base's.
+ *   rendering resolve, supersampling set, output layout, banding, the palette's wait-on-change rule and the statistics of
+ *             _compute are those of "Rendering".  Samples are 20 bytes: int32 count, binary64 nu, binary64 v.
+ * mrd 0 and 1 run no step: every count and value is 0.  Windows of a view are bit-identical to the whole view; any
+ * max_band_rows gives the same image.
+ *
+ * Held to the mathematics (tests/test_stripe.py): the same recurrences and the true sin(s arg z_k) with mpmath at 384 bits, from
+ * the same binary64 c, against the model's v at s = 1, 5, 16 (tests/stripe_model.py: MEASURED_TRUTH): 2.2e-16 .. 2.5e-15 at
+ * c = 0.37 + 0.6i (n = 17), 1.9e-14 .. 1.6e-13 at c = -1.75 + 0.02i (n = 12), 7.6e-7 .. 6.2e-6 at
+ * c = -0.7436438860371587 + 0.1318259043091895i (n = 1194, next to the boundary, where rounding in z is amplified as it is
+ * for the normals).  The value expression is within 1.45 ulp(v) of its correctly rounded value on the host
+ * (MEASURED_VALUE_ULPS_HOST, over the escaped pixels of a 67 x 45 view of the seahorse valley), one ulp more on the device.
+ * Along ci = 0.6 near cr = 0.404631, where N changes, the largest difference between neighbouring samples at density 5 halves
+ * with the spacing (3.0e-3 at 1e-9): steep, not a jump.
+ *
+ * One form (csrc/mbk_stripe.h), the two-pass form of the distance kernel: MBK_KERNEL_DEFAULT / _SCAN / _GROUP have the count
+ * kernels write the counts (into d_counts, or into scratch the ctx keeps per stream when d_counts is NULL), and a second
+ * kernel replays each escaped pixel for exactly its count and then the run-on.
+ * mbk_view_launch_stripe: asynchronous, DEVICE pointers on the caller's stream; d_stripe holds one binary64 per pixel of the
+ * window, 8-byte aligned; d_counts and d_state may be NULL.  d_state receives the exact state, 32 bytes per pixel in five
+ * arrays of px = ncols * nrows elements each, one after the other: S, t_last and mag_N as binary64, then N and cnt as int32;
+ * 8-byte aligned.  Nothing is written outside the window-sized buffers.  The launch forms obey "Graph capture" and "Streams".
+ * mbk_view_compute_stripe: synchronous into HOST buffers on slot 0 (the slot-0 rule applies), the same pointer rules and the
+ * same state layout, stats as for mbk_view_compute_distance.
+ * mbk_stripe_state_host: one pixel by coordinate on the HOST (the literal doubling throughout); mbk_stripe_value_host /
+ * mbk_stripe_shade_host: the value of one exact state and the shade q of one sample, compiled from the functions the kernel uses.
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_view_launch_distance refuses (MBK_PRECISION_F32, MBK_KERNEL_SIMPLE /
+ * _REFILL, mrd >= 2^31, a bad view), MBK_KERNEL_ASM (there is no one-pass form), any flag bit that is no kernel selector, a
+ * density outside 1 .. 16, a skip above 2^31 - 1, a NULL value pointer.
+ *
+ * Stripe renders are calls of their own, not an MBK_RENDER_* source.  A band computes the samples of mbk_view_launch_smooth
+ * (counts and nu, with the kernel `flags` select), runs the stripe kernel on those counts and resolves.
+ * MBK_ERR_INVALID, with nothing written: whatever mbk_view_render_* refuses for MBK_RENDER_SMOOTH, a NULL spec, palette or
+ * output pointer, a density or skip out of range, a lo or gain that is not finite or lies outside its range.
+ * mbk_stripe_resolve_host: colour and resolve on the HOST for caller-supplied samples of (width s) x (height s).
+ *
+ * Out of scope: Julia, deep and extended-range views; adaptive supersampling, sharding and slot forms; a one-pass or fp32
+ * form; other orbit statistics (triangle-inequality average, orbit traps); combining stripes with relief.
+ */
+typedef struct mbk_stripe_state {
+    double S, t_last, mag; /* the sum, the last term, mag_N */
+    double v;              /* the value of this state */
+    int32_t n, N, cnt;     /* the count, the index of the last point, the number of terms in S */
+    int32_t reserved;      /* 0 */
+} mbk_stripe_state;
+typedef struct mbk_stripe_spec {
+    uint32_t supersample;   /* 1, 2, 3, 4, 8 */
+    const uint8_t *palette; /* HOST pointer, palette_len x RGBA8; copied during the call */
+    uint32_t palette_len;   /* 2 .. 65536 */
+    uint8_t inside[4];      /* the colour of a sample that never escapes; not shaded */
+    double scale, offset;   /* as for MBK_RENDER_SMOOTH */
+    uint32_t density;       /* s, 1 .. 16 */
+    uint32_t skip;          /* leading orbit points left out, 0 .. 2^31 - 1 */
+    double lo;              /* the brightness of the darkest stripe, 0 .. 1 */
+    double gain;            /* contrast about v = 0.5, 0 .. 2^10 */
+    uint32_t max_band_rows; /* 0 = the library's choice; any value gives the same image */
+} mbk_stripe_spec;
+int mbk_view_launch_stripe(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t density, uint32_t skip,
+                           int32_t *d_counts, double *d_stripe, void *d_state, void *hip_stream);
+int mbk_view_compute_stripe(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, uint32_t density, uint32_t skip,
+                            int32_t *h_counts, double *h_stripe, void *h_state, mbk_stats *stats);
+int mbk_stripe_state_host(double c_r, double c_i, uint32_t mrd, uint32_t density, uint32_t skip, mbk_stripe_state *out);
+double mbk_stripe_value_host(double S, double t_last, int32_t cnt, double mag, int32_t count);
+uint32_t mbk_stripe_shade_host(double v, double lo, double gain);
+int mbk_view_stripe_render_launch(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_stripe_spec *spec,
+                                  uint8_t *d_rgba, void *hip_stream);
+int mbk_view_stripe_render_compute(mbk_ctx *ctx, const mbk_view *view, uint32_t mrd, uint32_t flags, const mbk_stripe_spec *spec,
+                                   uint8_t *h_rgba, mbk_stats *stats);
+int mbk_stripe_resolve_host(const mbk_stripe_spec *spec, uint32_t width, uint32_t height, const int32_t *counts,
+                            const double *smooth, const double *stripe, uint8_t *rgba);
+
+/*
  * Relief shading for deep views: the same normals and lit renders for mbk_deep_view, with the plain step and with the skips of
  * MBK_DEEP_BLA.  NOT in the reference; additive (the ABI version stays 5): no existing call changes.  At a span of 1e-60 a
  * count or nu picture is dense bands; slope lighting is what makes filaments and spirals readable there, and it is nearly free:
